@@ -1,6 +1,6 @@
 """bench.py -- cluster-pair ICP registrations / second on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,6 +20,14 @@ check) of every pair of the workload, inputs resident in HBM before the timed re
             N > 1 code path); the gathered rows are compared with the local ones after the timed region (`gather_check`).
   With no launcher around it (WORLD_SIZE unset) `--gpus N > 1` starts its N ranks itself (self_launch: the contract's
   own torch.distributed.run command line on 127.0.0.1 and a free port); fewer than N devices => "needs N devices, found M".
+
+  --full   everything beyond the headline as well, after the timed region: the CPU baseline, the extras (match_eval, other
+            search / stop modes, the ragged batches, the demo frame pair, clustering), config 4 on one GPU, the N = 1 point of an
+            N > 1 line (n1_same_workload, scaling_efficiency), the gathered rows' check and the stream's accuracy pass.  Without
+            it a run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, roofline of the
+            timed launches).
+  --dump-outputs DIR  after the timed region, what the timed path returned in its LAST step as DIR/<name>.npy (float32 /
+            float64; inputs are seeded, so two builds run with the same arguments can be compared array for array).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -61,12 +69,16 @@ def parse():
     ap.add_argument("--points", type=int, default=None, help="points per cluster (= padded length)")
     ap.add_argument("--iters", type=int, default=50, help="ICP iteration cap (BASELINE: 50)")
     ap.add_argument("--stop-mode", default="reference", choices=["reference", "per_pair"])
-    ap.add_argument("--cpu-pairs", type=int, default=256, help="pairs in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-pairs", type=int, default=256, help="--full: pairs in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--time-every", type=int, default=5, help="HIP events around the ICP launch in every n-th step of the timed region (1 = every step)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra measurements")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline (CPU baseline, "
+                                                        "extras, config 4 on one GPU, N = 1 points, gather check, stream accuracy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32/float64, <= 64 MB)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the untimed extra measurements")
     ap.add_argument("--force-collective", action="store_true", help="one rank: init RCCL and all_gather anyway")
-    ap.add_argument("--no-n1", action="store_true", help="N > 1: skip the single-GPU run of the same workload on rank 0 (n1_same_workload)")
-    ap.add_argument("--check-gather", action="store_true", help="compare the gathered rows with the local ones")
+    ap.add_argument("--no-n1", action="store_true", help="--full, N > 1: skip the single-GPU run of the same workload on rank 0 (n1_same_workload)")
+    ap.add_argument("--check-gather", action="store_true", help="compare the gathered rows with the local ones (always with --full)")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="no GPU work: the ranks run the launcher, the rendezvous, the sharding and the one all_gather of "
                          "[B,26] rows over gloo on CPU tensors (what tests/test_bench_launcher.py drives)")
@@ -212,14 +224,19 @@ def stream_main(a, rank, world, local):
             if id(fp) not in seen:
                 seen[id(fp)] = frame_pairs.make_resident(fp, dev)
 
-    def one_pass():
+    def one_pass(keep=None):
         n = matched = 0
         if selftest:
-            for fp in fps:
-                matched += int(stand_in(args, fp, dev)["pairs"].shape[0]); n += 1
-        else:
-            for _, fp, out in frame_pairs.register_in_flight(args, fps, dev, a.in_flight):
+            for i, fp in enumerate(fps):
+                out = stand_in(args, fp, dev)
                 matched += int(out["pairs"].shape[0]); n += 1
+                if keep is not None:
+                    keep[i] = out
+        else:
+            for i, fp, out in frame_pairs.register_in_flight(args, fps, dev, a.in_flight):
+                matched += int(out["pairs"].shape[0]); n += 1
+                if keep is not None:           # (--dump-outputs, last timed step only: this rank's results by frame pair)
+                    keep[i] = out
         tot = torch.tensor([n, matched], dtype=torch.float64, device=dev)
         if collective:
             dist.all_reduce(tot)              # the one collective of a step
@@ -234,11 +251,18 @@ def stream_main(a, rank, world, local):
     for _ in range(a.warmup):
         one_pass()
     sync()
+    last = {} if a.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        tot = one_pass()
+    for k in range(a.steps):
+        tot = one_pass(last if k == a.steps - 1 else None)
     sync()
     dt = time.perf_counter() - t0
+    if last is not None and rank == 0:
+        res = [last[i] for i in sorted(last)]          # (rank 0's frame pairs in stream order, each result's rows one after the other)
+        arrays = {k: torch.cat([r[k] for r in res]) for k in ("pairs", "transformations", "flow") if all(torch.is_tensor(r.get(k)) for r in res)}
+        arrays["pairs_per_frame_pair"] = np.array([len(r["pairs"]) for r in res])
+        dump_outputs(a.dump_outputs, arrays)
+    last = None
     if collective:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -246,7 +270,7 @@ def stream_main(a, rank, world, local):
     n_total, matched_total = int(tot[0].item()), int(tot[1].item())
     # the N = 1 point of this line: rank 0 runs the WHOLE stream alone (same in-flight depth, no collective), two passes after a warm-up
     n1 = None
-    if world > 1 and rank == 0 and not a.no_n1:
+    if a.full and world > 1 and rank == 0 and not a.no_n1:
         try:
             if selftest:
                 t1 = time.perf_counter(); k1 = sum(1 for _ in items); d1 = max(time.perf_counter() - t1, 1e-9); reps = 1
@@ -268,8 +292,10 @@ def stream_main(a, rank, world, local):
         except Exception as e:
             n1 = {"error": repr(e)}
     # accuracy, untimed: the stream through run_stream (EPE & co. against the frames' ground truth, its one all_reduce of the sums)
-    summary = frame_pairs.run_stream(args, items, dev, rank, world, register_fn=stand_in if selftest else None,
-                                     in_flight=1 if selftest else a.in_flight)
+    summary = None
+    if a.full:
+        summary = frame_pairs.run_stream(args, items, dev, rank, world, register_fn=stand_in if selftest else None,
+                                         in_flight=1 if selftest else a.in_flight)
     if rank == 0:
         lib = None if selftest else next((ln.split()[-1] for ln in open("/proc/self/maps") if "librccl" in ln or "libnccl" in ln), None)
         from icp_flow_amd import _lib
@@ -284,19 +310,21 @@ def stream_main(a, rank, world, local):
                           "sharding": "round-robin over ranks; ONE all_reduce of (frame pairs, matched cluster pairs) per step inside the timed region"
                                       if collective else "one rank, no exchange step"},
                "matched_cluster_pairs_per_step": matched_total,
-               "accuracy": {k: summary[k] for k in ("frame_pairs", "matched_cluster_pairs", "evaluated_points", "epe", "accs", "accr", "outlier", "Routlier", "pose_sources") if k in summary},
-               "reduce_check": {"frame_pairs_counted_by_all_ranks": n_total, "equals_sum_of_shares": n_total == sum(counts) == summary["frame_pairs"],
+               "reduce_check": {"frame_pairs_counted_by_all_ranks": n_total,
+                                "equals_sum_of_shares": n_total == sum(counts) and (summary is None or n_total == summary["frame_pairs"]),
                                 "backend": dist.get_backend() if collective else None, "rccl_library": lib},
                "library_build": None if selftest else _lib.BUILD_INFO}
+        if summary is not None:
+            out["accuracy"] = {k: summary[k] for k in ("frame_pairs", "matched_cluster_pairs", "evaluated_points", "epe", "accs", "accr", "outlier", "Routlier", "pose_sources") if k in summary}
         if selftest:
             out["launch_selftest"] = True
-        if world > 1:
+        if a.full and world > 1:
             out["n1_same_workload"] = n1
             out["scaling_efficiency"] = (round(n1["value"] / (world * out["value"]), 4) if n1 and n1.get("value") and out["value"] else None)
         print(json.dumps(out))
     if collective:
         dist.destroy_process_group()
-    if not (n_total == sum(counts) == summary["frame_pairs"]):
+    if not (n_total == sum(counts) and (summary is None or n_total == summary["frame_pairs"])):
         raise SystemExit("stream: the ranks' frame pairs do not add up to the stream")
 
 
@@ -327,6 +355,34 @@ def timed_steps(step, sync, steps, warmup, iters_cap, every=1):
     icp_ms, icp_launches = prof.collect()
     prof.close()
     return dt, icp_ms, icp_launches, T, iters, timed
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy -- float64 stays float64, integers become float64 (exact), the rest
+    float32.  Past DUMP_LIMIT_BYTES in all, the largest arrays are cut to a fixed, seeded sample of their rows (the row
+    indices in <name>_rows.npy): the same rows in every run of the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        out[name] = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 or x.dtype.kind in "iu" else np.float32)
+    total = sum(x.nbytes for x in out.values())
+    for name in sorted(out, key=lambda k: -out[k].nbytes):
+        if total <= DUMP_LIMIT_BYTES:
+            break
+        x = out[name]
+        if x.ndim == 0 or len(x) < 2:
+            continue
+        row = x.nbytes // len(x)
+        keep = max(1, min(len(x) - 1, (x.nbytes - (total - DUMP_LIMIT_BYTES)) // (row + 8)))
+        idx = np.sort(np.random.default_rng(0).choice(len(x), size=keep, replace=False))
+        out[name], out[name + "_rows"] = x[idx], idx.astype(np.float64)
+        total -= x.nbytes - out[name].nbytes - out[name + "_rows"].nbytes
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def main():
@@ -390,9 +446,11 @@ def main():
         torch.cuda.synchronize(dev)
 
     dt, icp_ms, icp_launches, T, iters, steps_timed = timed_steps(step, sync, a.steps, a.warmup, a.iters, every=(a.time_every if a.iters <= 128 else 1))
+    if a.dump_outputs and rank == 0:       # what the last timed step returned: hist_icp's (T, iterations), or the gathered rows
+        dump_outputs(a.dump_outputs, {"gathered_rows" if collective else "transformations": T, "icp_iterations": iters.reshape(1)})
     gather_check = None
     if collective:
-        if True:                # (always, outside the timed region) the rows this rank contributed, as every rank received them
+        if a.full or a.check_gather:   # (outside the timed region) the rows this rank contributed, as every rank received them
             Tl, ev, _ = utils_match.hist_icp_eval(args, src, dst, return_iterations=True)
             mine = pack_rows(Tl, first, ev[0], ev[1], ev[2], ev[3])
             gather_check = {"rows": list(T.shape), "identical_to_local_rows": bool(torch.equal(T[first:first + B], mine)),
@@ -419,7 +477,7 @@ def main():
     # protocol (the other ranks have left; nothing here is part of `value`).  A driver that divides this line's value by the
     # `--gpus 1` line's would divide config 4 by config 2: `scaling_efficiency` is the figure that means something.
     n1 = None
-    if collective and workload == "config4" and not a.no_n1:   # (--force-collective: a world of one exercises it too)
+    if a.full and collective and workload == "config4" and not a.no_n1:   # (--force-collective: a world of one exercises it too)
         try:
             n1 = same_workload_on_one_gpu(args, total, N, dev, a, utils_match, synthetic)
         except Exception as e:               # the line must survive (e.g. 8192 x 2048 pairs not fitting beside the shard)
@@ -427,14 +485,14 @@ def main():
     roofline = roofline_block(B, N, a.steps, iters_done, icp_ms, icp_launches, dt, _lib.BUILD_INFO, steps_timed)
 
     extras = {}
-    if not a.no_extras and world == 1 and workload == "config2":   # N > 1 runs measure scaling, nothing else
+    if a.full and not a.no_extras and world == 1 and workload == "config2":   # N > 1 runs measure scaling, nothing else
         try:
             extras = extra_measurements(args, src, dst, T, dev, a)
         except Exception as e:               # the headline line must survive a failing side measurement
             extras = {"error": repr(e)}
 
     cpu = None
-    if a.cpu_pairs > 0 and world == 1 and workload == "config2":
+    if a.full and a.cpu_pairs > 0 and world == 1 and workload == "config2":
         try:
             cpu = cpu_baseline(S, D, a)
         except Exception as e:                   # e.g. no C compiler for the oracle on this box
@@ -450,10 +508,10 @@ def main():
         "config": {"workload": f"{name}, <= {a.iters} ICP iters ({a.stop_mode} stop), thres_dist 0.1, "
                                f"translation_frame 2.0 (41x41x3 bins)" +
                                ("; NOTE: `--gpus 1` runs config 2 (the headline) and is NOT the N = 1 point of the config-4 curve that "
-                                "`--gpus N > 1` runs -- that point is `config4_on_one_gpu` here and `n1_same_workload` on every N > 1 line"
+                                "`--gpus N > 1` runs -- that point is `config4_on_one_gpu` here and `n1_same_workload` on every N > 1 line (both with --full)"
                                 if workload == "config2" and world == 1 and a.workload == "auto" else
                                 "; strong scaling of ONE workload: its single-GPU point is this line's `n1_same_workload` (not the `--gpus 1` "
-                                "line, which is config 2)" if workload == "config4" and world > 1 else ""),
+                                "line, which is config 2; with --full)" if workload == "config4" and world > 1 else ""),
                    "pairs_total": total, "pairs_per_gpu": counts, "points": N, "icp_iteration_cap": a.iters,
                    "stop_mode": a.stop_mode,
                    "sharding": (f"contiguous blocks of pairs over {world} rank(s); every step = hist_icp + match_eval + ONE "
@@ -461,17 +519,18 @@ def main():
                    if collective else "one rank, no exchange step"},
         "library_build": _lib.BUILD_INFO,
         "roofline": roofline,
-        "cpu_baseline": cpu,
-        "extras": extras,
     }
-    if world == 1 and workload == "config2" and not a.no_extras:
+    if a.full:
+        out["cpu_baseline"] = cpu
+        out["extras"] = extras
+    if a.full and world == 1 and workload == "config2" and not a.no_extras:
         try:
             out["config4_on_one_gpu"] = config4_single_gpu(dev, a)
         except Exception as e:
             out["config4_on_one_gpu"] = {"error": repr(e)}
     if gather_check is not None:
         out["gather_check"] = gather_check
-    if collective and workload == "config4":
+    if a.full and collective and workload == "config4":
         out["n1_same_workload"] = n1
         out["scaling_efficiency"] = (round(value / (world * n1["value"]), 4) if n1 and n1.get("value") else None)
     print(json.dumps(out))

@@ -1,7 +1,7 @@
 set -u
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/evidence; mkdir -p $O
-python bench.py > $O/r04_bench.json 2> $O/r04_bench.err
+python bench.py --full > $O/r04_bench.json 2> $O/r04_bench.err
 REPS=6 python tools/dbg/stream_stress.py > $O/stress_default.txt 2>&1
 REPS=6 NATIVE=0 DEVICE_ASSOC=1 python tools/dbg/stream_stress.py > $O/stress_device.txt 2>&1
 REPS=6 DEVICE_ASSOC=0 python tools/dbg/stream_stress.py > $O/stress_host.txt 2>&1

@@ -4,4 +4,4 @@
 cd "$(dirname "$0")/../.."
 for Q in ${QUEUES:-unset 8 16}; do for k in 1 2 3 4 5; do
   if [ $Q = unset ]; then unset GPU_MAX_HW_QUEUES; export ICPFLOW_KEEP_HW_QUEUES=1; else export GPU_MAX_HW_QUEUES=$Q; unset ICPFLOW_KEEP_HW_QUEUES; fi
-  timeout 300 python bench.py --cpu-pairs 0 > /tmp/b.json 2>/dev/null; echo "Q=$Q $(python tools/dbg/benchsum.py /tmp/b.json)"; done; done
+  timeout 300 python bench.py --full --cpu-pairs 0 > /tmp/b.json 2>/dev/null; echo "Q=$Q $(python tools/dbg/benchsum.py /tmp/b.json)"; done; done

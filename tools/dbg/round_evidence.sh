@@ -13,9 +13,9 @@ python tools/summarize_ragged.py $TAG > $O/summarize_ragged.log 2>&1
 bash tools/profile_workload.sh $TAG config4_shard python tools/dbg/config4_run.py 1024 > $O/profile_config4.log 2>&1
 python tools/summarize_workload.py $TAG config4_shard > $O/summarize_config4.log 2>&1
 mkdir -p gpurun_out/profiles_$TAG; cp profiles/${TAG}_* gpurun_out/profiles_$TAG/ 2>/dev/null
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python bench.py --workload stream --steps 20 --warmup 3 > $O/${TAG}_bench_stream.json 2>> $O/${TAG}_bench.err
-python bench.py --workload stream --steps 20 --warmup 3 --force-collective > $O/${TAG}_bench_stream_rccl.json 2>> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --workload stream --steps 20 --warmup 3 --full > $O/${TAG}_bench_stream.json 2>> $O/${TAG}_bench.err
+python bench.py --workload stream --steps 20 --warmup 3 --force-collective --full > $O/${TAG}_bench_stream_rccl.json 2>> $O/${TAG}_bench.err
 REPS=6 python tools/dbg/stream_stress.py > $O/stress_default.txt 2>&1
 for f in cert_fuzz frame_fuzz score_fuzz registration_fuzz native_fuzz vote_list_fuzz; do timeout 500 python tools/dbg/$f.py > $O/$f.txt 2>&1; echo "$f rc=$?"; done
 # round 6: the stream's spread per setting of GPU_MAX_HW_QUEUES, the A/Bs of the round's switches, the direction keys' fuzz

@@ -15,7 +15,7 @@ bash "$ROOT/tools/profile_pmc.sh" "$TAG" > "$ROOT/gpurun_out/pmc_$TAG.log" 2>&1
 cd "$ROOT"
 STATS_DIR=$(dirname "$(find gpurun_out/stats_$TAG -name '*kernel_stats.csv' | head -1)")
 python tools/summarize_profiles.py "$TAG" "$STATS_DIR" "gpurun_out/pmc_$TAG" > "gpurun_out/summary_$TAG.log" 2>&1
+timeout 900 python bench.py --full > "profiles/${TAG}_bench.json" 2> "profiles/${TAG}_bench.err"
 mkdir -p "gpurun_out/profiles_$TAG"
 cp profiles/${TAG}_* "gpurun_out/profiles_$TAG/" 2>/dev/null
-timeout 900 python bench.py > "gpurun_out/profiles_$TAG/${TAG}_bench.json" 2> "gpurun_out/profiles_$TAG/${TAG}_bench.err"
 tail -5 "gpurun_out/summary_$TAG.log"; head -c 600 "gpurun_out/profiles_$TAG/${TAG}_bench.json"
