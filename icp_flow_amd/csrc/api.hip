@@ -7,6 +7,7 @@
 
 #include "kernels.hpp"
 #include "posefuse.hpp"
+#include "kabsch.hpp"
 
 using namespace icpflow;
 
@@ -37,6 +38,44 @@ int report_error(int code, const char *message)
 {
     snprintf(g_err, sizeof(g_err), "%s", message);
     return code;
+}
+
+// icpflow_selftest_kabsch: the Kabsch solve of icp.hip / icp_fp32.hip alone, one wave per matrix, with the Newton start of either call site
+// (mode 0 / 1: icp_kernel's gsum from the caller, allow_reflection off / on; mode 2: icp_fp32ref_kernel's bound)
+__global__ __launch_bounds__(kWave) void kabsch_probe_kernel(const double *__restrict__ H, const double *__restrict__ gsum,
+                                                             int n, int mode, double *__restrict__ R,
+                                                             double *__restrict__ lamOut, int32_t *__restrict__ path)
+{
+    __shared__ double Hsh[9];
+    __shared__ double Nsh[16];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= n) return;
+    double frob2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double h = H[(size_t)b * 9 + k];
+        Hsh[k] = h;
+        frob2 += h * h;   // (as icp_fp32ref_kernel sums it)
+    }
+    const double g = mode == 2 ? horn_start_bound(frob2) : gsum[b];
+    double Rd[9], lam;
+    const bool mirror = kabsch_mirror(Hsh, mode == 1);
+    int pth = kabsch_solve(Hsh, g, Nsh, lane, Rd, lam);
+    kabsch_unmirror(Hsh, mirror, Rd);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[(size_t)b * 9 + k] = Rd[k];
+        lamOut[b] = lam;
+        path[b] = pth;
+    }
+}
+
+// (in this file, not in icp.hip: a second caller of the solve there changes how the ICP kernels' registers are allocated)
+hipError_t launch_kabsch_probe(const double *H, const double *gsum, int n, int mode, double *R, double *lam, int32_t *path,
+                               hipStream_t s)
+{
+    hipLaunchKernelGGL(kabsch_probe_kernel, dim3(n), dim3(kWave), 0, s, H, gsum, n, mode, R, lam, path);
+    return hipGetLastError();
 }
 }  // namespace icpflow
 
@@ -555,6 +594,17 @@ int icpflow_selftest_vote_quotient(const float *d_a, int n, float min_v, float m
     if (!d_a || !d_fast || !d_ieee) return fail(ICPFLOW_E_ARG, "icpflow_selftest_vote_quotient: null pointer");
     if (n <= 0) return fail(ICPFLOW_E_ARG, "icpflow_selftest_vote_quotient: n must be positive");
     ICPFLOW_TRY(launch_vote_quotient_probe(d_a, n, min_v, max_v, d_fast, d_ieee, (hipStream_t)stream));
+    return 0;
+}
+
+int icpflow_selftest_kabsch(const double *d_H, const double *d_gsum, int n, int mode, double *d_R, double *d_lam,
+                            int32_t *d_path, icpflow_stream_t stream)
+{
+    if (!d_H || !d_R || !d_lam || !d_path || (mode != 2 && !d_gsum))
+        return fail(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: null pointer");
+    if (n <= 0 || n > (1 << 24)) return fail(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: bad n %d", n);
+    if (mode < 0 || mode > 2) return fail(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: bad mode %d", mode);
+    ICPFLOW_TRY(launch_kabsch_probe(d_H, d_gsum, n, mode, d_R, d_lam, d_path, (hipStream_t)stream));
     return 0;
 }
 

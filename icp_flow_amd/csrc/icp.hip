@@ -2119,29 +2119,10 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
             }
             ICPFLOW_STAMP(5);
             double Rd[9];
-            // allow_reflection (:354-362 with E = I): R = U V^T is the best ORTHOGONAL matrix; for det H < 0 that is the
-            // reflection -R', R' the best proper rotation of -H (sum_ij (-R')_ij H_ij = sum_ij R'_ij (-H)_ij)
-            bool mirror = false;
-            if (p.allowReflection) {
-                const double *h = ksh + 8;
-                mirror = det3(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8]) < 0.0;
-                if (mirror) {
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) ksh[8 + k] = -ksh[8 + k];   // (every lane writes the same values)
-                }
-            }
-            double lam = 0.0;   // trace(E S): the scale's numerator (:364-366)
-            if (!horn_rotation(ksh + 8, ksh[6] + ksh[7], Nsh, lane, Rd, &lam)) {
-                rank1_rotation(ksh + 8, Rd);
-                double f2 = 0.0;   // rank <= 1: the one singular value is the Frobenius norm
-#pragma unroll
-                for (int k = 0; k < 9; ++k) f2 = fma(ksh[8 + k], ksh[8 + k], f2);
-                lam = sqrt(f2);
-            }
-            if (mirror) {
-#pragma unroll
-                for (int k = 0; k < 9; ++k) { Rd[k] = -Rd[k]; ksh[8 + k] = -ksh[8 + k]; }
-            }
+            double lam;   // trace(E S): the scale's numerator (:364-366)
+            const bool mirror = kabsch_mirror(ksh + 8, p.allowReflection);
+            kabsch_solve(ksh + 8, ksh[6] + ksh[7], Nsh, lane, Rd, lam);
+            kabsch_unmirror(ksh + 8, mirror, Rd);
             ICPFLOW_STAMP(6);
 #ifdef ICPFLOW_DEBUG_SOLVE
             if (b == g_dbg_pair && it == itBegin && lane == 0) {
@@ -2163,7 +2144,13 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
             double mR2 = fma(mux[2], Rd[8], fma(mux[1], Rd[5], mux[0] * Rd[2]));
             if constexpr (SCALE) {
                 if (p.estimateScale) {
-                    sd = lam / (ksh[6] > 1e-9 ? ksh[6] : 1e-9);
+                    // trace(E S) as the objective sum_ij R_ij H_ij of the returned R (the rh below): Newton's root is good to
+                    // ~sqrt(eps) only where the top eigenvalue is (nearly) double -- with H ~ 0 (every gated query on one
+                    // target) it stops at gsum/2 (3/4)^40, not at 0
+                    double obj = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) obj = fma(Rd[k], ksh[8 + k], obj);
+                    sd = obj / (ksh[6] > 1e-9 ? ksh[6] : 1e-9);
                     mR0 *= sd; mR1 *= sd; mR2 *= sd;
                 }
             }

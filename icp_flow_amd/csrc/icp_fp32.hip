@@ -162,8 +162,8 @@ __global__ __launch_bounds__(kBlock) void icp_fp32ref_kernel(Fp32Params p)
                 frob2 += (double)h * (double)h;
             }
             double Rd[9];
-            const double bound = 2.0 * 1.7320508075688774 * sqrt(frob2) * (1.0 + 1e-9);   // 2 (s1 + s2 + s3) at most
-            if (!horn_rotation(Hd, bound, Nsh, lane, Rd)) rank1_rotation(Hd, Rd);
+            double lam;
+            kabsch_solve(Hd, horn_start_bound(frob2), Nsh, lane, Rd, lam);
             if (lane == 0) {
                 float Rn[9];
 #pragma unroll

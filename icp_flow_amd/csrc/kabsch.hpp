@@ -102,7 +102,9 @@ static __device__ bool horn_rotation(const double *S, double gsum, double *Nsh, 
     }
     const double n00 = S[0] + S[4] + S[8], n11 = S[0] - S[4] - S[8], n22 = -S[0] + S[4] - S[8], n33 = -S[0] - S[4] + S[8];
     ICPFLOW_STAMP(13);
-    double lam = 0.5 * gsum, prevStep = 1e300;
+    // (a start ON a double top root -- gsum exactly 2 sigma*, Y = X R exactly with rank(H) <= 1 -- sees only the rounding of
+    // the quartic and steps anywhere, to the eigenvector of the smallest root among others: start a little above)
+    double lam = 0.5 * gsum * (1.0 + 1e-6), prevStep = 1e300;
     for (int it = 0; it < 40; ++it) {
         const double x2 = lam * lam;
         const double b = (x2 + c2) * lam;
@@ -216,6 +218,57 @@ static __device__ void rank1_rotation(const double *S, double (&R)[9])
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) R[i * 3 + j] = Rc[j * 3 + i];   // row convention
+}
+
+// allow_reflection (:354-362 with E = I): R = U V^T is the best ORTHOGONAL matrix; for det H < 0 that is the reflection
+// -R', R' the best proper rotation of -H (sum_ij (-R')_ij H_ij = sum_ij R'_ij (-H)_ij).  H (LDS) is negated in place
+// for the solve (every lane writes the same values) and restored by kabsch_unmirror.
+static __device__ __forceinline__ bool kabsch_mirror(double *S, bool allowReflection)
+{
+    bool mirror = false;
+    if (allowReflection) {
+        mirror = det3(S[0], S[1], S[2], S[3], S[4], S[5], S[6], S[7], S[8]) < 0.0;
+        if (mirror) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) S[k] = -S[k];
+        }
+    }
+    return mirror;
+}
+
+static __device__ __forceinline__ void kabsch_unmirror(double *S, bool mirror, double (&R)[9])
+{
+    if (mirror) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { R[k] = -R[k]; S[k] = -S[k]; }
+    }
+}
+
+// The solve of the Kabsch step as the ICP kernels call it (icp.hip, icp_fp32.hip; icpflow_selftest_kabsch runs it alone,
+// mirror included).  gsum: Newton's start, an upper bound of 2 (s1 + s2 + s3).  lam = trace(E S) (:364-366; icp.hip's
+// scale takes sum_ij R_ij H_ij instead, exact where R is): Newton's root on the closed form; on the rank-1 path sum_ij R_ij H_ij of the returned R, which is s1 for
+// rank(H) <= 1 and stays consistent with R where the fallback answers a matrix of higher rank.
+// Returns 0 where the closed form answered, 2 where rank1_rotation did (not 0 / 1: that form changes the register
+// allocation of the ICP kernels, tools/kernel_resources.py).
+static __device__ __forceinline__ int kabsch_solve(const double *S, double gsum, double *Nsh, int lane, double (&R)[9],
+                                                   double &lam)
+{
+    lam = 0.0;
+    const bool ok = horn_rotation(S, gsum, Nsh, lane, R, &lam);
+    if (!ok) {
+        rank1_rotation(S, R);
+        double rh = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) rh = fma(R[k], S[k], rh);
+        lam = rh;
+    }
+    return ok ? 0 : 2;
+}
+
+// Newton's start of the fp32-reference kernel: 2 (s1 + s2 + s3) <= 2 sqrt(3) |H|_F
+static __device__ __forceinline__ double horn_start_bound(double frob2)
+{
+    return 2.0 * 1.7320508075688774 * sqrt(frob2) * (1.0 + 1e-9);
 }
 
 }  // namespace icpflow

@@ -308,6 +308,8 @@ hipError_t launch_eval_epilogue(const double *partial, int qblocks, const int32_
                                 float *rotations, hipStream_t s);
 hipError_t launch_vote_quotient_probe(const float *a, int n, float mn, float mx, float *fast, float *ieee,
                                       hipStream_t s);
+hipError_t launch_kabsch_probe(const double *H, const double *gsum, int n, int mode, double *R, double *lam, int32_t *path,
+                               hipStream_t s);
 hipError_t launch_gather_pad(const float *points, const int32_t *rows, int B, int N, float *out, hipStream_t s);
 hipError_t launch_gather_segments(const float *points, const int64_t *order, const int64_t *seg, const int32_t *perm,
                                   int B, int N, float *out, hipStream_t s);

@@ -647,6 +647,19 @@ int icpflow_selftest_vote_quotient(const float *d_a, int n, float min_v, float m
                                    float *d_ieee, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Diagnostics: the Kabsch solve of the ICP iteration alone (the kernels' own code, csrc/kabsch.hpp
+ * kabsch_mirror / kabsch_solve / kabsch_unmirror), one wave per matrix.  d_H [n][9]: H = sum w x_c y_c^T / W
+ * (row-major, row-vector convention y = x R); d_gsum [n]: Newton's start, an upper bound of 2 (s1 + s2 + s3)
+ * -- what icpflow_icp passes is (sum w |x_c|^2 + sum w |y_c|^2) / W.  mode 0: as icpflow_icp; mode 1: as
+ * icpflow_icp with allow_reflection; mode 2: as the fp32-reference arithmetic, whose start is 2 sqrt(3) |H|_F
+ * (d_gsum unused, may be NULL).  Out: d_R [n][9] (y = x R), d_lam [n]: Newton's root of the closed form, sum_ij R_ij H_ij
+ * on the rank-1 path (icpflow_icp's scale takes sum_ij R_ij H_ij on both), d_path [n]:
+ * 0 = closed form (Horn), 2 = rank-1 fallback (rotation from u to v; R = I for H = 0).
+ * ------------------------------------------------------------------------- */
+int icpflow_selftest_kabsch(const double *d_H, const double *d_gsum, int n, int mode, double *d_R, double *d_lam,
+                            int32_t *d_path, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): per-launch timing of the dominant kernel, the ICP
  * iteration.  A recorder is an object the caller owns: every launch of that kernel made by a call
  * that carries it in its options (up to `capacity` launches) is bracketed by HIP events recorded on
