@@ -523,7 +523,7 @@ __device__ __forceinline__ bool team_collect(const IcpTeam &t, IcpCtrl *ctrl, in
 // HELP (persistent sorted-sweep kernels): role 0 = the pair's owner, role j + 1 = helper in slot j of pair b: it runs pass
 // `passes - 1 - j` of every iteration from the state the owner publishes and hands the pass's moment sums back (see
 // HelpPair in kernels.hpp and icp_kernel).
-template <int BLOCK, int Q, int TS, int GRID, bool TEAM, bool SCALE, bool HELP, bool LATE, bool SHAREK, typename P>
+template <int BLOCK, int Q, int TS, int GRID, bool TEAM, bool SCALE, bool HELP, bool LATE, bool SHAREK, bool WIDE, typename P>
 __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank, const int G, const int itBegin,
                                          const int itEnd, const int role = 0)
 {
@@ -627,7 +627,7 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
     // RESUME: the instantiation that serves the SECOND of two speculative launches (icp_split_kernel) -- a pair resumed at its own
     // iteration finds the states of the cycle detection and its own-convergence bits in its history rows.  (Only there: the code
     // costs the other instantiations registers they do not have.)
-    constexpr bool RESUME = BLOCK == 1024 && GRID == 4 && !TEAM && !SCALE && !HELP && LATE && Q == 1;
+    constexpr bool RESUME = BLOCK == 1024 && GRID == 4 && !TEAM && !SCALE && !HELP && LATE && Q == 1 && WIDE;
     const bool resumed = RESUME && itBegin > 0 && p.history != nullptr;
     if (itBegin == 0 || (resumed && itBegin < kRing)) {
         // state 0: identity (:140) or the caller's init_transform (:118-138)
@@ -871,14 +871,15 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
             const float4 *ys = p.sortY + (size_t)b * p.N;
             const float4 *xs = p.sortX + (size_t)b * p.N;
             const int axis = sweepAxis;   // the pair's sort key (sortdir.hpp): a coordinate (0 .. 2) or a horizontal direction (3 ..)
+            // (without WIDE every key is a coordinate and the key reads below compile to their axis forms)
             float dirX = 0.f, dirY = 0.f;
-            if (axis >= 3) sort_dir(axis, dirX, dirY);
+            if (WIDE && axis >= 3) sort_dir(axis, dirX, dirY);
             // GRID == 4: the sorted fixed cloud is staged into LDS once per launch and every
             // per-iteration access (window search, scan, resolve) stays on chip
             // dynamic LDS: [moment sums per (pass, wave): redPasses x NWAVE x 18 doubles][image][records][own points]
             unsigned char *dyn = dynLds + (size_t)p.redPasses * (NWAVE * kMoments * sizeof(double));
             float *lx = reinterpret_cast<float *>(dyn), *ly = lx + NP16, *lz = ly + NP16;
-            const bool perPass = !TEAM && p.redPasses != 0;
+            const bool perPass = !TEAM && WIDE && p.redPasses != 0;
             double *redDyn = reinterpret_cast<double *>(dynLds);
             // Neighbour certificates.  The search answers one question per query: which target is nearest, and is it
             // inside the gate.  After the first iterations the answer hardly ever changes, and that can be PROVEN
@@ -918,9 +919,13 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
                                             : (axis == 0 ? gx : (axis == 1 ? gy : gz));
             // the key of sorted target j (j < yc.n) and of a point: the coordinate, or the direction's two instructions (sortdir.hpp)
             auto tkey = [&](int j) -> float {
-                return axis >= 3 ? sort_key_dir(dirX, dirY, (GRID == 4 ? lx : gx)[j], (GRID == 4 ? ly : gy)[j]) : keyf[j];
+                return (WIDE && axis >= 3) ? sort_key_dir(dirX, dirY, (GRID == 4 ? lx : gx)[j], (GRID == 4 ? ly : gy)[j]) : keyf[j];
             };
-            auto pkey = [&](float x, float y, float z) -> float { return sort_key_of(axis, dirX, dirY, x, y, z); };
+            auto pkey = [&](float x, float y, float z) -> float {
+                if constexpr (WIDE) return sort_key_of(axis, dirX, dirY, x, y, z);
+                else return axis == 0 ? x : (axis == 1 ? y : z);
+            };
+            auto keySlack = [&](float x, float y, float r) -> float { return WIDE ? sort_key_slack(axis, x, y, r) : 0.f; };
             constexpr int PER = BLOCK * Q;            // a wave owns 64 CONSECUTIVE sorted queries
             const int ngr = (myCount + PER - 1) / PER;
             double fold[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -1163,7 +1168,7 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
 #pragma unroll
                     for (int q = 0; q < Q; ++q) {
                         const float qa = pkey(qx[q], qy[q], qz[q]);
-                        const float qm = recM[q] + sort_key_slack(axis, qx[q], qy[q], recM[q]);   // (a computed key: the window gives its rounding away)
+                        const float qm = recM[q] + keySlack(qx[q], qy[q], recM[q]);   // (a computed key: the window gives its rounding away)
                         if (live[q] && recM[q] >= 0.f) { lo = fminf(lo, qa - qm); hi = fmaxf(hi, qa + qm); }
                     }
                     ICPFLOW_STAMP(11);
@@ -1331,7 +1336,7 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
                             const float kHi = (bEnd < np16 && bEnd <= yc.n) ? tkey(bEnd - 1) : kInf;   // (beyond the last target: nothing is left on that side)
                             const float rL = qa - kLo, rR = kHi - qa;
                             rho = fminf(rL, rR);
-                            rho = (rho - sort_key_slack(axis, sx, sy, rho)) * 0.9999f - 1e-6f;
+                            rho = (rho - keySlack(sx, sy, rho)) * 0.9999f - 1e-6f;
                             const bool nn = rho > 0.f && rho * rho > rowbest * 1.000003f;
                             const bool out = !(rowbest <= p.thr2) && rho > gateOut;
                             if (!done) {
@@ -1426,7 +1431,7 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
                                 const float kHi = (bEnd < np16 && bEnd <= yc.n) ? tkey(bEnd - 1) : kInf;   // (beyond the last target: nothing is left on that side)
                                 const float rL = qa - kLo, rR = kHi - qa;
                                 rho = fminf(rL, rR);
-                                rho = (rho - sort_key_slack(axis, sx, sy, rho)) * 0.9999f - 1e-6f;
+                                rho = (rho - keySlack(sx, sy, rho)) * 0.9999f - 1e-6f;
                                 const bool nn = rho > 0.f && rho * rho > rowbest * 1.000003f;
                                 const bool out = !(rowbest <= p.thr2) && rho > gateOut;
                                 if (!done) {
@@ -1546,7 +1551,7 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
                     // outside the window differ by more than this query's half-window along the sort axis (the window
                     // bounds qa -+ m are rounded: 4 ulp of head-room, and 0.1 % on the half-width)
                     const float qa = pkey(qx[q], qy[q], qz[q]);
-                    const float cap = recM[q] * 0.999f - fabsf(qa) * 2.4e-7f - sort_key_slack(axis, qx[q], qy[q], recM[q]);
+                    const float cap = recM[q] * 0.999f - fabsf(qa) * 2.4e-7f - keySlack(qx[q], qy[q], recM[q]);
                     newL[q] = fmaxf(fminf(__builtin_amdgcn_sqrtf(second[q]), cap), 0.f);
                     if (!(acc.best[q] < kInf)) certJ[q] = -1;
                 }
@@ -2062,7 +2067,7 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
                 // all NWAVE loads in flight at once (left to itself the compiler alternates load, wait, add: NWAVE / 2
                 // dependent LDS round trips in the serial tail); the sum itself stays in wave order
                 // (sums per (pass, wave) in dynamic LDS: pass after pass, the same way; a single pass is the static case)
-                const bool perPassT = GRID == 4 && !TEAM && p.redPasses != 0;
+                const bool perPassT = GRID == 4 && !TEAM && WIDE && p.redPasses != 0;
                 const int passes = perPassT ? (xc.n + BLOCK * Q - 1) / (BLOCK * Q) : 1;
                 const double *src = perPassT ? reinterpret_cast<const double *>(dynLds) : red;
                 for (int gp = 0; gp < passes; ++gp) {
@@ -2266,7 +2271,11 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
 // the 512 slots are occupied.  A ticket has no such order.
 // (PERSIST is a template parameter: the loop keeps more scalar state alive than the one-pair kernel, whose register
 // allocation at 128 VGPRs must not move -- it is the kernel of batches that fit the GPU, config 2 among them.)
-template <int BLOCK, int Q, int TS, int GRID, bool TEAM, bool SCALE = false, bool PERSIST = false, bool HELPK = false>
+// WIDE = false (sorted sweep, one workgroup per pair, chosen by launch_icp_variant): the narrow form of a launch -- every pair's
+// sort key is a coordinate (launch_icp's dirKeys), the moment sums are one running total per lane (p.redPasses == 0) and no pair is
+// resumed (RESUME, pairList).  The code of the general form costs the 1024-thread kernel of config 2, which never needs it,
+// 4 KB of code and 20 spilled scalar registers (profiles/r07_kernel_resources.txt).
+template <int BLOCK, int Q, int TS, int GRID, bool TEAM, bool SCALE = false, bool PERSIST = false, bool HELPK = false, bool WIDE = true>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu((BLOCK == 512 && GRID == 4) ? 4 : 1)))
 void icp_kernel(IcpParams p, int itBegin, int itEnd)
 {
@@ -2278,7 +2287,7 @@ void icp_kernel(IcpParams p, int itBegin, int itEnd)
         G = p.team.teamSize[b];
         // a chain of single-pass pairs (icp_team_plan_kernel): one after the other, like the tickets of a persistent grid
         for (;;) {
-            icp_pair<BLOCK, Q, TS, GRID, TEAM, SCALE, false, true, HELPK>(p, b, rank, G, itBegin, itEnd);   // (teams: HELPK marks the instantiation with shared window scans)
+            icp_pair<BLOCK, Q, TS, GRID, TEAM, SCALE, false, true, HELPK, WIDE>(p, b, rank, G, itBegin, itEnd);   // (teams: HELPK marks the instantiation with shared window scans)
             b = __builtin_amdgcn_readfirstlane(p.team.next[b]);
             if (b < 0) return;
             __syncthreads();                 // the pair's last reads of the static LDS state are done
@@ -2290,7 +2299,7 @@ void icp_kernel(IcpParams p, int itBegin, int itEnd)
         // of iterations -- late bookkeeping.  512-thread workgroups share their CUs (two per CU: batches of two pairs per CU
         // and more), like the persistent grids below: one pair's bookkeeping already runs under another pair's search.
         int itB = itBegin;
-        if constexpr (BLOCK == 1024 && GRID == 4 && !TEAM && !SCALE && Q == 1) {
+        if constexpr (BLOCK == 1024 && GRID == 4 && !TEAM && !SCALE && Q == 1 && WIDE) {
             // the second of two launches (icp_split_kernel): workgroup w serves pair pairList[w] from the iteration IT had reached
             if (p.pairList != nullptr) {
                 if ((int)blockIdx.x >= p.pairMeta[0]) return;
@@ -2298,7 +2307,7 @@ void icp_kernel(IcpParams p, int itBegin, int itEnd)
                 itB = __builtin_amdgcn_readfirstlane(p.state[b].iters);
             }
         }
-        icp_pair<BLOCK, Q, TS, GRID, TEAM, SCALE, false, BLOCK != 512, false>(p, b, rank, G, itB, itEnd);
+        icp_pair<BLOCK, Q, TS, GRID, TEAM, SCALE, false, BLOCK != 512, false, WIDE>(p, b, rank, G, itB, itEnd);
     } else {
         static_assert(!PERSIST || !TEAM, "teams are planned per launch");
         constexpr bool HELP = HELPK && GRID == 4 && !SCALE && Q == 1;
@@ -2311,7 +2320,7 @@ void icp_kernel(IcpParams p, int itBegin, int itEnd)
         int role = 0;
         for (;;) {
             asm volatile("" : "+s"(pp));
-            icp_pair<BLOCK, Q, TS, GRID, TEAM, SCALE, HELP, false, false>(*pp, b, rank, G, itBegin, itEnd, role);
+            icp_pair<BLOCK, Q, TS, GRID, TEAM, SCALE, HELP, false, false, WIDE>(*pp, b, rank, G, itBegin, itEnd, role);
             __syncthreads();                     // the pair's last reads of the static LDS state are done
             if (threadIdx.x < kWave) {
                 int nb = -1, nr = 0;
@@ -2735,11 +2744,13 @@ __global__ __launch_bounds__(1024) void icp_split_kernel(const IcpCtrl *__restri
 }
 
 template <int BLOCK, int Q, int TS, int GRID, bool TEAM = false, bool SCALE = false>
-static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd, hipStream_t s)
+// dirKeys: some pair of the launch may have a direction key (a code >= 3, sortdir.hpp) -- false: every key is a coordinate,
+// which the narrow instantiation below needs.  (A host-side argument: the kernels' parameter block stays as it is.)
+static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd, hipStream_t s, bool dirKeys = true)
 {
     if constexpr (GRID >= 3 && !SCALE) {   // similarity transforms: the sweep kernels' SCALE instantiation
         if (p.estimateScale != 0 || p.initS != nullptr) {
-            launch_icp_variant<BLOCK, Q, TS, GRID, TEAM, true>(p, B, itBegin, itEnd, s);
+            launch_icp_variant<BLOCK, Q, TS, GRID, TEAM, true>(p, B, itBegin, itEnd, s, dirKeys);
             return;
         }
     }
@@ -2839,6 +2850,20 @@ static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd
                 hipLaunchKernelGGL(kern, dim3((int)cap), dim3(BLOCK), dyn, s, q, itBegin, itEnd);
                 return;
             }
+        }
+    }
+    if constexpr (GRID == 4 && !TEAM && !SCALE) {
+        // No pair of the launch can have a direction key (clouds below kSortDirMinN, or the option off) and the sums are one
+        // running total (a single pass, or no helpers' order to follow): the narrow instantiation (icp_kernel, WIDE) --
+        // config 2's kernel.  (Its pairList is NULL: only the second of two launches, kern2 above, has one.)
+        if (!dirKeys && q.redPasses == 0) {
+            constexpr auto kernA = &icp_kernel<BLOCK, Q, TS, GRID, false, false, false, false, false>;
+            if (dyn > 48 * 1024) {
+                static std::atomic<unsigned long long> raisedA{0ull};
+                ensure_dynamic_lds(reinterpret_cast<const void *>(kernA), 156 * 1024, &raisedA);
+            }
+            hipLaunchKernelGGL(kernA, dim3(B), dim3(BLOCK), dyn, s, q, itBegin, itEnd);
+            return;
         }
     }
     if (dyn > 48 * 1024) {   // above the default dynamic-LDS limit: opt in once per instantiation and device
@@ -3029,7 +3054,7 @@ void ensure_dynamic_lds(const void *func, int bytes, std::atomic<unsigned long l
     if (dev < 64) mask->fetch_or(bit, std::memory_order_release);
 }
 
-static void launch_icp_iters(const IcpParams &p, int B, int itBegin, int itEnd, LaunchProfile *prof, hipStream_t s)
+static void launch_icp_iters(const IcpParams &p, bool dirKeys, int B, int itBegin, int itEnd, LaunchProfile *prof, hipStream_t s)
 {
     const bool timed = prof != nullptr && prof->used < (int)prof->start.size();
     if (timed) (void)hipEventRecord(prof->start[prof->used], s);
@@ -3039,8 +3064,8 @@ static void launch_icp_iters(const IcpParams &p, int B, int itBegin, int itEnd, 
         // clouds longer than the workgroup take several passes.  GRID 4 keeps the sorted fixed cloud
         // in LDS (12 B/point, up to 144 KiB of the CU's 160 KiB at N = 12288); beyond that GRID 3
         // streams it through scalar loads (no LDS image, any N the sort can handle).
-        if (p.N <= 256) launch_icp_variant<256, 1, 1, 4>(p, B, itBegin, itEnd, s);
-        else if (p.N <= 512) launch_icp_variant<512, 1, 1, 4>(p, B, itBegin, itEnd, s);
+        if (p.N <= 256) launch_icp_variant<256, 1, 1, 4>(p, B, itBegin, itEnd, s, dirKeys);
+        else if (p.N <= 512) launch_icp_variant<512, 1, 1, 4>(p, B, itBegin, itEnd, s, dirKeys);
         else if (p.team.wgPair != nullptr) {   // several workgroups per large pair (N > 1024)
             // The members of a team wait for each other inside the launch.  Two team launches in flight at once (the
             // same host thread registering on several streams: hist_icp_many, frame pairs in flight) could each hold
@@ -3088,11 +3113,11 @@ static void launch_icp_iters(const IcpParams &p, int B, int itBegin, int itEnd, 
         }
         // 1024 threads (4 waves per SIMD, 128 VGPRs: the kernel fits but for three pointers spilled once
         // outside the loop) take a 1024-point cloud in one pass; up to 768 points 12 waves (170 VGPRs) do
-        else if (p.N <= 768) launch_icp_variant<768, 1, 1, 4>(p, B, itBegin, itEnd, s);
+        else if (p.N <= 768) launch_icp_variant<768, 1, 1, 4>(p, B, itBegin, itEnd, s, dirKeys);
         // batches larger than the GPU, clouds whose image and records fit half a CU's LDS: two 512-thread workgroups
         // per CU, so that one pair's serial tail (one wave) runs under the other pair's search phase
-        else if (p.halfCu) launch_icp_variant<512, 1, 1, 4>(p, B, itBegin, itEnd, s);
-        else if (p.N <= 12288) launch_icp_variant<1024, 1, 1, 4>(p, B, itBegin, itEnd, s);
+        else if (p.halfCu) launch_icp_variant<512, 1, 1, 4>(p, B, itBegin, itEnd, s, dirKeys);
+        else if (p.N <= 12288) launch_icp_variant<1024, 1, 1, 4>(p, B, itBegin, itEnd, s, dirKeys);
         else launch_icp_variant<768, 1, 1, 3>(p, B, itBegin, itEnd, s);   // (the scalar-load sweep spills at 1024 threads)
     } else if (p.gridPts != nullptr) {  // exact grid search; grid in LDS while it fits 48 KiB (N <= 2048)
         if (p.N <= 256) launch_icp_variant<256, 1, 1, 2>(p, B, itBegin, itEnd, s);
@@ -3164,6 +3189,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
                                   opts.fp32Scratch, s);
     }
     IcpParams p{};
+    bool dirKeys = true;   // some pair may have a direction key (set with the sorted sweep below; launch_icp_variant)
     p.B = B;
     p.X = X; p.Y = Y; p.lenX = lenX; p.lenY = lenY; p.swap = swap; p.prePose = prePose; p.N = N;
     p.thr2 = (float)(thres * thres);
@@ -3182,6 +3208,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
         // the scoring sweep of this batch left both clouds sorted along the fixed cloud's longest axis;
         // a translation-only pre-pose (hist_icp) keeps that order
         p.sortX = (const float4 *)grid->sortX; p.sortY = (const float4 *)grid->pts; p.sortAxis = grid->axis;
+        dirKeys = N >= kSortDirMinN;   // (sorted by an earlier call, whose options chose the keys: any code a cloud this long may have)
         p.sortYsoa = grid->sortYsoa;
         p.sweepMargin = (float)(1.01 * thres);
 #ifdef ICPFLOW_CERT_STATS
@@ -3203,6 +3230,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
                            swap, prePose, N, NP2, grid->axis, (float4 *)grid->sortX, (float4 *)grid->pts, grid->sortYsoa,
                            (float *)nullptr, 0, grid->dirKeys);
         p.sortX = (const float4 *)grid->sortX; p.sortY = (const float4 *)grid->pts; p.sortAxis = grid->axis;
+        dirKeys = grid->dirKeys && N >= kSortDirMinN;   // (the sort above chooses a direction only for such clouds, sortdir.hpp)
         p.sortYsoa = grid->sortYsoa;
         p.sweepMargin = (float)(1.01 * thres);
         recWanted = opts.adaptiveWindows;
@@ -3276,7 +3304,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
             p.splitScratch = opts.splitScratch;
             p.help = opts.help;
             p.helpOn = (opts.helpers && maxIter <= kHelpMaxEpoch - 2) ? 1 : 0;   // (always: maxIter <= kHistIters here)
-            launch_icp_iters(p, B, 0, maxIter, opts.profile, s);
+            launch_icp_iters(p, dirKeys, B, 0, maxIter, opts.profile, s);
             if (opts.historyPending != nullptr) {
                 *opts.historyPending = true;   // the consumers read the history themselves (posefuse.hpp)
             } else {
@@ -3284,7 +3312,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
                 if (e != hipSuccess) return e;
             }
         } else {
-            for (int it = 0; it < maxIter; ++it) launch_icp_iters(p, B, it, it + 1, opts.profile, s);
+            for (int it = 0; it < maxIter; ++it) launch_icp_iters(p, dirKeys, B, it, it + 1, opts.profile, s);
         }
     } else {
         p.persistent = opts.persistent ? 1 : 0;
@@ -3294,7 +3322,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
         // kMaxIterCap iterations in one go, and an epoch past 255 would spill into the workgroup / pair bits.  The
         // batch-global rule never gets there (one launch covers <= kHistIters = 128 iterations).
         p.helpOn = (opts.helpers && maxIter <= kHelpMaxEpoch - 2) ? 1 : 0;
-        launch_icp_iters(p, B, 0, maxIter, opts.profile, s);
+        launch_icp_iters(p, dirKeys, B, 0, maxIter, opts.profile, s);
     }
     return hipGetLastError();
 }

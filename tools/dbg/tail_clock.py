@@ -1,6 +1,7 @@
 """Developer tool (library built with -DICPFLOW_TAIL_CLOCK): per pair of BASELINE config 2, the shader clocks wave 0 spent
 in the serial tail (block barrier -> (R, T) published) and in the rest of the iteration loop, two clock reads per iteration.
-SPLIT=1 with a library built with -DICPFLOW_TAIL_CLOCK -DICPFLOW_TAIL_SPLIT: the tail of one sliding pair phase by phase."""
+SPLIT=1 with a library built with -DICPFLOW_TAIL_CLOCK -DICPFLOW_TAIL_SPLIT: the tail of one sliding pair phase by phase
+(the third slowest, or PAIR=b)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -30,7 +31,7 @@ _lib._L.icpflow_debug_tail_split(sp)
 w = np.array(sp[:], dtype=np.int64).reshape(1024, 16)[:B]
 names = {1: "top of loop -> queries loaded", 11: "certificates + probes", 12: "window", 2: "scan", 10: "resolve + records", 3: "moments", 4: "block barrier", 5: "totals + H", 13: "quartic coefficients",
          14: "newton", 6: "adjugate + rotation", 15: "T, rmse", 9: "history + tally + stop check", 7: "cycle detection + publish", 8: "loop exit"}
-b = int(order[2])
+b = int(os.environ.get("PAIR", order[2]))   # (PAIR=...: the same pair in the splits of two builds)
 print(f"pair {b}: clocks per iteration between the stamps of thread 0 (each stamp costs a clock read + an LDS update)")
 for k in (1, 11, 12, 2, 10, 3, 4, 5, 13, 14, 6, 15, 9, 7):
     print(f"   {names[k]:34s} {w[b, k] / max(v[b, 2], 1):8.0f}")
