@@ -160,3 +160,37 @@ def test_per_call_buffers_are_not_inherited_by_nested_option_blocks():
             assert inner["search"] == 2 and inner["flags"] & _lib.OPT_FLAGS["no_teams"] and inner["flags"] & _lib.OPT_FLAGS["no_score_prune"]
             assert inner["vote_bins"] is None and inner["icp_history"] is None and inner["icp_scale"] is None and inner["icp_init"] is None
         assert _lib._current()[-1]["vote_bins"] is marker
+
+
+def test_workspace_sizes_are_aligned_and_never_shrink_with_the_batch():
+    """icpflow_workspace_bytes and its four siblings over the shapes of tests/test_gpu_workspace_contract.py: multiples of
+    256 bytes, non-decreasing in B and in the histogram's Lx * Ly * Lz (in n / M / Lmax for the clustering carves) -- a carve
+    edit that makes a size shrink with a larger batch is caught without a GPU."""
+    from icp_flow_amd import _lib
+    L = _lib._L
+    Bs = [1, 2, 7, 12, 16, 48, 128, 255, 256, 257, 600, 700, 701, 900, 1024, 32767, 32768]
+    Ns = [1, 40, 63, 64, 1024, 1025, 1100, 2047, 2048, 4000, 4096, 4097, 10000, 16384, 16385, 16500]
+    hists = [(0, 0, 0), (5, 1, 1), (41, 41, 3), (135, 135, 3), (269, 269, 3)]
+    for N in Ns:
+        for lens in hists:
+            sizes = [L.icpflow_workspace_bytes(B, N, *lens) for B in Bs if B * N <= 1 << 30]
+            assert all(s > 0 and s % 256 == 0 for s in sizes), (N, lens, sizes)
+            assert sizes == sorted(sizes), (N, lens, sizes)
+        for B in (1, 256, 1024):
+            sizes = [L.icpflow_workspace_bytes(B, N, *lens) for lens in hists]
+            assert sizes == sorted(sizes), (B, N, sizes)
+    ns = [1, 2, 63, 64, 65, 300, 3000, 9000, 63276, 126598]
+    for fn in (L.icpflow_dbscan_workspace_bytes, L.icpflow_hdbscan_mst_workspace_bytes):
+        # (rocprim sizes the scratch of its longer sorts from the device's properties: without a device those queries answer 0)
+        sizes = [fn(n) for n in ns]
+        assert all(s > 0 for s in sizes[:6]), (fn.__name__, sizes)
+        sizes = [s for s in sizes if s > 0 or torch.cuda.is_available()]
+        assert all(s > 0 and s % 256 == 0 for s in sizes) and sizes == sorted(sizes), (fn.__name__, sizes)
+    for rows in (1, 512, 4096):
+        one = [L.icpflow_cluster_table_workspace_bytes(n, rows) for n in ns]
+        two = [L.icpflow_cluster_table_pair_workspace_bytes(n, n, rows) for n in ns]
+        assert all(s > 0 and s % 256 == 0 for s in one + two) and one == sorted(one) and two == sorted(two), (rows, one, two)
+        assert all(b >= a for a, b in zip(one, two))
+    for n in ns:
+        by_rows = [L.icpflow_cluster_table_pair_workspace_bytes(n, 5, rows) for rows in (1, 512, 4096)]
+        assert by_rows == sorted(by_rows), (n, by_rows)
