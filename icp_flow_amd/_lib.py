@@ -73,6 +73,18 @@ SIGNATURES = {
     "icpflow_hdbscan_mst_workspace_bytes": (_sz, [_i]),
     "icpflow_hdbscan_mst": (_i, [_p, _i, _p, _i, _i, _d, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_hdbscan_labels": (_i, [_p, _p, _p, _i, _i, _p]),
+    "icpflow_ego_default_params": (_i, [_p]),
+    "icpflow_ego_state_bytes": (_sz, [_p]),
+    "icpflow_ego_create": (_i, [_p, _p, _sz, _p, ctypes.POINTER(_p)]),
+    "icpflow_ego_destroy": (_i, [_p]),
+    "icpflow_ego_reset": (_i, [_p, _p]),
+    "icpflow_ego_register_frame": (_i, [_p, _p, _i, _p, _p]),
+    "icpflow_ego_poses": (_i, [_p, _p, _i, ctypes.POINTER(_i)]),
+    "icpflow_ego_frame_info": (_i, [_p, _p]),
+    "icpflow_ego_downsample": (_i, [_p, _p, _i, _p, _p, _p, _p]),
+    "icpflow_ego_register_step": (_i, [_p, _p, _i, _p, _d, _p, _p]),
+    "icpflow_ego_map_add": (_i, [_p, _p, _i, _p, _p]),
+    "icpflow_ego_map_export": (_i, [_p, _p, _p, _p, _i, _p, _p]),
     "icpflow_selftest_vote_quotient": (_i, [_p, _i, _f, _f, _p, _p, _p]),
     "icpflow_selftest_kabsch": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
     "icpflow_profile_create": (_i, [_i, ctypes.POINTER(_p)]),
@@ -173,6 +185,23 @@ class FrameParams(ctypes.Structure):
     _fields_ = [("struct_size", _sz), ("seed", ctypes.c_uint64), ("generator", _p), ("max_points", _i), ("min_cluster_size", _i),
                 ("translation_frame", _f), ("thres_box", _f), ("thres_iou", _f), ("rot_limit_deg", _f), ("thres_error", _f),
                 ("tight_padding", _i), ("superset_width", _i)]
+
+
+class EgoParams(ctypes.Structure):
+    """icpflow_ego_params_t: the constants of the ego-motion estimate (config_kiss_icp.yaml) and the state's capacities."""
+    _fields_ = [("struct_size", _sz), ("max_range", _d), ("min_range", _d), ("voxel_size", _d), ("min_motion_th", _d),
+                ("initial_threshold", _d), ("convergence", _d), ("max_points_per_voxel", _i), ("max_iterations", _i),
+                ("max_points", _i), ("map_capacity", _i)]
+
+    @staticmethod
+    def defaults(**over):
+        p = EgoParams()
+        call("icpflow_ego_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise TypeError(f"icpflow_ego_params_t has no field {k!r}")
+            setattr(p, k, v)
+        return p
 
 
 class Profile:

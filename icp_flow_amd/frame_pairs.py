@@ -150,7 +150,28 @@ def _pose_file(path):
     return None
 
 
-POSE_SOURCES = ("auto", "pose_file", "ego_motion", "ego_motion_gt")
+def _estimate_poses(path, raw, t, args):
+    """pose_source="estimate": the ego poses of the sample's frames from its raw points (every point of a frame, before any
+    crop of the scene: the reference estimates on the whole sweep, dataset_pca.py:126-130)."""
+    from . import utils_ego_motion
+    if len(t) == 0 or t.min() < 0:
+        raise ValueError(f"{path}: time_indice does not describe a sequence")
+    frames = [raw[t == j].astype(np.float32) for j in range(int(t.max()) + 1)]
+    poses = utils_ego_motion.estimate_poses(frames, args, getattr(args, "ego_device", None) if args is not None else None)
+    if args is not None and getattr(args, "save_poses", False):
+        parts = os.path.normpath(os.path.abspath(path)).split(os.sep)
+        for k in range(len(parts) - 2, -1, -1):
+            if parts[k] in ("train", "val", "test"):
+                side = os.sep.join(parts[:k] + [parts[k] + "_pose"] + parts[k + 1:])
+                os.makedirs(os.path.dirname(side), exist_ok=True)
+                np.savez(side, ego_motion=poses)
+                break
+        else:
+            raise ValueError(f"{path}: save_poses needs a split directory (train / val / test) to put <split>_pose next to")
+    return poses
+
+
+POSE_SOURCES = ("auto", "pose_file", "ego_motion", "ego_motion_gt", "estimate")
 
 
 def load_sequence(path, args=None, pose_source=None):
@@ -162,10 +183,13 @@ def load_sequence(path, args=None, pose_source=None):
     the scene like dataset_pca.py:61-64.
 
     Ego poses (`pose_source`, default args.pose_source or "auto"): the reference reads ESTIMATED poses from its
-    <split>_pose files (key `ego_motion`, dataset_pca.py:118-125) and estimates them itself (KISS-ICP, out of scope here)
+    <split>_pose files (key `ego_motion`, dataset_pca.py:118-125) and estimates them itself (KISS-ICP, dataset_pca.py:126-135)
     when the file is missing.  "pose_file": that file, an error without it; "ego_motion": the key of that name in the
     sample itself; "ego_motion_gt": the GROUND-TRUTH poses of the sample -- accuracy measured with them is not the
-    reference's protocol; "auto": pose file, else in-file `ego_motion`, else `ego_motion_gt` WITH a warning.  Every
+    reference's protocol; "auto": pose file, else in-file `ego_motion`, else `ego_motion_gt` WITH a warning;
+    "estimate" (explicit only, "auto" never picks it; needs a GPU): the poses are estimated from the sample's raw points,
+    frame by frame, by utils_ego_motion (scan-to-map odometry on the GPU; constants: args.ego_config), and written to the
+    <split>_pose file only when args.save_poses is set (as the reference does, dataset_pca.py:131-135).  Every
     frame pair records where its pose came from (`FramePair.pose_source`, carried into run_stream's results)."""
     import warnings
     source = pose_source or (getattr(args, "pose_source", None) if args is not None else None) or "auto"
@@ -180,6 +204,8 @@ def load_sequence(path, args=None, pose_source=None):
             with np.load(side) as zp:
                 poses = np.asarray(zp["ego_motion"]).astype(np.float64)
             used = "pose_file"
+        elif source == "estimate":
+            poses, used = _estimate_poses(path, raw, t, args), "estimate"
         elif source == "pose_file":
             raise FileNotFoundError(f"{path}: no <split>_pose file next to the split directory (pose_source='pose_file')")
         elif source in ("auto", "ego_motion") and "ego_motion" in keys:
@@ -778,6 +804,9 @@ def main(argv=None):
     for k, v in DEFAULT_ARGS.items():
         kind = str if k == "cluster" else flag if isinstance(v, bool) else float if isinstance(v, float) or v is None else type(v)
         ap.add_argument("--" + k.replace("_", "-"), type=kind, default=v)
+    ap.add_argument("--pose-source", choices=POSE_SOURCES, default=None,
+                    help="ego poses of sequence files (default auto; estimate = scan-to-map odometry on the GPU)")
+    ap.add_argument("--save-poses", action="store_true", help="with --pose-source estimate: write the <split>_pose files")
     ns = ap.parse_args(argv)
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -790,6 +819,7 @@ def main(argv=None):
     args = SimpleNamespace(**{k: getattr(ns, k) for k in DEFAULT_ARGS})
     args.max_points, args.min_cluster_size, args.chunk_size = int(args.max_points), int(args.min_cluster_size), int(args.chunk_size)
     args.num_clusters = int(args.num_clusters)
+    args.pose_source, args.save_poses = ns.pose_source, ns.save_poses
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         print(json.dumps(summary))

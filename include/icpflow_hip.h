@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 214 /* (icpflow_ego_*, the ego-motion estimate, is an addition under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -636,6 +636,83 @@ int icpflow_hdbscan_mst(const float *d_points, int stride, const uint8_t *d_mask
  * Returns ICPFLOW_E_ARG when the edges do not span the points or min_cluster_size < 2. */
 int icpflow_hdbscan_labels(const int32_t *h_edge_a, const int32_t *h_edge_b, const double *h_edge_w,
                            int n_points, int min_cluster_size, int32_t *h_labels);
+
+/* ---------------------------------------------------------------------------
+ * 8(f)  ego motion of a LiDAR sequence that comes without poses: scan-to-map odometry resident on the GPU.
+ * Replaces: `egomotion` -- utils_ego_motion.py:21-111 with config_kiss_icp.yaml (the reference hands every frame to the
+ * third-party kiss_icp package, dataset_pca.py:115-135; this is that METHOD as published, not the package's bits, and
+ * deskewing -- off in the reference's configuration -- is not built).  Poses are float64 [4,4] row-major, column-vector
+ * convention (x' = R x + t); poses[j] maps frame j into frame 0's coordinates.
+ *
+ * Per frame (float32 [n,3] in the sensor's coordinates):
+ *   1. crop          min_range^2 < x*x + y*y + z*z < max_range^2, evaluated in fp64
+ *   2. down-sample   voxel of a coordinate = floor(x / size) in fp64; the point kept in a voxel is the one with the LOWEST
+ *                    input index; `frame_ds`: size 0.5 v on the cropped frame, `source`: size 1.5 v on frame_ds
+ *                    (v = voxel_size, 0 = max_range / 100); both lists are in ascending input index
+ *   3. threshold     sigma = initial_threshold until the sensor has moved more than 5 min_motion_th from frame 0, then
+ *                    sqrt(sse / count) over the model deviations of step 6
+ *   4. guess         last_pose * inv(pose[-2]) * pose[-1], identity motion with fewer than two poses
+ *   5. registration  of `source` against the map, at most max_iterations Gauss-Newton steps in ONE launch (device-side stop):
+ *                    x = T p; correspondence q = the closest map point (fp64 squared distance, first minimum in the order
+ *                    voxel offset (dx, dy, dz ascending, dz fastest), then insertion order) among the 27 map voxels around
+ *                    floor(x / v), kept if |x - q|^2 < (3 sigma)^2; weight w = (k / (k + |r|^2))^2, k = sigma / 3, r = x - q;
+ *                    J = [I | -[x]_x]; (sum w J^T J) dx = -sum w J^T r in fp64, sums in a fixed order; T <- exp(dx) T;
+ *                    stop when |dx| < convergence.  Fewer than 3 correspondences, or a dx that is not finite: the loop stops
+ *                    without a step.  With an empty map the result is the guess, 0 iterations.
+ *   6. bookkeeping   deviation D = inv(guess) new_pose adds (|t_D| + 2 max_range sin(theta_D / 2))^2 to sse when that error
+ *                    exceeds min_motion_th; frame_ds moved by the new pose (fp64, ((R0 x + R1 y) + R2 z) + t, rounded to
+ *                    float32) is added to the map -- voxel size v, at most max_points_per_voxel points per voxel, in input
+ *                    order -- and map voxels whose FIRST point is farther than max_range from the new position are dropped.
+ *
+ * Memory: everything on the device lives in ONE caller-owned buffer of icpflow_ego_state_bytes(params) bytes handed to
+ * icpflow_ego_create (the map: two open-addressing tables of map_capacity slots that swap at every prune; the scratch of
+ * a frame of at most max_points points).  A frame that does not fit (n > max_points, a table full) is ICPFLOW_E_LIMIT.
+ * A state object must not be used by two host threads at once; distinct objects on distinct streams are independent.
+ *
+ * icpflow_ego_register_frame: steps 1-6, enqueued on `stream` without a host round trip per iteration; BLOCKING at its
+ *   end (one read-back per frame: the pose, which the host needs for steps 3, 4 and 6 of the next frame).  h_pose_out
+ *   float64 [16].  icpflow_ego_poses: the poses so far.  icpflow_ego_frame_info: float64 [8] of the last frame
+ *   (points kept by the crop and frame_ds, points of source, iterations, final |dx|, correspondences of the last
+ *   iteration, sigma, live map voxels, 0).
+ * The pieces, each asynchronous on `stream`, none touching the odometry (poses, sse); what register_frame chains:
+ *   icpflow_ego_downsample   steps 1-2: d_idx_ds / d_idx_source int32 [n] (rows of d_points), d_counts int32 [2]
+ *   icpflow_ego_register_step  step 5 alone, stateless: d_source float32 [m,3], h_guess float64 [16], sigma ->
+ *                            d_result float64 [20]: pose [16], iterations, final |dx|, correspondences, 0
+ *   icpflow_ego_map_add      the map half of step 6 for d_points float32 [n,3] (a frame_ds) under h_pose float64 [16]
+ *   icpflow_ego_map_export   the live voxels, unordered: d_keys int64 [capacity] ((ix + 2^20) << 42 | (iy + 2^20) << 21 |
+ *                            (iz + 2^20)), d_counts int32 [capacity], d_points float32 [capacity, max_points_per_voxel, 3];
+ *                            d_num int32 [1] = number of live voxels (may exceed capacity: the rest was not written)
+ * ------------------------------------------------------------------------- */
+typedef struct icpflow_ego icpflow_ego_t; /* opaque */
+typedef struct icpflow_ego_params {
+    size_t struct_size;       /* sizeof(icpflow_ego_params_t) */
+    double max_range;         /* 100.0  (config_kiss_icp.yaml data.max_range) */
+    double min_range;         /* 1.0    (the reference's setting of data.min_range) */
+    double voxel_size;        /* 0 = max_range / 100 (mapping.voxel_size) */
+    double min_motion_th;     /* 0.1    (adaptive_threshold.min_motion_th) */
+    double initial_threshold; /* 10.0   (adaptive_threshold.initial_threshold; the reference's setting) */
+    double convergence;       /* 1e-4   (registration.convergence_criterion) */
+    int max_points_per_voxel; /* 20, at most 20 (mapping.max_points_per_voxel) */
+    int max_iterations;       /* 500    (registration.max_num_iterations) */
+    int max_points;           /* capacity: points of one frame */
+    int map_capacity;         /* capacity: slots of each map table, a power of two >= 1024; at most half may be live */
+} icpflow_ego_params_t;
+int icpflow_ego_default_params(icpflow_ego_params_t *params);
+size_t icpflow_ego_state_bytes(const icpflow_ego_params_t *params);
+int icpflow_ego_create(const icpflow_ego_params_t *params, void *d_mem, size_t mem_bytes, icpflow_stream_t stream,
+                       icpflow_ego_t **out);
+int icpflow_ego_destroy(icpflow_ego_t *ego);
+int icpflow_ego_reset(icpflow_ego_t *ego, icpflow_stream_t stream);
+int icpflow_ego_register_frame(icpflow_ego_t *ego, const float *d_points, int n, double *h_pose_out, icpflow_stream_t stream);
+int icpflow_ego_poses(const icpflow_ego_t *ego, double *h_poses, int capacity, int *h_count);
+int icpflow_ego_frame_info(const icpflow_ego_t *ego, double *h_info);
+int icpflow_ego_downsample(icpflow_ego_t *ego, const float *d_points, int n, int32_t *d_idx_ds, int32_t *d_idx_source,
+                           int32_t *d_counts, icpflow_stream_t stream);
+int icpflow_ego_register_step(icpflow_ego_t *ego, const float *d_source, int m, const double *h_guess, double sigma,
+                              double *d_result, icpflow_stream_t stream);
+int icpflow_ego_map_add(icpflow_ego_t *ego, const float *d_points, int n, const double *h_pose, icpflow_stream_t stream);
+int icpflow_ego_map_export(icpflow_ego_t *ego, int64_t *d_keys, int32_t *d_counts, float *d_points, int capacity,
+                           int32_t *d_num, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Diagnostics: the vote kernels evaluate (v - min) / (max - min) with the loop-invariant part of

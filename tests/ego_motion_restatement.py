@@ -1,0 +1,237 @@
+"""The yardstick of the ego-motion tests: scan-to-map LiDAR odometry restated in plain fp64 numpy from the contract in
+include/icpflow_hip.h ("8(f) ego motion"), step by step, with the same tie rules (lowest input index; first minimum in
+the order voxel offset, insertion).  Test code, not product code: nothing under icp_flow_amd/ imports it, and it shares
+no line with the HIP implementation (a Python dict of lists where that has hash tables, scipy's matrix exponential where
+that has the closed form, numpy's solver where that eliminates by hand).
+
+    odo = Odometry()                       # the reference's constants (config_kiss_icp.yaml as its scripts set it)
+    pose = odo.register_frame(points)      # float32 [n,3] in the sensor's coordinates -> float64 [4,4], frame -> frame 0
+    odo.records[j]                         # everything frame j decided: idx_ds, idx_source, guess, sigma, pose, ...
+"""
+import numpy as np
+from scipy.linalg import expm
+
+BIAS = 1 << 20
+OFFSETS = np.array([(ox, oy, oz) for ox in (-1, 0, 1) for oy in (-1, 0, 1) for oz in (-1, 0, 1)], dtype=np.int64)
+
+DEFAULTS = dict(max_range=100.0, min_range=1.0, voxel_size=0.0, min_motion_th=0.1, initial_threshold=10.0,
+                convergence=1e-4, max_points_per_voxel=20, max_iterations=500)
+
+
+def voxel_coords(p, size):
+    """floor(x / size) per axis in fp64 -> int64 [n,3]"""
+    return np.floor(np.asarray(p, dtype=np.float64) / float(size)).astype(np.int64)
+
+
+def pack(ijk):
+    ijk = np.asarray(ijk, dtype=np.int64)
+    return ((ijk[..., 0] + BIAS) << 42) | ((ijk[..., 1] + BIAS) << 21) | (ijk[..., 2] + BIAS)
+
+
+def crop_mask(points, min_range, max_range):
+    p = np.asarray(points, dtype=np.float64)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    r2 = x * x + y * y + z * z
+    return (r2 > min_range * min_range) & (r2 < max_range * max_range)
+
+
+def lowest_index_per_voxel(points, rows, size):
+    """rows (ascending) of `points` -> the subset that is the lowest row of its voxel, ascending."""
+    rows = np.asarray(rows, dtype=np.int64)
+    if len(rows) == 0:
+        return rows
+    keys = pack(voxel_coords(points[rows], size))
+    _, first = np.unique(keys, return_index=True)        # index of the FIRST occurrence of every key
+    return rows[np.sort(first)]
+
+
+def downsample(points, min_range, max_range, voxel):
+    """steps 1-2 -> (idx_ds, idx_source): rows of `points`, ascending"""
+    rows = np.nonzero(crop_mask(points, min_range, max_range))[0]
+    idx_ds = lowest_index_per_voxel(points, rows, 0.5 * voxel)
+    idx_source = lowest_index_per_voxel(points, idx_ds, 1.5 * voxel)
+    return idx_ds, idx_source
+
+
+def move(pose, points):
+    """((R0 x + R1 y) + R2 z) + t in fp64, in that order"""
+    p = np.asarray(points, dtype=np.float64)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    T = np.asarray(pose, dtype=np.float64)
+    return np.stack([((T[r, 0] * x + T[r, 1] * y) + T[r, 2] * z) + T[r, 3] for r in range(3)], axis=1)
+
+
+class VoxelMap:
+    """voxel (packed key) -> list of float32 points in insertion order"""
+
+    def __init__(self, voxel, per_voxel, max_range):
+        self.voxel, self.per_voxel, self.max_range = float(voxel), int(per_voxel), float(max_range)
+        self.cells = {}
+
+    def add(self, points_f32):
+        keys = pack(voxel_coords(points_f32, self.voxel))
+        for k, p in zip(keys.tolist(), points_f32):
+            cell = self.cells.setdefault(k, [])
+            if len(cell) < self.per_voxel:
+                cell.append(p.copy())
+
+    def prune(self, position):
+        o = np.asarray(position, dtype=np.float64)
+        drop = []
+        for k, cell in self.cells.items():
+            e = cell[0].astype(np.float64) - o
+            if (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2] > self.max_range * self.max_range:
+                drop.append(k)
+        for k in drop:
+            del self.cells[k]
+
+    def update(self, frame_ds, pose):
+        """the map half of step 6"""
+        self.add(move(pose, frame_ds).astype(np.float32))
+        self.prune(np.asarray(pose)[0:3, 3])
+
+    def snapshot(self):
+        """{key: float32 [c,3]}"""
+        return {k: np.stack(v) for k, v in self.cells.items()}
+
+    def arrays(self):
+        """sorted keys [V], counts [V], points float64 [V, per_voxel, 3] (rows beyond the count: +inf)"""
+        keys = np.array(sorted(self.cells), dtype=np.int64)
+        counts = np.zeros(len(keys), dtype=np.int64)
+        pts = np.full((len(keys), self.per_voxel, 3), np.inf)
+        for v, k in enumerate(keys.tolist()):
+            cell = self.cells[k]
+            counts[v] = len(cell)
+            pts[v, : len(cell)] = np.stack(cell).astype(np.float64)
+        return keys, counts, pts
+
+
+def correspondences(map_arrays, x, voxel):
+    """closest map point of every x [m,3] among the 27 voxels around it -> (q [m,3], d2 [m]); d2 = inf without any.
+    First minimum in the order voxel offset (dx, dy, dz ascending, dz fastest), then insertion order."""
+    keys, counts, pts = map_arrays
+    m = len(x)
+    if len(keys) == 0 or m == 0:
+        return np.zeros((m, 3)), np.full(m, np.inf)
+    around = pack(voxel_coords(x, voxel)[:, None, :] + OFFSETS[None, :, :])            # [m,27]
+    at = np.clip(np.searchsorted(keys, around), 0, len(keys) - 1)
+    found = keys[at] == around
+    cand = pts[at]                                                                      # [m,27,P,3]
+    e = x[:, None, None, :] - cand
+    d2 = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+    d2 = np.where(found[:, :, None] & np.isfinite(d2), d2, np.inf).reshape(m, -1)
+    best = np.argmin(d2, axis=1)                                                        # the FIRST minimum
+    q = cand.reshape(m, -1, 3)[np.arange(m), best]
+    return q, d2[np.arange(m), best]
+
+
+def twist_matrix(dx):
+    v, w = dx[0:3], dx[3:6]
+    M = np.zeros((4, 4))
+    M[0:3, 0:3] = [[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]]
+    M[0:3, 3] = v
+    return M
+
+
+def register(source, map_arrays, guess, sigma, voxel, max_iterations=500, convergence=1e-4, trace=None):
+    """step 5 -> (pose [4,4], iterations, final |dx|, correspondences of the last iteration)"""
+    T = np.array(guess, dtype=np.float64)
+    if len(map_arrays[0]) == 0:
+        return T, 0, 0.0, 0
+    gate2, kern = (3.0 * sigma) ** 2, sigma / 3.0
+    iterations, last, ncorr = 0, 0.0, 0
+    for it in range(max_iterations):
+        x = move(T, source)
+        q, d2 = correspondences(map_arrays, x, voxel)
+        keep = d2 < gate2
+        ncorr = int(keep.sum())
+        iterations = it + 1
+        if trace is not None:
+            trace.append(dict(pose=T.copy(), d2=d2.copy(), keep=keep.copy(), q=q.copy()))
+        if ncorr < 3:
+            break
+        xk, r, w = x[keep], x[keep] - q[keep], (kern / (kern + d2[keep])) ** 2
+        J = np.zeros((len(xk), 3, 6))
+        J[:, 0, 0] = J[:, 1, 1] = J[:, 2, 2] = 1.0
+        J[:, 0, 4], J[:, 0, 5] = xk[:, 2], -xk[:, 1]
+        J[:, 1, 3], J[:, 1, 5] = -xk[:, 2], xk[:, 0]
+        J[:, 2, 3], J[:, 2, 4] = xk[:, 1], -xk[:, 0]
+        A = np.einsum("n,nka,nkb->ab", w, J, J)
+        b = -np.einsum("n,nka,nk->a", w, J, r)
+        try:
+            dx = np.linalg.solve(A, b)
+        except np.linalg.LinAlgError:
+            break
+        if not np.isfinite(dx).all():
+            break
+        T = expm(twist_matrix(dx)) @ T
+        last = float(np.linalg.norm(dx))
+        if last < convergence:
+            break
+    return T, iterations, last, ncorr
+
+
+def rigid_inverse(T):
+    out = np.eye(4)
+    out[0:3, 0:3] = T[0:3, 0:3].T
+    out[0:3, 3] = -T[0:3, 0:3].T @ T[0:3, 3]
+    return out
+
+
+def model_error(deviation, max_range):
+    theta = np.arccos(np.clip(0.5 * (np.trace(deviation[0:3, 0:3]) - 1.0), -1.0, 1.0))
+    return float(np.linalg.norm(deviation[0:3, 3]) + 2.0 * max_range * np.sin(0.5 * theta))
+
+
+class Odometry:
+    def __init__(self, **over):
+        unknown = set(over) - set(DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown constants {sorted(unknown)}")
+        self.c = dict(DEFAULTS, **over)
+        self.voxel = self.c["voxel_size"] if self.c["voxel_size"] > 0 else self.c["max_range"] / 100.0
+        self.map = VoxelMap(self.voxel, self.c["max_points_per_voxel"], self.c["max_range"])
+        self.poses, self.records = [], []
+        self.sse, self.samples = 0.0, 0
+
+    def threshold(self):
+        c = self.c
+        moved = float(np.linalg.norm(self.poses[-1][0:3, 3])) if self.poses else 0.0
+        if moved > 5.0 * c["min_motion_th"] and self.samples > 0:
+            return float(np.sqrt(self.sse / self.samples))
+        return float(c["initial_threshold"])
+
+    def guess(self):
+        if len(self.poses) >= 2:
+            return self.poses[-1] @ (rigid_inverse(self.poses[-2]) @ self.poses[-1])
+        return self.poses[-1].copy() if self.poses else np.eye(4)
+
+    def register_frame(self, points, keep_map=True):
+        c = self.c
+        points = np.ascontiguousarray(points, dtype=np.float32)[:, 0:3]
+        idx_ds, idx_source = downsample(points, c["min_range"], c["max_range"], self.voxel)
+        sigma, guess = self.threshold(), self.guess()
+        pose, iterations, last, ncorr = register(points[idx_source], self.map.arrays(), guess, sigma, self.voxel,
+                                                 c["max_iterations"], c["convergence"])
+        err = model_error(rigid_inverse(guess) @ pose, c["max_range"])
+        if err > c["min_motion_th"]:
+            self.sse += err * err
+            self.samples += 1
+        self.map.update(points[idx_ds], pose)
+        self.poses.append(pose)
+        self.records.append(dict(idx_ds=idx_ds, idx_source=idx_source, sigma=sigma, guess=guess, pose=pose,
+                                 iterations=iterations, final_dx=last, correspondences=ncorr,
+                                 map=self.map.snapshot() if keep_map else None))
+        return pose
+
+
+def rotation_angle(R):
+    """angle of a rotation matrix, accurate for small angles too (arccos of the trace resolves nothing below 3e-8 rad)"""
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return float(np.arctan2(np.linalg.norm(v), 0.5 * (np.trace(R) - 1.0)))
+
+
+def pose_error(pose, truth):
+    """-> (|dt| in metres, rotation angle of the difference in radians)"""
+    D = rigid_inverse(np.asarray(truth, dtype=np.float64)) @ np.asarray(pose, dtype=np.float64)
+    return float(np.linalg.norm(D[0:3, 3])), rotation_angle(D[0:3, 0:3])
