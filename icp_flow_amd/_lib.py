@@ -85,6 +85,10 @@ SIGNATURES = {
     "icpflow_ego_register_step": (_i, [_p, _p, _i, _p, _d, _p, _p]),
     "icpflow_ego_map_add": (_i, [_p, _p, _i, _p, _p]),
     "icpflow_ego_map_export": (_i, [_p, _p, _p, _p, _i, _p, _p]),
+    "icpflow_seq_gt_flow_workspace_bytes": (_sz, [_i]),
+    "icpflow_seq_gt_flow": (_i, [_p, _p, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "icpflow_seq_metrics_workspace_bytes": (_sz, [_i, _i]),
+    "icpflow_seq_metrics": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _p, _p, _p, _sz, _p]),
     "icpflow_selftest_vote_quotient": (_i, [_p, _i, _f, _f, _p, _p, _p]),
     "icpflow_selftest_kabsch": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
     "icpflow_profile_create": (_i, [_i, ctypes.POINTER(_p)]),
@@ -108,6 +112,9 @@ def call(name, *args):
         raise RuntimeError(f"{name} failed (code {rc}): {msg.decode() if msg else ''}")
 
 
+SEQ_MAX_FRAMES = 16
+SEQ_OUT_FLOW, SEQ_OUT_POINTS = 0, 1
+SEQ_CROP_NONE, SEQ_CROP_XY, SEQ_CROP_XYZ = 0, 1, 2
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical

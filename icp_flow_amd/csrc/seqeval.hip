@@ -1,0 +1,329 @@
+// seqeval.hip -- the evaluation of a whole sequence on the GPU (include/icpflow_hip.h, "8(f) sequence evaluation"):
+// the ground-truth scene flow the reference builds from its poses (utils_loading.py:21-48, dataset_pca.py:66-69) and the
+// sums behind the table its calculate_metrics fills (utils_eval.py:24-63, 162-180, 185-368).
+//
+// Determinism of icpflow_seq_metrics.  Counts are integers (ballots and popcounts): exact whatever the order.  The one
+// floating-point sum, the end point error of a (gap, class) cell, is added in an order that is a function of the arguments
+// alone:
+//   1. a wave takes the 64-row tiles  w, w + W, w + 2 W, ...  (w = its number in the grid, W = waves in the grid; the grid
+//      follows from m, never from the device), and inside a tile the gaps in the order of their first row;
+//   2. the 64 values of a tile go through one fixed butterfly (wave_sum), and lane 0 adds the total to the wave's own cell in
+//      LDS -- tile after tile, in the order of 1.;
+//   3. a workgroup's partial is its waves' cells added in wave order, stored to the workspace (every workgroup stores all of
+//      its cells: nothing there needs to be zero beforehand);
+//   4. a second, single-workgroup kernel adds the partials of a cell in workgroup order, then row 0 as the gap rows in gap order.
+// No floating-point atomic anywhere.  The file is compiled with -ffp-contract=off (build.py: CFLAGS): the squares, the two
+// additions, the square root and the division of a row's error are the separately rounded operations numpy performs.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/icpflow_hip.h"
+#include "common.hpp"
+
+namespace icpflow {
+int report_error(int code, const char *message);   // api.hip: what icpflow_last_error returns
+}
+using icpflow::kWave;
+using icpflow::report_error;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kRowsPerThread = 8;                       // rows a workgroup is sized for: kThreads * kRowsPerThread
+constexpr int kMaxGrid = 256;                           // workgroups at most (a CU each)
+constexpr int kClasses = 6, kValues = 6;                // overall static static_bg static_fg dynamic dynamic_fg; count, sum e, 4 predicates
+constexpr int kCell = kClasses * kValues;               // 64-bit words of one gap row
+constexpr int kMaxFrames = ICPFLOW_SEQ_MAX_FRAMES;
+constexpr int kInfo = 2;                                // kept rows of frame 0, rows whose time index is outside [0, F)
+
+int hipfail(hipError_t e, const char *what)
+{
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", what, hipGetErrorString(e));
+    return report_error((int)e, msg);
+}
+
+#define SEQ_HIP(call)                                     \
+    do {                                                  \
+        const hipError_t e_ = (call);                     \
+        if (e_ != hipSuccess) return hipfail(e_, #call);  \
+    } while (0)
+
+size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int grid_for(int m)
+{
+    const long long per = (long long)kThreads * kRowsPerThread;
+    const long long g = ((long long)m + per - 1) / per;
+    return (int)(g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g);
+}
+
+// words a workgroup of icpflow_seq_metrics leaves in the workspace
+size_t partial_words(int F) { return (size_t)(F - 1) * kCell + kInfo; }
+
+// ---- ground-truth flow -------------------------------------------------------------------------------------------
+// x' = R x + t with the rows of a row-major 4x4, every operation rounded by itself: ((R0 x + R1 y) + R2 z) + t
+__device__ __forceinline__ void rigid_apply(const double *__restrict__ T, double &x, double &y, double &z)
+{
+    const double ox = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+    const double oy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+    const double oz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    x = ox, y = oy, z = oz;
+}
+
+__global__ __launch_bounds__(kThreads) void seq_gt_flow_kernel(const double *__restrict__ pts, const int32_t *__restrict__ tim,
+                                                               const int32_t *__restrict__ inst, int m, const double *__restrict__ ego,
+                                                               int F, const double *__restrict__ tsfm, int K, int output,
+                                                               double *__restrict__ out, unsigned long long *__restrict__ partial)
+{
+    __shared__ unsigned long long bad_s[kWaves];
+    unsigned long long bad = 0;
+    const size_t stride = (size_t)gridDim.x * kThreads;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < (size_t)m; i += stride) {
+        const int t = tim[i];
+        const int k = tsfm ? inst[i] : 0;
+        if (t < 0 || t >= F || k < 0 || (tsfm && k >= K)) {   // not computed, counted; nothing is written for the row
+            ++bad;
+            continue;
+        }
+        const double px = pts[3 * i + 0], py = pts[3 * i + 1], pz = pts[3 * i + 2];
+        double x = px, y = py, z = pz;
+        if (ego) rigid_apply(ego + (size_t)t * 16, x, y, z);
+        if (tsfm) rigid_apply(tsfm + ((size_t)k * F + t) * 16, x, y, z);
+        if (output == ICPFLOW_SEQ_OUT_FLOW) x -= px, y -= py, z -= pz;
+        out[3 * i + 0] = x, out[3 * i + 1] = y, out[3 * i + 2] = z;
+    }
+    bad = icpflow::wave_sum(bad);
+    if ((threadIdx.x & (kWave - 1)) == 0) bad_s[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < kWaves; ++w) s += bad_s[w];
+        partial[blockIdx.x] = s;
+    }
+}
+
+__global__ void seq_count_final_kernel(const unsigned long long *__restrict__ partial, int G, long long *__restrict__ d_bad)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    unsigned long long s = 0;
+    for (int g = 0; g < G; ++g) s += partial[g];
+    *d_bad = (long long)s;
+}
+
+// ---- the table ---------------------------------------------------------------------------------------------------
+struct Crop {
+    int mode;
+    double rx, ry, zmin;
+};
+
+__global__ __launch_bounds__(kThreads) void seq_metrics_kernel(const double *__restrict__ pts, const int32_t *__restrict__ tim,
+                                                               const int32_t *__restrict__ sd, const int32_t *__restrict__ fb,
+                                                               const double *__restrict__ gt, const float *__restrict__ pred, int m, int F,
+                                                               Crop crop, unsigned long long *__restrict__ partial)
+{
+    // a wave's own cells: [wave][gap - 1][class][value]; value 1 holds a double
+    __shared__ unsigned long long cell[kWaves][(kMaxFrames - 1) * kCell];
+    __shared__ unsigned long long info[kWaves][kInfo];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int words = (F - 1) * kCell;
+    for (int k = lane; k < words; k += kWave) cell[wave][k] = 0;   // (the bits of +0.0 are zero too)
+    if (lane < kInfo) info[wave][lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    const size_t tiles = ((size_t)m + kWave - 1) / kWave;
+    const size_t W = (size_t)gridDim.x * kWaves;
+    unsigned long long kept0 = 0, outside = 0;                    // wave-uniform, kept by every lane
+    for (size_t tile = (size_t)blockIdx.x * kWaves + wave; tile < tiles; tile += W) {
+        const size_t i = tile * kWave + lane;
+        const bool row = i < (size_t)m;
+        int t = -1;
+        bool keep = false;
+        double e = 0.0, r = 0.0;
+        int s = 2, f = 2;
+        if (row) {
+            t = tim[i];
+            const double x = pts[3 * i + 0], y = pts[3 * i + 1], z = pts[3 * i + 2];
+            // crop_data, utils_eval.py:33-38 (a NaN coordinate fails every comparison there and here)
+            keep = crop.mode == ICPFLOW_SEQ_CROP_NONE || (fabs(x) < crop.rx && fabs(y) < crop.ry && (crop.mode == ICPFLOW_SEQ_CROP_XY || z > crop.zmin));
+            const double gx = gt[3 * i + 0], gy = gt[3 * i + 1], gz = gt[3 * i + 2];
+            const double dx = gx - (double)pred[3 * i + 0], dy = gy - (double)pred[3 * i + 1], dz = gz - (double)pred[3 * i + 2];
+            // compute_epe_test, utils_eval.py:163-168: numpy's norm is sqrt((x*x + y*y) + z*z), each operation rounded
+            e = sqrt((dx * dx + dy * dy) + dz * dz);
+            r = e / (sqrt((gx * gx + gy * gy) + gz * gz) + 1e-20);
+            s = sd[i], f = fb[i];
+        }
+        outside += __popcll(__ballot(row && (t < 0 || t >= F)));
+        kept0 += __popcll(__ballot(row && keep && t == 0));
+        // utils_eval.py:170-180
+        const bool p0 = e < 0.05 || r < 0.05, p1 = e < 0.1 || r < 0.1, p2 = e > 0.3 || r > 0.1, p3 = e > 0.3 && r > 0.3;
+        const bool counted = row && keep && t >= 1 && t < F;
+        unsigned long long todo = __ballot(counted);
+        while (todo) {                                             // the gaps of the tile, in the order of their first row
+            const int leader = __ffsll((long long)todo) - 1;
+            const int j = __shfl(t, leader, kWave);
+            const bool mine = counted && t == j;
+            todo &= ~__ballot(mine);
+            unsigned long long *c = cell[wave] + (size_t)(j - 1) * kCell;
+#pragma unroll
+            for (int k = 0; k < kClasses; ++k) {
+                // utils_eval.py:217, 225, 233, 241, 253: a label that is neither 0 nor 1 counts in `overall` only
+                const bool in = mine && (k == 0 || (k == 1 && s == 0) || (k == 2 && s == 0 && f == 0) || (k == 3 && s == 0 && f == 1) ||
+                                         (k == 4 && s == 1) || (k == 5 && s == 1 && f == 1));
+                const unsigned long long members = __ballot(in);
+                if (members == 0) continue;                        // (wave-uniform)
+                const double sum = icpflow::wave_sum(in ? e : 0.0);
+                const unsigned long long n0 = __popcll(__ballot(in && p0)), n1 = __popcll(__ballot(in && p1));
+                const unsigned long long n2 = __popcll(__ballot(in && p2)), n3 = __popcll(__ballot(in && p3));
+                if (lane == 0) {
+                    unsigned long long *v = c + k * kValues;
+                    v[0] += __popcll(members);
+                    v[1] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)v[1]) + sum);
+                    v[2] += n0, v[3] += n1, v[4] += n2, v[5] += n3;
+                }
+            }
+        }
+    }
+    if (lane == 0) info[wave][0] = kept0, info[wave][1] = outside;
+    __syncthreads();
+    // the workgroup's partial: its waves in wave order
+    unsigned long long *mine = partial + (size_t)blockIdx.x * ((size_t)words + kInfo);
+    for (int k = threadIdx.x; k < words + kInfo; k += kThreads) {
+        const bool is_info = k >= words;
+        const bool is_sum = !is_info && (k % kValues) == 1;
+        unsigned long long acc = 0;
+        double accd = 0.0;
+        for (int w = 0; w < kWaves; ++w) {
+            const unsigned long long v = is_info ? info[w][k - words] : cell[w][k];
+            if (is_sum) accd += __longlong_as_double((long long)v);
+            else acc += v;
+        }
+        mine[k] = is_sum ? (unsigned long long)__double_as_longlong(accd) : acc;
+    }
+}
+
+// One workgroup: the partials of a cell in workgroup order, then row 0 as the gap rows in gap order.
+__global__ __launch_bounds__(kThreads) void seq_metrics_final_kernel(const unsigned long long *__restrict__ partial, int G, int F,
+                                                                     unsigned long long *__restrict__ table,
+                                                                     unsigned long long *__restrict__ d_info)
+{
+    __shared__ unsigned long long total[(kMaxFrames - 1) * kCell + kInfo];
+    const int words = (F - 1) * kCell;
+    const size_t pitch = (size_t)words + kInfo;
+    for (int k = threadIdx.x; k < words + kInfo; k += kThreads) {
+        const bool is_sum = k < words && (k % kValues) == 1;
+        unsigned long long acc = 0;
+        double accd = 0.0;
+        for (int g = 0; g < G; ++g) {
+            const unsigned long long v = partial[(size_t)g * pitch + k];
+            if (is_sum) accd += __longlong_as_double((long long)v);
+            else acc += v;
+        }
+        total[k] = is_sum ? (unsigned long long)__double_as_longlong(accd) : acc;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < words; k += kThreads) table[kCell + k] = total[k];
+    if (threadIdx.x < kInfo) d_info[threadIdx.x] = total[words + threadIdx.x];
+    if (threadIdx.x < kCell) {
+        const bool is_sum = (threadIdx.x % kValues) == 1;
+        unsigned long long acc = 0;
+        double accd = 0.0;
+        for (int j = 1; j < F; ++j) {
+            const unsigned long long v = total[(j - 1) * kCell + threadIdx.x];
+            if (is_sum) accd += __longlong_as_double((long long)v);
+            else acc += v;
+        }
+        table[threadIdx.x] = is_sum ? (unsigned long long)__double_as_longlong(accd) : acc;
+    }
+}
+
+int pointer_error(const char *fn)
+{
+    char msg[128];
+    snprintf(msg, sizeof(msg), "%s: null pointer", fn);
+    return report_error(ICPFLOW_E_ARG, msg);
+}
+
+int workspace_error(const char *fn, const void *ws, size_t have, size_t need)
+{
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: workspace of %zu bytes, %s_workspace_bytes says %zu", fn, ws ? have : (size_t)0, fn, need);
+    return report_error(ICPFLOW_E_WORKSPACE, msg);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t icpflow_seq_gt_flow_workspace_bytes(int m)
+{
+    if (m < 0) return 0;
+    return round256((size_t)grid_for(m) * sizeof(unsigned long long));
+}
+
+int icpflow_seq_gt_flow(const double *d_points, const int32_t *d_time_indice, const int32_t *d_inst_labels, int m, const double *d_ego,
+                        int F, const double *d_inst_tsfm, int K, int output, double *d_out, int64_t *d_bad_rows, void *d_ws,
+                        size_t ws_bytes, icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_seq_gt_flow";
+    if (m < 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_gt_flow: m < 0");
+    if (F < 1 || K < 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_gt_flow: F must be >= 1 and K >= 0");
+    if (output != ICPFLOW_SEQ_OUT_FLOW && output != ICPFLOW_SEQ_OUT_POINTS)
+        return report_error(ICPFLOW_E_ARG, "icpflow_seq_gt_flow: output must be ICPFLOW_SEQ_OUT_FLOW or ICPFLOW_SEQ_OUT_POINTS");
+    if (!d_bad_rows || (!d_ego && !d_inst_tsfm) || (m > 0 && (!d_points || !d_time_indice || !d_out || (d_inst_tsfm && !d_inst_labels))))
+        return pointer_error(fn);
+    const size_t need = icpflow_seq_gt_flow_workspace_bytes(m);
+    if (!d_ws || ws_bytes < need) return workspace_error(fn, d_ws, ws_bytes, need);
+    if (((uintptr_t)d_ws & 7) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_gt_flow: d_ws must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int G = grid_for(m);
+    unsigned long long *partial = (unsigned long long *)d_ws;
+    seq_gt_flow_kernel<<<G, kThreads, 0, st>>>(d_points, d_time_indice, d_inst_labels, m, d_ego, F, d_inst_tsfm, K, output, d_out, partial);
+    SEQ_HIP(hipGetLastError());
+    seq_count_final_kernel<<<1, kWave, 0, st>>>(partial, G, (long long *)d_bad_rows);
+    SEQ_HIP(hipGetLastError());
+    return ICPFLOW_OK;
+}
+
+size_t icpflow_seq_metrics_workspace_bytes(int m, int F)
+{
+    if (m < 0 || F < 1 || F > kMaxFrames) return 0;
+    return round256((size_t)grid_for(m) * partial_words(F) * sizeof(unsigned long long));
+}
+
+int icpflow_seq_metrics(const double *d_points, const int32_t *d_time_indice, const int32_t *d_sd_labels, const int32_t *d_fb_labels,
+                        const double *d_gt_flow, const float *d_pred_flow, int m, int F, int crop, double range_x, double range_y,
+                        double z_min, int64_t *d_table, int64_t *d_info, void *d_ws, size_t ws_bytes, icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_seq_metrics";
+    if (m < 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: m < 0");
+    if (F < 1) return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: F must be >= 1");
+    if (F > kMaxFrames) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "icpflow_seq_metrics: F = %d frames, the table of at most %d is kept in LDS", F, kMaxFrames);
+        return report_error(ICPFLOW_E_LIMIT, msg);
+    }
+    if (crop != ICPFLOW_SEQ_CROP_NONE && crop != ICPFLOW_SEQ_CROP_XY && crop != ICPFLOW_SEQ_CROP_XYZ)
+        return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: crop must be ICPFLOW_SEQ_CROP_NONE, _XY or _XYZ");
+    if (!d_table || !d_info || (m > 0 && (!d_points || !d_time_indice || !d_sd_labels || !d_fb_labels || !d_gt_flow || !d_pred_flow)))
+        return pointer_error(fn);
+    const size_t need = icpflow_seq_metrics_workspace_bytes(m, F);
+    if (!d_ws || ws_bytes < need) return workspace_error(fn, d_ws, ws_bytes, need);
+    if (((uintptr_t)d_ws & 7) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: d_ws must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int G = grid_for(m);
+    unsigned long long *partial = (unsigned long long *)d_ws;
+    const Crop c = {crop, range_x, range_y, z_min};
+    seq_metrics_kernel<<<G, kThreads, 0, st>>>(d_points, d_time_indice, d_sd_labels, d_fb_labels, d_gt_flow, d_pred_flow, m, F, c, partial);
+    SEQ_HIP(hipGetLastError());
+    seq_metrics_final_kernel<<<1, kThreads, 0, st>>>(partial, G, F, (unsigned long long *)d_table, (unsigned long long *)d_info);
+    SEQ_HIP(hipGetLastError());
+    return ICPFLOW_OK;
+}
+
+}  // extern "C"

@@ -29,6 +29,16 @@ in (main.py:230-234, utils_flow.py:23-50).  Ground segmentation is upstream (BAS
 independent, main.py:184), and reports ms / frame pair and the reference's accuracy metrics.
 
     python -m icp_flow_amd.frame_pairs DIR [--max-points 10000] [--speed 1.0] [--repeat 3]
+
+`run_sequences` (`--protocol reference`) evaluates whole sequence files by the reference's metric protocol instead
+(utils_eval.py:185-368, main.py:173-181, 285-296): the frame pairs of a file as above, their flows assembled on the device
+into the sequence's flow (zeros for frame 0, main.py:217-260), one pass of icpflow_seq_metrics over it and ONE small
+read-back per sequence -- the table from which the reference's 6 x (num_frames + 1) meters are updated.  A sample without a
+`scene_flow` key (every sample of the reference) gets its ground truth from `inst_labels`, `bbox_tsfm` and `ego_motion_gt`
+on the GPU (dataset_pca.py:66-69, utils_loading.py).
+
+    python -m icp_flow_amd.frame_pairs DIR --protocol reference --num-frames 5 --range-x 32 --range-y 32 [--eval-ground]
+                                           [--range-z 0.0 --ground-slack 0.3]
 """
 import argparse
 import glob
@@ -717,6 +727,116 @@ def register_in_flight_native(args, fps, device, in_flight=4):
         raise error
 
 
+def load_sequence_sample(path, args):
+    """The WHOLE sample of a sequence file as the reference's loader returns it (dataset_pca.py:41-69, 103-111): raw_points (in
+    the file's own dtype), time_indice, sd_labels, fb_labels, inst_labels, ego_motion_gt, bbox_tsfm, scene_flow (float64) and
+    data_path, cropped in x and y like dataset_pca.py:61-64 (args.range_x / range_y; numpy's comparison for the file's dtype).
+    A file without `scene_flow` -- every sample of the reference -- gets it from its poses on the GPU
+    (utils_loading.scene_flow: icpflow_seq_gt_flow); ours (synthetic.make_sequence) carry the key and keep it.  `nonground`
+    is kept when present.  -> dict of numpy arrays."""
+    from . import utils_loading
+    with np.load(path, allow_pickle=False) as z:
+        keys = set(z.files)
+        need = ("raw_points", "time_indice", "sd_labels", "fb_labels")
+        missing = [k for k in need if k not in keys]
+        if missing:
+            raise KeyError(f"{path}: not an evaluable sequence sample, missing {missing} (keys: {sorted(keys)})")
+        d = {k: np.asarray(z[k]) for k in need}
+        for k in ("inst_labels", "ego_motion_gt", "bbox_tsfm", "scene_flow", "nonground"):
+            d[k] = np.asarray(z[k]) if k in keys else None
+    m = len(d["raw_points"])
+    rows = ("raw_points", "time_indice", "sd_labels", "fb_labels", "inst_labels", "scene_flow", "nonground")
+    if any(d[k] is not None and len(d[k]) != m for k in rows):                   # dataset_pca.py:54
+        raise ValueError(f"{path}: one row per point required in {rows}")
+    rx, ry = getattr(args, "range_x", None), getattr(args, "range_y", None)
+    if rx is not None and ry is not None:
+        raw = d["raw_points"]
+        keep = np.logical_and(np.abs(raw[:, 0]) < rx, np.abs(raw[:, 1]) < ry)   # dataset_pca.py:61-64
+        for k in rows:
+            if d[k] is not None:
+                d[k] = d[k][keep]
+    if d["scene_flow"] is None:
+        if d["inst_labels"] is None or d["bbox_tsfm"] is None or d["ego_motion_gt"] is None:
+            raise KeyError(f"{path}: no scene_flow and not all of inst_labels / bbox_tsfm / ego_motion_gt to build it from")
+        if d["bbox_tsfm"].shape[1] != d["ego_motion_gt"].shape[0]:              # dataset_pca.py:56
+            raise ValueError(f"{path}: bbox_tsfm and ego_motion_gt disagree on the number of frames")
+        d["scene_flow"] = utils_loading.scene_flow(d["raw_points"][:, 0:3], d["time_indice"], d["inst_labels"], d["ego_motion_gt"],
+                                                   d["bbox_tsfm"])
+    else:
+        d["scene_flow"] = d["scene_flow"][:, 0:3].astype(np.float64)
+    d["data_path"] = path
+    return d
+
+
+def _sequence_ground(args, sample, fps):
+    """Ground removal stays upstream of the registration: the sample's `nonground` key (load_sequence has put it into the frame
+    pairs), else the height threshold of utils_ground.segment_ground_thres on the raw points (utils_ground.py:27-30; Patchwork++,
+    the other half of the reference's segment_ground, is not built) when args carries range_z / ground_slack.  -> how"""
+    from . import utils_ground
+    if sample["nonground"] is not None:
+        return "nonground key"
+    if getattr(args, "range_z", None) is None or getattr(args, "ground_slack", None) is None:
+        return "none"
+    ng = utils_ground.segment_ground_thres(args, sample["raw_points"])
+    t = sample["time_indice"]
+    for fp in fps:
+        fp.nonground_src, fp.nonground_dst = ng[t == fp.gap], ng[t == 0]
+    return "threshold"
+
+
+def run_sequences(args, paths, device, in_flight=1):
+    """Evaluate sequence files by the reference's protocol (main.py:173-296) on one GPU.  Per file: the sample
+    (`load_sequence_sample`) and its num_frames - 1 frame pairs (`load_sequence`), registered by the existing path
+    (`register_frame_pair`, or `register_in_flight` with in_flight > 1); the flows are put into the sequence's flow ON THE
+    DEVICE (zeros for frame 0, main.py:217-260) and `utils_eval.calculate_metrics` takes it from there: one launch pair, one
+    read-back of the table.  args: the registration's (default_args) plus num_frames, range_x, range_y, range_z,
+    ground_slack, eval_ground.
+    -> dict(metrics = the reference's meters, sequences, frame_pairs, ms_per_sequence (registration + evaluation, the
+    sample's evaluation inputs resident beforehand like the loader's work), ms_eval_per_sequence, ground, pose_sources)."""
+    device = torch.device(device)
+    F = int(args.num_frames)
+    metrics = utils_eval.new_metric_table(F)
+    times, eval_times, n_pairs, ground, pose_sources = [], [], 0, {}, {}
+    for path in paths:
+        sample = load_sequence_sample(path, args)
+        fps = load_sequence(path, args)
+        t = sample["time_indice"]
+        counts = [int((t == j).sum()) for j in range(F)]
+        if len(fps) != F - 1 or [len(fp.points_src) for fp in fps] != counts[1:] or (fps and len(fps[0].points_dst) != counts[0]):
+            raise ValueError(f"{path}: the frame pairs do not cover the sample's points (num_frames {F}, points per frame {counts})")
+        how = _sequence_ground(args, sample, fps)
+        ground[how] = ground.get(how, 0) + 1
+        for fp in fps:
+            pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
+        # resident before the clock starts: what the evaluation reads besides the flows, and where each frame's rows are
+        on = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device).to(dt)   # noqa: E731
+        data = dict(raw_points=on(sample["raw_points"][:, 0:3], torch.float64 if sample["raw_points"].dtype == np.float64 else torch.float32),
+                    time_indice=on(t, torch.int32), sd_labels=on(sample["sd_labels"], torch.int32),
+                    fb_labels=on(sample["fb_labels"], torch.int32), scene_flow=on(sample["scene_flow"], torch.float64))
+        if not (np.isin(sample["sd_labels"], (0, 1)).all() and np.isin(sample["fb_labels"], (0, 1)).all()):
+            data["sd_labels"], data["fb_labels"] = utils_eval._binary_labels(sample["sd_labels"], device), utils_eval._binary_labels(sample["fb_labels"], device)
+        rows = [on(np.flatnonzero(t == j), torch.int64) for j in range(F)]
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        flow_seq = torch.zeros((len(t), 3), dtype=torch.float32, device=device)
+        if int(in_flight) > 1:
+            done = register_in_flight(args, fps, device, in_flight)
+        else:
+            done = ((k, fp, register_frame_pair(args, fp, device)) for k, fp in enumerate(fps))
+        for _, fp, out in done:
+            flow_seq.index_copy_(0, rows[fp.gap], out["flow"].to(torch.float32))
+            n_pairs += 1
+        torch.cuda.synchronize(device)
+        t1 = time.perf_counter()
+        utils_eval.calculate_metrics(args, data, flow_seq, metrics)     # (its read-back of the table is the synchronisation)
+        t2 = time.perf_counter()
+        times.append((t2 - t0) * 1e3)
+        eval_times.append((t2 - t1) * 1e3)
+    return dict(metrics=metrics, sequences=len(times), frame_pairs=n_pairs, ms_per_sequence=sum(times) / max(len(times), 1),
+                ms_eval_per_sequence=sum(eval_times) / max(len(eval_times), 1),
+                ground="+".join(sorted(ground)) if ground else "none", pose_sources=pose_sources)
+
+
 def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, register_fn=None, in_flight=1):
     """Register this rank's share of `paths`; -> summary dict (identical on every rank).
     ms / frame pair is the mean wall time per pair, host -> device upload of the clouds included
@@ -807,6 +927,12 @@ def main(argv=None):
     ap.add_argument("--pose-source", choices=POSE_SOURCES, default=None,
                     help="ego poses of sequence files (default auto; estimate = scan-to-map odometry on the GPU)")
     ap.add_argument("--save-poses", action="store_true", help="with --pose-source estimate: write the <split>_pose files")
+    ap.add_argument("--protocol", choices=("reference",), default=None,
+                    help="reference: evaluate sequence files by the reference's table of 6 classes x (num_frames + 1) rows")
+    ap.add_argument("--num-frames", type=int, default=5, help="--protocol reference: frames per sequence (main.py:67)")
+    ap.add_argument("--range-z", type=float, default=0.0, help="--protocol reference: ground <= range_z (main.py:73)")
+    ap.add_argument("--ground-slack", type=float, default=0.3, help="--protocol reference (main.py:113)")
+    ap.add_argument("--eval-ground", action="store_true", help="--protocol reference: evaluate ground points too (main.py:115)")
     ns = ap.parse_args(argv)
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -820,6 +946,16 @@ def main(argv=None):
     args.max_points, args.min_cluster_size, args.chunk_size = int(args.max_points), int(args.min_cluster_size), int(args.chunk_size)
     args.num_clusters = int(args.num_clusters)
     args.pose_source, args.save_poses = ns.pose_source, ns.save_poses
+    if ns.protocol == "reference":
+        if world > 1:
+            raise SystemExit("--protocol reference is single-process (the table is not reduced across ranks)")
+        if args.range_x is None or args.range_y is None:
+            args.range_x, args.range_y = 32.0, 32.0                                    # main.py:69-72
+        args.num_frames, args.range_z, args.ground_slack, args.eval_ground = ns.num_frames, ns.range_z, ns.ground_slack, ns.eval_ground
+        res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_sequence(p)], device, in_flight=ns.in_flight)
+        print(utils_eval.format_metric_table(res.pop("metrics"), args.num_frames))
+        print(json.dumps(res))
+        return
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         print(json.dumps(summary))

@@ -1,5 +1,9 @@
 """Scene-flow accuracy metrics of the reference's evaluation (utils_eval.py:65-182), numpy on the
-host like the reference's.  Pinned by tests/golden/g9_epe.npz."""
+host like the reference's.  Pinned by tests/golden/g9_epe.npz.
+
+The evaluation of a whole sequence -- crop_data / calculate_metrics, utils_eval.py:24-63 and 185-368 -- runs on the GPU
+(icpflow_seq_metrics, csrc/seqeval.hip): one pass over the points, one table of F x 6 x 6 numbers back, from which the
+reference's meters are updated row by row.  Pinned by tests/golden/g13_seqeval_*.npz."""
 import numpy as np
 
 METRIC_NAMES = ("epe", "accs", "accr", "outlier", "Routlier")
@@ -58,3 +62,183 @@ class AverageMeter:
 
     def averages(self):
         return {m: float(getattr(self, m + "_avg")) for m in METRIC_NAMES}
+
+
+METRIC_CLASSES = ("overall", "static", "static_bg", "static_fg", "dynamic", "dynamic_fg")
+
+
+def metric_table_names(num_frames):
+    """The keys of the reference's table in the order main.py:173-180 creates them: per class, row 0 (per point over all
+    gaps), rows 1 .. num_frames - 1 (per gap), row num_frames (per scene)."""
+    return [f"{metric}_{k:d}" for metric in METRIC_CLASSES for k in range(0, num_frames + 1)]
+
+
+def new_metric_table(num_frames):
+    """main.py:173-180: a fresh AverageMeter under every name."""
+    return {name: AverageMeter() for name in metric_table_names(num_frames)}
+
+
+def format_metric_table(metrics_per_frame, num_frames):
+    """The reference's closing lines (main.py:288-296) as one string; the run of blanks inside a line is the
+    continuation of the reference's source line, which is part of its string."""
+    gap = ", " + " " * 18
+    lines = ["################# Results over the entire dataset #####################################"]
+    for k in range(0, num_frames + 1):
+        for metric in METRIC_CLASSES:
+            name = metric + f"_{k:d}"
+            m = metrics_per_frame[name]
+            lines.append(f"{name:12}, EPE3D: {m.epe_avg:.6f}{gap}ACC3DS: {m.accs_avg:.6f}{gap}ACC3DR: {m.accr_avg:.6f}{gap}"
+                         f"Outlier: {m.outlier_avg:.6f}{gap}Routlier: {m.Routlier_avg:.6f}.")
+    return "\n".join(lines)
+
+
+def _crop_mask(args, raw_points):
+    """utils_eval.py:33-38 with the array's own comparison (numpy rounds the threshold to a float32 array's type,
+    torch does the same)."""
+    import torch
+    absf = torch.abs if isinstance(raw_points, torch.Tensor) else np.abs
+    keep = (absf(raw_points[:, 0]) < args.range_x) & (absf(raw_points[:, 1]) < args.range_y)
+    if not args.eval_ground:
+        keep = keep & (raw_points[:, 2] > args.range_z + args.ground_slack)
+    return keep
+
+
+def crop_data(args, data, pred):
+    """utils_eval.py:24-63: crop the scene in x and y and, unless args.eval_ground, drop what lies below
+    range_z + ground_slack.  numpy arrays or device tensors (a gather per array on whichever side they live;
+    calculate_metrics does not call this -- its kernel applies the same test row by row)."""
+    keep = _crop_mask(args, data["raw_points"])
+    out = dict(data)
+    for k in ("raw_points", "time_indice", "sd_labels", "fb_labels", "scene_flow"):
+        out[k] = data[k][keep]
+    return out, pred[keep]
+
+
+def _threshold_for(value, raw_points):
+    """A crop threshold as numpy compares it with the sample's coordinates: a float32 (float16) array is compared with the
+    threshold rounded to its type; the kernel compares the exactly widened coordinate with this number in fp64."""
+    import torch
+    dt = raw_points.dtype
+    if isinstance(raw_points, torch.Tensor):
+        dt = {torch.float32: np.float32, torch.float16: np.float16}.get(dt, np.float64)
+    dt = np.dtype(dt)
+    if dt.kind == "f" and dt.itemsize < 8:
+        return float(np.asarray(value, dtype=np.float64).astype(dt))
+    return float(value)
+
+
+def _binary_labels(labels, device):
+    """Labels as the kernel reads them: 0, 1, or 2 for anything that equals neither (`== 0` / `== 1` on the sample's own type)."""
+    import torch
+    from . import utils_loading
+    if isinstance(labels, torch.Tensor):
+        t = labels.to(device)
+        return torch.where(t == 0, 0, torch.where(t == 1, 1, 2)).to(torch.int32).contiguous()
+    a = np.asarray(labels)
+    return utils_loading.to_device(np.where(a == 0, 0, np.where(a == 1, 1, 2)).astype(np.int32), torch.int32, device)
+
+
+def sequence_table(args, data, flow_seq):
+    """icpflow_seq_metrics on one sequence -> (table int64 [F,6,6] numpy, sum of e float64 [F,6] numpy, kept points of
+    frame 0, rows with a time index outside [0,F)).  Inputs may live on either side; with device tensors the only
+    device -> host copy is the table (F * 36 + 2 words, one copy)."""
+    import ctypes
+    import torch
+    from . import _lib, utils_loading
+    device = utils_loading._device_for(flow_seq, data["raw_points"], data["scene_flow"])
+    F = int(args.num_frames)
+    raw = data["raw_points"]
+    pts = utils_loading.to_device(raw, torch.float64, device)[:, 0:3].contiguous()
+    m = pts.shape[0]
+    tim = utils_loading.to_device(data["time_indice"], torch.int32, device)
+    sd, fb = _binary_labels(data["sd_labels"], device), _binary_labels(data["fb_labels"], device)
+    gt = utils_loading.to_device(data["scene_flow"], torch.float64, device)[:, 0:3].contiguous()
+    pred = utils_loading.to_device(flow_seq, torch.float32, device)[:, 0:3].contiguous()
+    for name, t in (("time_indice", tim), ("sd_labels", sd), ("fb_labels", fb), ("scene_flow", gt), ("flow_seq", pred)):
+        if t.shape[0] != m:
+            raise ValueError(f"{name}: {t.shape[0]} rows for {m} points")
+    if args.eval_ground:                 # utils_eval.py:186-189: no crop at all
+        crop, rx, ry, zmin = _lib.SEQ_CROP_NONE, 0.0, 0.0, 0.0
+    else:
+        crop = _lib.SEQ_CROP_XYZ
+        rx, ry = _threshold_for(args.range_x, raw), _threshold_for(args.range_y, raw)
+        zmin = _threshold_for(args.range_z + args.ground_slack, raw)
+    out = torch.empty(F * 36 + 2, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        need = int(_lib._L.icpflow_seq_metrics_workspace_bytes(m, F))
+        ws = _lib.workspace(device, need)
+        _lib.call("icpflow_seq_metrics", _lib.ptr(pts), _lib.ptr(tim), _lib.ptr(sd), _lib.ptr(fb), _lib.ptr(gt), _lib.ptr(pred), m, F,
+                  crop, rx, ry, zmin, _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + F * 36 * 8), _lib.ptr(ws),
+                  ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    host = out.cpu().numpy()             # the one read-back
+    table = host[: F * 36].reshape(F, 6, 6)
+    esum = np.ascontiguousarray(table[:, :, 1]).view(np.float64)
+    return table, esum, int(host[F * 36]), int(host[F * 36 + 1])
+
+
+def _cell_metrics(table, esum, j, c):
+    """The five numbers compute_epe_test returns for one cell, in the reference's types: the mean error float64, the four
+    fractions float32 means of 0/1 flags (count / n rounded once: exact sums below 2^24 points).  An empty cell gives what numpy's
+    mean of nothing gives, NaN."""
+    n = int(table[j, c, 0])
+    if n == 0:
+        return (np.float64("nan"),) + (np.float32("nan"),) * 4
+    return (np.float64(esum[j, c]) / n,) + tuple(np.float32(np.float32(int(table[j, c, 2 + k])) / np.float32(n)) for k in range(4))
+
+
+def calculate_metrics(args, data, flow_seq, metrics_per_frame):
+    """utils_eval.py:185-368 with the reference's signature and its meter updates, row by row: `data` is the sample
+    (raw_points, time_indice, sd_labels, fb_labels, scene_flow), `flow_seq` the predicted flow of every point (zeros for
+    frame 0), `metrics_per_frame` the dict of AverageMeters under metric_table_names(args.num_frames); args carries
+    num_frames, eval_ground, range_x, range_y, range_z, ground_slack.  The per-point work is icpflow_seq_metrics (GPU; numpy
+    arrays are uploaded, device tensors are used where they are and only the table comes back); there is no CPU path.
+
+    The reference's quirks, kept:
+      * `overall_0` is weighted with the number of cropped points INCLUDING frame 0 (utils_eval.py:275, len(flow_seq)),
+        although its values average the points of the other frames only;
+      * `overall_j` and `static_j` (and `static_0`, `static_F`) are updated even when the class is empty -- with NaN and weight 0, after
+        which that meter's sums stay NaN; the other four classes skip an empty row (utils_eval.py:226, 234, 242, 254);
+      * the per-scene rows (`*_F`) are weighted 1 per sequence, whatever its size;
+      * with eval_ground nothing is cropped, not even in x and y (utils_eval.py:186-189);
+      * the weights keep the reference's types (len() is an int, sum(mask) a numpy integer): numpy's promotion of a float32 fraction
+        times the weight follows from them.
+    Not kept: the reference prints three lines per gap; pass args.if_verbose to get them."""
+    F = int(args.num_frames)
+    table, esum, kept0, outside = sequence_table(args, data, flow_seq)
+    if outside:
+        raise ValueError(f"{outside} points have a time index outside [0, {F})")
+    present = int(kept0 > 0) + sum(int(table[j, 0, 0] > 0) for j in range(1, F))
+    assert present == args.num_frames, f"{present} frames have points after the crop, args.num_frames is {args.num_frames}"   # utils_eval.py:197-198
+    return update_meters(args, metrics_per_frame, table, esum, kept0)
+
+
+def update_meters(args, metrics_per_frame, table, esum, kept0):
+    """The host half of calculate_metrics: one sequence's table (icpflow_seq_metrics: counts int64 [F,6,6], sums of e
+    float64 [F,6], kept points of frame 0) -> the reference's meter updates (utils_eval.py:200-366)."""
+    with np.errstate(all="ignore"):                      # (NaN rows of empty classes: the reference silences every warning)
+        return _update_meters(args, metrics_per_frame, table, esum, kept0)
+
+
+def _update_meters(args, metrics_per_frame, table, esum, kept0):
+    F = int(args.num_frames)
+    weight = lambda n: np.int64(n) if n else 0          # noqa: E731  (sum(mask): a numpy integer, the int 0 for an empty mask)
+    for j in range(1, F):
+        for c, metric in enumerate(METRIC_CLASSES):
+            n = int(table[j, c, 0])
+            if c >= 2 and n == 0:
+                continue
+            vals = _cell_metrics(table, esum, j, c)
+            if getattr(args, "if_verbose", False) and c in (0, 1, 4):
+                print(f"frame: {j:02d}, {metric:>7}, EPE3D: {vals[0]:.4f}, ACC3DS: {vals[1]:.4f}, ACC3DR: {vals[2]:.4f}, "
+                      f"Outlier: {vals[3]:.4f}, Routlier: {vals[4]:.4f}")
+            metrics_per_frame[f"{metric}_{j:d}"].update(*vals, n if c == 0 else weight(n))
+    total = kept0 + int(table[0, 0, 0])                  # len(flow_seq) after the crop
+    for row, per_scene in ((0, False), (F, True)):
+        for c, metric in enumerate(METRIC_CLASSES):
+            n = int(table[0, c, 0])
+            if c >= 2 and n == 0:
+                continue
+            vals = _cell_metrics(table, esum, 0, c)
+            w = 1 if per_scene else total if c == 0 else weight(n)
+            metrics_per_frame[f"{metric}_{row:d}"].update(*vals, w)
+    return metrics_per_frame

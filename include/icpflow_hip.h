@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* (icpflow_ego_*, the ego-motion estimate, is an addition under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 214 /* (icpflow_seq_*, the evaluation of a sequence, and icpflow_ego_*, the ego-motion estimate, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -713,6 +713,61 @@ int icpflow_ego_register_step(icpflow_ego_t *ego, const float *d_source, int m, 
 int icpflow_ego_map_add(icpflow_ego_t *ego, const float *d_points, int n, const double *h_pose, icpflow_stream_t stream);
 int icpflow_ego_map_export(icpflow_ego_t *ego, int64_t *d_keys, int32_t *d_counts, float *d_points, int capacity,
                            int32_t *d_num, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * 8(f)  evaluation of a whole sequence (a Waymo / nuScenes sample of the reference: m points of F frames, frame j = the
+ * rows with time_indice == j) by the reference's metric protocol, without the points or the flows crossing to the host.
+ * All arrays are row-major and contiguous; points and the ground truth are float64 (a float32 sample is widened by the
+ * caller: exact), labels and time indices int32, poses float64 [4,4] row-major in the column-vector convention.
+ *
+ * icpflow_seq_gt_flow -- replaces utils_loading.py:21-31 (ego_motion_compensation), :33-48 (reconstruct_sequence) and the
+ *   subtraction of dataset_pca.py:66-69.  Per row, in fp64, every operation rounded by itself
+ *   (((R0 x + R1 y) + R2 z) + t per coordinate):
+ *       p_ego  = R_ego[t] p + t_ego[t]                     d_ego [F,4,4]; NULL = this step is skipped
+ *       p_full = R_inst[inst * F + t] p_ego + t_inst[..]   d_inst_tsfm [K,F,4,4], inst = d_inst_labels[row]; NULL = skipped
+ *       out    = p_full - p (ICPFLOW_SEQ_OUT_FLOW: the scene flow) or p_full (ICPFLOW_SEQ_OUT_POINTS: what the two functions
+ *                of the reference return, one step each)
+ *   d_out float64 [m,3].  A row with t outside [0, F) or inst outside [0, K) is NOT computed: nothing is written for it and
+ *   it is counted in d_bad_rows (int64 [1]).  numpy's wrap-around of a negative index (tsfm[-1] is the last pose) is NOT
+ *   reproduced, and inst and t are checked each by itself, where the reference checks only their combination inst * F + t.
+ *
+ * icpflow_seq_metrics -- replaces utils_eval.py:24-63 (crop_data), :162-180 (compute_epe_test's per-point part) and the
+ *   masks and sums of :185-368 (calculate_metrics); the meters' arithmetic on the resulting table is host code
+ *   (icp_flow_amd/utils_eval.py).  One pass over the rows.  A row is kept (utils_eval.py:33-38) when
+ *       crop = ICPFLOW_SEQ_CROP_NONE: always          (calculate_metrics with eval_ground, which does not crop at all)
+ *       crop = ICPFLOW_SEQ_CROP_XY:   |x| < range_x and |y| < range_y                      (crop_data with eval_ground)
+ *       crop = ICPFLOW_SEQ_CROP_XYZ:  ... and z > z_min, z_min = range_z + ground_slack    (crop_data without)
+ *   -- thresholds as the caller rounds them: numpy compares a float32 coordinate with the float32-rounded threshold.
+ *   Per kept row, in fp64 with numpy's operation order: d = gt - pred (d_pred_flow float32 [m,3], as the flow kernel leaves
+ *   it; widened), e = sqrt((dx dx + dy dy) + dz dz), r = e / (sqrt((gx gx + gy gy) + gz gz) + 1e-20), the square root
+ *   correctly rounded and the division IEEE; nothing is contracted into a fused multiply-add.  Predicates
+ *   (utils_eval.py:170-180): e < 0.05 or r < 0.05;  e < 0.1 or r < 0.1;  e > 0.3 or r > 0.1;  e > 0.3 and r > 0.3.
+ *   d_table int64 [F][6][6]: row j = 1 .. F-1 is gap j (the kept rows with time index j), row 0 the sum of the gap rows (the
+ *   reference's rows 0 and F: every kept point of a frame other than 0); classes in the order overall, static (sd == 0),
+ *   static_bg (sd == 0 and fb == 0), static_fg (sd == 0 and fb == 1), dynamic (sd == 1), dynamic_fg (sd == 1 and fb == 1) --
+ *   a row whose labels are neither 0 nor 1 counts in `overall` only; values: number of rows, sum of e (the BITS OF A
+ *   float64 in the int64 word), and the number of rows satisfying each of the four predicates.
+ *   d_info int64 [2]: the kept rows of frame 0 (utils_eval.py:275 weights `overall_0` with len(flow_seq), which includes
+ *   them), and the rows whose time index is outside [0, F) (counted nowhere else).
+ *   Counts are exact.  The sums of e are a function of the arguments alone -- not of the device, the stream or the
+ *   scheduling: a fixed reduction order, no floating-point atomics (csrc/seqeval.hip).  F > ICPFLOW_SEQ_MAX_FRAMES is
+ *   ICPFLOW_E_LIMIT (the table of a workgroup lives in LDS).
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_SEQ_MAX_FRAMES 16
+#define ICPFLOW_SEQ_OUT_FLOW 0
+#define ICPFLOW_SEQ_OUT_POINTS 1
+#define ICPFLOW_SEQ_CROP_NONE 0
+#define ICPFLOW_SEQ_CROP_XY 1
+#define ICPFLOW_SEQ_CROP_XYZ 2
+size_t icpflow_seq_gt_flow_workspace_bytes(int m);
+int icpflow_seq_gt_flow(const double *d_points, const int32_t *d_time_indice, const int32_t *d_inst_labels, int m,
+                        const double *d_ego, int F, const double *d_inst_tsfm, int K, int output, double *d_out,
+                        int64_t *d_bad_rows, void *d_ws, size_t ws_bytes, icpflow_stream_t stream);
+size_t icpflow_seq_metrics_workspace_bytes(int m, int F);
+int icpflow_seq_metrics(const double *d_points, const int32_t *d_time_indice, const int32_t *d_sd_labels,
+                        const int32_t *d_fb_labels, const double *d_gt_flow, const float *d_pred_flow, int m, int F, int crop,
+                        double range_x, double range_y, double z_min, int64_t *d_table, int64_t *d_info, void *d_ws,
+                        size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Diagnostics: the vote kernels evaluate (v - min) / (max - min) with the loop-invariant part of
