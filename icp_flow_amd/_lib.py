@@ -89,6 +89,9 @@ SIGNATURES = {
     "icpflow_seq_gt_flow": (_i, [_p, _p, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "icpflow_seq_metrics_workspace_bytes": (_sz, [_i, _i]),
     "icpflow_seq_metrics": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _p, _p, _p, _sz, _p]),
+    "icpflow_ground_default_params": (_i, [_p]),
+    "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
+    "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "icpflow_selftest_vote_quotient": (_i, [_p, _i, _f, _f, _p, _p, _p]),
     "icpflow_selftest_kabsch": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
     "icpflow_profile_create": (_i, [_i, ctypes.POINTER(_p)]),
@@ -112,6 +115,7 @@ def call(name, *args):
         raise RuntimeError(f"{name} failed (code {rc}): {msg.decode() if msg else ''}")
 
 
+GROUND_PATCHES, GROUND_TABLE_COLS = 504, 16
 SEQ_MAX_FRAMES = 16
 SEQ_OUT_FLOW, SEQ_OUT_POINTS = 0, 1
 SEQ_CROP_NONE, SEQ_CROP_XY, SEQ_CROP_XYZ = 0, 1, 2
@@ -208,6 +212,20 @@ class EgoParams(ctypes.Structure):
             if not hasattr(p, k):
                 raise TypeError(f"icpflow_ego_params_t has no field {k!r}")
             setattr(p, k, v)
+        return p
+
+
+class GroundParams(ctypes.Structure):
+    """icpflow_ground_params_t: the constants of the ground segmentation (utils_ground.py:52-57, patchworkpp.h:75-107)."""
+    _fields_ = [("struct_size", _sz), ("sensor_height", _d), ("min_range", _d), ("max_range", _d), ("th_seeds", _d), ("th_dist", _d),
+                ("th_seeds_v", _d), ("th_dist_v", _d), ("uprightness_thr", _d), ("adaptive_seed_selection_margin", _d),
+                ("num_iter", _i), ("num_lpr", _i), ("num_min_pts", _i), ("num_rings_of_interest", _i),
+                ("num_sectors_each_zone", _i * 4), ("num_rings_each_zone", _i * 4)]
+
+    @staticmethod
+    def defaults():
+        p = GroundParams()
+        call("icpflow_ground_default_params", ctypes.byref(p))
         return p
 
 

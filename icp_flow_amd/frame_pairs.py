@@ -38,7 +38,7 @@ read-back per sequence -- the table from which the reference's 6 x (num_frames +
 on the GPU (dataset_pca.py:66-69, utils_loading.py).
 
     python -m icp_flow_amd.frame_pairs DIR --protocol reference --num-frames 5 --range-x 32 --range-y 32 [--eval-ground]
-                                           [--range-z 0.0 --ground-slack 0.3]
+                                           [--range-z 0.0 --ground-slack 0.3] [--ground patchwork]
 """
 import argparse
 import glob
@@ -770,9 +770,21 @@ def load_sequence_sample(path, args):
 
 def _sequence_ground(args, sample, fps):
     """Ground removal stays upstream of the registration: the sample's `nonground` key (load_sequence has put it into the frame
-    pairs), else the height threshold of utils_ground.segment_ground_thres on the raw points (utils_ground.py:27-30; Patchwork++,
-    the other half of the reference's segment_ground, is not built) when args carries range_z / ground_slack.  -> how"""
+    pairs), else the height threshold of utils_ground.segment_ground_thres on the raw points (utils_ground.py:27-30; under "auto"
+    Patchwork++, the other half of the reference's segment_ground, is not applied) when args carries range_z / ground_slack.  Opt-in,
+    args.ground == "patchwork": the reference's own segment_ground (Patchwork++ AND the threshold) per frame on the raw points
+    of each time_indice, like dataset_pca.py:152-161, whatever key the sample carries.  -> how"""
     from . import utils_ground
+    if getattr(args, "ground", "auto") == "patchwork":
+        if getattr(args, "range_z", None) is None or getattr(args, "ground_slack", None) is None:
+            raise ValueError("ground = 'patchwork' needs range_z and ground_slack (the threshold half of segment_ground)")
+        t = sample["time_indice"]
+        ng = np.zeros(len(t), dtype=bool)
+        for j in np.unique(t):
+            ng[t == j] = utils_ground.segment_ground(args, sample["raw_points"][t == j, 0:3])
+        for fp in fps:
+            fp.nonground_src, fp.nonground_dst = ng[t == fp.gap], ng[t == 0]
+        return "patchwork+threshold"
     if sample["nonground"] is not None:
         return "nonground key"
     if getattr(args, "range_z", None) is None or getattr(args, "ground_slack", None) is None:
@@ -933,6 +945,9 @@ def main(argv=None):
     ap.add_argument("--range-z", type=float, default=0.0, help="--protocol reference: ground <= range_z (main.py:73)")
     ap.add_argument("--ground-slack", type=float, default=0.3, help="--protocol reference (main.py:113)")
     ap.add_argument("--eval-ground", action="store_true", help="--protocol reference: evaluate ground points too (main.py:115)")
+    ap.add_argument("--ground", choices=("auto", "patchwork"), default="auto",
+                    help="--protocol reference: auto = the file's nonground key, else the height threshold; patchwork = "
+                         "Patchwork++ AND the threshold per frame on the GPU (utils_ground.py:16-23)")
     ns = ap.parse_args(argv)
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -952,6 +967,7 @@ def main(argv=None):
         if args.range_x is None or args.range_y is None:
             args.range_x, args.range_y = 32.0, 32.0                                    # main.py:69-72
         args.num_frames, args.range_z, args.ground_slack, args.eval_ground = ns.num_frames, ns.range_z, ns.ground_slack, ns.eval_ground
+        args.ground = ns.ground
         res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_sequence(p)], device, in_flight=ns.in_flight)
         print(utils_eval.format_metric_table(res.pop("metrics"), args.num_frames))
         print(json.dumps(res))

@@ -770,6 +770,68 @@ int icpflow_seq_metrics(const double *d_points, const int32_t *d_time_indice, co
                         size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
+ * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
+ * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
+ * deviations).
+ *
+ * icpflow_ground_default_params -- replaces utils_ground.py:52-57 and the constructor defaults of patchworkpp.h:75-107.
+ * icpflow_ground_segment -- replaces utils_ground.py:43-66 (segment_ground_pypatchworkpp) = estimateGround of
+ *   patchworkpp.cpp:141-319 with pc2czm :561-605, extract_initial_seeds :67-139, estimate_plane :37-65,
+ *   extract_piecewiseground :450-532, temporal_ground_revert :385-447 and calc_mean_stdev :540-549.
+ *   d_points float32 [n] rows of `stride` >= 3 floats (x, y, z first); d_nonground uint8 [n]: 1 = non-ground (rows out of
+ *   range, rows with a non-finite coordinate and the rows of patches with fewer than num_min_pts points are non-ground).
+ *   d_patch_table (may be NULL) float64 [ICPFLOW_GROUND_PATCHES][ICPFLOW_GROUND_TABLE_COLS]; patch = the zone's first patch
+ *   (0, 32, 160, 376) + ring * sectors + sector; columns:
+ *       0      points of the patch                      1      points of its ground part (R-GPF's last round)
+ *       2-4    mean of the last plane estimate           5-7    its normal (normal_z >= 0)
+ *       8-10   its singular values, descending           11     d = -normal . mean
+ *       12     the decision, ICPFLOW_GROUND_*            13     the revert, ICPFLOW_GROUND_TGR_*
+ *       14     points R-VPF removed                      15     0
+ *   A patch with fewer than num_min_pts points has its count and zeros.  A plane estimated from a single point is NaN
+ *   (0 / 0, IEEE): every comparison with it is false and the patch ends non-ground.
+ *   The workspace is the caller's: icpflow_ground_workspace_bytes(n, params) bytes, 8-byte aligned; nothing in it is read
+ *   before it is written; fewer bytes are ICPFLOW_E_WORKSPACE before anything is written.  Asynchronous on `stream`, no host
+ *   round trip.  n == 0 succeeds and writes nothing.  The result is a function of the arguments alone: fixed reduction
+ *   orders, no floating-point atomics, a patch's points in row order (csrc/ground.hip).  One zone layout is built: rings
+ *   {2,4,4,4}, sectors {16,32,54,32}, 4 rings of interest; any other is ICPFLOW_E_ARG ("zone layout").
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_GROUND_PATCHES 504
+#define ICPFLOW_GROUND_TABLE_COLS 16
+#define ICPFLOW_GROUND_TOO_FEW 0     /* fewer than num_min_pts points: non-ground      */
+#define ICPFLOW_GROUND_NOT_UPRIGHT 1 /* normal_z <= uprightness_thr: non-ground        */
+#define ICPFLOW_GROUND_FAR 2         /* upright, outside the rings of interest: ground */
+#define ICPFLOW_GROUND_HEADING 3     /* mean . normal >= 0: non-ground                 */
+#define ICPFLOW_GROUND_ACCEPTED 4    /* mean_z < 0 (or flat): ground                   */
+#define ICPFLOW_GROUND_CANDIDATE 5   /* decided by the temporal ground revert          */
+#define ICPFLOW_GROUND_TGR_NONE 0
+#define ICPFLOW_GROUND_TGR_REVERTED 1 /* back to ground */
+#define ICPFLOW_GROUND_TGR_REJECTED 2 /* non-ground     */
+typedef struct icpflow_ground_params {
+    size_t struct_size;                    /* sizeof(icpflow_ground_params_t) */
+    double sensor_height;                  /* 1.723  (utils_ground.py:55) */
+    double min_range;                      /* 1.0    (utils_ground.py:56) */
+    double max_range;                      /* 64     (utils_ground.py:57) */
+    double th_seeds;                       /* 0.125 */
+    double th_dist;                        /* 0.125 */
+    double th_seeds_v;                     /* 0.25 */
+    double th_dist_v;                      /* 0.1 */
+    double uprightness_thr;                /* 0.707 */
+    double adaptive_seed_selection_margin; /* -1.2 */
+    int num_iter;                          /* 3 */
+    int num_lpr;                           /* 20 */
+    int num_min_pts;                       /* 10 */
+    int num_rings_of_interest;             /* 4 */
+    int num_sectors_each_zone[4];          /* {16, 32, 54, 32} */
+    int num_rings_each_zone[4];            /* {2, 4, 4, 4} */
+} icpflow_ground_params_t;
+int icpflow_ground_default_params(icpflow_ground_params_t *params);
+size_t icpflow_ground_workspace_bytes(int n, const icpflow_ground_params_t *params);
+int icpflow_ground_segment(const float *d_points, int stride, int n, const icpflow_ground_params_t *params,
+                           uint8_t *d_nonground, double *d_patch_table, void *d_ws, size_t ws_bytes,
+                           icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Diagnostics: the vote kernels evaluate (v - min) / (max - min) with the loop-invariant part of
  * the IEEE division hoisted (hist.hip, AxisQuot).  For numerators d_a [n] this returns that
  * quotient (d_fast) next to the compiler's correctly rounded a / (max - min) (d_ieee); the two
