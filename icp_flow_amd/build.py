@@ -1,6 +1,7 @@
 """Build libicpflow_hip.so in-tree with hipcc for gfx950 (no torch, no cmake).
 
     python icp_flow_amd/build.py [--force] [--save-temps]
+    python icp_flow_amd/build.py --define NAME[=VALUE] ... --out PATH [--dry-run]     an instrumented variant
 
 hipcc cross-compiles without a GPU; the .so travels with the tree to the GPU box.  Every source is
 compiled to its own object (in parallel, cached by content hash under csrc/_obj/) and linked once.
@@ -10,7 +11,12 @@ Flags that matter for parity:
                                             correctly rounded sqrt of the NN distances
 The library carries the hash of the sources it was built from (icpflow_build_info()); a library whose
 hash differs from the tree's is stale and rebuilt, whatever the file times say.
+
+SOURCES, HEADERS and CFLAGS below are the only copy of what the library is built from.  A variant (tools/dbg: the same
+sources with extra -D defines, linked to a path of its own) is built by build(defines=..., out=...); its objects are cached
+under csrc/_obj/variant/, so it neither replaces the product library nor evicts the product's objects.
 """
+import argparse
 import concurrent.futures
 import hashlib
 import os
@@ -23,7 +29,7 @@ OBJ = os.path.join(CSRC, "_obj")
 OUT = os.path.join(HERE, "libicpflow_hip.so")
 SOURCES = ["api.hip", "hist.hip", "nn.hip", "icp.hip", "icp_fp32.hip", "pose.hip", "sort.hip", "cluster.hip", "hdbscan.hip", "table.hip", "assoc.hip", "frame.hip", "ego.hip", "seqeval.hip", "ground.hip",
            "hdbscan_tree.cpp"]
-HEADERS = ["common.hpp", "scan.hpp", "kernels.hpp", "kabsch.hpp", "posefuse.hpp", "votekey.hpp", "cluster_util.hpp", "sortdir.hpp",
+HEADERS = ["common.hpp", "scan.hpp", "kernels.hpp", "kabsch.hpp", "posefuse.hpp", "votekey.hpp", "cluster_util.hpp", "sortdir.hpp", "host.hpp", "carver.hpp",
            os.path.join("..", "..", "include", "icpflow_hip.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
@@ -75,35 +81,71 @@ def stale():
     return built_hash() != source_hash()
 
 
-def _compile(src, extra):
+def _object(src, extra, objdir):
     hdr = _digest([os.path.join(CSRC, f) for f in HEADERS], CFLAGS + list(extra))
     tag = _digest([os.path.join(CSRC, src)], [hdr])[:16]
-    obj = os.path.join(OBJ, f"{os.path.splitext(src)[0]}.{tag}.o")
-    if not os.path.exists(obj) or "-save-temps=obj" in extra:
-        for old in os.listdir(OBJ):
+    return os.path.join(objdir, f"{os.path.splitext(src)[0]}.{tag}.o")
+
+
+def _compile(src, obj, argv):
+    if not os.path.exists(obj) or "-save-temps=obj" in argv:
+        os.makedirs(os.path.dirname(obj), exist_ok=True)
+        for old in os.listdir(os.path.dirname(obj)):   # (the older objects of this source, in this directory only)
             if old.startswith(os.path.splitext(src)[0] + ".") and old.endswith(".o"):
-                os.remove(os.path.join(OBJ, old))
-        subprocess.check_call([hipcc()] + CFLAGS + list(extra) + ["-c", os.path.join(CSRC, src), "-o", obj], cwd=CSRC)
+                os.remove(os.path.join(os.path.dirname(obj), old))
+        subprocess.check_call(argv, cwd=CSRC)
     return obj
 
 
-def build(force=False, extra=()):
-    if not force and not stale():
-        return OUT
-    os.makedirs(OBJ, exist_ok=True)
+def plan(defines=(), out=None, extra=()):
+    """The commands of one build, nothing run: {"compile": {source: argv}, "link": argv, "out": path}.  With an `out` of
+    its own it is a variant: every source of SOURCES with CFLAGS and -D<d> for each d of `defines` (["NAME", "NAME=VALUE",
+    ...]), objects under csrc/_obj/variant/."""
+    out = os.path.abspath(out) if out else OUT
+    variant = out != OUT
+    if defines and not variant:
+        raise ValueError("a build with defines is a variant: give it an `out` of its own (the product library is built as shipped)")
+    objdir = os.path.join(OBJ, "variant") if variant else OBJ
+    extra = list(extra) + ["-D" + d for d in defines]
     stamp = source_hash()
-    jobs = {}
+    compile_, objs = {}, []
+    for src in SOURCES:
+        # only api.hip sees the hash (the other objects stay cached when an unrelated file changes)
+        e = extra + ([f'-DICPFLOW_SOURCE_HASH="{stamp}"'] if src == "api.hip" else [])
+        objs.append(_object(src, e, objdir))
+        compile_[src] = [hipcc()] + CFLAGS + e + ["-c", os.path.join(CSRC, src), "-o", objs[-1]]
+    return {"compile": compile_, "link": [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out + ".tmp"], "out": out}
+
+
+def build(force=False, extra=(), defines=(), out=None, dry_run=False):
+    """Build the product library (only when it is stale, or with force) or, with defines / out, a variant (always linked
+    anew).  dry_run: -> plan(), nothing compiled."""
+    p = plan(defines, out, extra)
+    if dry_run:
+        return p
+    if p["out"] == OUT and not force and not stale():
+        return OUT
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
-        for src in SOURCES:
-            # only api.hip sees the hash (the other objects stay cached when an unrelated file changes)
-            e = list(extra) + ([f'-DICPFLOW_SOURCE_HASH="{stamp}"'] if src == "api.hip" else [])
-            jobs[src] = ex.submit(_compile, src, e)
-        objs = [jobs[s].result() for s in SOURCES]
-    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", OUT + ".tmp"], cwd=CSRC)
-    os.replace(OUT + ".tmp", OUT)
-    return OUT
+        jobs = [ex.submit(_compile, src, argv[-1], argv) for src, argv in p["compile"].items()]
+        for j in jobs:
+            j.result()
+    subprocess.check_call(p["link"], cwd=CSRC)
+    os.replace(p["out"] + ".tmp", p["out"])
+    return p["out"]
 
 
 if __name__ == "__main__":
-    extra = ["-save-temps=obj"] if "--save-temps" in sys.argv else []
-    print(build(force="--force" in sys.argv or bool(extra), extra=extra), source_hash())
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--force", action="store_true")
+    ap.add_argument("--save-temps", action="store_true")
+    ap.add_argument("--define", action="append", default=[], metavar="NAME[=VALUE]", help="build a variant with -DNAME[=VALUE] (repeatable)")
+    ap.add_argument("--out", metavar="PATH", help="where the variant is linked to")
+    ap.add_argument("--dry-run", action="store_true", help="print the commands, run nothing")
+    a = ap.parse_args()
+    extra = ["-save-temps=obj"] if a.save_temps else []
+    res = build(force=a.force or bool(extra), extra=extra, defines=a.define, out=a.out, dry_run=a.dry_run)
+    if a.dry_run:
+        for argv in list(res["compile"].values()) + [res["link"]]:
+            print(" ".join(argv))
+    else:
+        print(res, source_hash())

@@ -8,6 +8,7 @@
 #include "kernels.hpp"
 #include "posefuse.hpp"
 #include "kabsch.hpp"
+#include "host.hpp"
 
 using namespace icpflow;
 
@@ -15,28 +16,22 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, ...)
+}  // namespace
+
+namespace icpflow {
+// what icpflow_last_error returns, for the entry points of every file (host.hpp)
+int report_error(int code, const char *message)
+{
+    snprintf(g_err, sizeof(g_err), "%s", message);
+    return code;
+}
+
+int report_errorf(int code, const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
-    return code;
-}
-
-int hipfail(hipError_t e, const char *what)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return (int)e;
-}
-
-}  // namespace
-
-namespace icpflow {
-// icpflow_last_error for the entry points that live in other files (frame.hip)
-int report_error(int code, const char *message)
-{
-    snprintf(g_err, sizeof(g_err), "%s", message);
     return code;
 }
 
@@ -80,12 +75,6 @@ hipError_t launch_kabsch_probe(const double *H, const double *gsum, int n, int m
 }  // namespace icpflow
 
 namespace {
-
-#define ICPFLOW_TRY(expr)                                  \
-    do {                                                   \
-        hipError_t e__ = (expr);                           \
-        if (e__ != hipSuccess) return hipfail(e__, #expr); \
-    } while (0)
 
 // The options of one call (icpflow_options_t, validated): nothing here outlives the call.
 struct Opts {
@@ -148,9 +137,6 @@ inline bool score_by_sweep(int N, bool sortedAnyway, const Opts &o)
     const int minN = (sortedAnyway && o.on(ICPFLOW_OPT_NO_SCORE_PRUNE)) ? kScoreSweepMinNSorted : kScoreSweepMinN;
     return N > minN && N <= kMaxSortN && o.on(ICPFLOW_OPT_NO_SCORE_SWEEP);
 }
-constexpr size_t kAlign = 256;
-size_t up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-
 // One carve of the caller's workspace; the same layout backs workspace_bytes().
 struct Workspace {
     int32_t *lenA = nullptr, *lenC = nullptr;
@@ -189,82 +175,77 @@ struct Workspace {
 
     Workspace(void *base, int B, int N, size_t L)
     {
-        size_t off = 0;
-        auto take = [&](size_t n) {
-            void *p = base ? (void *)((char *)base + off) : nullptr;
-            off += up(n);
-            return p;
-        };
+        Carver mem(base);
         const size_t b = (size_t)B;
-        lenA = (int32_t *)take(b * 4);
-        lenC = (int32_t *)take(b * 4);
-        swap = (uint8_t *)take(b);
-        bins = (uint32_t *)take(b * L * 4);
-        volA = (uint32_t *)take(b * L * 4);
-        volB = (uint32_t *)take(b * L * 4);
-        peakVotes = (float *)take(b * kTopK * 4);
-        peakIdx = (int64_t *)take(b * kTopK * 8);
-        cand = (float *)take(b * kCand * 3 * 4);
+        lenA = mem.take<int32_t>(b * 4);
+        lenC = mem.take<int32_t>(b * 4);
+        swap = mem.take<uint8_t>(b);
+        bins = mem.take<uint32_t>(b * L * 4);
+        volA = mem.take<uint32_t>(b * L * 4);
+        volB = mem.take<uint32_t>(b * L * 4);
+        peakVotes = mem.take<float>(b * kTopK * 4);
+        peakIdx = mem.take<int64_t>(b * kTopK * 8);
+        cand = mem.take<float>(b * kCand * 3 * 4);
         {
             size_t qb = (size_t)(scan_qblocks(N, B) > sweep_qblocks(N) ? scan_qblocks(N, B) : sweep_qblocks(N));
             if ((size_t)score_qblocks(N) > qb) qb = (size_t)score_qblocks(N);
-            partial = (double *)take(b * 12 * qb * kPartial * 8);
-            scoreAccum = (double *)take(b * 12 * 8);
+            partial = mem.take<double>(b * 12 * qb * kPartial * 8);
+            scoreAccum = mem.take<double>(b * 12 * 8);
             // (the sweeps' delivery counters right behind it: the clear at the start of a registration covers both -- accumBytes --,
             // and every sweep launch leaves its counters at zero again, so that none of them needs a memset of its own)
-            ticketScratch = (int *)take(256);   // (the count of the scoring's listed scans: grid.sweepTicket once a call has cleared it)
-            if (shareScratch(B, N)) grid.shareCount = (int *)take(b * 12 * kSweepShareSlots * 4);
-            accumBytes = up(b * 12 * 8) + up(256) + (shareScratch(B, N) ? up(b * 12 * kSweepShareSlots * 4) : 0);
+            ticketScratch = mem.take<int>(256);   // (the count of the scoring's listed scans: grid.sweepTicket once a call has cleared it)
+            if (shareScratch(B, N)) grid.shareCount = mem.take<int>(b * 12 * kSweepShareSlots * 4);
+            accumBytes = align256(b * 12 * 8) + align256(256) + (shareScratch(B, N) ? align256(b * 12 * kSweepShareSlots * 4) : 0);
         }
-        Tinit = (float *)take(b * 16 * 4);
-        M = (float *)take(b * 16 * 4);
-        state = (IcpState *)take(b * sizeof(IcpState));
-        ctrl = (IcpCtrl *)take(icp_ctrl_bytes(B));   // + the helpers' per-pair words and tags, cleared with it
-        helpState = (float *)take(b * 32 * 4);
-        helpOut = (double *)take((size_t)kHelpMaxWG * kHelpOutStride * 8);
+        Tinit = mem.take<float>(b * 16 * 4);
+        M = mem.take<float>(b * 16 * 4);
+        state = mem.take<IcpState>(b * sizeof(IcpState));
+        ctrl = mem.take<IcpCtrl>(icp_ctrl_bytes(B));   // + the helpers' per-pair words and tags, cleared with it
+        helpState = mem.take<float>(b * 32 * 4);
+        helpOut = mem.take<double>((size_t)kHelpMaxWG * kHelpOutStride * 8);
         grid.H = grid_buckets(N);
-        grid.origin = (float *)take(b * 4 * 4);
-        grid.start = (int32_t *)take(b * ((size_t)grid.H + 1) * 4);
-        grid.cursor = (int32_t *)take(b * (size_t)grid.H * 4);
-        grid.pts = (float *)take(b * (size_t)N * 16);
-        grid.sortX = (float *)take(b * (size_t)N * 16);
-        grid.sortYsoa = (float *)take(b * 3 * (size_t)((N + 15) / 16 * 16) * 4 + 256);  // + prefetch slack
-        grid.sortXsoa = (float *)take(b * 3 * (size_t)((N + 15) / 16 * 16) * 4 + 256);
-        zsortA = (float *)take(b * (size_t)N * 16);
-        zsortC = (float *)take(b * (size_t)N * 16);
-        voteKey = (float *)take(b * 8 * 4);
+        grid.origin = mem.take<float>(b * 4 * 4);
+        grid.start = mem.take<int32_t>(b * ((size_t)grid.H + 1) * 4);
+        grid.cursor = mem.take<int32_t>(b * (size_t)grid.H * 4);
+        grid.pts = mem.take<float>(b * (size_t)N * 16);
+        grid.sortX = mem.take<float>(b * (size_t)N * 16);
+        grid.sortYsoa = mem.take<float>(b * 3 * (size_t)((N + 15) / 16 * 16) * 4 + 256);  // + prefetch slack
+        grid.sortXsoa = mem.take<float>(b * 3 * (size_t)((N + 15) / 16 * 16) * 4 + 256);
+        zsortA = mem.take<float>(b * (size_t)N * 16);
+        zsortC = mem.take<float>(b * (size_t)N * 16);
+        voteKey = mem.take<float>(b * 8 * 4);
         voteWorkCap = vote_work_capacity(B, N);
-        if (voteWorkCap != 0) { voteWork = (int32_t *)take(voteWorkCap * 4); pairOrder = (int32_t *)take(b * 4); }
+        if (voteWorkCap != 0) { voteWork = mem.take<int32_t>(voteWorkCap * 4); pairOrder = mem.take<int32_t>(b * 4); }
         if (N > kChunkSortMinN) {   // scratch of the multi-workgroup sorts (one set per concurrent sort)
             const size_t cs = b * 2 * (size_t)chunk_sort_length(N) * 4;
-            grid.ckey = (float *)take(cs);
-            grid.cidx = (int *)take(cs);
-            zckey = (float *)take(cs);
-            zcidx = (int *)take(cs);
-            pairBox = (float *)take(b * kPairBoxStride * 4);
+            grid.ckey = mem.take<float>(cs);
+            grid.cidx = mem.take<int>(cs);
+            zckey = mem.take<float>(cs);
+            zcidx = mem.take<int>(cs);
+            pairBox = mem.take<float>(b * kPairBoxStride * 4);
         }
-        grid.axis = (int32_t *)take(b * 4);
-        grid.scoreList = (int *)take(b * 12 * 4);
+        grid.axis = mem.take<int32_t>(b * 4);
+        grid.scoreList = mem.take<int>(b * 12 * 4);
         // (occupancy grids of both sorted clouds for the pre-bound of the scoring sweeps, nn.hip: 24 KiB per pair)
         if (N <= kMaxSortN) {
-            grid.occHdr = (float *)take(b * 2 * 8 * 4);
-            grid.occBits = (uint32_t *)take(b * 2 * (size_t)kOccRings * kOccWords * 4);
+            grid.occHdr = mem.take<float>(b * 2 * 8 * 4);
+            grid.occBits = mem.take<uint32_t>(b * 2 * (size_t)kOccRings * kOccWords * 4);
         }
         // (sweeps of a small cloud against a long one, shared by several blocks: nn.hip; only where the partial minima stay small)
         if (shareScratch(B, N)) {
-            grid.shareBest = (float *)take(b * 12 * kSweepShareSlots * 256 * 4);
-            if (B <= 32767 && N <= 255 * 256) pairTab = (int32_t *)take(b * 4 * 4);
+            grid.shareBest = mem.take<float>(b * 12 * kSweepShareSlots * 256 * 4);
+            if (B <= 32767 && N <= 255 * 256) pairTab = mem.take<int32_t>(b * 4 * 4);
         }
-        history = (float *)take(b * (size_t)kHistIters * kHistStride * 4);
+        history = mem.take<float>(b * (size_t)kHistIters * kHistStride * 4);
         team.maxWG = 1024;
-        team.wgPair = (int32_t *)take((size_t)team.maxWG * 4);
-        team.wgRank = (int32_t *)take((size_t)team.maxWG * 4);
-        team.teamSize = (int32_t *)take(b * 4);
-        team.next = (int32_t *)take(b * 4);
-        team.arrived = (unsigned int *)take(b * 4);
-        team.mom = (double *)take((b < 256 ? b : 256) * 2 * (size_t)kMaxTeam * kTeamStride * 8);
-        icpSplit = (int32_t *)take((b + 64) * 4);
-        bytes = off;
+        team.wgPair = mem.take<int32_t>((size_t)team.maxWG * 4);
+        team.wgRank = mem.take<int32_t>((size_t)team.maxWG * 4);
+        team.teamSize = mem.take<int32_t>(b * 4);
+        team.next = mem.take<int32_t>(b * 4);
+        team.arrived = mem.take<unsigned int>(b * 4);
+        team.mom = mem.take<double>((b < 256 ? b : 256) * 2 * (size_t)kMaxTeam * kTeamStride * 8);
+        icpSplit = mem.take<int32_t>((b + 64) * 4);
+        bytes = mem.total();
     }
 };
 
@@ -285,20 +266,20 @@ int parse_options(const char *fn, const icpflow_options_t *opt, Opts &o)
 {
     if (opt == nullptr) return 0;
     if (opt->struct_size != sizeof(icpflow_options_t))
-        return fail(ICPFLOW_E_ARG, "%s: options struct_size %zu, this library expects %zu", fn, opt->struct_size,
-                    sizeof(icpflow_options_t));
+        return report_errorf(ICPFLOW_E_ARG, "%s: options struct_size %zu, this library expects %zu", fn, opt->struct_size,
+                             sizeof(icpflow_options_t));
     if (opt->icp_search < 0 || opt->icp_search > 3)
-        return fail(ICPFLOW_E_ARG, "%s: options.icp_search must be 0..3 (got %d)", fn, opt->icp_search);
+        return report_errorf(ICPFLOW_E_ARG, "%s: options.icp_search must be 0..3 (got %d)", fn, opt->icp_search);
     if (opt->icp_arith != ICPFLOW_ARITH_FP64 && opt->icp_arith != ICPFLOW_ARITH_FP32_REFERENCE)
-        return fail(ICPFLOW_E_ARG, "%s: options.icp_arith must be 0 or 1 (got %d)", fn, opt->icp_arith);
-    if (opt->flags >> 19) return fail(ICPFLOW_E_ARG, "%s: unknown option flags 0x%x", fn, opt->flags);
+        return report_errorf(ICPFLOW_E_ARG, "%s: options.icp_arith must be 0 or 1 (got %d)", fn, opt->icp_arith);
+    if (opt->flags >> 19) return report_errorf(ICPFLOW_E_ARG, "%s: unknown option flags 0x%x", fn, opt->flags);
     o.search = opt->icp_search;
     o.arith = opt->icp_arith;
     o.flags = opt->flags;
     o.profile = reinterpret_cast<LaunchProfile *>(opt->profile);
     o.voteBins = opt->d_vote_bins_u32;
     if ((opt->d_icp_init_R == nullptr) != (opt->d_icp_init_T == nullptr))
-        return fail(ICPFLOW_E_ARG, "%s: options.d_icp_init_R and d_icp_init_T come together", fn);
+        return report_errorf(ICPFLOW_E_ARG, "%s: options.d_icp_init_R and d_icp_init_T come together", fn);
     o.initR = opt->d_icp_init_R;
     o.initT = opt->d_icp_init_T;
     o.history = opt->d_icp_history;
@@ -308,7 +289,7 @@ int parse_options(const char *fn, const icpflow_options_t *opt, Opts &o)
     o.initS = opt->d_icp_init_s;
     o.pairActive = opt->d_pair_active;
     if (o.initS != nullptr && o.initR == nullptr)
-        return fail(ICPFLOW_E_ARG, "%s: options.d_icp_init_s comes with d_icp_init_R / d_icp_init_T", fn);
+        return report_errorf(ICPFLOW_E_ARG, "%s: options.d_icp_init_s comes with d_icp_init_R / d_icp_init_T", fn);
     return 0;
 }
 
@@ -316,11 +297,11 @@ int parse_options(const char *fn, const icpflow_options_t *opt, Opts &o)
 int check_pair_active(const char *fn, const Opts &o, bool fused, int maxIter, int stopMode)
 {
     if (o.pairActive == nullptr) return 0;
-    if (!fused) return fail(ICPFLOW_E_ARG, "%s: options.d_pair_active is honoured by icpflow_hist_icp / icpflow_hist_icp_eval only", fn);
+    if (!fused) return report_errorf(ICPFLOW_E_ARG, "%s: options.d_pair_active is honoured by icpflow_hist_icp / icpflow_hist_icp_eval only", fn);
     if (stopMode != ICPFLOW_STOP_REFERENCE || maxIter < 2 || maxIter > kHistIters || !o.on(ICPFLOW_OPT_NO_SPECULATIVE) ||
         o.arith != ICPFLOW_ARITH_FP64)
-        return fail(ICPFLOW_E_ARG, "%s: options.d_pair_active needs the single-launch reference stop (2 <= max_iterations <= %d, "
-                                   "fp64 arithmetic, speculation on)", fn, kHistIters);
+        return report_errorf(ICPFLOW_E_ARG, "%s: options.d_pair_active needs the single-launch reference stop (2 <= max_iterations <= %d, "
+                                            "fp64 arithmetic, speculation on)", fn, kHistIters);
     return 0;
 }
 
@@ -328,33 +309,33 @@ int check_arith(const char *fn, const Opts &o, int maxIter, int stopMode)
 {
     if (o.arith != ICPFLOW_ARITH_FP32_REFERENCE) return 0;
     if (stopMode != ICPFLOW_STOP_REFERENCE)
-        return fail(ICPFLOW_E_ARG, "%s: ICPFLOW_ARITH_FP32_REFERENCE implements the reference's batch-global stop only", fn);
+        return report_errorf(ICPFLOW_E_ARG, "%s: ICPFLOW_ARITH_FP32_REFERENCE implements the reference's batch-global stop only", fn);
     if (maxIter > kHistIters)
-        return fail(ICPFLOW_E_LIMIT, "%s: ICPFLOW_ARITH_FP32_REFERENCE keeps a per-iteration history: max_iterations <= %d",
-                    fn, kHistIters);
+        return report_errorf(ICPFLOW_E_LIMIT, "%s: ICPFLOW_ARITH_FP32_REFERENCE keeps a per-iteration history: max_iterations <= %d",
+                             fn, kHistIters);
     return 0;
 }
 
 int check_ws(void *ws, size_t have, size_t need)
 {
     if (ws == nullptr || have < need)
-        return fail(ICPFLOW_E_WORKSPACE, "workspace too small: have %zu bytes, need %zu", have, need);
-    if (((uintptr_t)ws & 15) != 0) return fail(ICPFLOW_E_WORKSPACE, "workspace must be 16-byte aligned");
+        return report_errorf(ICPFLOW_E_WORKSPACE, "workspace too small: have %zu bytes, need %zu", have, need);
+    if (((uintptr_t)ws & 15) != 0) return report_errorf(ICPFLOW_E_WORKSPACE, "workspace must be 16-byte aligned");
     return 0;
 }
 
 int check_batch(const char *fn, int B, int N)
 {
-    if (B <= 0 || N <= 0) return fail(ICPFLOW_E_ARG, "%s: B (%d) and N (%d) must be positive", fn, B, N);
-    if ((long long)B * N > (1ll << 30)) return fail(ICPFLOW_E_LIMIT, "%s: B*N exceeds 2^30 rows", fn);
+    if (B <= 0 || N <= 0) return report_errorf(ICPFLOW_E_ARG, "%s: B (%d) and N (%d) must be positive", fn, B, N);
+    if ((long long)B * N > (1ll << 30)) return report_errorf(ICPFLOW_E_LIMIT, "%s: B*N exceeds 2^30 rows", fn);
     return 0;
 }
 
 int check_hist_dims(const char *fn, int lx, int ly, int lz)
 {
     if (lx <= 0 || ly <= 0 || lz <= 0)
-        return fail(ICPFLOW_E_ARG, "%s: histogram lengths must be positive (%d,%d,%d)", fn, lx, ly, lz);
-    if ((long long)lx * ly * lz > (1ll << 28)) return fail(ICPFLOW_E_LIMIT, "%s: histogram too large", fn);
+        return report_errorf(ICPFLOW_E_ARG, "%s: histogram lengths must be positive (%d,%d,%d)", fn, lx, ly, lz);
+    if ((long long)lx * ly * lz > (1ll << 28)) return report_errorf(ICPFLOW_E_LIMIT, "%s: histogram too large", fn);
     return 0;
 }
 
@@ -458,7 +439,7 @@ int run_icp_and_select(const float *src, const float *dst, Workspace &w, const u
         ICPFLOW_TRY(launch_icp(src, dst, w.lenA, w.lenC, swap, init, B, N, thres, maxIter, relThr, stopMode,
                                w.state, w.ctrl, search, w.history, &w.team, io, s));
         if (part == 1) {
-            if (!historyPending) return fail(ICPFLOW_E_ARG, "icpflow_register_stage_begin: the ICP launch kept no history");
+            if (!historyPending) return report_errorf(ICPFLOW_E_ARG, "icpflow_register_stage_begin: the ICP launch kept no history");
             *pending = 1;
             return 0;
         }
@@ -566,18 +547,18 @@ size_t icpflow_workspace_bytes(int B, int N, int Lx, int Ly, int Lz)
 
 int icpflow_profile_create(int capacity, icpflow_profile_t **out)
 {
-    if (out == nullptr) return fail(ICPFLOW_E_ARG, "icpflow_profile_create: null pointer");
-    if (capacity < 0 || capacity > (1 << 20)) return fail(ICPFLOW_E_ARG, "icpflow_profile_create: bad capacity %d", capacity);
+    if (out == nullptr) return report_errorf(ICPFLOW_E_ARG, "icpflow_profile_create: null pointer");
+    if (capacity < 0 || capacity > (1 << 20)) return report_errorf(ICPFLOW_E_ARG, "icpflow_profile_create: bad capacity %d", capacity);
     hipError_t e = hipSuccess;
     LaunchProfile *p = profile_create(capacity, &e);
-    if (p == nullptr) return hipfail(e, "icpflow_profile_create");
+    if (p == nullptr) return hip_error(e, "icpflow_profile_create");
     *out = reinterpret_cast<icpflow_profile_t *>(p);
     return 0;
 }
 
 int icpflow_profile_collect(icpflow_profile_t *profile, double *total_ms, int *launches)
 {
-    if (profile == nullptr) return fail(ICPFLOW_E_ARG, "icpflow_profile_collect: null recorder");
+    if (profile == nullptr) return report_errorf(ICPFLOW_E_ARG, "icpflow_profile_collect: null recorder");
     ICPFLOW_TRY(profile_collect(reinterpret_cast<LaunchProfile *>(profile), total_ms, launches));
     return 0;
 }
@@ -591,8 +572,8 @@ int icpflow_profile_destroy(icpflow_profile_t *profile)
 int icpflow_selftest_vote_quotient(const float *d_a, int n, float min_v, float max_v, float *d_fast,
                                    float *d_ieee, icpflow_stream_t stream)
 {
-    if (!d_a || !d_fast || !d_ieee) return fail(ICPFLOW_E_ARG, "icpflow_selftest_vote_quotient: null pointer");
-    if (n <= 0) return fail(ICPFLOW_E_ARG, "icpflow_selftest_vote_quotient: n must be positive");
+    if (!d_a || !d_fast || !d_ieee) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_vote_quotient: null pointer");
+    if (n <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_vote_quotient: n must be positive");
     ICPFLOW_TRY(launch_vote_quotient_probe(d_a, n, min_v, max_v, d_fast, d_ieee, (hipStream_t)stream));
     return 0;
 }
@@ -601,9 +582,9 @@ int icpflow_selftest_kabsch(const double *d_H, const double *d_gsum, int n, int 
                             int32_t *d_path, icpflow_stream_t stream)
 {
     if (!d_H || !d_R || !d_lam || !d_path || (mode != 2 && !d_gsum))
-        return fail(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: null pointer");
-    if (n <= 0 || n > (1 << 24)) return fail(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: bad n %d", n);
-    if (mode < 0 || mode > 2) return fail(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: bad mode %d", mode);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: null pointer");
+    if (n <= 0 || n > (1 << 24)) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: bad n %d", n);
+    if (mode < 0 || mode > 2) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_kabsch: bad mode %d", mode);
     ICPFLOW_TRY(launch_kabsch_probe(d_H, d_gsum, n, mode, d_R, d_lam, d_path, (hipStream_t)stream));
     return 0;
 }
@@ -612,7 +593,7 @@ int icpflow_hist_vote(const float *d_X, const float *d_Y, int B, int NX, int NY,
                       float min_y, float min_z, float max_x, float max_y, float max_z, int len_x,
                       int len_y, int len_z, float *d_bins, icpflow_stream_t stream)
 {
-    if (!d_X || !d_Y || !d_bins) return fail(ICPFLOW_E_ARG, "icpflow_hist_vote: null pointer");
+    if (!d_X || !d_Y || !d_bins) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_vote: null pointer");
     if (int r = check_batch("icpflow_hist_vote", B, NX)) return r;
     if (int r = check_batch("icpflow_hist_vote", B, NY)) return r;
     if (int r = check_hist_dims("icpflow_hist_vote", len_x, len_y, len_z)) return r;
@@ -630,15 +611,15 @@ int icpflow_hist_peaks(const float *d_bins, int B, int len_x, int len_y, int len
                        int kernel_size, float *d_votes, int64_t *d_idx, void *d_ws, size_t ws_bytes,
                        icpflow_stream_t stream)
 {
-    if (!d_bins || !d_votes || !d_idx) return fail(ICPFLOW_E_ARG, "icpflow_hist_peaks: null pointer");
-    if (B <= 0) return fail(ICPFLOW_E_ARG, "icpflow_hist_peaks: B must be positive");
+    if (!d_bins || !d_votes || !d_idx) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_peaks: null pointer");
+    if (B <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_peaks: B must be positive");
     if (int r = check_hist_dims("icpflow_hist_peaks", len_x, len_y, len_z)) return r;
-    if (k <= 0 || k > 8) return fail(ICPFLOW_E_ARG, "icpflow_hist_peaks: k must be in 1..8 (got %d)", k);
+    if (k <= 0 || k > 8) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_peaks: k must be in 1..8 (got %d)", k);
     if (kernel_size <= 0 || kernel_size % 2 == 0)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_peaks: kernel_size must be odd and positive");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_peaks: kernel_size must be odd and positive");
     const size_t L = (size_t)len_x * len_y * len_z;
-    if ((size_t)k > L) return fail(ICPFLOW_E_ARG, "icpflow_hist_peaks: k exceeds the number of bins");
-    const size_t vol = up((size_t)B * L * 4);
+    if ((size_t)k > L) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_peaks: k exceeds the number of bins");
+    const size_t vol = align256((size_t)B * L * 4);
     if (int r = check_ws(d_ws, ws_bytes, 2 * vol)) return r;
     uint32_t *A = (uint32_t *)d_ws;
     uint32_t *Bv = (uint32_t *)((char *)d_ws + vol);
@@ -651,13 +632,13 @@ int icpflow_nn_batch(const float *d_Q, const float *d_T, int B, int NQ, int NT, 
                      int t_stride, const int32_t *d_len_q, const int32_t *d_len_t, int sqrt_dist,
                      int64_t *d_idx, float *d_dist, icpflow_stream_t stream)
 {
-    if (!d_Q || !d_T || !d_idx || !d_dist) return fail(ICPFLOW_E_ARG, "icpflow_nn_batch: null pointer");
+    if (!d_Q || !d_T || !d_idx || !d_dist) return report_errorf(ICPFLOW_E_ARG, "icpflow_nn_batch: null pointer");
     if (int r = check_batch("icpflow_nn_batch", B, NQ)) return r;
     if (int r = check_batch("icpflow_nn_batch", B, NT)) return r;
     if (q_stride < 3 || t_stride < 3)
-        return fail(ICPFLOW_E_ARG, "icpflow_nn_batch: row strides must be >= 3 floats (got %d, %d)", q_stride, t_stride);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_nn_batch: row strides must be >= 3 floats (got %d, %d)", q_stride, t_stride);
     if ((q_stride == 4 && ((uintptr_t)d_Q & 15)) || (t_stride == 4 && ((uintptr_t)d_T & 15)))
-        return fail(ICPFLOW_E_ARG, "icpflow_nn_batch: stride-4 clouds must be 16-byte aligned");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_nn_batch: stride-4 clouds must be 16-byte aligned");
     ICPFLOW_TRY(launch_scan_nn(d_Q, d_T, B, NQ, NT, q_stride, t_stride, d_len_q, d_len_t, sqrt_dist, d_idx,
                                d_dist, (hipStream_t)stream));
     return 0;
@@ -666,7 +647,7 @@ int icpflow_nn_batch(const float *d_Q, const float *d_T, int B, int NQ, int NT, 
 int icpflow_transform_points(const float *d_xyz, const float *d_pose, int B, int N, float *d_out,
                              icpflow_stream_t stream)
 {
-    if (!d_xyz || !d_pose || !d_out) return fail(ICPFLOW_E_ARG, "icpflow_transform_points: null pointer");
+    if (!d_xyz || !d_pose || !d_out) return report_errorf(ICPFLOW_E_ARG, "icpflow_transform_points: null pointer");
     if (int r = check_batch("icpflow_transform_points", B, N)) return r;
     ICPFLOW_TRY(launch_transform_points(d_xyz, d_pose, B, N, d_out, (hipStream_t)stream));
     return 0;
@@ -675,7 +656,7 @@ int icpflow_transform_points(const float *d_xyz, const float *d_pose, int B, int
 int icpflow_gather_pad(const float *d_points, const int32_t *d_rows, int B, int N, float *d_out,
                        icpflow_stream_t stream)
 {
-    if (!d_points || !d_rows || !d_out) return fail(ICPFLOW_E_ARG, "icpflow_gather_pad: null pointer");
+    if (!d_points || !d_rows || !d_out) return report_errorf(ICPFLOW_E_ARG, "icpflow_gather_pad: null pointer");
     if (int r = check_batch("icpflow_gather_pad", B, N)) return r;
     ICPFLOW_TRY(launch_gather_pad(d_points, d_rows, B, N, d_out, (hipStream_t)stream));
     return 0;
@@ -684,7 +665,7 @@ int icpflow_gather_pad(const float *d_points, const int32_t *d_rows, int B, int 
 int icpflow_gather_segments(const float *d_points, const int64_t *d_order, const int64_t *d_seg,
                             const int32_t *d_perm, int B, int N, float *d_out, icpflow_stream_t stream)
 {
-    if (!d_points || !d_order || !d_seg || !d_out) return fail(ICPFLOW_E_ARG, "icpflow_gather_segments: null pointer");
+    if (!d_points || !d_order || !d_seg || !d_out) return report_errorf(ICPFLOW_E_ARG, "icpflow_gather_segments: null pointer");
     if (int r = check_batch("icpflow_gather_segments", B, N)) return r;
     ICPFLOW_TRY(launch_gather_segments(d_points, d_order, d_seg, d_perm, B, N, d_out, (hipStream_t)stream));
     return 0;
@@ -695,11 +676,11 @@ int icpflow_assoc_assign(const float *d_result, const int32_t *d_si, const int32
                          int32_t *d_best, int K2, const int32_t *d_si2, const int32_t *d_di2, int64_t *d_seg2,
                          uint8_t *d_active2, icpflow_stream_t stream)
 {
-    if (!d_result || !d_si || !d_di || !d_best) return fail(ICPFLOW_E_ARG, "icpflow_assoc_assign: null pointer");
+    if (!d_result || !d_si || !d_di || !d_best) return report_errorf(ICPFLOW_E_ARG, "icpflow_assoc_assign: null pointer");
     if (K <= 0 || S <= 0 || D <= 0 || S > assoc_max_rows() || D > assoc_max_rows())
-        return fail(ICPFLOW_E_LIMIT, "icpflow_assoc_assign: K (%d) must be positive and S, D (%d, %d) in 1..%d", K, S, D, assoc_max_rows());
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_assoc_assign: K (%d) must be positive and S, D (%d, %d) in 1..%d", K, S, D, assoc_max_rows());
     if (K2 < 0 || (K2 > 0 && (!d_si2 || !d_di2 || !d_seg2 || !d_active2)))
-        return fail(ICPFLOW_E_ARG, "icpflow_assoc_assign: the next stage's candidates come with d_si2, d_di2, d_seg2 and d_active2");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_assoc_assign: the next stage's candidates come with d_si2, d_di2, d_seg2 and d_active2");
     ICPFLOW_TRY(launch_assoc_assign(d_result, d_si, d_di, K, d_active, S, D, translation_frame, thres_iou, rot_limit_deg,
                                     thres_error, d_best, K2, d_si2, d_di2, d_seg2, d_active2, (hipStream_t)stream));
     return 0;
@@ -711,12 +692,12 @@ int icpflow_assoc_collect(const int32_t *d_best1, const float *d_result1, const 
                           float *d_rows, float *d_T, int32_t *d_count, icpflow_stream_t stream)
 {
     if (!d_best1 || !d_result1 || !d_si1 || !d_di1 || !d_src_table || !d_dst_table || !d_rows || !d_T || !d_count)
-        return fail(ICPFLOW_E_ARG, "icpflow_assoc_collect: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_assoc_collect: null pointer");
     if (K1 <= 0 || S <= 0 || S > assoc_max_rows() || cap <= 0 || label_stride <= 0)
-        return fail(ICPFLOW_E_LIMIT, "icpflow_assoc_collect: K1 (%d), cap (%d), label_stride (%d) must be positive and S (%d) in 1..%d", K1, cap,
-                    label_stride, S, assoc_max_rows());
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_assoc_collect: K1 (%d), cap (%d), label_stride (%d) must be positive and S (%d) in 1..%d", K1, cap,
+                             label_stride, S, assoc_max_rows());
     if (K2 < 0 || (K2 > 0 && (!d_best2 || !d_result2 || !d_si2 || !d_di2)))
-        return fail(ICPFLOW_E_ARG, "icpflow_assoc_collect: stage 2 comes with d_best2, d_result2, d_si2 and d_di2");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_assoc_collect: stage 2 comes with d_best2, d_result2, d_si2 and d_di2");
     ICPFLOW_TRY(launch_assoc_collect(d_best1, d_result1, d_si1, d_di1, K1, K2 > 0 ? d_best2 : nullptr, d_result2, d_si2, d_di2, K2,
                                      d_src_table, d_dst_table, label_stride, S, cap, d_rows, d_T, d_count, (hipStream_t)stream));
     return 0;
@@ -735,9 +716,9 @@ int icpflow_flow_rigid_rows(const float *d_points, const float *d_labels, int N,
 int icpflow_register_stage(const icpflow_tables_t *t, const icpflow_stage_t *st, const icpflow_registration_t *reg,
                            void *d_ws, size_t ws_bytes, icpflow_stream_t stream, const icpflow_options_t *opt)
 {
-    if (!t || !st || !reg) return fail(ICPFLOW_E_ARG, "icpflow_register_stage: null argument");
+    if (!t || !st || !reg) return report_errorf(ICPFLOW_E_ARG, "icpflow_register_stage: null argument");
     if (!t->d_points_src || !t->d_order_src || !t->d_points_dst || !t->d_order_dst || !st->d_seg || !st->d_clouds || !st->d_result)
-        return fail(ICPFLOW_E_ARG, "icpflow_register_stage: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_register_stage: null pointer");
     const int K = st->K, N = st->N;
     if (int r = check_batch("icpflow_register_stage", K, N)) return r;
     const size_t cloud = (size_t)K * N * 4;
@@ -759,12 +740,12 @@ static int associate_frame_impl(const icpflow_tables_t *t, const icpflow_stage_t
                             const float *d_flow_labels, int n_flow, const float *d_pose, float *d_flow, void *d_ws,
                             size_t ws_bytes, icpflow_stream_t stream, const icpflow_options_t *opt, const int32_t *h_carry2)
 {
-    if (!t || !s1 || !reg || !d_best || !d_rows || !d_T) return fail(ICPFLOW_E_ARG, "icpflow_associate_frame: null argument");
+    if (!t || !s1 || !reg || !d_best || !d_rows || !d_T) return report_errorf(ICPFLOW_E_ARG, "icpflow_associate_frame: null argument");
     if (!t->d_table_src || !t->d_table_dst || !s1->d_result || !s1->d_si || !s1->d_di)
-        return fail(ICPFLOW_E_ARG, "icpflow_associate_frame: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_associate_frame: null pointer");
     const int S = t->S, D = t->D, K1 = s1->K, K2 = s2 ? s2->K : 0;
     if (K2 > 0 && (!d_active2 || !s2->d_si || !s2->d_di || !s2->d_seg || !s2->d_result))
-        return fail(ICPFLOW_E_ARG, "icpflow_associate_frame: stage 2 comes with d_active2, d_si, d_di, d_seg and d_result");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_associate_frame: stage 2 comes with d_active2, d_si, d_di, d_seg and d_result");
     int32_t *best1 = d_best, *best2 = d_best + S, *count = d_best + 2 * (size_t)S;
     // (stage 2's segment rows are written by the assignment: the lengths of the switched-off candidates become 0)
     if (int r = icpflow_assoc_assign(s1->d_result, s1->d_si, s1->d_di, K1, nullptr, S, D, translation_frame, thres_iou, rot_limit_deg,
@@ -810,7 +791,7 @@ int icpflow_associate_frame_begun(const icpflow_tables_t *t, const icpflow_stage
                                   const float *d_flow_labels, int n_flow, const float *d_pose, float *d_flow, void *d_ws2,
                                   size_t ws2_bytes, icpflow_stream_t stream, const icpflow_options_t *opt, const int32_t *h_carry2)
 {
-    if (!h_carry2) return fail(ICPFLOW_E_ARG, "icpflow_associate_frame_begun: null argument");
+    if (!h_carry2) return report_errorf(ICPFLOW_E_ARG, "icpflow_associate_frame_begun: null argument");
     return associate_frame_impl(t, s1, s2, d_active2, reg, translation_frame, thres_iou, rot_limit_deg, thres_error, d_best, cap, d_rows, d_T,
                                 d_flow_points, d_flow_labels, n_flow, d_pose, d_flow, d_ws2, ws2_bytes, stream, opt, h_carry2);
 }
@@ -828,19 +809,19 @@ int icpflow_dbscan(const float *d_points, int stride, const uint8_t *d_mask, int
                    icpflow_stream_t stream)
 {
     if (!d_points || !d_labels || !d_counts || !d_num_clusters)
-        return fail(ICPFLOW_E_ARG, "icpflow_dbscan: null pointer");
-    if (n <= 0) return fail(ICPFLOW_E_ARG, "icpflow_dbscan: n must be positive (got %d)", n);
-    if (stride < 3) return fail(ICPFLOW_E_ARG, "icpflow_dbscan: stride must be >= 3 floats (got %d)", stride);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_dbscan: null pointer");
+    if (n <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_dbscan: n must be positive (got %d)", n);
+    if (stride < 3) return report_errorf(ICPFLOW_E_ARG, "icpflow_dbscan: stride must be >= 3 floats (got %d)", stride);
     if (!(eps > 0.0) || min_points < 1)
-        return fail(ICPFLOW_E_ARG, "icpflow_dbscan: eps must be positive and min_points >= 1 (got %g, %d)", eps,
-                    min_points);
-    if (!d_ws) return fail(ICPFLOW_E_WORKSPACE, "icpflow_dbscan: workspace is NULL");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_dbscan: eps must be positive and min_points >= 1 (got %g, %d)", eps,
+                             min_points);
+    if (!d_ws) return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_dbscan: workspace is NULL");
     bool tooSmall = false;
     ICPFLOW_TRY(launch_dbscan(d_points, stride, d_mask, n, eps, min_points, d_labels, d_counts, d_num_clusters, d_ws,
                               ws_bytes, &tooSmall, (hipStream_t)stream));
     if (tooSmall)
-        return fail(ICPFLOW_E_WORKSPACE, "icpflow_dbscan: workspace too small (%zu bytes, need %zu)", ws_bytes,
-                    icpflow_dbscan_workspace_bytes(n));
+        return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_dbscan: workspace too small (%zu bytes, need %zu)", ws_bytes,
+                             icpflow_dbscan_workspace_bytes(n));
     return 0;
 }
 
@@ -858,20 +839,20 @@ int icpflow_hdbscan_mst(const float *d_points, int stride, const uint8_t *d_mask
                         icpflow_stream_t stream)
 {
     if (!d_points || !d_edge_a || !d_edge_b || !d_edge_w2 || !d_num_edges || !d_num_live)
-        return fail(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: null pointer");
-    if (n <= 0) return fail(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: n must be positive (got %d)", n);
-    if (stride < 3) return fail(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: stride must be >= 3 floats (got %d)", stride);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: null pointer");
+    if (n <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: n must be positive (got %d)", n);
+    if (stride < 3) return report_errorf(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: stride must be >= 3 floats (got %d)", stride);
     if (min_samples < 1 || min_samples > 64)
-        return fail(ICPFLOW_E_LIMIT, "icpflow_hdbscan_mst: min_samples must be in 1..64 (got %d)", min_samples);
-    if (!(cell > 0.0)) return fail(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: cell must be positive (got %g)", cell);
-    if (!d_ws) return fail(ICPFLOW_E_WORKSPACE, "icpflow_hdbscan_mst: workspace is NULL");
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_hdbscan_mst: min_samples must be in 1..64 (got %d)", min_samples);
+    if (!(cell > 0.0)) return report_errorf(ICPFLOW_E_ARG, "icpflow_hdbscan_mst: cell must be positive (got %g)", cell);
+    if (!d_ws) return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_hdbscan_mst: workspace is NULL");
     bool tooSmall = false;
     ICPFLOW_TRY(launch_hdbscan_mst(d_points, stride, d_mask, n, min_samples, cell, d_core2, d_edge_a, d_edge_b,
                                    d_edge_w2, d_num_edges, d_num_live, d_ws, ws_bytes, &tooSmall,
                                    (hipStream_t)stream));
     if (tooSmall)
-        return fail(ICPFLOW_E_WORKSPACE, "icpflow_hdbscan_mst: workspace too small (%zu bytes, need %zu)", ws_bytes,
-                    icpflow_hdbscan_mst_workspace_bytes(n));
+        return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_hdbscan_mst: workspace too small (%zu bytes, need %zu)", ws_bytes,
+                             icpflow_hdbscan_mst_workspace_bytes(n));
     return 0;
 }
 
@@ -880,8 +861,8 @@ int icpflow_cluster_stats(const float *d_points, const int64_t *d_order, const i
                           icpflow_stream_t stream)
 {
     if (!d_points || !d_order || !d_start || !d_count || !d_mean || !d_extent)
-        return fail(ICPFLOW_E_ARG, "icpflow_cluster_stats: null pointer");
-    if (L <= 0) return fail(ICPFLOW_E_ARG, "icpflow_cluster_stats: L must be positive (got %d)", L);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_cluster_stats: null pointer");
+    if (L <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_cluster_stats: L must be positive (got %d)", L);
     ICPFLOW_TRY(launch_cluster_stats(d_points, d_order, d_start, d_count, d_labels, L, d_mean, d_extent,
                                      (hipStream_t)stream));
     return 0;
@@ -899,16 +880,16 @@ int icpflow_cluster_table(const float *d_points, const float *d_labels, int M, i
                           int32_t *d_num, void *d_ws, size_t ws_bytes, icpflow_stream_t stream)
 {
     if (!d_points || !d_labels || !d_order || !d_table || !d_num)
-        return fail(ICPFLOW_E_ARG, "icpflow_cluster_table: null pointer");
-    if (M <= 0) return fail(ICPFLOW_E_ARG, "icpflow_cluster_table: M must be positive (got %d)", M);
-    if (Lmax <= 0 || Lmax > 4096) return fail(ICPFLOW_E_LIMIT, "icpflow_cluster_table: 1 <= Lmax <= 4096 (got %d)", Lmax);
-    if (!d_ws) return fail(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table: workspace is NULL");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_cluster_table: null pointer");
+    if (M <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_cluster_table: M must be positive (got %d)", M);
+    if (Lmax <= 0 || Lmax > 4096) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_cluster_table: 1 <= Lmax <= 4096 (got %d)", Lmax);
+    if (!d_ws) return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table: workspace is NULL");
     bool tooSmall = false;
     ICPFLOW_TRY(launch_cluster_table(d_points, d_labels, M, d_order, d_table, Lmax, d_num, d_ws, ws_bytes, &tooSmall,
                                      (hipStream_t)stream));
     if (tooSmall)
-        return fail(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table: workspace too small (%zu bytes, need %zu)", ws_bytes,
-                    icpflow_cluster_table_workspace_bytes(M, Lmax));
+        return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table: workspace too small (%zu bytes, need %zu)", ws_bytes,
+                             icpflow_cluster_table_workspace_bytes(M, Lmax));
     return 0;
 }
 
@@ -927,30 +908,30 @@ int icpflow_cluster_table_pair(const float *d_points_a, const float *d_labels_a,
 {
     if (!d_points_a || !d_labels_a || !d_order_a || !d_table_a || !d_num_a || !d_points_b || !d_labels_b || !d_order_b ||
         !d_table_b || !d_num_b)
-        return fail(ICPFLOW_E_ARG, "icpflow_cluster_table_pair: null pointer");
-    if (MA <= 0 || MB <= 0) return fail(ICPFLOW_E_ARG, "icpflow_cluster_table_pair: MA, MB must be positive (got %d, %d)", MA, MB);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_cluster_table_pair: null pointer");
+    if (MA <= 0 || MB <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_cluster_table_pair: MA, MB must be positive (got %d, %d)", MA, MB);
     if ((long long)MA + MB > 0x7fffffffll)
-        return fail(ICPFLOW_E_LIMIT, "icpflow_cluster_table_pair: MA + MB must stay below 2^31 (got %d + %d)", MA, MB);
-    if (Lmax <= 0 || Lmax > 4096) return fail(ICPFLOW_E_LIMIT, "icpflow_cluster_table_pair: 1 <= Lmax <= 4096 (got %d)", Lmax);
-    if (!d_ws) return fail(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table_pair: workspace is NULL");
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_cluster_table_pair: MA + MB must stay below 2^31 (got %d + %d)", MA, MB);
+    if (Lmax <= 0 || Lmax > 4096) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_cluster_table_pair: 1 <= Lmax <= 4096 (got %d)", Lmax);
+    if (!d_ws) return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table_pair: workspace is NULL");
     bool tooSmall = false;
     ICPFLOW_TRY(launch_cluster_table_pair(d_points_a, d_labels_a, MA, d_order_a, d_table_a, d_num_a, d_points_b, d_labels_b, MB,
                                           d_order_b, d_table_b, d_num_b, Lmax, d_ws, ws_bytes, &tooSmall, (hipStream_t)stream));
     if (tooSmall)
-        return fail(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table_pair: workspace too small (%zu bytes, need %zu)", ws_bytes,
-                    icpflow_cluster_table_pair_workspace_bytes(MA, MB, Lmax));
+        return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_cluster_table_pair: workspace too small (%zu bytes, need %zu)", ws_bytes,
+                             icpflow_cluster_table_pair_workspace_bytes(MA, MB, Lmax));
     return 0;
 }
 
 int icpflow_flow_rigid_rows(const float *d_points, const float *d_labels, int N, const float *d_pair_rows, int pair_stride,
                             const float *d_T, int P, const float *d_pose, float *d_flow, icpflow_stream_t stream)
 {
-    if (!d_points || !d_labels || !d_pose || !d_flow) return fail(ICPFLOW_E_ARG, "icpflow_flow_rigid: null pointer");
-    if (N <= 0) return fail(ICPFLOW_E_ARG, "icpflow_flow_rigid: N must be positive");
-    if (P < 0 || P > (1 << 24)) return fail(ICPFLOW_E_LIMIT, "icpflow_flow_rigid: 0 <= P <= 2^24 pairs (got %d)", P);
-    if (P > 0 && (!d_pair_rows || !d_T)) return fail(ICPFLOW_E_ARG, "icpflow_flow_rigid: null pair arrays");
+    if (!d_points || !d_labels || !d_pose || !d_flow) return report_errorf(ICPFLOW_E_ARG, "icpflow_flow_rigid: null pointer");
+    if (N <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_flow_rigid: N must be positive");
+    if (P < 0 || P > (1 << 24)) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_flow_rigid: 0 <= P <= 2^24 pairs (got %d)", P);
+    if (P > 0 && (!d_pair_rows || !d_T)) return report_errorf(ICPFLOW_E_ARG, "icpflow_flow_rigid: null pair arrays");
     if (pair_stride < 1 || pair_stride > 1024)
-        return fail(ICPFLOW_E_ARG, "icpflow_flow_rigid: pair_stride must be in 1 ... 1024 floats (got %d)", pair_stride);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_flow_rigid: pair_stride must be in 1 ... 1024 floats (got %d)", pair_stride);
     ICPFLOW_TRY(launch_flow_rigid(d_points, d_labels, N, d_pair_rows, pair_stride, d_T, P, d_pose, d_flow, (hipStream_t)stream));
     return 0;
 }
@@ -966,7 +947,7 @@ int icpflow_flow_rigid(const float *d_points, const float *d_labels, int N, cons
 
 int icpflow_count_valid(const float *d_pts, int B, int N, int32_t *d_len, icpflow_stream_t stream)
 {
-    if (!d_pts || !d_len) return fail(ICPFLOW_E_ARG, "icpflow_count_valid: null pointer");
+    if (!d_pts || !d_len) return report_errorf(ICPFLOW_E_ARG, "icpflow_count_valid: null pointer");
     if (int r = check_batch("icpflow_count_valid", B, N)) return r;
     launch_count_valid(d_pts, B, N, d_len, (hipStream_t)stream);
     ICPFLOW_TRY(hipGetLastError());
@@ -982,11 +963,11 @@ int icpflow_estimate_init_pose(const float *d_src, const float *d_dst, int B, in
     if (int r = parse_options("icpflow_estimate_init_pose", opt, o)) return r;
     if (int r = check_pair_active("icpflow_estimate_init_pose", o, false, 0, 0)) return r;
     if (!d_src || !d_dst || !d_edges_x || !d_edges_y || !d_edges_z || !d_T_out)
-        return fail(ICPFLOW_E_ARG, "icpflow_estimate_init_pose: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_estimate_init_pose: null pointer");
     if (int r = check_batch("icpflow_estimate_init_pose", B, N)) return r;
     if (int r = check_hist_dims("icpflow_estimate_init_pose", len_x, len_y, len_z)) return r;
     const size_t L = (size_t)len_x * len_y * len_z;
-    if (L < (size_t)kTopK) return fail(ICPFLOW_E_ARG, "icpflow_estimate_init_pose: fewer than 5 bins");
+    if (L < (size_t)kTopK) return report_errorf(ICPFLOW_E_ARG, "icpflow_estimate_init_pose: fewer than 5 bins");
     Workspace w(d_ws, B, N, L);
     if (int r = check_ws(d_ws, ws_bytes, w.bytes)) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1004,12 +985,12 @@ int icpflow_icp(const float *d_X, const float *d_Y, const float *d_pre_pose, int
     if (int r = parse_options("icpflow_icp", opt, o)) return r;
     if (int r = check_pair_active("icpflow_icp", o, false, 0, 0)) return r;
     if (int r = check_arith("icpflow_icp", o, max_iterations, stop_mode)) return r;
-    if (!d_X || !d_Y) return fail(ICPFLOW_E_ARG, "icpflow_icp: null pointer");
+    if (!d_X || !d_Y) return report_errorf(ICPFLOW_E_ARG, "icpflow_icp: null pointer");
     if (int r = check_batch("icpflow_icp", B, N)) return r;
     if (max_iterations <= 0 || max_iterations > kMaxIterCap)
-        return fail(ICPFLOW_E_ARG, "icpflow_icp: max_iterations must be in 1..%d (got %d)", kMaxIterCap, max_iterations);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_icp: max_iterations must be in 1..%d (got %d)", kMaxIterCap, max_iterations);
     if (stop_mode != ICPFLOW_STOP_REFERENCE && stop_mode != ICPFLOW_STOP_PER_PAIR)
-        return fail(ICPFLOW_E_ARG, "icpflow_icp: unknown stop_mode %d", stop_mode);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_icp: unknown stop_mode %d", stop_mode);
     Workspace w(d_ws, B, N, 0);
     if (int r = check_ws(d_ws, ws_bytes, w.bytes)) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1023,14 +1004,14 @@ int icpflow_icp(const float *d_X, const float *d_Y, const float *d_pre_pose, int
     io.initS = o.initS;
     // (every argument check sits in front of the first launch: a refused call leaves the stream untouched)
     if ((o.allowReflection || o.estimateScale) && o.arith != ICPFLOW_ARITH_FP64)
-        return fail(ICPFLOW_E_ARG, "icpflow_icp: allow_reflection / estimate_scale are not built for ICPFLOW_ARITH_FP32_REFERENCE");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_icp: allow_reflection / estimate_scale are not built for ICPFLOW_ARITH_FP32_REFERENCE");
     if (o.history != nullptr &&
         !(stop_mode == ICPFLOW_STOP_REFERENCE && max_iterations > 1 && max_iterations <= kHistIters &&
           o.arith == ICPFLOW_ARITH_FP64 && io.speculative))
-        return fail(ICPFLOW_E_ARG, "icpflow_icp: options.d_icp_history needs the single-launch reference stop mode "
-                                   "(2 <= max_iterations <= %d, fp64 arithmetic)", kHistIters);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_icp: options.d_icp_history needs the single-launch reference stop mode "
+                                            "(2 <= max_iterations <= %d, fp64 arithmetic)", kHistIters);
     if (o.initR != nullptr && o.arith != ICPFLOW_ARITH_FP64)
-        return fail(ICPFLOW_E_ARG, "icpflow_icp: an initial transform is not built for ICPFLOW_ARITH_FP32_REFERENCE");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_icp: an initial transform is not built for ICPFLOW_ARITH_FP32_REFERENCE");
     // similarity transforms are built into the sorted-sweep kernels only: below 64 points, where the automatic choice is the
     // all-pairs scan, a request for a scale takes the sweep (the drop-in must not raise where the
     // reference works); beyond the sort's length (kMaxSortN) it is still refused
@@ -1038,8 +1019,8 @@ int icpflow_icp(const float *d_X, const float *d_Y, const float *d_pre_pose, int
     if ((o.estimateScale || o.initS != nullptr) && o.search == 0 && N < 64) os.search = 3;
     const GridScratch *search = search_scratch(w, N, os);
     if ((o.estimateScale || o.initS != nullptr) && (search == nullptr || search->mode != 3))
-        return fail(ICPFLOW_E_ARG, "icpflow_icp: estimate_scale / an initial transform with a scale need the sorted-sweep "
-                                   "search (the default up to N = %d)", kMaxSortN);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_icp: estimate_scale / an initial transform with a scale need the sorted-sweep "
+                                            "search (the default up to N = %d)", kMaxSortN);
     launch_count_pair(d_X, d_Y, B, N, w.lenA, w.lenC, nullptr, s, w.ctrl, icp_ctrl_bytes(B));
     ICPFLOW_TRY(launch_icp(d_X, d_Y, w.lenA, w.lenC, nullptr, d_pre_pose, B, N, thres, max_iterations,
                            relative_rmse_thr, stop_mode, w.state, w.ctrl, search, w.history, &w.team,
@@ -1060,12 +1041,12 @@ int icpflow_apply_icp(const float *d_src, const float *d_dst, const float *d_ini
     if (int r = parse_options("icpflow_apply_icp", opt, o)) return r;
     if (int r = check_arith("icpflow_apply_icp", o, max_iterations, stop_mode)) return r;
     if (int r = check_pair_active("icpflow_apply_icp", o, false, max_iterations, stop_mode)) return r;
-    if (!d_src || !d_dst || !d_init || !d_T_out) return fail(ICPFLOW_E_ARG, "icpflow_apply_icp: null pointer");
+    if (!d_src || !d_dst || !d_init || !d_T_out) return report_errorf(ICPFLOW_E_ARG, "icpflow_apply_icp: null pointer");
     if (int r = check_batch("icpflow_apply_icp", B, N)) return r;
     if (max_iterations <= 0 || max_iterations > kMaxIterCap)
-        return fail(ICPFLOW_E_ARG, "icpflow_apply_icp: max_iterations must be in 1..%d", kMaxIterCap);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_apply_icp: max_iterations must be in 1..%d", kMaxIterCap);
     if (stop_mode != ICPFLOW_STOP_REFERENCE && stop_mode != ICPFLOW_STOP_PER_PAIR)
-        return fail(ICPFLOW_E_ARG, "icpflow_apply_icp: unknown stop_mode %d", stop_mode);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_apply_icp: unknown stop_mode %d", stop_mode);
     Workspace w(d_ws, B, N, 0);
     if (int r = check_ws(d_ws, ws_bytes, w.bytes)) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1179,15 +1160,15 @@ int icpflow_hist_icp(const float *d_src, const float *d_dst, int B, int N, const
     if (int r = check_arith("icpflow_hist_icp", o, max_iterations, stop_mode)) return r;
     if (int r = check_pair_active("icpflow_hist_icp", o, true, max_iterations, stop_mode)) return r;
     if (!d_src || !d_dst || !d_edges_x || !d_edges_y || !d_edges_z || !d_T_out)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_icp: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp: null pointer");
     if (int r = check_batch("icpflow_hist_icp", B, N)) return r;
     if (int r = check_hist_dims("icpflow_hist_icp", len_x, len_y, len_z)) return r;
     if (max_iterations <= 0 || max_iterations > kMaxIterCap)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_icp: max_iterations must be in 1..%d", kMaxIterCap);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp: max_iterations must be in 1..%d", kMaxIterCap);
     if (stop_mode != ICPFLOW_STOP_REFERENCE && stop_mode != ICPFLOW_STOP_PER_PAIR)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_icp: unknown stop_mode %d", stop_mode);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp: unknown stop_mode %d", stop_mode);
     const size_t L = (size_t)len_x * len_y * len_z;
-    if (L < (size_t)kTopK) return fail(ICPFLOW_E_ARG, "icpflow_hist_icp: fewer than 5 bins");
+    if (L < (size_t)kTopK) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp: fewer than 5 bins");
     Workspace w(d_ws, B, N, L);
     if (int r = check_ws(d_ws, ws_bytes, w.bytes)) return r;
     return hist_icp_core(d_src, d_dst, B, N, d_edges_x, len_x, d_edges_y, len_y, d_edges_z, len_z, decode_shift,
@@ -1206,12 +1187,12 @@ int icpflow_hist_icp_many(int K, const float *const *d_src, const float *const *
                           int32_t *const *d_iters, void *const *d_ws, const size_t *ws_bytes,
                           icpflow_stream_t stream, const icpflow_options_t *opt)
 {
-    if (K <= 0 || K > 64) return fail(ICPFLOW_E_ARG, "icpflow_hist_icp_many: K must be in 1..64 (got %d)", K);
+    if (K <= 0 || K > 64) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp_many: K must be in 1..64 (got %d)", K);
     if (!d_src || !d_dst || !B || !d_T_out || !d_iters || !d_ws || !ws_bytes)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_icp_many: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp_many: null pointer");
     for (int k = 0; k < K; ++k)
         for (int j = 0; j < k; ++j)
-            if (d_ws[k] == d_ws[j]) return fail(ICPFLOW_E_WORKSPACE, "icpflow_hist_icp_many: batches %d and %d share a workspace", j, k);
+            if (d_ws[k] == d_ws[j]) return report_errorf(ICPFLOW_E_WORKSPACE, "icpflow_hist_icp_many: batches %d and %d share a workspace", j, k);
     hipStream_t s = (hipStream_t)stream;
     constexpr int kWorkers = 4;
     struct Pool {
@@ -1246,7 +1227,7 @@ int icpflow_hist_icp_many(int K, const float *const *d_src, const float *const *
     for (int k = 0; k < used; ++k) {
         const hipError_t e1 = hipEventRecord(pool.join[k], pool.w[k]);
         const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s, pool.join[k], 0) : e1;
-        if (rc == 0 && e2 != hipSuccess) rc = hipfail(e2, "icpflow_hist_icp_many: join");
+        if (rc == 0 && e2 != hipSuccess) rc = hip_error(e2, "icpflow_hist_icp_many: join");
     }
     return rc;
 }
@@ -1286,7 +1267,7 @@ int icpflow_match_eval(const float *d_pcd1, const float *d_pcd2, const float *d_
     if (int r = check_pair_active("icpflow_match_eval", o, false, 0, 0)) return r;
     if (!d_pcd1 || !d_pcd2 || !d_T || !d_errors || !d_inliers || !d_ratios || !d_ious || !d_translations ||
         !d_rotations)
-        return fail(ICPFLOW_E_ARG, "icpflow_match_eval: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_match_eval: null pointer");
     if (int r = check_batch("icpflow_match_eval", B, N)) return r;
     Workspace w(d_ws, B, N, 0);
     if (int r = check_ws(d_ws, ws_bytes, w.bytes)) return r;
@@ -1310,15 +1291,15 @@ static int hist_icp_eval_phase(int phase, int32_t *carry, const float *d_src, co
     if (int r = check_pair_active("icpflow_hist_icp_eval", o, true, max_iterations, stop_mode)) return r;
     if (!d_src || !d_dst || !d_edges_x || !d_edges_y || !d_edges_z || !d_T_out || !d_errors || !d_inliers || !d_ratios ||
         !d_ious || !d_translations || !d_rotations)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: null pointer");
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: null pointer");
     if (int r = check_batch("icpflow_hist_icp_eval", B, N)) return r;
     if (int r = check_hist_dims("icpflow_hist_icp_eval", len_x, len_y, len_z)) return r;
     if (max_iterations <= 0 || max_iterations > kMaxIterCap)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: max_iterations must be in 1..%d", kMaxIterCap);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: max_iterations must be in 1..%d", kMaxIterCap);
     if (stop_mode != ICPFLOW_STOP_REFERENCE && stop_mode != ICPFLOW_STOP_PER_PAIR)
-        return fail(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: unknown stop_mode %d", stop_mode);
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: unknown stop_mode %d", stop_mode);
     const size_t L = (size_t)len_x * len_y * len_z;
-    if (L < (size_t)kTopK) return fail(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: fewer than 5 bins");
+    if (L < (size_t)kTopK) return report_errorf(ICPFLOW_E_ARG, "icpflow_hist_icp_eval: fewer than 5 bins");
     Workspace w(d_ws, B, N, L);
     if (int r = check_ws(d_ws, ws_bytes, w.bytes)) return r;
     hipStream_t s = (hipStream_t)stream;
@@ -1348,9 +1329,9 @@ static int register_stage_phase(int phase, int32_t *carry, const icpflow_tables_
                                 const icpflow_options_t *opt)
 {
     const char *fn = phase == 1 ? "icpflow_register_stage_begin" : "icpflow_register_stage_finish";
-    if (!t || !st || !reg || !carry) return fail(ICPFLOW_E_ARG, "%s: null argument", fn);
+    if (!t || !st || !reg || !carry) return report_errorf(ICPFLOW_E_ARG, "%s: null argument", fn);
     if (!t->d_points_src || !t->d_order_src || !t->d_points_dst || !t->d_order_dst || !st->d_seg || !st->d_clouds || !st->d_result)
-        return fail(ICPFLOW_E_ARG, "%s: null pointer", fn);
+        return report_errorf(ICPFLOW_E_ARG, "%s: null pointer", fn);
     const int K = st->K, N = st->N;
     if (int r = check_batch(fn, K, N)) return r;
     const size_t cloud = (size_t)K * N * 4;
@@ -1378,7 +1359,7 @@ int icpflow_register_stage_finish(const icpflow_tables_t *t, const icpflow_stage
                                   void *d_ws, size_t ws_bytes, icpflow_stream_t stream, const icpflow_options_t *opt, const int32_t *h_carry)
 {
     int32_t carry[4] = {h_carry ? h_carry[0] : 0, h_carry ? h_carry[1] : 0, h_carry ? h_carry[2] : 0, h_carry ? h_carry[3] : 0};
-    if (!h_carry) return fail(ICPFLOW_E_ARG, "icpflow_register_stage_finish: null argument");
+    if (!h_carry) return report_errorf(ICPFLOW_E_ARG, "icpflow_register_stage_finish: null argument");
     return register_stage_phase(2, carry, t, st, reg, d_ws, ws_bytes, stream, opt);
 }
 

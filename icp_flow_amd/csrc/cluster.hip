@@ -22,6 +22,7 @@
 
 #include "kernels.hpp"
 #include "cluster_util.hpp"
+#include "host.hpp"
 
 namespace icpflow {
 
@@ -362,29 +363,23 @@ hipError_t carve(int n, void *ws, Carve *c, hipStream_t s)
                                              (unsigned long long *)nullptr, (int *)nullptr, (int *)nullptr,
                                              (size_t)n, 0, 63, s);
     if (e != hipSuccess) return e;
-    char *p = (char *)ws;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = p ? p + off : nullptr;
-        off += up256(bytes);
-        return q;
-    };
+    Carver mem(ws);
     const size_t N = (size_t)n;
-    c->keyIn = (unsigned long long *)take(N * 8);
-    c->keyOut = (unsigned long long *)take(N * 8);
-    c->valIn = (int *)take(N * 4);
-    c->valOut = (int *)take(N * 4);
-    c->parent = (int *)take(N * 4);
-    c->firstRow = (int *)take(N * 4);
-    c->chunkRoot = (int *)take(((N + 63) / 64) * 4);
-    c->rootOf = (int *)take(N * 4);
-    c->rank = (int *)take(N * 4);
-    c->sorted = (float4 *)take(N * 16);
-    c->runs = (int2 *)take(N * kRuns * 8);
-    c->core = (uint8_t *)take(N);
-    c->sortTmp = take(tmp);
+    c->keyIn = mem.take<unsigned long long>(N * 8);
+    c->keyOut = mem.take<unsigned long long>(N * 8);
+    c->valIn = mem.take<int>(N * 4);
+    c->valOut = mem.take<int>(N * 4);
+    c->parent = mem.take<int>(N * 4);
+    c->firstRow = mem.take<int>(N * 4);
+    c->chunkRoot = mem.take<int>(((N + 63) / 64) * 4);
+    c->rootOf = mem.take<int>(N * 4);
+    c->rank = mem.take<int>(N * 4);
+    c->sorted = mem.take<float4>(N * 16);
+    c->runs = mem.take<int2>(N * kRuns * 8);
+    c->core = mem.take<uint8_t>(N);
+    c->sortTmp = mem.take<void>(tmp);
     c->sortTmpBytes = tmp;
-    c->total = off;
+    c->total = mem.total();
     return hipSuccess;
 }
 

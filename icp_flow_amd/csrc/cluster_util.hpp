@@ -58,7 +58,5 @@ __device__ inline void uf_union(int *parent, int a, int b)
     }
 }
 
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 }  // namespace icpflow

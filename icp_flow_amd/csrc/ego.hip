@@ -17,16 +17,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
-#include "../../include/icpflow_hip.h"
+#include "host.hpp"
 
-namespace icpflow {
-int report_error(int code, const char *message);   // api.hip: what icpflow_last_error returns
-}
+using icpflow::Carver;
+using icpflow::pointer_error;
 using icpflow::report_error;
 
 namespace {
@@ -447,8 +445,6 @@ __global__ void map_export_kernel(MapTable map, unsigned mask, int per_voxel, lo
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Carve {
     size_t keys[2], count[2], pts[2], tkeys, tmin, slotOf, idxDs, idxSrc, moved, sameTotal, counts, result, flags, total;
     unsigned tcap;
@@ -457,28 +453,27 @@ struct Carve {
 Carve carve(const icpflow_ego_params_t &p)
 {
     Carve c{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+    Carver mem;
     const size_t C = (size_t)p.map_capacity, n = (size_t)p.max_points;
     for (int k = 0; k < 2; ++k) {
-        c.keys[k] = take(C * 8);
-        c.count[k] = take(C * 4);
-        c.pts[k] = take(C * kVoxelPoints * 3 * 4);
+        c.keys[k] = mem.take(C * 8);
+        c.count[k] = mem.take(C * 4);
+        c.pts[k] = mem.take(C * kVoxelPoints * 3 * 4);
     }
     unsigned tcap = 1024;
     while ((size_t)tcap < 2 * n) tcap <<= 1;
     c.tcap = tcap;
-    c.tkeys = take((size_t)tcap * 8);
-    c.tmin = take((size_t)tcap * 4);
-    c.slotOf = take(n * 4);
-    c.idxDs = take(n * 4);
-    c.idxSrc = take(n * 4);
-    c.moved = take(n * 12);
-    c.sameTotal = take(n * 4);
-    c.counts = take(4 * 4);
-    c.result = take(20 * 8);
-    c.flags = take(kNumFlags * 4);
-    c.total = at;
+    c.tkeys = mem.take((size_t)tcap * 8);
+    c.tmin = mem.take((size_t)tcap * 4);
+    c.slotOf = mem.take(n * 4);
+    c.idxDs = mem.take(n * 4);
+    c.idxSrc = mem.take(n * 4);
+    c.moved = mem.take(n * 12);
+    c.sameTotal = mem.take(n * 4);
+    c.counts = mem.take(4 * 4);
+    c.result = mem.take(20 * 8);
+    c.flags = mem.take(kNumFlags * 4);
+    c.total = mem.total();
     return c;
 }
 
@@ -497,19 +492,6 @@ const char *check_params(const icpflow_ego_params_t *p)
         return "icpflow_ego: map_capacity must be a power of two, 1024 .. 2^26";
     return nullptr;
 }
-
-int hipfail(hipError_t e, const char *what)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", what, hipGetErrorString(e));
-    return report_error((int)e, msg);
-}
-
-#define EGO_HIP(call)                                     \
-    do {                                                  \
-        const hipError_t e_ = (call);                     \
-        if (e_ != hipSuccess) return hipfail(e_, #call);  \
-    } while (0)
 
 struct Mat4 {
     double v[16];
@@ -571,8 +553,8 @@ constexpr int kBackDoubles = 20 + 4;   // result, then (as int32) flags [4] + co
 
 int clear_scratch_table(icpflow_ego *e, hipStream_t st)
 {
-    EGO_HIP(hipMemsetAsync(e->mem + e->c.tkeys, 0xFF, (size_t)e->c.tcap * 8, st));
-    EGO_HIP(hipMemsetAsync(e->mem + e->c.tmin, 0x7F, (size_t)e->c.tcap * 4, st));
+    ICPFLOW_TRY(hipMemsetAsync(e->mem + e->c.tkeys, 0xFF, (size_t)e->c.tcap * 8, st));
+    ICPFLOW_TRY(hipMemsetAsync(e->mem + e->c.tmin, 0x7F, (size_t)e->c.tcap * 4, st));
     return 0;
 }
 
@@ -592,7 +574,7 @@ int enqueue_downsample(icpflow_ego *e, const float *d_points, int n, hipStream_t
     ds_vote_kernel<<<blocks, 256, 0, st>>>(d_points, e->at<int32_t>(e->c.idxDs), counts, n, 1.5 * e->voxel, 0, 0.0, 0.0, tkeys, tmin,
                                            e->c.tcap - 1, slotOf, flags);
     ds_compact_kernel<<<1, 1024, 0, st>>>(e->at<int32_t>(e->c.idxDs), counts, n, tmin, slotOf, e->at<int32_t>(e->c.idxSrc), counts + 1);
-    EGO_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     return 0;
 }
 
@@ -613,7 +595,7 @@ int enqueue_register(icpflow_ego *e, const float *pts, const int32_t *rows, cons
         ego_guess_kernel<<<1, 64, 0, st>>>(a, d_result);
     else
         ego_register_kernel<<<1, kRegThreads, 0, st>>>(pts, rows, d_m, m_max, e->table(e->cur), (unsigned)e->par.map_capacity - 1, a, d_result);
-    EGO_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     return 0;
 }
 
@@ -632,11 +614,11 @@ int enqueue_map_add(icpflow_ego *e, const float *pts, const int32_t *rows, const
         map_append_kernel<<<blocks, 256, 0, st>>>(d_n, n_max, moved, slotOf, cur, p.max_points_per_voxel, same);
         map_count_kernel<<<blocks, 256, 0, st>>>(d_n, n_max, slotOf, same, cur, p.max_points_per_voxel);
     }
-    EGO_HIP(hipMemsetAsync(nxt.keys, 0xFF, (size_t)p.map_capacity * 8, st));
-    EGO_HIP(hipMemsetAsync(nxt.count, 0, (size_t)p.map_capacity * 4, st));
-    EGO_HIP(hipMemsetAsync(flags + kFlagLive, 0, 4, st));
+    ICPFLOW_TRY(hipMemsetAsync(nxt.keys, 0xFF, (size_t)p.map_capacity * 8, st));
+    ICPFLOW_TRY(hipMemsetAsync(nxt.count, 0, (size_t)p.map_capacity * 4, st));
+    ICPFLOW_TRY(hipMemsetAsync(flags + kFlagLive, 0, 4, st));
     map_prune_kernel<<<(p.map_capacity + 255) / 256, 256, 0, st>>>(cur, nxt, mask, d_pose, p.max_range * p.max_range, flags);
-    EGO_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     e->cur ^= 1;
     e->mapEmpty = false;
     return 0;
@@ -645,10 +627,10 @@ int enqueue_map_add(icpflow_ego *e, const float *pts, const int32_t *rows, const
 int enqueue_reset(icpflow_ego *e, hipStream_t st)
 {
     const MapTable t = e->table(e->cur);
-    EGO_HIP(hipMemsetAsync(t.keys, 0xFF, (size_t)e->par.map_capacity * 8, st));
-    EGO_HIP(hipMemsetAsync(t.count, 0, (size_t)e->par.map_capacity * 4, st));
-    EGO_HIP(hipMemsetAsync(e->mem + e->c.flags, 0, kNumFlags * 4, st));
-    EGO_HIP(hipMemsetAsync(e->mem + e->c.counts, 0, 16, st));
+    ICPFLOW_TRY(hipMemsetAsync(t.keys, 0xFF, (size_t)e->par.map_capacity * 8, st));
+    ICPFLOW_TRY(hipMemsetAsync(t.count, 0, (size_t)e->par.map_capacity * 4, st));
+    ICPFLOW_TRY(hipMemsetAsync(e->mem + e->c.flags, 0, kNumFlags * 4, st));
+    ICPFLOW_TRY(hipMemsetAsync(e->mem + e->c.counts, 0, 16, st));
     e->mapEmpty = true;
     e->poses.clear();
     e->sse = 0.0, e->numSamples = 0;
@@ -663,13 +645,6 @@ double model_error(const Mat4 &dev, double max_range)
     const double theta = std::acos(cs);
     const double dt = std::sqrt(dev.v[3] * dev.v[3] + dev.v[7] * dev.v[7] + dev.v[11] * dev.v[11]);
     return dt + 2.0 * max_range * std::sin(0.5 * theta);
-}
-
-int pointer_error(const char *fn)
-{
-    char msg[128];
-    snprintf(msg, sizeof(msg), "%s: null pointer", fn);
-    return report_error(ICPFLOW_E_ARG, msg);
 }
 
 }  // namespace
@@ -699,11 +674,7 @@ int icpflow_ego_create(const icpflow_ego_params_t *params, void *d_mem, size_t m
     if (!out) return pointer_error("icpflow_ego_create");
     *out = nullptr;
     const Carve c = carve(*params);
-    if (!d_mem || mem_bytes < c.total) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "icpflow_ego_create: workspace of %zu bytes, icpflow_ego_state_bytes says %zu", d_mem ? mem_bytes : (size_t)0, c.total);
-        return report_error(ICPFLOW_E_WORKSPACE, msg);
-    }
+    if (!d_mem || mem_bytes < c.total) return icpflow::workspace_error("icpflow_ego_create", "icpflow_ego_state_bytes", d_mem, mem_bytes, c.total);
     if (((uintptr_t)d_mem & 7) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_ego_create: d_mem must be 8-byte aligned");
     icpflow_ego *e = new (std::nothrow) icpflow_ego();
     if (!e) return report_error(ICPFLOW_E_HOSTMEM, "icpflow_ego_create: out of host memory");
@@ -748,13 +719,13 @@ int icpflow_ego_downsample(icpflow_ego_t *e, const float *d_points, int n, int32
     if (n > e->par.max_points) return report_error(ICPFLOW_E_LIMIT, "icpflow_ego_downsample: n beyond the state's max_points");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        EGO_HIP(hipMemsetAsync(d_counts, 0, 8, st));
+        ICPFLOW_TRY(hipMemsetAsync(d_counts, 0, 8, st));
         return ICPFLOW_OK;
     }
     if (int rc = enqueue_downsample(e, d_points, n, st)) return rc;
-    EGO_HIP(hipMemcpyAsync(d_idx_ds, e->mem + e->c.idxDs, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    EGO_HIP(hipMemcpyAsync(d_idx_source, e->mem + e->c.idxSrc, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    EGO_HIP(hipMemcpyAsync(d_counts, e->mem + e->c.counts, 8, hipMemcpyDeviceToDevice, st));
+    ICPFLOW_TRY(hipMemcpyAsync(d_idx_ds, e->mem + e->c.idxDs, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    ICPFLOW_TRY(hipMemcpyAsync(d_idx_source, e->mem + e->c.idxSrc, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    ICPFLOW_TRY(hipMemcpyAsync(d_counts, e->mem + e->c.counts, 8, hipMemcpyDeviceToDevice, st));
     return ICPFLOW_OK;
 }
 
@@ -785,11 +756,11 @@ int icpflow_ego_map_export(icpflow_ego_t *e, int64_t *d_keys, int32_t *d_counts,
     if (!e || !d_num || (capacity > 0 && (!d_keys || !d_counts || !d_points))) return pointer_error("icpflow_ego_map_export");
     if (capacity < 0) return report_error(ICPFLOW_E_ARG, "icpflow_ego_map_export: capacity < 0");
     hipStream_t st = (hipStream_t)stream;
-    EGO_HIP(hipMemsetAsync(d_num, 0, 4, st));
+    ICPFLOW_TRY(hipMemsetAsync(d_num, 0, 4, st));
     map_export_kernel<<<(e->par.map_capacity + 255) / 256, 256, 0, st>>>(e->table(e->cur), (unsigned)e->par.map_capacity - 1,
                                                                          e->par.max_points_per_voxel, (long long *)d_keys, d_counts,
                                                                          d_points, capacity, d_num);
-    EGO_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }
 
@@ -812,15 +783,15 @@ int icpflow_ego_register_frame(icpflow_ego_t *e, const float *d_points, int n, d
     if (n > 0) {
         if (int rc = enqueue_downsample(e, d_points, n, st)) return rc;
     } else {
-        EGO_HIP(hipMemsetAsync(counts, 0, 8, st));
+        ICPFLOW_TRY(hipMemsetAsync(counts, 0, 8, st));
     }
     if (int rc = enqueue_register(e, d_points, e->at<int32_t>(e->c.idxSrc), counts + 1, n, guess.v, sigma, d_result, st)) return rc;
     if (int rc = enqueue_map_add(e, d_points, e->at<int32_t>(e->c.idxDs), counts, n, d_result, st)) return rc;
     // the frame's one read-back
-    EGO_HIP(hipMemcpyAsync(e->h_back, d_result, 20 * 8, hipMemcpyDeviceToHost, st));
-    EGO_HIP(hipMemcpyAsync(e->h_back + 20, e->mem + e->c.flags, kNumFlags * 4, hipMemcpyDeviceToHost, st));
-    EGO_HIP(hipMemcpyAsync(e->h_back + 22, counts, 16, hipMemcpyDeviceToHost, st));
-    EGO_HIP(hipStreamSynchronize(st));
+    ICPFLOW_TRY(hipMemcpyAsync(e->h_back, d_result, 20 * 8, hipMemcpyDeviceToHost, st));
+    ICPFLOW_TRY(hipMemcpyAsync(e->h_back + 20, e->mem + e->c.flags, kNumFlags * 4, hipMemcpyDeviceToHost, st));
+    ICPFLOW_TRY(hipMemcpyAsync(e->h_back + 22, counts, 16, hipMemcpyDeviceToHost, st));
+    ICPFLOW_TRY(hipStreamSynchronize(st));
     const int32_t *hflags = (const int32_t *)(e->h_back + 20), *hcounts = (const int32_t *)(e->h_back + 22);
     Mat4 pose;
     std::memcpy(pose.v, e->h_back, sizeof(pose.v));

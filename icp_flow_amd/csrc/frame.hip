@@ -25,11 +25,10 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/icpflow_hip.h"
+#include "host.hpp"
 
-namespace icpflow {
-int report_error(int code, const char *message);   // api.hip: what icpflow_last_error returns
-}
+using icpflow::align256;
+using icpflow::Carver;
 using icpflow::report_error;
 
 namespace {
@@ -451,7 +450,6 @@ inline SecondStream &second_stream()
     return e;
 }
 
-inline size_t up(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int round64(int64_t x) { return (int)((x + 63) / 64 * 64); }
 
 }  // namespace
@@ -477,13 +475,13 @@ extern "C" int icpflow_track_frame(const float *d_points_src, const float *d_lab
 
     // ---- device scratch, first part: the label-sorted orders, both tables, the tables' workspace
     char *base = static_cast<char *>(d_scratch);
-    size_t off = 0;
-    const size_t oOrderS = off; off += up(sizeof(int64_t) * (size_t)n_src);
-    const size_t oOrderD = off; off += up(sizeof(int64_t) * (size_t)n_dst);
-    const size_t oTables = off; off += up(sizeof(double) * 2 * kTableDoubles);
+    Carver scratch;   // (offsets only: the scratch is addressed through `base`)
+    const size_t oOrderS = scratch.take(sizeof(int64_t) * (size_t)n_src);
+    const size_t oOrderD = scratch.take(sizeof(int64_t) * (size_t)n_dst);
+    const size_t oTables = scratch.take(sizeof(double) * 2 * kTableDoubles);
     const size_t tableWs = icpflow_cluster_table_pair_workspace_bytes(n_src, n_dst, kTableRows);
-    const size_t oTableWs = off; off += up(tableWs);
-    const size_t fixedBytes = off;
+    const size_t oTableWs = scratch.take(tableWs);
+    const size_t fixedBytes = scratch.total();
     *scratch_needed = fixedBytes;
     if (d_scratch == nullptr || scratch_bytes < fixedBytes) return report_error(ICPFLOW_E_WORKSPACE, "icpflow_track_frame: scratch too small (see *scratch_needed)");
     int64_t *orderS = reinterpret_cast<int64_t *>(base + oOrderS), *orderD = reinterpret_cast<int64_t *>(base + oOrderD);
@@ -590,22 +588,22 @@ extern "C" int icpflow_track_frame(const float *d_points_src, const float *d_lab
     // ---- device scratch, second part
     const size_t ws1 = icpflow_workspace_bytes(K1, N1, reg->len_x, reg->len_y, reg->len_z);
     const size_t ws2 = K2 ? icpflow_workspace_bytes(K2, N2, reg->len_x, reg->len_y, reg->len_z) : 0;
-    const size_t oClouds1 = off; off += up(sizeof(float) * 8 * (size_t)K1 * N1);
-    const size_t oRes1 = off; off += up(sizeof(float) * (30 * (size_t)K1 + 1));
-    const size_t oClouds2 = off; off += up(sizeof(float) * 8 * (size_t)K2 * N2);
-    const size_t oRes2 = off; off += up(sizeof(float) * (30 * (size_t)K2 + 1));
-    const size_t oActive = off; off += up((size_t)K2 + 1);
-    const size_t oBest = off; off += up(sizeof(int32_t) * (2 * (size_t)S + 2));
-    const size_t oWs = off; off += up(ws1);
-    const size_t oWs2 = off; off += up(ws2);     // (a workspace of its own: stage 2 estimates its initial poses beside stage 1's ICP)
-    *scratch_needed = off;
-    if (scratch_bytes < off) return report_error(ICPFLOW_E_WORKSPACE, "icpflow_track_frame: scratch too small (see *scratch_needed)");
+    const size_t oClouds1 = scratch.take(sizeof(float) * 8 * (size_t)K1 * N1);
+    const size_t oRes1 = scratch.take(sizeof(float) * (30 * (size_t)K1 + 1));
+    const size_t oClouds2 = scratch.take(sizeof(float) * 8 * (size_t)K2 * N2);
+    const size_t oRes2 = scratch.take(sizeof(float) * (30 * (size_t)K2 + 1));
+    const size_t oActive = scratch.take((size_t)K2 + 1);
+    const size_t oBest = scratch.take(sizeof(int32_t) * (2 * (size_t)S + 2));
+    const size_t oWs = scratch.take(ws1);
+    const size_t oWs2 = scratch.take(ws2);     // (a workspace of its own: stage 2 estimates its initial poses beside stage 1's ICP)
+    *scratch_needed = scratch.total();
+    if (scratch_bytes < scratch.total()) return report_error(ICPFLOW_E_WORKSPACE, "icpflow_track_frame: scratch too small (see *scratch_needed)");
 
     g_frameStamp[10] = now_us();   // (workspace sizes)
     // pinned staging: [tables (done with) | seg1 int64 [2,3,K1] | perm int32 [nPerm, maxPoints] | seg2 int64 [2,3,K2] |
     //                  si1, di1, si2, di2 int32 | best int32 [2S+2]]
-    const size_t pSeg1 = 0, pPerm = pSeg1 + 48 * (size_t)K1, pSeg2 = up(pPerm + 4 * (size_t)nPerm * maxPoints);
-    const size_t pIdx = pSeg2 + 48 * (size_t)K2, pBest = up(pIdx + 8 * ((size_t)K1 + K2));
+    const size_t pSeg1 = 0, pPerm = pSeg1 + 48 * (size_t)K1, pSeg2 = align256(pPerm + 4 * (size_t)nPerm * maxPoints);
+    const size_t pIdx = pSeg2 + 48 * (size_t)K2, pBest = align256(pIdx + 8 * ((size_t)K1 + K2));
     const size_t pinBytes = pBest + 4 * (2 * (size_t)S + 2);
     pin = H.need(pinBytes);   // (the tables have been parsed: the buffer may move)
     if (pin == nullptr) return report_error(ICPFLOW_E_HOSTMEM, "icpflow_track_frame: no pinned host memory");
@@ -734,12 +732,12 @@ extern "C" int icpflow_track_frame(const float *d_points_src, const float *d_lab
         const int K3 = (int)si3.size();
         const int N3 = par->tight_padding ? std::min(maxPoints, std::max(64, round64(longest3))) : maxPoints;
         const size_t ws3 = K3 ? icpflow_workspace_bytes(K3, N3, reg->len_x, reg->len_y, reg->len_z) : 0;
-        const size_t oClouds3 = off; off += up(sizeof(float) * 8 * (size_t)K3 * N3);
-        const size_t oRes3 = off; off += up(sizeof(float) * (30 * (size_t)K3 + 1));
-        const size_t oWs3 = off; off += up(ws3);
-        *scratch_needed = off;
-        if (scratch_bytes < off) return report_error(ICPFLOW_E_WORKSPACE, "icpflow_track_frame: scratch too small (see *scratch_needed)");
-        const size_t qPerm = 48 * (size_t)K3, qIdx = up(qPerm + 4 * (size_t)nPerm3 * maxPoints), qBest = up(qIdx + 8 * (size_t)K3);
+        const size_t oClouds3 = scratch.take(sizeof(float) * 8 * (size_t)K3 * N3);
+        const size_t oRes3 = scratch.take(sizeof(float) * (30 * (size_t)K3 + 1));
+        const size_t oWs3 = scratch.take(ws3);
+        *scratch_needed = scratch.total();
+        if (scratch_bytes < scratch.total()) return report_error(ICPFLOW_E_WORKSPACE, "icpflow_track_frame: scratch too small (see *scratch_needed)");
+        const size_t qPerm = 48 * (size_t)K3, qIdx = align256(qPerm + 4 * (size_t)nPerm3 * maxPoints), qBest = align256(qIdx + 8 * (size_t)K3);
         char *pin3 = H.second.need(qBest + 4 * (2 * (size_t)S + 2));
         if (pin3 == nullptr) return report_error(ICPFLOW_E_HOSTMEM, "icpflow_track_frame: no pinned host memory");
         int64_t *seg3 = reinterpret_cast<int64_t *>(pin3);

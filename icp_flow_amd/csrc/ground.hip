@@ -29,13 +29,12 @@
 #include <cstdio>
 #include <cstring>
 
-#include "../../include/icpflow_hip.h"
 #include "common.hpp"
+#include "host.hpp"
 
-namespace icpflow {
-int report_error(int code, const char *message);   // api.hip: what icpflow_last_error returns
-}
+using icpflow::Carver;
 using icpflow::kWave;
+using icpflow::pointer_error;
 using icpflow::report_error;
 
 namespace {
@@ -72,21 +71,6 @@ struct Plane {
     double mean[3], normal[3], sv[3], d;
 };
 
-int hipfail(hipError_t e, const char *what)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", what, hipGetErrorString(e));
-    return report_error((int)e, msg);
-}
-
-#define GROUND_HIP(call)                                  \
-    do {                                                  \
-        const hipError_t e_ = (call);                     \
-        if (e_ != hipSuccess) return hipfail(e_, #call);  \
-    } while (0)
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct Carve {
     int waves, chunk;                      // binning waves and the rows of each
     size_t pid, order, points, state, wave_count, start, table, total;
@@ -99,15 +83,15 @@ Carve carve(int n)
     c.waves = (int)(want < 1 ? 1 : want > kMaxBinWaves ? kMaxBinWaves : want);
     const long long per = ((long long)n + c.waves - 1) / c.waves;
     c.chunk = (int)((per + kWave - 1) / kWave * kWave);
-    size_t at = 0;
-    c.pid = at, at += round256((size_t)n * sizeof(int32_t));
-    c.order = at, at += round256((size_t)n * sizeof(int32_t));
-    c.points = at, at += round256((size_t)n * 3 * sizeof(float));
-    c.state = at, at += round256((size_t)n);
-    c.wave_count = at, at += round256((size_t)c.waves * kPatches * sizeof(int32_t));
-    c.start = at, at += round256((size_t)(kPatches + 1) * sizeof(int32_t));
-    c.table = at, at += round256((size_t)kPatches * kCols * sizeof(double));
-    c.total = at;
+    Carver mem;
+    c.pid = mem.take((size_t)n * sizeof(int32_t));
+    c.order = mem.take((size_t)n * sizeof(int32_t));
+    c.points = mem.take((size_t)n * 3 * sizeof(float));
+    c.state = mem.take((size_t)n);
+    c.wave_count = mem.take((size_t)c.waves * kPatches * sizeof(int32_t));
+    c.start = mem.take((size_t)(kPatches + 1) * sizeof(int32_t));
+    c.table = mem.take((size_t)kPatches * kCols * sizeof(double));
+    c.total = mem.total();
     return c;
 }
 
@@ -509,13 +493,6 @@ __global__ __launch_bounds__(kThreads) void ground_revert_kernel(const int32_t *
         for (int k = threadIdx.x; k < kPatches * kCols; k += kThreads) table_out[k] = table[k];
 }
 
-int pointer_error(const char *fn)
-{
-    char msg[128];
-    snprintf(msg, sizeof(msg), "%s: null pointer", fn);
-    return report_error(ICPFLOW_E_ARG, msg);
-}
-
 const int kRingsWanted[4] = {2, 4, 4, 4}, kSectorsWanted[4] = {16, 32, 54, 32};
 
 // nullptr = fine
@@ -576,10 +553,7 @@ int icpflow_ground_segment(const float *d_points, int stride, int n, const icpfl
     if (stride < 3) return report_error(ICPFLOW_E_ARG, "icpflow_ground_segment: stride must be >= 3 floats");
     if (n == 0) return ICPFLOW_OK;
     const Carve c = carve(n);
-    if (!d_ws || ws_bytes < c.total) {
-        snprintf(msg, sizeof(msg), "%s: workspace of %zu bytes, %s says %zu", fn, d_ws ? ws_bytes : (size_t)0, "icpflow_ground_workspace_bytes", c.total);
-        return report_error(ICPFLOW_E_WORKSPACE, msg);
-    }
+    if (!d_ws || ws_bytes < c.total) return icpflow::workspace_error(fn, "icpflow_ground_workspace_bytes", d_ws, ws_bytes, c.total);
     if (((uintptr_t)d_ws & 7) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_ground_segment: d_ws must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)d_ws;
@@ -605,15 +579,15 @@ int icpflow_ground_segment(const float *d_points, int stride, int n, const icpfl
 
     const int blocks = (c.waves + kWaves - 1) / kWaves;
     ground_bin_kernel<<<blocks, kThreads, 0, st>>>(d_points, stride, n, g, c.waves, c.chunk, pid, d_nonground, wave_count);
-    GROUND_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     ground_scan_kernel<<<1, kScanThreads, 0, st>>>(wave_count, c.waves, start);
-    GROUND_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     ground_scatter_kernel<<<blocks, kThreads, 0, st>>>(d_points, stride, n, c.waves, c.chunk, pid, wave_count, start, order, sorted);
-    GROUND_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     ground_patch_kernel<<<kPatches, kThreads, 0, st>>>(sorted, order, start, par, state, d_nonground, table);
-    GROUND_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     ground_revert_kernel<<<1, kThreads, 0, st>>>(order, start, state, par, table, d_nonground, d_patch_table);
-    GROUND_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }
 

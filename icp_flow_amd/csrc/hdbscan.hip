@@ -28,6 +28,7 @@
 
 #include "kernels.hpp"
 #include "cluster_util.hpp"
+#include "host.hpp"
 
 namespace icpflow {
 
@@ -546,42 +547,36 @@ hipError_t carve(int n, void *ws, Carve *c, hipStream_t s)
                                              (unsigned long long *)nullptr, (int *)nullptr, (int *)nullptr,
                                              (size_t)n, 0, 63, s);
     if (e != hipSuccess) return e;
-    char *p = (char *)ws;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = p ? p + off : nullptr;
-        off += up256(bytes);
-        return q;
-    };
+    Carver mem(ws);
     const size_t N = (size_t)n;
     c->numChunks = (n + 63) / 64;
     c->rounds = boruvka_rounds(n);
     const size_t C = (size_t)c->numChunks;
-    c->keyIn = (unsigned long long *)take(N * 8);
-    c->keyOut = (unsigned long long *)take(N * 8);
-    c->valIn = (int *)take(N * 4);
-    c->valOut = (int *)take(N * 4);
-    c->sorted = (float4 *)take(N * 16);
-    c->core2 = (double *)take(N * 8);
-    c->bmin = (float *)take(C * 12);
-    c->bmax = (float *)take(C * 12);
-    c->sufMinX = (double *)take(C * 8);
-    c->preMaxX = (double *)take(C * 8);
-    c->nLive = (int *)take(4);
-    c->numComp = (int *)take((size_t)(c->rounds + 2) * 4);
-    c->comp = (int *)take(N * 4);
-    c->compSize = (int *)take(N * 4);
-    c->giant = (unsigned long long *)take((size_t)(c->rounds + 2) * 8);
-    c->parent = (int *)take(N * 4);
-    c->chunkComp = (int *)take(C * 4);
-    c->bestQ = (int *)take(N * 4);
-    c->bestW2 = (double *)take(N * 8);
-    c->bestKey = (unsigned long long *)take(N * 8);
-    c->compW = (unsigned long long *)take(N * 8);
-    c->compKey = (unsigned long long *)take(N * 8);
-    c->sortTmp = take(tmp);
+    c->keyIn = mem.take<unsigned long long>(N * 8);
+    c->keyOut = mem.take<unsigned long long>(N * 8);
+    c->valIn = mem.take<int>(N * 4);
+    c->valOut = mem.take<int>(N * 4);
+    c->sorted = mem.take<float4>(N * 16);
+    c->core2 = mem.take<double>(N * 8);
+    c->bmin = mem.take<float>(C * 12);
+    c->bmax = mem.take<float>(C * 12);
+    c->sufMinX = mem.take<double>(C * 8);
+    c->preMaxX = mem.take<double>(C * 8);
+    c->nLive = mem.take<int>(4);
+    c->numComp = mem.take<int>((size_t)(c->rounds + 2) * 4);
+    c->comp = mem.take<int>(N * 4);
+    c->compSize = mem.take<int>(N * 4);
+    c->giant = mem.take<unsigned long long>((size_t)(c->rounds + 2) * 8);
+    c->parent = mem.take<int>(N * 4);
+    c->chunkComp = mem.take<int>(C * 4);
+    c->bestQ = mem.take<int>(N * 4);
+    c->bestW2 = mem.take<double>(N * 8);
+    c->bestKey = mem.take<unsigned long long>(N * 8);
+    c->compW = mem.take<unsigned long long>(N * 8);
+    c->compKey = mem.take<unsigned long long>(N * 8);
+    c->sortTmp = mem.take<void>(tmp);
     c->sortTmpBytes = tmp;
-    c->total = off;
+    c->total = mem.total();
     return hipSuccess;
 }
 

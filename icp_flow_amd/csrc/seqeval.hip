@@ -17,16 +17,15 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
 
-#include "../../include/icpflow_hip.h"
 #include "common.hpp"
+#include "host.hpp"
 
-namespace icpflow {
-int report_error(int code, const char *message);   // api.hip: what icpflow_last_error returns
-}
+using icpflow::align256;
 using icpflow::kWave;
+using icpflow::pointer_error;
 using icpflow::report_error;
+using icpflow::workspace_error;
 
 namespace {
 
@@ -38,21 +37,6 @@ constexpr int kClasses = 6, kValues = 6;                // overall static static
 constexpr int kCell = kClasses * kValues;               // 64-bit words of one gap row
 constexpr int kMaxFrames = ICPFLOW_SEQ_MAX_FRAMES;
 constexpr int kInfo = 2;                                // kept rows of frame 0, rows whose time index is outside [0, F)
-
-int hipfail(hipError_t e, const char *what)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", what, hipGetErrorString(e));
-    return report_error((int)e, msg);
-}
-
-#define SEQ_HIP(call)                                     \
-    do {                                                  \
-        const hipError_t e_ = (call);                     \
-        if (e_ != hipSuccess) return hipfail(e_, #call);  \
-    } while (0)
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int grid_for(int m)
 {
@@ -242,20 +226,6 @@ __global__ __launch_bounds__(kThreads) void seq_metrics_final_kernel(const unsig
     }
 }
 
-int pointer_error(const char *fn)
-{
-    char msg[128];
-    snprintf(msg, sizeof(msg), "%s: null pointer", fn);
-    return report_error(ICPFLOW_E_ARG, msg);
-}
-
-int workspace_error(const char *fn, const void *ws, size_t have, size_t need)
-{
-    char msg[192];
-    snprintf(msg, sizeof(msg), "%s: workspace of %zu bytes, %s_workspace_bytes says %zu", fn, ws ? have : (size_t)0, fn, need);
-    return report_error(ICPFLOW_E_WORKSPACE, msg);
-}
-
 }  // namespace
 
 extern "C" {
@@ -263,7 +233,7 @@ extern "C" {
 size_t icpflow_seq_gt_flow_workspace_bytes(int m)
 {
     if (m < 0) return 0;
-    return round256((size_t)grid_for(m) * sizeof(unsigned long long));
+    return align256((size_t)grid_for(m) * sizeof(unsigned long long));
 }
 
 int icpflow_seq_gt_flow(const double *d_points, const int32_t *d_time_indice, const int32_t *d_inst_labels, int m, const double *d_ego,
@@ -278,22 +248,22 @@ int icpflow_seq_gt_flow(const double *d_points, const int32_t *d_time_indice, co
     if (!d_bad_rows || (!d_ego && !d_inst_tsfm) || (m > 0 && (!d_points || !d_time_indice || !d_out || (d_inst_tsfm && !d_inst_labels))))
         return pointer_error(fn);
     const size_t need = icpflow_seq_gt_flow_workspace_bytes(m);
-    if (!d_ws || ws_bytes < need) return workspace_error(fn, d_ws, ws_bytes, need);
+    if (!d_ws || ws_bytes < need) return workspace_error(fn, "icpflow_seq_gt_flow_workspace_bytes", d_ws, ws_bytes, need);
     if (((uintptr_t)d_ws & 7) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_gt_flow: d_ws must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int G = grid_for(m);
     unsigned long long *partial = (unsigned long long *)d_ws;
     seq_gt_flow_kernel<<<G, kThreads, 0, st>>>(d_points, d_time_indice, d_inst_labels, m, d_ego, F, d_inst_tsfm, K, output, d_out, partial);
-    SEQ_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     seq_count_final_kernel<<<1, kWave, 0, st>>>(partial, G, (long long *)d_bad_rows);
-    SEQ_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }
 
 size_t icpflow_seq_metrics_workspace_bytes(int m, int F)
 {
     if (m < 0 || F < 1 || F > kMaxFrames) return 0;
-    return round256((size_t)grid_for(m) * partial_words(F) * sizeof(unsigned long long));
+    return align256((size_t)grid_for(m) * partial_words(F) * sizeof(unsigned long long));
 }
 
 int icpflow_seq_metrics(const double *d_points, const int32_t *d_time_indice, const int32_t *d_sd_labels, const int32_t *d_fb_labels,
@@ -303,26 +273,23 @@ int icpflow_seq_metrics(const double *d_points, const int32_t *d_time_indice, co
     const char *fn = "icpflow_seq_metrics";
     if (m < 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: m < 0");
     if (F < 1) return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: F must be >= 1");
-    if (F > kMaxFrames) {
-        char msg[128];
-        snprintf(msg, sizeof(msg), "icpflow_seq_metrics: F = %d frames, the table of at most %d is kept in LDS", F, kMaxFrames);
-        return report_error(ICPFLOW_E_LIMIT, msg);
-    }
+    if (F > kMaxFrames)
+        return icpflow::report_errorf(ICPFLOW_E_LIMIT, "icpflow_seq_metrics: F = %d frames, the table of at most %d is kept in LDS", F, kMaxFrames);
     if (crop != ICPFLOW_SEQ_CROP_NONE && crop != ICPFLOW_SEQ_CROP_XY && crop != ICPFLOW_SEQ_CROP_XYZ)
         return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: crop must be ICPFLOW_SEQ_CROP_NONE, _XY or _XYZ");
     if (!d_table || !d_info || (m > 0 && (!d_points || !d_time_indice || !d_sd_labels || !d_fb_labels || !d_gt_flow || !d_pred_flow)))
         return pointer_error(fn);
     const size_t need = icpflow_seq_metrics_workspace_bytes(m, F);
-    if (!d_ws || ws_bytes < need) return workspace_error(fn, d_ws, ws_bytes, need);
+    if (!d_ws || ws_bytes < need) return workspace_error(fn, "icpflow_seq_metrics_workspace_bytes", d_ws, ws_bytes, need);
     if (((uintptr_t)d_ws & 7) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_metrics: d_ws must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int G = grid_for(m);
     unsigned long long *partial = (unsigned long long *)d_ws;
     const Crop c = {crop, range_x, range_y, z_min};
     seq_metrics_kernel<<<G, kThreads, 0, st>>>(d_points, d_time_indice, d_sd_labels, d_fb_labels, d_gt_flow, d_pred_flow, m, F, c, partial);
-    SEQ_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     seq_metrics_final_kernel<<<1, kThreads, 0, st>>>(partial, G, F, (unsigned long long *)d_table, (unsigned long long *)d_info);
-    SEQ_HIP(hipGetLastError());
+    ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }
 

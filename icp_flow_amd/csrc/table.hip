@@ -13,6 +13,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "host.hpp"
 
 namespace icpflow {
 namespace {
@@ -361,20 +362,14 @@ inline int table_chunks(int M) { return (M + kChunkRows - 1) / kChunkRows; }
 
 void table_carve(int MA, int MB, int Lmax, void *ws, TableCarve *c)
 {
-    char *p = (char *)ws;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = p ? p + off : nullptr;
-        off += (bytes + 255) / 256 * 256;
-        return q;
-    };
+    Carver mem(ws);
     for (int k = 0; k < 2; ++k) {
-        c->dict[k] = (uint32_t *)take((size_t)Lmax * 4);
-        c->start[k] = (int *)take((size_t)Lmax * 4);
+        c->dict[k] = mem.take<uint32_t>((size_t)Lmax * 4);
+        c->start[k] = mem.take<int>((size_t)Lmax * 4);
     }
-    c->rowOf = (uint16_t *)take(((size_t)MA + MB) * 2);
-    c->counts = (int *)take((size_t)(table_chunks(MA) + table_chunks(MB)) * Lmax * 4);
-    c->total = off;
+    c->rowOf = mem.take<uint16_t>(((size_t)MA + MB) * 2);
+    c->counts = mem.take<int>((size_t)(table_chunks(MA) + table_chunks(MB)) * Lmax * 4);
+    c->total = mem.total();
 }
 
 hipError_t table_chain(TableSides t, int Lmax, void *ws, size_t wsBytes, bool *wsTooSmall, hipStream_t s)

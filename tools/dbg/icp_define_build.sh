@@ -6,16 +6,18 @@
 cd "$(dirname "$0")/../.."
 SRC=${SWEEP_SRC:-icp.hip}
 C=icp_flow_amd/csrc
-BASE=$(basename $SRC .hip)
-OTHERS=$(ls $C/_obj/*.o | grep -v "/$BASE\.[0-9a-f]*\.o")
+python icp_flow_amd/build.py --force > /dev/null || exit 1   # (every object of the product in the cache; only what is missing compiles)
+# the compile flags and the product's other objects are build.py's: nothing is repeated here
+BUILD='import sys; sys.path.insert(0, "icp_flow_amd"); import build'
+CFLAGS=$(python -c "$BUILD; print(*build.CFLAGS)")
+OTHERS=$(python -c "$BUILD; print(*[argv[-1] for src, argv in build.plan()['compile'].items() if src != '$SRC'])")
 rm -f tools/dbg/sweep_*.so tools/dbg/sweep_*.txt
 k=0
 for DEFS in "$@"; do
   k=$((k+1))
   FLAGS=""; for d in $DEFS; do FLAGS="$FLAGS -D$d"; done
   echo "$DEFS" > tools/dbg/sweep_$k.txt
-  ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-      -Wno-unused-function $FLAGS -Iinclude -I$C -c $C/$SRC -o /tmp/sweep_$k.o 2>&1 | grep -v warning | head -5
+  ( /opt/rocm/bin/hipcc $CFLAGS $FLAGS -c $C/$SRC -o /tmp/sweep_$k.o 2>&1 | grep -v warning | head -5
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OTHERS /tmp/sweep_$k.o -o tools/dbg/sweep_$k.so && echo "built sweep_$k [$DEFS]" ) &
   [ $((k % ${SWEEP_JOBS:-6})) -eq 0 ] && wait
 done
