@@ -85,6 +85,10 @@ SIGNATURES = {
     "icpflow_ego_register_step": (_i, [_p, _p, _i, _p, _d, _p, _p]),
     "icpflow_ego_map_add": (_i, [_p, _p, _i, _p, _p]),
     "icpflow_ego_map_export": (_i, [_p, _p, _p, _p, _i, _p, _p]),
+    "icpflow_egomotion_default_params": (_i, [_p]),
+    "icpflow_egomotion_set_params": (_i, [_p, _p]),
+    "icpflow_egomotion_deskew": (_i, [_p, _p, _p, _i, _p, _p, _p]),
+    "icpflow_egomotion_register_frame_stamped": (_i, [_p, _p, _p, _i, _p, _p, _p]),
     "icpflow_seq_gt_flow_workspace_bytes": (_sz, [_i]),
     "icpflow_seq_gt_flow": (_i, [_p, _p, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "icpflow_seq_metrics_workspace_bytes": (_sz, [_i, _i]),
@@ -211,6 +215,21 @@ class EgoParams(ctypes.Structure):
         for k, v in over.items():
             if not hasattr(p, k):
                 raise TypeError(f"icpflow_ego_params_t has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+class EgoMotionParams(ctypes.Structure):
+    """icpflow_ego_motion_params_t: the ego-motion estimate's second configuration (deskewing, a fixed threshold)."""
+    _fields_ = [("struct_size", _sz), ("deskew", _i), ("reserved", _i), ("mid_stamp", _d), ("fixed_threshold", _d)]
+
+    @staticmethod
+    def defaults(**over):
+        p = EgoMotionParams()
+        call("icpflow_egomotion_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise TypeError(f"icpflow_ego_motion_params_t has no field {k!r}")
             setattr(p, k, v)
         return p
 

@@ -93,6 +93,49 @@ __device__ __forceinline__ int find_slot(const unsigned long long *__restrict__ 
     return -1;
 }
 
+// ---- step 0 (optional): motion compensation by per-point stamps ------------------------------------------------------------
+// The twist of the last motion, xi = log(inv(P[-2]) P[-1]) = (rho, omega), split on the host into the angle per unit stamp
+// w = |omega| and the unit axis a; K = [a]_x, K2 = K K.  With phi = d w (signed) the closed forms of exp(d xi) become
+//   R = I + sin(phi) K + (1 - cos(phi)) K2,   V = I + ((1 - cos(phi)) / phi) K + ((phi - sin(phi)) / phi) K2,   t = V (d rho)
+// and only the two coefficients of V divide by phi: below kSeriesBelow they come from their series.
+struct DeskewArgs {
+    double mid, w;
+    double rho[3], K[9], K2[9];
+};
+
+constexpr double kSeriesBelow = 0x1p-13;   // |phi| below which V's coefficients are series (include/icpflow_hip.h, 8(f) step 0)
+
+// one thread per point; a wave reads 768 consecutive bytes of rows and 256 of stamps, and writes 768: every fetched line
+// is used whole, whatever the alignment of the caller's buffers (12-byte rows leave nothing wider to rely on)
+__global__ __launch_bounds__(256) void ego_deskew_kernel(const float *__restrict__ pts, const float *__restrict__ stamps, int n,
+                                                         DeskewArgs a, float *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double p[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
+    const double d = (double)stamps[i] - a.mid;
+    const double phi = d * a.w;
+    double sh, ch;
+    sincos(0.5 * phi, &sh, &ch);
+    const double a1 = 2.0 * (sh * ch), a2 = 2.0 * (sh * sh);   // sin(phi), 1 - cos(phi) without the cancellation
+    double v1, v2;
+    if (fabs(phi) < kSeriesBelow) {
+        const double q = phi * phi;
+        v1 = phi * (0.5 - q / 24.0), v2 = q * (1.0 / 6.0 - q / 120.0);
+    } else {   // (a stamp that is not finite lands here: phi is NaN and so is the row)
+        v1 = a2 / phi, v2 = 1.0 - a1 / phi;
+    }
+    const double u[3] = {d * a.rho[0], d * a.rho[1], d * a.rho[2]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double kp = (a.K[3 * r] * p[0] + a.K[3 * r + 1] * p[1]) + a.K[3 * r + 2] * p[2];
+        const double k2p = (a.K2[3 * r] * p[0] + a.K2[3 * r + 1] * p[1]) + a.K2[3 * r + 2] * p[2];
+        const double ku = (a.K[3 * r] * u[0] + a.K[3 * r + 1] * u[1]) + a.K[3 * r + 2] * u[2];
+        const double k2u = (a.K2[3 * r] * u[0] + a.K2[3 * r + 1] * u[1]) + a.K2[3 * r + 2] * u[2];
+        out[3 * (size_t)i + r] = (float)((p[r] + (a1 * kp + a2 * k2p)) + (u[r] + (v1 * ku + v2 * k2u)));
+    }
+}
+
 // ---- steps 1-2: crop + voxel key + lowest index ----------------------------------------------------------------------------
 // pass 1: every candidate claims its voxel in the scratch table and lowers the voxel's index to its own
 __global__ void ds_vote_kernel(const float *__restrict__ pts, const int32_t *__restrict__ rows, const int32_t *__restrict__ d_n,
@@ -539,6 +582,7 @@ struct icpflow_ego {
     int numSamples;
     double *h_back;           // pinned: result [20] + flags + counts
     double info[kInfoWords];
+    icpflow_ego_motion_params_t motion;   // host only; kept across a reset
 
     MapTable table(int k) const
     {
@@ -638,6 +682,71 @@ int enqueue_reset(icpflow_ego *e, hipStream_t st)
     return 0;
 }
 
+void default_motion(icpflow_ego_motion_params_t *p)
+{
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = sizeof(*p);
+    p->deskew = 0, p->mid_stamp = 0.5, p->fixed_threshold = 0.0;
+}
+
+// the log of the rigid motion D in the kernel's terms: angle w, K = [axis]_x, K2 = K K, rho = V^-1 t with
+// V^-1 = I - (w / 2) K + (1 - (w / 2) cot(w / 2)) K2; false for a half turn, which has no axis to read off the skew part
+bool twist_of(const Mat4 &D, double mid, DeskewArgs *a)
+{
+    std::memset(a, 0, sizeof(*a));
+    a->mid = mid;
+    const double v[3] = {0.5 * (D.v[9] - D.v[6]), 0.5 * (D.v[2] - D.v[8]), 0.5 * (D.v[4] - D.v[1])};
+    const double s = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]), c = 0.5 * (((D.v[0] + D.v[5]) + D.v[10]) - 1.0);
+    const double t[3] = {D.v[3], D.v[7], D.v[11]};
+    if (!(s > 0.0)) {
+        if (!(c > 0.0)) return false;
+        for (int k = 0; k < 3; ++k) a->rho[k] = t[k];   // no rotation: w = 0, K = K2 = 0
+        return true;
+    }
+    const double w = std::atan2(s, c), ax[3] = {v[0] / s, v[1] / s, v[2] / s};
+    const double K[9] = {0.0, -ax[2], ax[1], ax[2], 0.0, -ax[0], -ax[1], ax[0], 0.0};
+    a->w = w;
+    for (int r = 0; r < 3; ++r)
+        for (int cc = 0; cc < 3; ++cc) {
+            a->K[3 * r + cc] = K[3 * r + cc];
+            a->K2[3 * r + cc] = (K[3 * r] * K[cc] + K[3 * r + 1] * K[3 + cc]) + K[3 * r + 2] * K[6 + cc];
+        }
+    const double h = 0.5 * w;
+    const double g = w < kSeriesBelow ? (w * w) * (1.0 / 12.0 + (w * w) / 720.0) : 1.0 - h * std::cos(h) / std::sin(h);
+    for (int r = 0; r < 3; ++r) {
+        const double kt = (a->K[3 * r] * t[0] + a->K[3 * r + 1] * t[1]) + a->K[3 * r + 2] * t[2];
+        const double k2t = (a->K2[3 * r] * t[0] + a->K2[3 * r + 1] * t[1]) + a->K2[3 * r + 2] * t[2];
+        a->rho[r] = t[r] + (g * k2t - h * kt);
+    }
+    return true;
+}
+
+// step 0 into d_out: the points moved by exp((stamp - mid_stamp) xi), xi from h_poses [2][16] or the state's last two
+// poses; a copy with fewer than two poses
+int enqueue_deskew(icpflow_ego *e, const char *fn, const float *d_points, const float *d_stamps, int n, const double *h_poses,
+                   float *d_out, hipStream_t st)
+{
+    if (n == 0) return 0;
+    const size_t np = e->poses.size();
+    if (!h_poses && np < 2) {
+        if (d_out != d_points) ICPFLOW_TRY(hipMemcpyAsync(d_out, d_points, (size_t)n * 12, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    Mat4 prev, last;
+    if (h_poses) {
+        std::memcpy(prev.v, h_poses, sizeof(prev.v));
+        std::memcpy(last.v, h_poses + 16, sizeof(last.v));
+    } else {
+        prev = e->poses[np - 2], last = e->poses[np - 1];
+    }
+    DeskewArgs a;
+    if (!twist_of(mul(rigid_inverse(prev), last), e->motion.mid_stamp, &a))
+        return icpflow::report_errorf(ICPFLOW_E_ARG, "%s: the two poses differ by a half turn (or are not finite): no twist to interpolate", fn);
+    ego_deskew_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_points, d_stamps, n, a, d_out);
+    ICPFLOW_TRY(hipGetLastError());
+    return 0;
+}
+
 double model_error(const Mat4 &dev, double max_range)
 {
     const double tr = dev.v[0] + dev.v[5] + dev.v[10];
@@ -684,6 +793,7 @@ int icpflow_ego_create(const icpflow_ego_params_t *params, void *d_mem, size_t m
     e->c = c;
     e->cur = 0;
     e->h_back = nullptr;
+    default_motion(&e->motion);
     if (hipHostMalloc((void **)&e->h_back, kBackDoubles * sizeof(double), hipHostMallocDefault) != hipSuccess) {
         delete e;
         return report_error(ICPFLOW_E_HOSTMEM, "icpflow_ego_create: pinned host memory could not be allocated");
@@ -777,7 +887,9 @@ int icpflow_ego_register_frame(icpflow_ego_t *e, const float *d_points, int n, d
     const Mat4 guess = np >= 2 ? mul(last, mul(rigid_inverse(e->poses[np - 2]), last)) : last;
     const double moved = std::sqrt(last.v[3] * last.v[3] + last.v[7] * last.v[7] + last.v[11] * last.v[11]);
     const bool adaptive = moved > 5.0 * p.min_motion_th && e->numSamples > 0;
-    const double sigma = adaptive ? std::sqrt(e->sse / e->numSamples) : p.initial_threshold;
+    const double sigma = e->motion.fixed_threshold > 0.0 ? e->motion.fixed_threshold
+                         : adaptive                      ? std::sqrt(e->sse / e->numSamples)
+                                                         : p.initial_threshold;
     int32_t *counts = e->at<int32_t>(e->c.counts);
     double *d_result = e->at<double>(e->c.result);
     if (n > 0) {
@@ -828,6 +940,53 @@ int icpflow_ego_frame_info(const icpflow_ego_t *e, double *h_info)
     if (!e || !h_info) return pointer_error("icpflow_ego_frame_info");
     std::memcpy(h_info, e->info, sizeof(e->info));
     return ICPFLOW_OK;
+}
+
+// ---- motion compensation and the fixed threshold (the estimator's second configuration) --------------------------------------
+int icpflow_egomotion_default_params(icpflow_ego_motion_params_t *p)
+{
+    if (!p) return pointer_error("icpflow_egomotion_default_params");
+    default_motion(p);
+    return ICPFLOW_OK;
+}
+
+int icpflow_egomotion_set_params(icpflow_ego_t *e, const icpflow_ego_motion_params_t *p)
+{
+    if (!e || !p) return pointer_error("icpflow_egomotion_set_params");
+    if (p->struct_size != sizeof(icpflow_ego_motion_params_t))
+        return icpflow::report_errorf(ICPFLOW_E_ARG, "icpflow_egomotion_set_params: struct_size is %zu, sizeof(icpflow_ego_motion_params_t) is %zu",
+                                      p->struct_size, sizeof(icpflow_ego_motion_params_t));
+    if (p->deskew != 0 && p->deskew != 1) return icpflow::report_errorf(ICPFLOW_E_ARG, "icpflow_egomotion_set_params: deskew is %d, not 0 or 1", p->deskew);
+    if (!std::isfinite(p->mid_stamp) || p->mid_stamp < 0.0)
+        return icpflow::report_errorf(ICPFLOW_E_ARG, "icpflow_egomotion_set_params: mid_stamp is %g, need a finite value >= 0", p->mid_stamp);
+    if (!std::isfinite(p->fixed_threshold) || p->fixed_threshold < 0.0)
+        return icpflow::report_errorf(ICPFLOW_E_ARG, "icpflow_egomotion_set_params: fixed_threshold is %g, need a finite value >= 0 (0 = adaptive)",
+                                      p->fixed_threshold);
+    e->motion = *p;
+    e->motion.reserved = 0;
+    return ICPFLOW_OK;
+}
+
+int icpflow_egomotion_deskew(icpflow_ego_t *e, const float *d_points, const float *d_stamps, int n, const double *h_poses, float *d_out,
+                             icpflow_stream_t stream)
+{
+    if (!e || (n > 0 && (!d_points || !d_stamps || !d_out))) return pointer_error("icpflow_egomotion_deskew");
+    if (n < 0) return report_error(ICPFLOW_E_ARG, "icpflow_egomotion_deskew: n < 0");
+    if (n > e->par.max_points) return report_error(ICPFLOW_E_LIMIT, "icpflow_egomotion_deskew: n beyond the state's max_points");
+    return enqueue_deskew(e, "icpflow_egomotion_deskew", d_points, d_stamps, n, h_poses, d_out, (hipStream_t)stream);
+}
+
+int icpflow_egomotion_register_frame_stamped(icpflow_ego_t *e, const float *d_points, const float *d_stamps, int n, float *d_corrected,
+                                             double *h_pose_out, icpflow_stream_t stream)
+{
+    if (!e) return pointer_error("icpflow_egomotion_register_frame_stamped");
+    if (!e->motion.deskew || !d_stamps) return icpflow_ego_register_frame(e, d_points, n, h_pose_out, stream);
+    if (!h_pose_out || (n > 0 && (!d_points || !d_corrected))) return pointer_error("icpflow_egomotion_register_frame_stamped");
+    if (n < 0) return report_error(ICPFLOW_E_ARG, "icpflow_egomotion_register_frame_stamped: n < 0");
+    if (n > e->par.max_points) return report_error(ICPFLOW_E_LIMIT, "icpflow_egomotion_register_frame_stamped: n beyond the state's max_points");
+    if (int rc = enqueue_deskew(e, "icpflow_egomotion_register_frame_stamped", d_points, d_stamps, n, nullptr, d_corrected, (hipStream_t)stream))
+        return rc;
+    return icpflow_ego_register_frame(e, d_corrected, n, h_pose_out, stream);
 }
 
 }  // extern "C"

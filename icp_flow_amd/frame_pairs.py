@@ -160,14 +160,21 @@ def _pose_file(path):
     return None
 
 
-def _estimate_poses(path, raw, t, args):
+def _estimate_poses(path, raw, t, args, point_time=None):
     """pose_source="estimate": the ego poses of the sample's frames from its raw points (every point of a frame, before any
-    crop of the scene: the reference estimates on the whole sweep, dataset_pca.py:126-130)."""
+    crop of the scene: the reference estimates on the whole sweep, dataset_pca.py:126-130).  `point_time` [m], the file's
+    optional per-point stamps (in [0, 1] over each sweep), is used only when args.ego_motion turns deskewing on."""
     from . import utils_ego_motion
     if len(t) == 0 or t.min() < 0:
         raise ValueError(f"{path}: time_indice does not describe a sequence")
     frames = [raw[t == j].astype(np.float32) for j in range(int(t.max()) + 1)]
-    poses = utils_ego_motion.estimate_poses(frames, args, getattr(args, "ego_device", None) if args is not None else None)
+    stamps = None
+    if point_time is not None and utils_ego_motion.read_motion(args)["deskew"]:
+        if point_time.shape != t.shape:
+            raise ValueError(f"{path}: point_time {point_time.shape} does not go with time_indice {t.shape}")
+        stamps = [point_time[t == j].astype(np.float32) for j in range(len(frames))]
+    poses = utils_ego_motion.estimate_poses(frames, args, getattr(args, "ego_device", None) if args is not None else None,
+                                            timestamps=stamps)
     if args is not None and getattr(args, "save_poses", False):
         parts = os.path.normpath(os.path.abspath(path)).split(os.sep)
         for k in range(len(parts) - 2, -1, -1):
@@ -198,7 +205,8 @@ def load_sequence(path, args=None, pose_source=None):
     sample itself; "ego_motion_gt": the GROUND-TRUTH poses of the sample -- accuracy measured with them is not the
     reference's protocol; "auto": pose file, else in-file `ego_motion`, else `ego_motion_gt` WITH a warning;
     "estimate" (explicit only, "auto" never picks it; needs a GPU): the poses are estimated from the sample's raw points,
-    frame by frame, by utils_ego_motion (scan-to-map odometry on the GPU; constants: args.ego_config), and written to the
+    frame by frame, by utils_ego_motion (scan-to-map odometry on the GPU; constants: args.ego_config; args.ego_motion =
+    dict(deskew=True) deskews every frame by the file's optional `point_time` [m], stamps in [0, 1] over each sweep), and written to the
     <split>_pose file only when args.save_poses is set (as the reference does, dataset_pca.py:131-135).  Every
     frame pair records where its pose came from (`FramePair.pose_source`, carried into run_stream's results)."""
     import warnings
@@ -215,7 +223,7 @@ def load_sequence(path, args=None, pose_source=None):
                 poses = np.asarray(zp["ego_motion"]).astype(np.float64)
             used = "pose_file"
         elif source == "estimate":
-            poses, used = _estimate_poses(path, raw, t, args), "estimate"
+            poses, used = _estimate_poses(path, raw, t, args, np.asarray(z["point_time"]) if "point_time" in keys else None), "estimate"
         elif source == "pose_file":
             raise FileNotFoundError(f"{path}: no <split>_pose file next to the split directory (pose_source='pose_file')")
         elif source in ("auto", "ego_motion") and "ego_motion" in keys:
@@ -939,6 +947,10 @@ def main(argv=None):
     ap.add_argument("--pose-source", choices=POSE_SOURCES, default=None,
                     help="ego poses of sequence files (default auto; estimate = scan-to-map odometry on the GPU)")
     ap.add_argument("--save-poses", action="store_true", help="with --pose-source estimate: write the <split>_pose files")
+    ap.add_argument("--ego-deskew", action="store_true",
+                    help="with --pose-source estimate: deskew every frame by the file's point_time key (stamps in [0, 1] over a sweep)")
+    ap.add_argument("--ego-fixed-threshold", type=float, default=0.0, metavar="X",
+                    help="with --pose-source estimate: sigma = X metres on every frame instead of the adaptive threshold (0 = adaptive)")
     ap.add_argument("--protocol", choices=("reference",), default=None,
                     help="reference: evaluate sequence files by the reference's table of 6 classes x (num_frames + 1) rows")
     ap.add_argument("--num-frames", type=int, default=5, help="--protocol reference: frames per sequence (main.py:67)")
@@ -961,6 +973,8 @@ def main(argv=None):
     args.max_points, args.min_cluster_size, args.chunk_size = int(args.max_points), int(args.min_cluster_size), int(args.chunk_size)
     args.num_clusters = int(args.num_clusters)
     args.pose_source, args.save_poses = ns.pose_source, ns.save_poses
+    if ns.ego_deskew or ns.ego_fixed_threshold:
+        args.ego_motion = dict(deskew=ns.ego_deskew, fixed_threshold=ns.ego_fixed_threshold)
     if ns.protocol == "reference":
         if world > 1:
             raise SystemExit("--protocol reference is single-process (the table is not reduced across ranks)")

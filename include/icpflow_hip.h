@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* (icpflow_seq_*, the evaluation of a sequence, and icpflow_ego_*, the ego-motion estimate, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 214 /* (icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -640,17 +640,21 @@ int icpflow_hdbscan_labels(const int32_t *h_edge_a, const int32_t *h_edge_b, con
 /* ---------------------------------------------------------------------------
  * 8(f)  ego motion of a LiDAR sequence that comes without poses: scan-to-map odometry resident on the GPU.
  * Replaces: `egomotion` -- utils_ego_motion.py:21-111 with config_kiss_icp.yaml (the reference hands every frame to the
- * third-party kiss_icp package, dataset_pca.py:115-135; this is that METHOD as published, not the package's bits, and
- * deskewing -- off in the reference's configuration -- is not built).  Poses are float64 [4,4] row-major, column-vector
- * convention (x' = R x + t); poses[j] maps frame j into frame 0's coordinates.
+ * third-party kiss_icp package, dataset_pca.py:115-135; this is that METHOD as published, not the package's bits).
+ * Poses are float64 [4,4] row-major, column-vector convention (x' = R x + t); poses[j] maps frame j into frame 0's
+ * coordinates.  The estimator's second configuration (config_kiss_icp.yaml's "advanced" block: deskew, fixed_threshold) is
+ * the icpflow_egomotion_* block below; both are off by default, as in the reference's configuration.
  *
  * Per frame (float32 [n,3] in the sensor's coordinates):
+ *   0. deskew        only through icpflow_egomotion_register_frame_stamped with deskew on: every point is moved by
+ *                    exp((stamp - mid_stamp) xi), xi = log(inv(pose[-2]) pose[-1]); unchanged with fewer than two poses
  *   1. crop          min_range^2 < x*x + y*y + z*z < max_range^2, evaluated in fp64
  *   2. down-sample   voxel of a coordinate = floor(x / size) in fp64; the point kept in a voxel is the one with the LOWEST
  *                    input index; `frame_ds`: size 0.5 v on the cropped frame, `source`: size 1.5 v on frame_ds
  *                    (v = voxel_size, 0 = max_range / 100); both lists are in ascending input index
  *   3. threshold     sigma = initial_threshold until the sensor has moved more than 5 min_motion_th from frame 0, then
- *                    sqrt(sse / count) over the model deviations of step 6
+ *                    sqrt(sse / count) over the model deviations of step 6; with a fixed_threshold > 0 sigma is that value
+ *                    on every frame (step 6 keeps its books all the same)
  *   4. guess         last_pose * inv(pose[-2]) * pose[-1], identity motion with fewer than two poses
  *   5. registration  of `source` against the map, at most max_iterations Gauss-Newton steps in ONE launch (device-side stop):
  *                    x = T p; correspondence q = the closest map point (fp64 squared distance, first minimum in the order
@@ -713,6 +717,51 @@ int icpflow_ego_register_step(icpflow_ego_t *ego, const float *d_source, int m, 
 int icpflow_ego_map_add(icpflow_ego_t *ego, const float *d_points, int n, const double *h_pose, icpflow_stream_t stream);
 int icpflow_ego_map_export(icpflow_ego_t *ego, int64_t *d_keys, int32_t *d_counts, float *d_points, int capacity,
                            int32_t *d_num, icpflow_stream_t stream);
+
+/* 8(f), second configuration: motion compensation ("deskewing") by per-point stamps, and a fixed threshold.
+ * Replaces: the motion compensator the reference's estimator calls on every frame with `deskew: True`
+ * (utils_ego_motion.py:29, :54) and `fixed_threshold` of the same block; restated from the published method.
+ *
+ * Step 0.  xi = (rho, omega) = log(inv(pose[-2]) pose[-1]) on the host in fp64.  Point i with stamp s_i: d = s_i - mid_stamp,
+ * p_i' = R p_i + V (d rho), R | V (d rho) = exp(d xi): with theta = |d omega|, K = [d omega]_x
+ *     R = I + (sin theta / theta) K + ((1 - cos theta) / theta^2) K^2
+ *     V = I + ((1 - cos theta) / theta^2) K + ((theta - sin theta) / theta^3) K^2
+ * evaluated per point in fp64 in a fixed order from the unit axis' K and K^2 scaled by the signed angle phi = d |omega|
+ * (one sincos, of phi / 2: sin phi = 2 s c and 1 - cos phi = 2 s s carry no cancellation), rounded ONCE to float32.  The
+ * two coefficients that divide by phi, (1 - cos phi) / phi and (phi - sin phi) / phi, come from their series
+ * phi (1/2 - phi^2 / 24) and phi^2 (1/6 - phi^2 / 120) for |phi| < 2^-13: there the series' next term is below 2^-54 of
+ * the coefficient, and the closed forms differ from the series by less than 2^-52 of the order-1 entries of V they add to,
+ * i.e. both branches give the coordinates to fp64 rounding.  The log reads the axis off the skew part of the rotation
+ * (angle = atan2(|skew|, (trace - 1) / 2)): two poses a half turn apart have no twist and are ICPFLOW_E_ARG.
+ * Stamps are used AS GIVEN: the caller normalises them to [0, 1] over the sweep (mid_stamp 0.5 = the middle of the sweep is
+ * where the frame's pose holds).  A stamp that is not finite gives a row that is not finite, which the crop of step 1
+ * drops (its comparisons are false).
+ *
+ * icpflow_egomotion_default_params: deskew 0, mid_stamp 0.5, fixed_threshold 0 (= adaptive).
+ * icpflow_egomotion_set_params: host only, no launch; the settings are kept across icpflow_ego_reset.  mid_stamp and
+ *   fixed_threshold must be finite and >= 0, deskew 0 or 1.
+ * icpflow_egomotion_deskew: step 0 alone, a piece like those above: asynchronous on `stream`, poses and sse untouched.
+ *   d_points float32 [n,3], d_stamps float32 [n] -> d_out float32 [n,3] (must not overlap d_points).  h_poses float64
+ *   [2][16] = (pose[-2], pose[-1]) to interpolate between, read before the call returns; NULL = the state's last two poses,
+ *   and with fewer than two of those d_out is a copy of d_points.
+ * icpflow_egomotion_register_frame_stamped: step 0 into d_corrected (float32 [n,3], the caller's: the state keeps its
+ *   size), then steps 1-6 on d_corrected exactly as icpflow_ego_register_frame runs them; on return d_corrected holds the
+ *   corrected frame.  With deskew 0 or d_stamps NULL it IS icpflow_ego_register_frame on d_points, bit for bit, and
+ *   d_corrected may be NULL; with deskew on, stamps given and d_corrected NULL it is ICPFLOW_E_ARG before anything is
+ *   enqueued. */
+typedef struct icpflow_ego_motion_params {
+    size_t struct_size;     /* sizeof(icpflow_ego_motion_params_t) */
+    int deskew;             /* 0      (config_kiss_icp.yaml data.deskew) */
+    int reserved;           /* 0 */
+    double mid_stamp;       /* 0.5    the stamp at which the frame's pose holds */
+    double fixed_threshold; /* 0 = adaptive (adaptive_threshold.fixed_threshold) */
+} icpflow_ego_motion_params_t;
+int icpflow_egomotion_default_params(icpflow_ego_motion_params_t *params);
+int icpflow_egomotion_set_params(icpflow_ego_t *ego, const icpflow_ego_motion_params_t *params);
+int icpflow_egomotion_deskew(icpflow_ego_t *ego, const float *d_points, const float *d_stamps, int n, const double *h_poses,
+                             float *d_out, icpflow_stream_t stream);
+int icpflow_egomotion_register_frame_stamped(icpflow_ego_t *ego, const float *d_points, const float *d_stamps, int n,
+                                             float *d_corrected, double *h_pose_out, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * 8(f)  evaluation of a whole sequence (a Waymo / nuScenes sample of the reference: m points of F frames, frame j = the

@@ -1,10 +1,11 @@
 """ms per frame of the ego-motion estimate at the demo frame's size, split into down-sampling, registration and map update
-(HIP events around the pieces of the C ABI, which is what icpflow_ego_register_frame chains), next to the whole call and to
-the fp64 restatement's CPU time for the same frames.
+(HIP events around the pieces of the C ABI, which is what icpflow_ego_register_frame chains) and the deskew launch of a
+stamped frame, next to the whole call and to the fp64 restatement's CPU time for the same frames.
 
     python tools/dbg/ego_motion_time.py [--frames 32] [--warmup 4]
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -78,6 +79,18 @@ def main():
         b.record()
         torch.cuda.synchronize()
         split["downsample"].append(a.elapsed_time(b))
+    # the deskew launch alone (step 0 of a stamped frame): stamps over the sweep, the twist of the last two poses
+    deskew_ms = []
+    for f in resident[1:]:
+        a, b = ev(), ev()
+        stamps = torch.linspace(0.0, 1.0, len(f), device=dev)
+        out = torch.empty((len(f), 3), dtype=torch.float32, device=dev)
+        two = (ctypes.c_double * 32)(*np.stack(poses[-2:]).reshape(32))
+        a.record()
+        _lib.call("icpflow_egomotion_deskew", ego._h, _lib.ptr(f), _lib.ptr(stamps), len(f), two, _lib.ptr(out), _lib.stream(dev))
+        b.record()
+        torch.cuda.synchronize()
+        deskew_ms.append(a.elapsed_time(b))
     # (c) the restatement on the CPU
     odo = rest.Odometry()
     cpu = []
@@ -88,7 +101,7 @@ def main():
     stat = lambda v: dict(median=float(np.median(v)), p10=float(np.percentile(v, 10)), p90=float(np.percentile(v, 90)), n=len(v))   # noqa: E731
     out = dict(points_per_frame=int(np.median([len(f) for f in frames])), last_frame=info, frames=len(whole) - 1,
                whole_call_ms=stat(whole[1 + ns.warmup:]), iterations=stat(iters[1:]),
-               downsample_ms=stat(split["downsample"]), registration_ms=stat(split["registration"]), map_update_ms=stat(split["map_update"]),
+               downsample_ms=stat(split["downsample"]), registration_ms=stat(split["registration"]), map_update_ms=stat(split["map_update"]), deskew_ms=stat(deskew_ms),
                registration_iterations=stat(split["step_iterations"]), restatement_cpu_ms=stat(cpu[1:]),
                worst_cap_m=float(max(scenes.cap_expression(p, t) for p, t in zip(poses, truth))))
     print(json.dumps(out))
