@@ -331,6 +331,11 @@ hipError_t launch_cluster_table_pair(const float *pointsA, const float *labelsA,
                                      hipStream_t s);
 hipError_t launch_cluster_table(const float *points, const float *labels, int M, int64_t *order, double *table, int Lmax,
                                 int32_t *num, void *ws, size_t wsBytes, bool *wsTooSmall, hipStream_t s);
+// ... its dictionary and stable order alone: table rows of kLabelOrderCols doubles, of which label, count and start are written
+// (workspace: cluster_table_workspace_bytes)
+constexpr int kLabelOrderCols = 9;
+hipError_t launch_label_order(const float *labels, int M, int64_t *order, double *table, int Lmax, int32_t *num, void *ws,
+                              size_t wsBytes, bool *wsTooSmall, hipStream_t s);
 
 // cluster.hip: DBSCAN of a frame pair's points (labels int32 [n]: cluster id, -1 noise, -2 masked out)
 hipError_t dbscan_workspace_bytes(int n, size_t *bytes);

@@ -1,0 +1,32 @@
+// rowerr.hpp -- the per-row arithmetic of the reference's compute_epe_test (utils_eval.py:162-180), shared by the two
+// kernels that evaluate flows: seq_metrics_kernel (seqeval.hip: sums per gap and class) and seg_chunk_kernel (segeval.hip:
+// sums per segment).  fp64 with numpy's operation order; the files that include this are compiled with -ffp-contract=off
+// (build.py: CFLAGS), so the squares, the two additions, the square root and the division are the separately rounded
+// operations numpy performs, the square root correctly rounded and the division IEEE.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace icpflow {
+
+struct RowError {
+    double e, r;             // end point error, relative error
+    bool p0, p1, p2, p3;     // strict, relax, outlier, Routlier
+};
+
+// utils_eval.py:170-180 on a row's e and r
+__device__ __forceinline__ RowError row_predicates(double e, double r)
+{
+    return RowError{e, r, e < 0.05 || r < 0.05, e < 0.1 || r < 0.1, e > 0.3 || r > 0.1, e > 0.3 && r > 0.3};
+}
+
+// utils_eval.py:163-168: numpy's norm is sqrt((x*x + y*y) + z*z), each operation rounded; the predicted flow is float32,
+// widened (exact)
+__device__ __forceinline__ RowError row_error(double gx, double gy, double gz, float px, float py, float pz)
+{
+    const double dx = gx - (double)px, dy = gy - (double)py, dz = gz - (double)pz;
+    const double e = sqrt((dx * dx + dy * dy) + dz * dz);
+    const double r = e / (sqrt((gx * gx + gy * gy) + gz * gz) + 1e-20);
+    return row_predicates(e, r);
+}
+
+}  // namespace icpflow

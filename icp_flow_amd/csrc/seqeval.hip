@@ -20,6 +20,7 @@
 
 #include "common.hpp"
 #include "host.hpp"
+#include "rowerr.hpp"
 
 using icpflow::align256;
 using icpflow::kWave;
@@ -128,24 +129,21 @@ __global__ __launch_bounds__(kThreads) void seq_metrics_kernel(const double *__r
         const bool row = i < (size_t)m;
         int t = -1;
         bool keep = false;
-        double e = 0.0, r = 0.0;
+        icpflow::RowError q = icpflow::row_predicates(0.0, 0.0);   // (of no row: read by none of the sums below)
         int s = 2, f = 2;
         if (row) {
             t = tim[i];
             const double x = pts[3 * i + 0], y = pts[3 * i + 1], z = pts[3 * i + 2];
             // crop_data, utils_eval.py:33-38 (a NaN coordinate fails every comparison there and here)
             keep = crop.mode == ICPFLOW_SEQ_CROP_NONE || (fabs(x) < crop.rx && fabs(y) < crop.ry && (crop.mode == ICPFLOW_SEQ_CROP_XY || z > crop.zmin));
-            const double gx = gt[3 * i + 0], gy = gt[3 * i + 1], gz = gt[3 * i + 2];
-            const double dx = gx - (double)pred[3 * i + 0], dy = gy - (double)pred[3 * i + 1], dz = gz - (double)pred[3 * i + 2];
-            // compute_epe_test, utils_eval.py:163-168: numpy's norm is sqrt((x*x + y*y) + z*z), each operation rounded
-            e = sqrt((dx * dx + dy * dy) + dz * dz);
-            r = e / (sqrt((gx * gx + gy * gy) + gz * gz) + 1e-20);
+            // compute_epe_test, utils_eval.py:163-168 (rowerr.hpp)
+            q = icpflow::row_error(gt[3 * i + 0], gt[3 * i + 1], gt[3 * i + 2], pred[3 * i + 0], pred[3 * i + 1], pred[3 * i + 2]);
             s = sd[i], f = fb[i];
         }
         outside += __popcll(__ballot(row && (t < 0 || t >= F)));
         kept0 += __popcll(__ballot(row && keep && t == 0));
-        // utils_eval.py:170-180
-        const bool p0 = e < 0.05 || r < 0.05, p1 = e < 0.1 || r < 0.1, p2 = e > 0.3 || r > 0.1, p3 = e > 0.3 && r > 0.3;
+        const double e = q.e;
+        const bool p0 = q.p0, p1 = q.p1, p2 = q.p2, p3 = q.p3;     // utils_eval.py:170-180
         const bool counted = row && keep && t >= 1 && t < F;
         unsigned long long todo = __ballot(counted);
         while (todo) {                                             // the gaps of the tile, in the order of their first row

@@ -372,7 +372,7 @@ void table_carve(int MA, int MB, int Lmax, void *ws, TableCarve *c)
     c->total = mem.total();
 }
 
-hipError_t table_chain(TableSides t, int Lmax, void *ws, size_t wsBytes, bool *wsTooSmall, hipStream_t s)
+hipError_t table_chain(TableSides t, int Lmax, void *ws, size_t wsBytes, bool *wsTooSmall, hipStream_t s, bool stats = true)
 {
     const int sides = t.M[1] > 0 ? 2 : 1;
     if (Lmax > kDictMax) return hipErrorInvalidValue;      // (api.hip refuses it before: Lmax <= 4096)
@@ -389,7 +389,7 @@ hipError_t table_chain(TableSides t, int Lmax, void *ws, size_t wsBytes, bool *w
     table_count_kernel<<<chunks, 256, 0, s>>>(t, Lmax);
     table_scan_kernel<<<sides, 1024, 0, s>>>(t, Lmax);
     table_scatter_kernel<<<chunks, kWave, 0, s>>>(t, Lmax);
-    table_stats_kernel<<<dim3(Lmax, sides), kRowsBlock, 0, s>>>(t);
+    if (stats) table_stats_kernel<<<dim3(Lmax, sides), kRowsBlock, 0, s>>>(t);
     return hipGetLastError();
 }
 
@@ -417,6 +417,15 @@ hipError_t launch_cluster_table(const float *points, const float *labels, int M,
     TableSides t{};
     t.points[0] = points; t.labels[0] = labels; t.M[0] = M; t.order[0] = order; t.table[0] = table; t.num[0] = num;
     return table_chain(t, Lmax, ws, wsBytes, wsTooSmall, s);
+}
+
+// the dictionary and the stable order alone (segeval.hip): columns 0-2 of the table's rows (label, count, start), no statistics
+hipError_t launch_label_order(const float *labels, int M, int64_t *order, double *table, int Lmax, int32_t *num, void *ws,
+                              size_t wsBytes, bool *wsTooSmall, hipStream_t s)
+{
+    TableSides t{};
+    t.labels[0] = labels; t.M[0] = M; t.order[0] = order; t.table[0] = table; t.num[0] = num;
+    return table_chain(t, Lmax, ws, wsBytes, wsTooSmall, s, false);
 }
 
 hipError_t launch_cluster_table_pair(const float *pointsA, const float *labelsA, int MA, int64_t *orderA, double *tableA,

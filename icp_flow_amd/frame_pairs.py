@@ -39,6 +39,11 @@ on the GPU (dataset_pca.py:66-69, utils_loading.py).
 
     python -m icp_flow_amd.frame_pairs DIR --protocol reference --num-frames 5 --range-x 32 --range-y 32 [--eval-ground]
                                            [--range-z 0.0 --ground-slack 0.3] [--ground patchwork]
+                                           [--if-verbose] [--report worst.json [--report-epe 2.0]]
+
+`--if-verbose` is the reference's verbose loop (utils_debug.debug_frame, utils_flow.flow_evaluation): per frame pair three
+lines (overall, static, dynamic) and the per-segment evaluation, from one more pass over what is resident
+(icpflow_seq_segment_table) and a read-back of two small tables.
 """
 import argparse
 import glob
@@ -367,7 +372,10 @@ def register_frame_pair_steps(args, fp, device, gap=None, asynchronous=False):
         flow = a.flow_result
     else:
         flow = utils_flow.flow_estimation_torch(a, flow_src, pd, ls, ld, pairs, T, pose)
-    return dict(pairs=pairs, transformations=T, flow=flow, translation_frame=a.translation_frame, association=a.association_path or "host")
+    out = dict(pairs=pairs, transformations=T, flow=flow, translation_frame=a.translation_frame, association=a.association_path or "host")
+    if getattr(args, "if_verbose", False):      # what the per-segment report reads besides the flow (run_sequences)
+        out.update(labels_src=ls, labels_dst=ld)
+    return out
 
 
 def _native_host(args):
@@ -601,6 +609,8 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
     out = dict(pairs=rows[:P], transformations=T[:P], translation_frame=a.translation_frame, association="device")
     if flow is not None:
         out["flow"] = flow
+    if getattr(a, "if_verbose", False):         # what the per-segment report reads besides the flow (run_sequences)
+        out.update(labels_src=ls, labels_dst=ld)
     return out
 
 
@@ -804,6 +814,34 @@ def _sequence_ground(args, sample, fps):
     return "threshold"
 
 
+def _sequence_reports(args, path, data, rows, kept):
+    """The reference's verbose loop for the frame pairs of one sequence (main.py:262-263: debug_frame per frame, which prints
+    its three lines and, under if_verbose, flow_evaluation's): per frame pair the `result` dict of main.py:236-259 from what is
+    resident -- the sample's rows of gap j and of frame 0, the labels, pairs and transforms the registration left -- through
+    utils_debug.debug_frame.  -> [dict(sequence, gap, frame, lines, segments)]"""
+    from . import utils_debug
+    out = []
+    for fp, reg in sorted(kept, key=lambda x: x[0].gap):
+        if "labels_src" not in reg:
+            raise RuntimeError("if_verbose: this registration path does not hand the cluster labels over")
+        dev = reg["flow"].device
+        r = rows[fp.gap]
+        result = dict(j=fp.gap, src=data["raw_points"][r], dst=data["raw_points"][rows[0]], pose=torch.from_numpy(fp.pose).to(dev),
+                      sd_label=data["sd_labels"][r], fb_label=data["fb_labels"][r], scene_flow=data["scene_flow"][r],
+                      src_label=reg["labels_src"], dst_label=reg["labels_dst"], flow=reg["flow"], transformations=reg["transformations"],
+                      pairs=reg["pairs"])
+        got = utils_debug.debug_frame(args, result)
+        out.append(dict(sequence=path, gap=fp.gap, **got))
+    return out
+
+
+def worst_segments(reports, threshold=2.0):
+    """The segments of run_sequences' reports whose EPE exceeds `threshold`, worst first: [dict(sequence, gap, label, n, epe,
+    matched_label, translation, rotation_zyx_deg)] (what --report writes)."""
+    rows = [dict(sequence=r["sequence"], gap=r["gap"], **seg) for r in reports for seg in r["segments"].worst(threshold)]
+    return sorted(rows, key=lambda x: -x["epe"])
+
+
 def run_sequences(args, paths, device, in_flight=1):
     """Evaluate sequence files by the reference's protocol (main.py:173-296) on one GPU.  Per file: the sample
     (`load_sequence_sample`) and its num_frames - 1 frame pairs (`load_sequence`), registered by the existing path
@@ -812,11 +850,16 @@ def run_sequences(args, paths, device, in_flight=1):
     read-back of the table.  args: the registration's (default_args) plus num_frames, range_x, range_y, range_z,
     ground_slack, eval_ground.
     -> dict(metrics = the reference's meters, sequences, frame_pairs, ms_per_sequence (registration + evaluation, the
-    sample's evaluation inputs resident beforehand like the loader's work), ms_eval_per_sequence, ground, pose_sources)."""
+    sample's evaluation inputs resident beforehand like the loader's work), ms_eval_per_sequence, ground, pose_sources).
+    With args.if_verbose (absent = False): after a sequence's evaluation the reference's per-frame lines and per-segment
+    report of each of its frame pairs (utils_debug.debug_frame, utils_flow.flow_evaluation; printed as the reference prints
+    them), returned under `segments` and timed on their own as ms_report_per_sequence; the other two times keep their meaning."""
     device = torch.device(device)
     F = int(args.num_frames)
     metrics = utils_eval.new_metric_table(F)
     times, eval_times, n_pairs, ground, pose_sources = [], [], 0, {}, {}
+    verbose = bool(getattr(args, "if_verbose", False))
+    segments, report_times = [], []
     for path in paths:
         sample = load_sequence_sample(path, args)
         fps = load_sequence(path, args)
@@ -843,18 +886,27 @@ def run_sequences(args, paths, device, in_flight=1):
             done = register_in_flight(args, fps, device, in_flight)
         else:
             done = ((k, fp, register_frame_pair(args, fp, device)) for k, fp in enumerate(fps))
+        kept = []
         for _, fp, out in done:
             flow_seq.index_copy_(0, rows[fp.gap], out["flow"].to(torch.float32))
             n_pairs += 1
+            if verbose:
+                kept.append((fp, out))
         torch.cuda.synchronize(device)
         t1 = time.perf_counter()
         utils_eval.calculate_metrics(args, data, flow_seq, metrics)     # (its read-back of the table is the synchronisation)
         t2 = time.perf_counter()
         times.append((t2 - t0) * 1e3)
         eval_times.append((t2 - t1) * 1e3)
-    return dict(metrics=metrics, sequences=len(times), frame_pairs=n_pairs, ms_per_sequence=sum(times) / max(len(times), 1),
-                ms_eval_per_sequence=sum(eval_times) / max(len(eval_times), 1),
-                ground="+".join(sorted(ground)) if ground else "none", pose_sources=pose_sources)
+        if verbose:
+            segments.extend(_sequence_reports(args, path, data, rows, kept))
+            report_times.append((time.perf_counter() - t2) * 1e3)
+    res = dict(metrics=metrics, sequences=len(times), frame_pairs=n_pairs, ms_per_sequence=sum(times) / max(len(times), 1),
+               ms_eval_per_sequence=sum(eval_times) / max(len(eval_times), 1),
+               ground="+".join(sorted(ground)) if ground else "none", pose_sources=pose_sources)
+    if verbose:
+        res.update(segments=segments, ms_report_per_sequence=sum(report_times) / max(len(report_times), 1))
+    return res
 
 
 def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, register_fn=None, in_flight=1):
@@ -960,6 +1012,11 @@ def main(argv=None):
     ap.add_argument("--ground", choices=("auto", "patchwork"), default="auto",
                     help="--protocol reference: auto = the file's nonground key, else the height threshold; patchwork = "
                          "Patchwork++ AND the threshold per frame on the GPU (utils_ground.py:16-23)")
+    ap.add_argument("--if-verbose", action="store_true",
+                    help="--protocol reference: print the per-frame and per-segment lines of the reference's --if_verbose (main.py:117)")
+    ap.add_argument("--report", metavar="FILE", default=None,
+                    help="--protocol reference: write a JSON list of the segments with EPE above --report-epe, worst first")
+    ap.add_argument("--report-epe", type=float, default=2.0, help="threshold of --report in metres (utils_flow.py:112)")
     ns = ap.parse_args(argv)
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -982,7 +1039,13 @@ def main(argv=None):
             args.range_x, args.range_y = 32.0, 32.0                                    # main.py:69-72
         args.num_frames, args.range_z, args.ground_slack, args.eval_ground = ns.num_frames, ns.range_z, ns.ground_slack, ns.eval_ground
         args.ground = ns.ground
+        if ns.if_verbose or ns.report:
+            args.if_verbose = True
         res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_sequence(p)], device, in_flight=ns.in_flight)
+        reports = res.pop("segments", None)
+        if ns.report:
+            with open(ns.report, "w") as f:
+                json.dump(worst_segments(reports, ns.report_epe), f, indent=1)
         print(utils_eval.format_metric_table(res.pop("metrics"), args.num_frames))
         print(json.dumps(res))
         return

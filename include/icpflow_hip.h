@@ -819,6 +819,41 @@ int icpflow_seq_metrics(const double *d_points, const int32_t *d_time_indice, co
                         size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(f)  per-segment evaluation of one labelled cloud of one frame pair: the numbers behind the reference's verbose loop,
+ * without the flows crossing to the host.
+ *
+ * icpflow_seq_segment_table -- replaces the per-segment masks and reductions of utils_flow.py:86-95 (idx_i, idx_j,
+ *   compute_epe_test of the segment's rows), :110 (len_i, len_j, mean_i, mean_j), :123 (mean(x + flow), mean(x)), on the
+ *   rows utils_debug.py:37-46 keeps.  A segment is one distinct value of d_labels (float32 [n]); segments appear in ascending
+ *   order exactly as icpflow_cluster_table defines them (its dictionary and stable order are reused): ground (-1e8) and
+ *   noise (-1) are segments like any other, Lmax <= 4096 (else ICPFLOW_E_LIMIT), and *d_num (int32) is the number of
+ *   segments, or the NEGATIVE count when there are more distinct labels than Lmax (nothing of the table is written then).
+ *   A row is kept when z > z_min (-inf: no crop; the caller rounds the threshold to the points' stored dtype, as for
+ *   icpflow_seq_metrics).  d_points float64 [n,3], d_gt_flow float64 [n,3], d_pred_flow float32 [n,3].  Per kept row e, r and
+ *   the four predicates are icpflow_seq_metrics' per-row arithmetic (one __device__ function, csrc/rowerr.hpp).
+ *   d_table double [Lmax][ICPFLOW_SEG_COLS], row c = the c-th distinct label (rows from *d_num on are not written):
+ *       0       label                                1       rows of the segment
+ *       2       kept rows                            3       sum of e over the kept rows
+ *       4 - 7   kept rows satisfying each predicate (strict, relax, outlier, Routlier)
+ *       8 - 10  sum x, sum y, sum z over the kept rows
+ *       11 - 13 sum (x + fx), (y + fy), (z + fz), f the predicted flow widened to fp64, each term rounded once
+ *       14 - 15 zero
+ *   Counts are exact in a double.  With d_gt_flow == NULL and d_pred_flow == NULL only columns 0 - 2 and 8 - 10 are filled
+ *   (the others are zero): the destination cloud, for len_j and mean_j.  Exactly one of the two NULL is ICPFLOW_E_ARG.
+ *   Every sum is a function of the arguments alone: segments are cut into chunks of 1024 rows of the stable order, a
+ *   workgroup per chunk (a large segment does not serialise on one wave), fixed order inside the chunk, chunks added in
+ *   ascending order; no floating-point atomics (csrc/segeval.hip).
+ *   The workspace is the caller's: icpflow_seq_segment_table_workspace_bytes(n, Lmax) bytes (0 for arguments the call
+ *   refuses), 8-byte aligned; nothing in it is read before it is written; fewer bytes are ICPFLOW_E_WORKSPACE before anything
+ *   is written.  n == 0 succeeds with *d_num = 0.  Asynchronous on `stream`.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_SEG_COLS 16
+size_t icpflow_seq_segment_table_workspace_bytes(int n, int Lmax);
+int icpflow_seq_segment_table(const double *d_points, const float *d_labels, int n, const double *d_gt_flow,
+                              const float *d_pred_flow, double z_min, double *d_table, int Lmax, int32_t *d_num, void *d_ws,
+                              size_t ws_bytes, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
