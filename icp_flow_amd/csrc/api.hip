@@ -230,6 +230,9 @@ struct Workspace {
         if (N <= kMaxSortN) {
             grid.occHdr = mem.take<float>(b * 2 * 8 * 4);
             grid.occBits = mem.take<uint32_t>(b * 2 * (size_t)kOccRings * kOccWords * 4);
+            // (the ring-level counts of the scans 2 .. 11, [B,12] int32, written and read within one scoring by pair: the words of
+            // the list of the scoring in two launches, which is the other form of the same launch -- a call takes one of the two)
+            grid.occTot = grid.scoreList;
         }
         // (sweeps of a small cloud against a long one, shared by several blocks: nn.hip; only where the partial minima stay small)
         if (shareScratch(B, N)) {

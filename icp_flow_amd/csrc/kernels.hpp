@@ -225,8 +225,12 @@ struct GridScratch {   // scratch of the exact gated NN searches of the ICP loop
     float *occHdr;
     uint32_t *occBits;
     int occReady;
+    // [B,12] per scan the sum of its queries' ring levels in the other cloud's grids (the integer the pre-bound is formed from): written
+    // beside candidate 0's scans, read by the launch of the other ten (nn.hip: sweep_tot_job, sweep_pair_kernel), or NULL
+    // (api.hip: the same words as scoreList -- the scoring by pair and the scoring in two launches never run in one call)
+    int32_t *occTot;
     int *sweepTicket;   // pruned scoring in two launches (nn.hip): the number of listed scans, cleared with the scoring scratch (api.hip), or NULL: one plain grid
-    int *scoreList;     //   [B * 10] the scans that go on behind the deciding launch
+    int *scoreList;     //   [B * 12] ints; the scans that go on behind the deciding launch, B * 10 at most
     int presorted;     // sortX / pts / sortYsoa / axis already hold both clouds sorted WITHOUT the pre-pose
                        // (scoring sweep ran on this batch): the ICP applies the pre-pose when it loads
 };

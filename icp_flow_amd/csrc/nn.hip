@@ -365,6 +365,11 @@ struct SweepParams {
     int listMode;
     int *list, *listCount;
     int boundBoth;          // SWEEP_SCORE, prune == 1: candidate 0's BACKWARD scan is complete as well (the first launch ran both): the bound is its score, min(forward, backward)
+    // The pre-bound's integer ahead of its comparison (launch_sweep_score_pruned): occTot [B,12]; totBase > 0: the blocks from that
+    // one on count the ring levels of the scans 2 .. 11, one block per scan (sweep_tot_job), beside the scans of this launch;
+    // pairSlots > 0: the launch of the other ten scans by (pair, query block, survivor slot) -- sweep_pair_kernel
+    int32_t *occTot;
+    int totBase, pairSlots;
 };
 
 #ifdef ICPFLOW_OCC_STATS
@@ -394,15 +399,124 @@ constexpr int kSweepStage = 4096;   // sort keys staged in LDS up to this many t
 enum SweepMode : int { SWEEP_SCORE = 0, SWEEP_CHECK = 1, SWEEP_EVAL = 2 };
 
 #ifdef ICPFLOW_SWEEP_CLOCK
+// per workgroup of the scoring launches (tools/dbg/sweep_clocks.py): wall start, wall end; [0 .. 65536) the launch of the other ten
+// scans in either layout, [65536 .. 131072) the launch of candidate 0's scans.  The last call overwrites.
+__device__ long long g_sweep_blk[131072 * 2];
+__device__ __forceinline__ void sweep_blk_clock(const SweepParams &p, const long long w0)
+{
+    const int at = (p.prune == 1 ? 0 : 65536) + (int)blockIdx.x;
+    if (threadIdx.x == 0 && blockIdx.x < 65536u) { g_sweep_blk[2 * at] = w0; g_sweep_blk[2 * at + 1] = wall_clock64(); }
+}
 __device__ long long g_sweep_clk[4096 * 8];   // per (mode 1 job, block 0): wall start, wall end, shader clocks: entry->loop, loop, rounds, nt, nq, chunks scanned
 #endif
+// This thread's share of a scan's ring levels (the occupancy pre-bound, see sweep_job): over the queries threadIdx.x, + kSweepBlock, ..
+// of the scan `sub` of pair b, the sum of their levels (0 .. kOccRings): level L = no target within L cells of the query.
+__device__ __forceinline__ int sweep_ring_levels(const SweepParams &p, const int b, const int sub, const bool backward, const float *qs,
+                                                 const int nq)
+{
+    const float *t3 = p.cand + ((size_t)b * 6 + (sub >> 1)) * 3;
+    const float ptx = t3[0], pty = t3[1], ptz = t3[2];
+    const int role = backward ? 0 : 1;   // the targets' cloud: src role for a backward scan, dst role for a forward one
+    const float *hdr = p.occHdr + ((size_t)b * 2 + role) * 8;
+    const uint32_t *bits = p.occBits + ((size_t)b * 2 + role) * kOccRings * kOccWords;
+    const float gox = hdr[0], goy = hdr[1], goz = hdr[2], ginv = hdr[3];
+    const int gnx = __float_as_int(hdr[5]), gny = __float_as_int(hdr[6]), gnz = __float_as_int(hdr[7]);
+    int cnt = 0;
+    if (gnx > 0) {
+        for (int i = threadIdx.x; i < nq; i += kSweepBlock) {
+            float x = qs[i], y = qs[p.NP16 + i], z = qs[2 * p.NP16 + i];
+            if (!backward) { x += ptx; y += pty; z += ptz; }   // the moved source cloud against dst
+            else { x -= ptx; y -= pty; z -= ptz; }             // dst against the moved source cloud: |c - (a + t)| = |(c - t) - a| to rounding
+            const float ux = floorf((x - gox) * ginv), uy = floorf((y - goy) * ginv), uz = floorf((z - goz) * ginv);
+            // (NaN coordinates fail the range test below and count as "occupied": no bound from them)
+            const bool inside = ux >= 0.f && ux < (float)gnx && uy >= 0.f && uy < (float)gny && uz >= 0.f && uz < (float)gnz;
+            const bool finite = fabsf(x) < 1e30f && fabsf(y) < 1e30f && fabsf(z) < 1e30f;
+            int level = (finite && !inside) ? kOccRings : 0;   // beyond the grid: kOccRings + 1 cells or more from every target's cell
+            if (inside) {
+                const int c = ((int)ux * gny + (int)uy) * gnz + (int)uz;
+#pragma unroll
+                for (int ring = 0; ring < kOccRings; ++ring)   // (the planes are nested: empty in plane k implies empty in the planes below)
+                    level += ((bits[ring * kOccWords + (c >> 5)] >> (c & 31)) & 1u) == 0u ? 1 : 0;
+            }
+            cnt += level;
+        }
+    }
+    return cnt;
+}
+
+// The pre-bound of one scan from its ring-level total, and whether it ends the scan against candidate 0's score (one copy of the
+// arithmetic for the block that counts for itself and for sweep_pair_kernel, which reads the total of an earlier launch)
+__device__ __forceinline__ bool sweep_prebound_ends(const int tot, const float hlb, const int n, const float bound, float *lowOut = nullptr)
+{
+    const float low = ((float)tot * hlb * 0.999f) / (float)n;
+    if (lowOut != nullptr) *lowOut = low;
+    return low > bound * 1.0001f;   // NaN / inf bounds never prune
+}
+
+// Candidate 0's score as score_pick_kernel forms it -- the bound the other scans are pruned against: its forward total (and, with
+// `both`, its backward total) over the query blocks in block order, fminf(forward mean, backward mean).  Run by ONE WHOLE WAVE (one
+// query block per lane, all loads in flight at once, up to kWave blocks; a loop beyond); every lane returns the bound.  The one copy
+// of this arithmetic: sweep_job's prologue and sweep_pair_kernel both call it.
+__device__ __forceinline__ float sweep_cand0_bound(const SweepParams &p, const int b, const int na, const int nc, const bool both,
+                                                   const int lane)
+{
+    const double *fw = p.partial + (size_t)(b * 12 + 0) * p.qblocks * kPartial, *bw = p.partial + (size_t)(b * 12 + 1) * p.qblocks * kPartial;
+    double f0 = 0.0, b0 = 0.0;
+    if (p.qblocks <= kWave) {
+        const int q = min(lane, p.qblocks - 1);
+        const double v0 = fw[(size_t)q * kPartial], v1 = both ? bw[(size_t)q * kPartial] : 0.0;
+        for (int qq = 0; qq < p.qblocks; ++qq) { f0 += __shfl(v0, qq, kWave); b0 += __shfl(v1, qq, kWave); }
+    } else {
+        for (int q = 0; q < p.qblocks; ++q) { f0 += fw[(size_t)q * kPartial]; if (both) b0 += bw[(size_t)q * kPartial]; }
+    }
+    float bound = (float)f0 / (float)na;
+    if (both) bound = fminf(bound, (float)b0 / (float)nc);
+    return bound;
+}
+
+// What sweep_pair_kernel hands to sweep_job: the scan (in the launch's own numbering), the query block, and the pair's bound, which
+// the caller has formed -- and against which it has settled the occupancy pre-bound: this scan goes on.  job < 0: sweep_job finds
+// its job from the block's number and does all of that itself.
+struct SweepDirect {
+    int job, qb;
+    float bound;
+};
+
+// One block of the launch of candidate 0's scans that counts, for one of the other ten scans of a pair, the ring levels of ALL its
+// queries: the integer depends on the candidate's translation and the occupancy grids alone, both complete before that launch, and
+// nothing in that launch waits for it -- the launch of the other scans (sweep_pair_kernel) only compares.  lin = pair in dispatch
+// order * 10 + (scan - 2).
+__device__ __forceinline__ void sweep_tot_job(const SweepParams &p, const int lin)
+{
+    __shared__ int totCount[kSweepBlock / kWave];
+    const int k = lin / 10, sub = 2 + lin % 10;
+    const int b = p.pairOrder != nullptr ? p.pairOrder[k] : k;
+    const bool backward = (sub & 1) != 0;
+    const bool sw = p.swap != nullptr && p.swap[b] != 0;
+    const int na = (sw ? p.lenC : p.lenA)[b], nc = (sw ? p.lenA : p.lenC)[b];
+    const float *qs = (backward ? p.Csoa : p.Asoa) + (size_t)b * 3 * p.NP16;
+    int cnt = sweep_ring_levels(p, b, sub, backward, qs, backward ? nc : na);
+    cnt = wave_sum(cnt);
+    if ((threadIdx.x & (kWave - 1)) == 0) totCount[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < kSweepBlock / kWave; ++w) tot += totCount[w];
+        p.occTot[b * 12 + sub] = tot;
+#ifdef ICPFLOW_OCC_STATS
+        atomicAdd(&g_occStats[2], (unsigned long long)tot); atomicAdd(&g_occStats[3], (unsigned long long)(backward ? nc : na));
+#endif
+    }
+}
+
 // SHARE: the instantiation whose blocks may share a window (one-wave blocks: over their four waves; one-block clouds against a long
 // one: over several blocks) -- batches of a few hundred pairs; batches that fill the GPU many times over keep the plain loop
 // One block's job (the kernel's body since round 5's end: sweep_scan_kernel runs it for lin = blockIdx.x, sweep_list_kernel for the
 // jobs of the listed scans).  Every `return` below is taken by the whole block alike.
 template <int MODE, bool SHARE>
-__device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin)
+__device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin, const SweepDirect d = SweepDirect{-1, 0, 0.f})
 {
+    const bool direct = d.job >= 0;   // (sweep_pair_kernel)
 #ifdef ICPFLOW_SWEEP_CLOCK
     const long long dbgW0 = wall_clock64(), dbgC0 = clock64();
     long long dbgC1 = 0, dbgC2 = 0;
@@ -421,6 +535,7 @@ __device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin)
             qb = lin / cnt;
             job = p.list[lin % cnt];
         }
+        if (direct) { qb = d.qb; job = d.job; }
     }
     if (MODE == SWEEP_CHECK && p.initSum != nullptr) {
         // Two halves, each dealt like the whole (eight pairs to the eight XCDs): the scans under the final pose first, then
@@ -466,7 +581,7 @@ __device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin)
         double *rec = p.partial + ((size_t)job * p.qblocks + 1) * kPartial;
         for (int k = threadIdx.x; k < (p.qblocks - 1) * kPartial; k += kSweepBlock) rec[k] = 0.0;
     }
-    if (MODE == SWEEP_SCORE && p.prune == 1 && p.occBits != nullptr && qb > 0) {
+    if (MODE == SWEEP_SCORE && p.prune == 1 && p.occBits != nullptr && qb > 0 && !direct) {
         // a scan that its block 0 has ended by the occupancy pre-bound (below): +inf in its running sum -- one load and out
         const double seen = __hip_atomic_load(p.accum + job, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (seen == __builtin_huge_val()) {
@@ -536,41 +651,26 @@ __device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin)
         // thread these were 8, in the third launch 88, dependent scalar loads of a few hundred nanoseconds each: the
         // whole third launch, and the first microseconds of every block of the second.)
         __shared__ double scanSum[12];
-        if (wave == 0 && p.qblocks <= kWave) {
-            const int q = min(lane, p.qblocks - 1);
-            double v[11];
+        if (wave == 0 && !direct) {
+            const float bd = sweep_cand0_bound(p, b, na, nc, p.boundBoth != 0, lane);
+            if (lane == 0) boundSh = bd;
+            if (p.prune == 2 && p.qblocks <= kWave) {   // the totals of the other ten scans
+                const int q = min(lane, p.qblocks - 1);
+                double v[10];
 #pragma unroll
-            for (int u = 0; u < 11; ++u) {
-                const int sc = u == 0 ? 0 : u + 1;                                     // scans 0, 2 .. 11
-                v[u] = (u == 0 || p.prune == 2) ? p.partial[((size_t)(b * 12 + sc) * p.qblocks + q) * kPartial] : 0.0;
-            }
-            if (p.boundBoth) {   // candidate 0's backward scan, complete since the first launch
-                const double v1 = p.partial[((size_t)(b * 12 + 1) * p.qblocks + q) * kPartial];
-                double t = 0.0;
-                for (int qq = 0; qq < p.qblocks; ++qq) t += __shfl(v1, qq, kWave);
-                if (lane == 0) scanSum[1] = t;
-            }
+                for (int u = 0; u < 10; ++u) v[u] = p.partial[((size_t)(b * 12 + 2 + u) * p.qblocks + q) * kPartial];
 #pragma unroll
-            for (int u = 0; u < 11; ++u) {
-                if (u > 0 && p.prune != 2) break;
-                double t = 0.0;
-                for (int qq = 0; qq < p.qblocks; ++qq) t += __shfl(v[u], qq, kWave);   // block order, as before
-                if (lane == 0) scanSum[u == 0 ? 0 : u + 1] = t;
+                for (int u = 0; u < 10; ++u) {
+                    double t = 0.0;
+                    for (int qq = 0; qq < p.qblocks; ++qq) t += __shfl(v[u], qq, kWave);   // block order, as before
+                    if (lane == 0) scanSum[2 + u] = t;
+                }
             }
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            double f0 = 0.0;
-            if (p.qblocks <= kWave) f0 = scanSum[0];
-            else for (int q = 0; q < p.qblocks; ++q) f0 += p.partial[((size_t)(b * 12 + 0) * p.qblocks + q) * kPartial];
-            float bound = (float)f0 / (float)na;
-            if (p.boundBoth) {   // candidate 0's score as score_pick_kernel forms it: fminf(forward mean, backward mean)
-                double b0 = 0.0;
-                if (p.qblocks <= kWave) b0 = scanSum[1];
-                else for (int q = 0; q < p.qblocks; ++q) b0 += p.partial[((size_t)(b * 12 + 1) * p.qblocks + q) * kPartial];
-                bound = fminf(bound, (float)b0 / (float)nc);
-            }
-            boundSh = bound;
+            if (direct) boundSh = d.bound;
+            const float bound = boundSh;
             if (p.prune == 2) {
                 bool othersOut = true;
                 for (int k = 1; k < 6; ++k) {
@@ -607,44 +707,20 @@ __device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin)
         // ONE block per scan does it -- query block 0, dispatched before the others (query-block-major grid) -- and, where the bound ends
         // the scan, leaves +inf in the scan's running sum: the prologue above then ends every later block of the scan at once.  (A block
         // that starts before block 0 has got that far simply scans as it always did.)
-        if (p.prune == 1 && p.occBits != nullptr && sub != 1 && qb == 0 && p.listMode != 2) {
+        if (p.prune == 1 && p.occBits != nullptr && sub != 1 && qb == 0 && p.listMode != 2 && !direct) {
             __shared__ int occCount[kSweepBlock / kWave];
             __shared__ int occLeave;
-            const float *t3 = p.cand + ((size_t)b * 6 + (sub >> 1)) * 3;
-            const float ptx = t3[0], pty = t3[1], ptz = t3[2];
-            const int role = backward ? 0 : 1;   // the targets' cloud: src role for a backward scan, dst role for a forward one
-            const float *hdr = p.occHdr + ((size_t)b * 2 + role) * 8;
-            const uint32_t *bits = p.occBits + ((size_t)b * 2 + role) * kOccRings * kOccWords;
-            const float gox = hdr[0], goy = hdr[1], goz = hdr[2], ginv = hdr[3], hlb = hdr[4];
-            const int gnx = __float_as_int(hdr[5]), gny = __float_as_int(hdr[6]), gnz = __float_as_int(hdr[7]);
-            int cnt = 0;   // sum over the queries of their ring level (0 .. kOccRings): level L = no target within L cells
-            if (gnx > 0) {
-                for (int i = threadIdx.x; i < nq; i += kSweepBlock) {
-                    float x = qs[i], y = qs[p.NP16 + i], z = qs[2 * p.NP16 + i];
-                    if (!backward) { x += ptx; y += pty; z += ptz; }   // the moved source cloud against dst
-                    else { x -= ptx; y -= pty; z -= ptz; }             // dst against the moved source cloud: |c - (a + t)| = |(c - t) - a| to rounding
-                    const float ux = floorf((x - gox) * ginv), uy = floorf((y - goy) * ginv), uz = floorf((z - goz) * ginv);
-                    // (NaN coordinates fail the range test below and count as "occupied": no bound from them)
-                    const bool inside = ux >= 0.f && ux < (float)gnx && uy >= 0.f && uy < (float)gny && uz >= 0.f && uz < (float)gnz;
-                    const bool finite = fabsf(x) < 1e30f && fabsf(y) < 1e30f && fabsf(z) < 1e30f;
-                    int level = (finite && !inside) ? kOccRings : 0;   // beyond the grid: kOccRings + 1 cells or more from every target's cell
-                    if (inside) {
-                        const int c = ((int)ux * gny + (int)uy) * gnz + (int)uz;
-#pragma unroll
-                        for (int ring = 0; ring < kOccRings; ++ring)   // (the planes are nested: empty in plane k implies empty in the planes below)
-                            level += ((bits[ring * kOccWords + (c >> 5)] >> (c & 31)) & 1u) == 0u ? 1 : 0;
-                    }
-                    cnt += level;
-                }
-            }
+            const float hlb = p.occHdr[((size_t)b * 2 + (backward ? 0 : 1)) * 8 + 4];
+            int cnt = sweep_ring_levels(p, b, sub, backward, qs, nq);   // sum over the queries of their ring level
             cnt = wave_sum(cnt);
             if (lane == 0) occCount[wave] = cnt;
             __syncthreads();
             if (threadIdx.x == 0) {
                 int tot = 0;
                 for (int w = 0; w < kSweepBlock / kWave; ++w) tot += occCount[w];
-                const float low = ((float)tot * hlb * 0.999f) / (float)(backward ? nc : na);
-                occLeave = low > boundSh * 1.0001f ? 1 : 0;   // NaN / inf bounds never prune
+                float low;
+                occLeave = sweep_prebound_ends(tot, hlb, backward ? nc : na, boundSh, &low) ? 1 : 0;
+                (void)low;
 #ifdef ICPFLOW_OCC_STATS
                 atomicAdd(&g_occStats[0], 1ull); if (occLeave) atomicAdd(&g_occStats[1], 1ull);
                 if (!occLeave && b < 1024) atomicAdd(&g_occPair[b], 1u);   // scans of the pair that go on (tools/dbg/order_predictor.py)
@@ -937,7 +1013,120 @@ __device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin)
 template <int MODE, bool SHARE = false>
 __global__ __launch_bounds__(kSweepBlock) void sweep_scan_kernel(SweepParams p)
 {
+#ifdef ICPFLOW_SWEEP_CLOCK
+    const long long dbgBlk0 = wall_clock64();
+#endif
+    if (MODE == SWEEP_SCORE && p.totBase > 0 && (int)blockIdx.x >= p.totBase) {   // (behind the scanning blocks in dispatch order)
+        sweep_tot_job(p, (int)blockIdx.x - p.totBase);
+#ifdef ICPFLOW_SWEEP_CLOCK
+        sweep_blk_clock(p, dbgBlk0);
+#endif
+        return;
+    }
     sweep_job<MODE, SHARE>(p, (int)blockIdx.x);
+#ifdef ICPFLOW_SWEEP_CLOCK
+    if (MODE == SWEEP_SCORE) sweep_blk_clock(p, dbgBlk0);
+#endif
+}
+
+// The launch of the other ten scans behind the occupancy pre-bound, by (pair, query block, survivor slot): the ring-level totals are
+// there (sweep_tot_job, beside candidate 0's scans), so EVERY block of a pair forms the pair's bound and settles the ten comparisons
+// for itself -- ten lanes, one load each -- instead of one block per scan counting in front of 7680 blocks that load one word and
+// leave.  Slot 0 writes this query block's records of the scans that end (+inf, zeros behind it); slot s scans query block qb of the
+// pair's s-th surviving scan.  A uniform batch has at most three survivors in a pair, a ragged one has pairs whose ten scans all go
+// on (small clusters: every query within three cells of a target) -- so the first kSweepPairSlots slots are one block per (pair,
+// query block) and the slots from there to the tenth ONE block per pair, which takes the query blocks of its scan in turn (clouds of
+// up to four query blocks; on wider ones all ten slots are of the first kind: launch_sweep_score_pruned): no block
+// ever scans two scans, and the blocks that find nothing to do are 4 x pairs x query blocks + 6 x pairs instead of ten times the
+// former.  The grid is slot major -- slot 0 of every pair first -- so that the blocks that scan are placed first and the others are
+// dispatched while those scan.  All blocks of a pair decide from the same words of earlier launches: they agree, nobody waits
+// for anybody.
+#ifndef ICPFLOW_SCORE_PAIR_SLOTS
+#define ICPFLOW_SCORE_PAIR_SLOTS 4
+#endif
+constexpr int kSweepPairSlots = ICPFLOW_SCORE_PAIR_SLOTS;   // (0: the launch as one grid of (query block, scan), query block 0 deciding)
+static_assert(kSweepPairSlots >= 0 && kSweepPairSlots <= 10, "a pair has ten scans beside candidate 0's");
+template <bool SHARE>
+__global__ __launch_bounds__(kSweepBlock) void sweep_pair_kernel(SweepParams p)
+{
+    __shared__ float pairBound;
+    __shared__ unsigned pairGoesOn;
+#ifdef ICPFLOW_SWEEP_CLOCK
+    const long long dbgBlk0 = wall_clock64();
+#endif
+    const int lin = (int)blockIdx.x;
+    const int pairs = p.njobs / p.subCount, pairBlocks = pairs * p.qblocks;
+    const bool whole = lin >= p.pairSlots * pairBlocks;   // one of the slots that take a whole scan
+    const int slot = whole ? p.pairSlots + (lin - p.pairSlots * pairBlocks) / pairs : lin / pairBlocks;
+    const int k = whole ? (lin - p.pairSlots * pairBlocks) % pairs : (lin % pairBlocks) / p.qblocks;
+    const int qb = whole ? 0 : (lin % pairBlocks) % p.qblocks;
+    const int b = p.pairOrder != nullptr ? p.pairOrder[k] : k;
+    const bool sw = p.swap != nullptr && p.swap[b] != 0;
+    const int na = (sw ? p.lenC : p.lenA)[b], nc = (sw ? p.lenA : p.lenC)[b];
+    const bool sharing = SHARE && p.shareCount != nullptr;   // (small-against-long scans take blocks beyond their rows: sweep_job)
+    // a query block beyond the rows of both clouds (and of the shares): its records are zeros whatever becomes of the scans -- an
+    // ended scan reports its +inf through block 0.  These are sweep_job's own two rules ("block beyond the cloud", and the pair
+    // table's short cut with sweep_pair_table_kernel's encoding: pair << 16 | blocks with shares << 8 | blocks with rows), taken
+    // over BOTH directions, since a block of this kernel may meet a forward or a backward scan: sweep_job applies the rule of the
+    // scan's own direction to whatever gets past this one.  A change of either rule there belongs here as well.
+    bool beyond = qb > 0 && !sharing && qb * kSweepBlock >= max(na, nc);
+    if (qb > 0 && SHARE && p.pairTab != nullptr) {
+        const int e0 = p.pairTab[k * 4 + 0], e1 = p.pairTab[k * 4 + 1];
+        const int sh = sharing ? 8 : 0;
+        beyond = qb >= max((e0 >> sh) & 255, (e1 >> sh) & 255);
+    }
+    if (beyond) {
+        if (slot == 0 && threadIdx.x < 10 * kPartial)
+            p.partial[((size_t)(b * 12 + 2 + threadIdx.x / kPartial) * p.qblocks + qb) * kPartial + threadIdx.x % kPartial] = 0.0;
+#ifdef ICPFLOW_SWEEP_CLOCK
+        sweep_blk_clock(p, dbgBlk0);
+#endif
+        return;
+    }
+    if (threadIdx.x < kWave) {
+        const int lane = threadIdx.x;
+        const float bound = sweep_cand0_bound(p, b, na, nc, true, lane);
+        bool goesOn = false;
+        if (lane < 10) {
+            const int sub = 2 + lane;
+            const bool backward = (sub & 1) != 0;
+            const int nq = backward ? nc : na, nt = backward ? na : nc;
+            const int nqb = (nq + kSweepBlock - 1) / kSweepBlock;
+            // the scans that never met the pre-bound stay out of it: no rows, or shared between blocks (sweep_job: fullScan)
+            const bool fullScan = sharing && nq > 0 && nqb <= kSweepFullQb && nt >= kSweepFullScanMinNt && p.qblocks >= 2 * nqb;
+            const float hlb = p.occHdr[((size_t)b * 2 + (backward ? 0 : 1)) * 8 + 4];
+            const int tot = p.occTot[b * 12 + sub];
+            goesOn = nq <= 0 || fullScan || !sweep_prebound_ends(tot, hlb, nq, bound);
+        }
+        const unsigned mask = (unsigned)(__ballot(goesOn) & 0x3ffull);
+        if (lane == 0) { pairBound = bound; pairGoesOn = mask; }
+#ifdef ICPFLOW_OCC_STATS
+        if (lane == 0 && qb == 0 && slot == 0) {
+            atomicAdd(&g_occStats[0], 10ull); atomicAdd(&g_occStats[1], (unsigned long long)(10 - __popc(mask)));
+            if (b < 1024) atomicAdd(&g_occPair[b], (unsigned)__popc(mask));
+        }
+#endif
+    }
+    __syncthreads();
+    const unsigned goesOn = pairGoesOn;
+    const float bound = pairBound;
+    if (slot == 0 && threadIdx.x < 10 * kPartial && ((goesOn >> (threadIdx.x / kPartial)) & 1u) == 0u)
+        p.partial[((size_t)(b * 12 + 2 + threadIdx.x / kPartial) * p.qblocks + qb) * kPartial + threadIdx.x % kPartial] =
+            threadIdx.x % kPartial == 0 ? __builtin_huge_val() : 0.0;
+    // this slot's scan: the slot-th surviving one
+    unsigned rest = goesOn;
+    for (int nth = 0; nth < slot && rest != 0u; ++nth) rest &= rest - 1u;
+    if (rest != 0u) {
+        const int job = k * 10 + (__ffs(rest) - 1);
+        if (!whole) sweep_job<SWEEP_SCORE, SHARE>(p, 0, SweepDirect{job, qb, bound});
+        else for (int q = 0; q < p.qblocks; ++q) {
+            sweep_job<SWEEP_SCORE, SHARE>(p, 0, SweepDirect{job, q, bound});
+            __syncthreads();   // (the job's LDS -- records, flags, staged keys -- is this block's again)
+        }
+    }
+#ifdef ICPFLOW_SWEEP_CLOCK
+    sweep_blk_clock(p, dbgBlk0);
+#endif
 }
 
 // The pruned scoring launch behind the occupancy pre-bound: 98 % of its (scan, query block) jobs ended at their first load, and a
@@ -978,6 +1167,11 @@ extern "C" int icpflow_debug_sweep_clk(long long *out32768)
 {
     return (int)hipMemcpyFromSymbol(out32768, HIP_SYMBOL(g_sweep_clk), sizeof(long long) * 32768);
 }
+extern "C" int icpflow_debug_sweep_blk(long long *out262144)
+{
+    return (int)hipMemcpyFromSymbol(out262144, HIP_SYMBOL(g_sweep_blk), sizeof(long long) * 262144);
+}
+extern "C" int icpflow_debug_sweep_layout(void) { return kSweepPairSlots; }   // (0: one grid of (query block, scan))
 #endif
 int sweep_qblocks(int maxRows) { return (maxRows + kSweepBlock - 1) / kSweepBlock; }
 
@@ -1052,10 +1246,23 @@ static hipError_t launch_sweep(SweepParams p, hipStream_t s)
             hipLaunchKernelGGL((sweep_list_kernel<MODE, false>), dim3((unsigned)wgs), dim3(kSweepBlock), lds, s, p);
         return hipGetLastError();
     }
+    if (MODE == SWEEP_SCORE && p.pairSlots > 0) {   // the other ten scans by (pair, query block, survivor slot)
+        const unsigned blocks = (unsigned)((p.njobs / p.subCount) * (p.qblocks * p.pairSlots + 10 - p.pairSlots));
+        if (p.shareWindows != 0 && p.N >= kSweepFullScanMinTargets && p.njobs <= 12 * 700)
+            hipLaunchKernelGGL((sweep_pair_kernel<true>), dim3(blocks), dim3(kSweepBlock), lds, s, p);
+        else
+            hipLaunchKernelGGL((sweep_pair_kernel<false>), dim3(blocks), dim3(kSweepBlock), lds, s, p);
+        return hipGetLastError();
+    }
+    unsigned blocks = (unsigned)total;
+    if (MODE == SWEEP_SCORE && p.totBase != 0) {   // ... and one block per scan 2 .. 11 of every pair behind them (sweep_tot_job)
+        p.totBase = total;
+        blocks += (unsigned)((p.njobs / p.subCount) * 10);
+    }
     if (p.shareWindows != 0 && p.N >= kSweepFullScanMinTargets && p.njobs <= 12 * 700)
-        hipLaunchKernelGGL((sweep_scan_kernel<MODE, true>), dim3((unsigned)total), dim3(kSweepBlock), lds, s, p);
+        hipLaunchKernelGGL((sweep_scan_kernel<MODE, true>), dim3(blocks), dim3(kSweepBlock), lds, s, p);
     else
-        hipLaunchKernelGGL((sweep_scan_kernel<MODE, false>), dim3((unsigned)total), dim3(kSweepBlock), lds, s, p);
+        hipLaunchKernelGGL((sweep_scan_kernel<MODE, false>), dim3(blocks), dim3(kSweepBlock), lds, s, p);
     return hipGetLastError();
 }
 
@@ -1206,18 +1413,42 @@ hipError_t launch_sweep_score_pruned(const GridScratch *grid, const int32_t *len
         // target: what is left of the second launch is candidate 0's backward scan, which nothing ends before its last block.  It
         // runs to the end beside the forward scan instead (the first launch filled half of the GPU at config 2), and the others are
         // pruned against candidate 0's SCORE, min(forward, backward), instead of its forward mean alone.
-        p.njobs = B * 2; p.subBegin = 0; p.subCount = 2; p.prune = 0;
-        hipError_t e2 = launch_sweep<SWEEP_SCORE>(p, s);
-        if (e2 != hipSuccess) return e2;
-        p.njobs = B * 10; p.subBegin = 2; p.subCount = 10; p.prune = 1; p.boundBoth = 1;
-        // In two launches (sweep_list_kernel) where the dead jobs' dispatch is what the launch lasts: batches several times the GPU
-        // (config 4's shard: 81 920 jobs, 168 -> 66 + 43 us).  Smaller batches keep the one launch -- there the scans that go on
-        // start at once instead of behind the last deciding block (ragged 600 x 1024: 0.818 against 0.825 ms per step).
+        // Batches below the two-launch form: the first launch also counts the ring levels of the other ten scans (they need the
+        // peaks and the grids only), and the second is laid out by pair: every block compares for itself and only survivors scan.
 #ifndef ICPFLOW_SCORE_LIST_MIN_JOBS
 #define ICPFLOW_SCORE_LIST_MIN_JOBS 65536
 #endif
-        if (grid->sweepTicket != nullptr && grid->scoreList != nullptr &&   // (the call has cleared the counter)
-            (long long)B * 10 * sweep_qblocks(N) >= ICPFLOW_SCORE_LIST_MIN_JOBS) {
+        const bool listed = grid->sweepTicket != nullptr && grid->scoreList != nullptr &&   // (the call has cleared the counter)
+                            (long long)B * 10 * sweep_qblocks(N) >= ICPFLOW_SCORE_LIST_MIN_JOBS;
+        // By pair up to 1024 (pair, query block)s (config 2: second launch 34.7 -> 22.9 us, step 0.637 -> 0.626 ms; the ragged shapes
+        // inside the limit: profiles/r09_bench_ab.txt).  Measured slower beyond, on the two ragged batches tried: 600 x 1024 (2400:
+        // step 0.839 -> 0.859 ms) and 128 x 10000 (5120: 1.40 -> 1.76 ms) -- there many pairs keep all ten scans (small clusters: every
+        // query within three cells of a target).  Those keep the one grid.
+        // A slot of one block per PAIR walks the query blocks of its scan in turn: a chain that is harmless at four query blocks and
+        // forty scans long at forty.  Wider batches therefore get all ten slots as one block per (pair, query block).
+        // occTot ALIASES scoreList (api.hip): `byPair` requires `!listed`, and nothing else reads or writes scoreList -- this
+        // exclusivity is what carries the aliasing; a new user of scoreList on the path that is not listed needs words of its own.
+#ifndef ICPFLOW_SCORE_PAIR_MAX_BLOCKS
+#define ICPFLOW_SCORE_PAIR_MAX_BLOCKS 1024
+#endif
+#ifndef ICPFLOW_SCORE_PAIR_WHOLE_MAX_QBLOCKS
+#define ICPFLOW_SCORE_PAIR_WHOLE_MAX_QBLOCKS 4
+#endif
+        const bool byPair = kSweepPairSlots > 0 && !listed && grid->occTot != nullptr && (long long)B * sweep_qblocks(N) <= ICPFLOW_SCORE_PAIR_MAX_BLOCKS;
+        p.njobs = B * 2; p.subBegin = 0; p.subCount = 2; p.prune = 0;
+        if (byPair) { p.occTot = grid->occTot; p.totBase = 1; }   // (launch_sweep puts the counting blocks behind the scanning ones)
+        hipError_t e2 = launch_sweep<SWEEP_SCORE>(p, s);
+        if (e2 != hipSuccess) return e2;
+        p.totBase = 0;
+        p.njobs = B * 10; p.subBegin = 2; p.subCount = 10; p.prune = 1; p.boundBoth = 1;
+        if (byPair) {
+            p.pairSlots = sweep_qblocks(N) <= ICPFLOW_SCORE_PAIR_WHOLE_MAX_QBLOCKS ? kSweepPairSlots : 10;
+            return launch_sweep<SWEEP_SCORE>(p, s);
+        }
+        // In two launches (sweep_list_kernel) where the dead jobs' dispatch is what the launch lasts: batches several times the GPU
+        // (config 4's shard: 81 920 jobs, 168 -> 66 + 43 us).  Smaller batches keep the one launch -- there the scans that go on
+        // start at once instead of behind the last deciding block (ragged 600 x 1024: 0.818 against 0.825 ms per step).
+        if (listed) {
             p.list = grid->scoreList; p.listCount = grid->sweepTicket;
             p.listMode = 1;
             const hipError_t e3 = launch_sweep<SWEEP_SCORE>(p, s);
