@@ -93,6 +93,7 @@ SIGNATURES = {
     "icpflow_seq_gt_flow": (_i, [_p, _p, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "icpflow_seq_metrics_workspace_bytes": (_sz, [_i, _i]),
     "icpflow_seq_metrics": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _p, _p, _p, _sz, _p]),
+    "icpflow_seq_argo_sample": (_i, [_p, _i, _p, _i, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _d, _p, _p, _p, _p, _p, _p, _p]),
     "icpflow_seq_segment_table_workspace_bytes": (_sz, [_i, _i]),
     "icpflow_seq_segment_table": (_i, [_p, _p, _i, _p, _p, _d, _p, _i, _p, _p, _sz, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
@@ -126,6 +127,8 @@ SEQ_MAX_FRAMES = 16
 SEG_COLS, SEG_CHUNK_ROWS = 16, 1024       # icpflow_seq_segment_table: columns of a row; rows of a chunk (csrc/segeval.hip)
 SEQ_OUT_FLOW, SEQ_OUT_POINTS = 0, 1
 SEQ_CROP_NONE, SEQ_CROP_XY, SEQ_CROP_XYZ = 0, 1, 2
+DTYPE_FLOAT32, DTYPE_FLOAT64 = 0, 1       # icpflow_seq_argo_sample: the type a file stores its points / its flow in
+ARGO_MAX_BACKGROUND = 64
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical

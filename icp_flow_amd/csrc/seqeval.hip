@@ -1,6 +1,7 @@
 // seqeval.hip -- the evaluation of a whole sequence on the GPU (include/icpflow_hip.h, "8(f) sequence evaluation"):
-// the ground-truth scene flow the reference builds from its poses (utils_loading.py:21-48, dataset_pca.py:66-69) and the
-// sums behind the table its calculate_metrics fills (utils_eval.py:24-63, 162-180, 185-368).
+// the ground-truth scene flow the reference builds from its poses (utils_loading.py:21-48, dataset_pca.py:66-69), the
+// two-frame sample it builds from an Argoverse 2 file (dataset_argo.py:47-50, 66-71, 83-89) and the sums behind the table its
+// calculate_metrics fills (utils_eval.py:24-63, 162-180, 185-368).
 //
 // Determinism of icpflow_seq_metrics.  Counts are integers (ballots and popcounts): exact whatever the order.  The one
 // floating-point sum, the end point error of a (gap, class) cell, is added in an order that is a function of the arguments
@@ -97,6 +98,59 @@ __global__ void seq_count_final_kernel(const unsigned long long *__restrict__ pa
     unsigned long long s = 0;
     for (int g = 0; g < G; ++g) s += partial[g];
     *d_bad = (long long)s;
+}
+
+// ---- an Argoverse 2 sample -----------------------------------------------------------------------------------------
+// dataset_argo.py:47-50, 66-71, 83-89: output row i < m2 is pc2[valid2[i]] (frame 0: no labels, no flow), row m2 + k is
+// pc1[valid1[k]] (frame 1) with its flow row and the two labels.  P, Q: the types the file stores points and flow in.
+struct Background {
+    int n;
+    int32_t id[ICPFLOW_ARGO_MAX_BACKGROUND];
+};
+
+// np.linalg.norm(flow, axis=-1) in the flow's own type: (x x + y y) + z z, every operation rounded by itself, and a
+// correctly rounded square root (-fhip-fp32-correctly-rounded-divide-sqrt for float)
+__device__ __forceinline__ float row_norm(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
+__device__ __forceinline__ double row_norm(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
+
+template <typename P, typename Q>
+__global__ __launch_bounds__(kThreads) void seq_argo_sample_kernel(const P *__restrict__ pc1, int n1, const P *__restrict__ pc2, int n2,
+                                                                   const Q *__restrict__ flow, const double *__restrict__ cls,
+                                                                   const long long *__restrict__ valid1, int m1,
+                                                                   const long long *__restrict__ valid2, int m2, Background bg,
+                                                                   double threshold, double *__restrict__ pts, int32_t *__restrict__ tim,
+                                                                   int32_t *__restrict__ sd, int32_t *__restrict__ fb,
+                                                                   double *__restrict__ out_flow, unsigned long long *__restrict__ d_bad)
+{
+    const size_t m = (size_t)m1 + (size_t)m2;
+    const size_t stride = (size_t)gridDim.x * kThreads;
+    unsigned long long bad = 0;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < m; i += stride) {
+        const bool first = i < (size_t)m2;                         // frame 0
+        const long long idx = first ? valid2[i] : valid1[i - (size_t)m2];
+        if (idx < 0 || idx >= (long long)(first ? n2 : n1)) {      // not gathered, counted; nothing is written for the row
+            ++bad;
+            continue;
+        }
+        const P *p = (first ? pc2 : pc1) + 3 * (size_t)idx;
+        pts[3 * i + 0] = (double)p[0], pts[3 * i + 1] = (double)p[1], pts[3 * i + 2] = (double)p[2];
+        if (first) {
+            tim[i] = 0, sd[i] = 0, fb[i] = 0;
+            out_flow[3 * i + 0] = 0.0, out_flow[3 * i + 1] = 0.0, out_flow[3 * i + 2] = 0.0;
+            continue;
+        }
+        const Q fx = flow[3 * (size_t)idx + 0], fy = flow[3 * (size_t)idx + 1], fz = flow[3 * (size_t)idx + 2];
+        out_flow[3 * i + 0] = (double)fx, out_flow[3 * i + 1] = (double)fy, out_flow[3 * i + 2] = (double)fz;
+        // dataset_argo.py:67: a float norm is compared with the threshold rounded to float; widening both is the same test
+        const bool moving = (double)row_norm(fx, fy, fz) > threshold;
+        const double c = cls[idx];
+        bool object = !(c == -1.0);                                // dataset_argo.py:68-71 (a NaN class equals nothing)
+        for (int k = 0; k < bg.n; ++k) object = object && !(c == (double)bg.id[k]);
+        tim[i] = 1, sd[i] = moving ? 1 : 0, fb[i] = object ? 1 : 0;
+    }
+    // integers: the total is the same whatever order the waves arrive in
+    bad = icpflow::wave_sum(bad);
+    if ((threadIdx.x & (kWave - 1)) == 0 && bad) atomicAdd(d_bad, bad);
 }
 
 // ---- the table ---------------------------------------------------------------------------------------------------
@@ -254,6 +308,47 @@ int icpflow_seq_gt_flow(const double *d_points, const int32_t *d_time_indice, co
     seq_gt_flow_kernel<<<G, kThreads, 0, st>>>(d_points, d_time_indice, d_inst_labels, m, d_ego, F, d_inst_tsfm, K, output, d_out, partial);
     ICPFLOW_TRY(hipGetLastError());
     seq_count_final_kernel<<<1, kWave, 0, st>>>(partial, G, (long long *)d_bad_rows);
+    ICPFLOW_TRY(hipGetLastError());
+    return ICPFLOW_OK;
+}
+
+int icpflow_seq_argo_sample(const void *d_pc1, int n1, const void *d_pc2, int n2, int points_dtype, const void *d_flow_0_1, int flow_dtype,
+                            const double *d_classes1, const int64_t *d_valid1, int m1, const int64_t *d_valid2, int m2,
+                            const int32_t *h_background, int n_background, double sd_threshold, double *d_points, int32_t *d_time_indice,
+                            int32_t *d_sd_labels, int32_t *d_fb_labels, double *d_scene_flow, int64_t *d_bad_rows, icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_seq_argo_sample";
+    if (n1 < 0 || n2 < 0 || m1 < 0 || m2 < 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_argo_sample: n1, n2, m1 and m2 must be >= 0");
+    if (n_background < 0) return report_error(ICPFLOW_E_ARG, "icpflow_seq_argo_sample: n_background < 0");
+    const bool p32 = points_dtype == ICPFLOW_DTYPE_FLOAT32, f32 = flow_dtype == ICPFLOW_DTYPE_FLOAT32;
+    if ((!p32 && points_dtype != ICPFLOW_DTYPE_FLOAT64) || (!f32 && flow_dtype != ICPFLOW_DTYPE_FLOAT64))
+        return report_error(ICPFLOW_E_ARG, "icpflow_seq_argo_sample: points_dtype and flow_dtype must be ICPFLOW_DTYPE_FLOAT32 or _FLOAT64");
+    if (n_background > ICPFLOW_ARGO_MAX_BACKGROUND)
+        return icpflow::report_errorf(ICPFLOW_E_LIMIT, "icpflow_seq_argo_sample: %d background classes, at most %d go with the launch",
+                                      n_background, ICPFLOW_ARGO_MAX_BACKGROUND);
+    if ((long long)m1 + m2 > 0x7fffffffLL) return report_error(ICPFLOW_E_LIMIT, "icpflow_seq_argo_sample: m1 + m2 beyond 2^31 - 1 rows");
+    const int m = m1 + m2;
+    if (!d_bad_rows || (n_background > 0 && !h_background) || (m1 > 0 && (!d_pc1 || !d_flow_0_1 || !d_classes1 || !d_valid1)) ||
+        (m2 > 0 && (!d_pc2 || !d_valid2)) || (m > 0 && (!d_points || !d_time_indice || !d_sd_labels || !d_fb_labels || !d_scene_flow)))
+        return pointer_error(fn);
+    hipStream_t st = (hipStream_t)stream;
+    ICPFLOW_TRY(hipMemsetAsync(d_bad_rows, 0, sizeof(int64_t), st));
+    if (m == 0) return ICPFLOW_OK;
+    Background bg;
+    bg.n = n_background;
+    for (int k = 0; k < ICPFLOW_ARGO_MAX_BACKGROUND; ++k) bg.id[k] = k < n_background ? h_background[k] : 0;
+    const int G = grid_for(m);
+    const long long *v1 = (const long long *)d_valid1, *v2 = (const long long *)d_valid2;
+    unsigned long long *bad = (unsigned long long *)d_bad_rows;
+#define ICPFLOW_ARGO_LAUNCH(P, Q)                                                                                                  \
+    seq_argo_sample_kernel<P, Q><<<G, kThreads, 0, st>>>((const P *)d_pc1, n1, (const P *)d_pc2, n2, (const Q *)d_flow_0_1, d_classes1, \
+                                                         v1, m1, v2, m2, bg, sd_threshold, d_points, d_time_indice, d_sd_labels,       \
+                                                         d_fb_labels, d_scene_flow, bad)
+    if (p32 && f32) ICPFLOW_ARGO_LAUNCH(float, float);
+    else if (p32) ICPFLOW_ARGO_LAUNCH(float, double);
+    else if (f32) ICPFLOW_ARGO_LAUNCH(double, float);
+    else ICPFLOW_ARGO_LAUNCH(double, double);
+#undef ICPFLOW_ARGO_LAUNCH
     ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }

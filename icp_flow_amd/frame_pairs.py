@@ -41,6 +41,13 @@ on the GPU (dataset_pca.py:66-69, utils_loading.py).
                                            [--range-z 0.0 --ground-slack 0.3] [--ground patchwork]
                                            [--if-verbose] [--report worst.json [--report-epe 2.0]]
 
+`--dataset argo` evaluates Argoverse 2 files (pc1, pc2, pc*_flows_valid_idx, gt_flow_0_1, pc1_classes; dataset_argo.py:34-101)
+the same way, one two-frame sample per file: the sample and its static / dynamic and foreground / background labels are built
+on the device (`load_argo_sample`, icpflow_seq_argo_sample).  main.sh:38's ranges:
+
+    python -m icp_flow_amd.frame_pairs DIR --protocol reference --dataset argo --range-x 10000 --range-y 10000
+                                           --range-z -10000 --ground-slack 0 --cluster hdbscan --speed 1.67
+
 `--if-verbose` is the reference's verbose loop (utils_debug.debug_frame, utils_flow.flow_evaluation): per frame pair three
 lines (overall, static, dynamic) and the per-segment evaluation, from one more pass over what is resident
 (icpflow_seq_segment_table) and a read-back of two small tables.
@@ -786,6 +793,37 @@ def load_sequence_sample(path, args):
     return d
 
 
+ARGO_KEYS = ("pc1", "pc2", "pc1_flows_valid_idx", "pc2_flows_valid_idx", "gt_flow_0_1", "pc1_classes")
+
+
+def is_argo(path):
+    """An Argoverse 2 file as ZeroFlow exports it (dataset_argo.py:36-45) with what its evaluation reads."""
+    with np.load(path) as z:
+        return all(k in z.files for k in ARGO_KEYS)
+
+
+def load_argo_sample(path, args, device):
+    """One Argoverse 2 file as the reference's other loader returns it (dataset_argo.py:34-101): the file's arrays are uploaded
+    once and utils_loading.argo_sample (icpflow_seq_argo_sample) builds the two-frame sample on the device -- frame 0 = pc2's
+    valid rows, frame 1 = pc1's with the ground-truth flow, sd = (|flow| > 0.05) and fb from pc1_classes (args.argo_background,
+    default utils_loading.ARGO_BACKGROUND_IDXES).  The frame pair is what `load_frame_pair(path)` returns: gap 1, identity
+    pose, no non-ground flags -- everything is clustered, as dataset_argo.py:140 does.  There is no CPU path.
+    -> (dict of device tensors for calculate_metrics, FramePair)"""
+    from . import utils_loading
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ARGO_KEYS if k not in z.files]
+        if missing:
+            raise KeyError(f"{path}: not an Argoverse 2 sample, missing {missing} (keys: {sorted(z.files)})")
+        arrays = {k: np.asarray(z[k]) for k in ARGO_KEYS}
+    data = utils_loading.argo_sample(arrays["pc1"], arrays["pc2"], arrays["gt_flow_0_1"], arrays["pc1_classes"],
+                                     arrays["pc1_flows_valid_idx"], arrays["pc2_flows_valid_idx"],
+                                     background=getattr(args, "argo_background", None), device=device)
+    data["data_path"] = path
+    fp = load_frame_pair(path)
+    fp.nonground_src = fp.nonground_dst = None
+    return data, fp
+
+
 def _sequence_ground(args, sample, fps):
     """Ground removal stays upstream of the registration: the sample's `nonground` key (load_sequence has put it into the frame
     pairs), else the height threshold of utils_ground.segment_ground_thres on the raw points (utils_ground.py:27-30; under "auto"
@@ -842,7 +880,43 @@ def worst_segments(reports, threshold=2.0):
     return sorted(rows, key=lambda x: -x["epe"])
 
 
-def run_sequences(args, paths, device, in_flight=1):
+def _pca_inputs(args, path, device, F, ground, pose_sources):
+    """run_sequences, a Waymo / nuScenes file: what is resident before the clock starts.  -> (data, frame pairs, rows per frame)"""
+    sample = load_sequence_sample(path, args)
+    fps = load_sequence(path, args)
+    t = sample["time_indice"]
+    counts = [int((t == j).sum()) for j in range(F)]
+    if len(fps) != F - 1 or [len(fp.points_src) for fp in fps] != counts[1:] or (fps and len(fps[0].points_dst) != counts[0]):
+        raise ValueError(f"{path}: the frame pairs do not cover the sample's points (num_frames {F}, points per frame {counts})")
+    how = _sequence_ground(args, sample, fps)
+    ground[how] = ground.get(how, 0) + 1
+    for fp in fps:
+        pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
+    # resident before the clock starts: what the evaluation reads besides the flows, and where each frame's rows are
+    on = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device).to(dt)   # noqa: E731
+    data = dict(raw_points=on(sample["raw_points"][:, 0:3], torch.float64 if sample["raw_points"].dtype == np.float64 else torch.float32),
+                time_indice=on(t, torch.int32), sd_labels=on(sample["sd_labels"], torch.int32),
+                fb_labels=on(sample["fb_labels"], torch.int32), scene_flow=on(sample["scene_flow"], torch.float64))
+    if not (np.isin(sample["sd_labels"], (0, 1)).all() and np.isin(sample["fb_labels"], (0, 1)).all()):
+        data["sd_labels"], data["fb_labels"] = utils_eval._binary_labels(sample["sd_labels"], device), utils_eval._binary_labels(sample["fb_labels"], device)
+    rows = [on(np.flatnonzero(t == j), torch.int64) for j in range(F)]
+    return data, fps, rows
+
+
+def _argo_inputs(args, path, device, ground, pose_sources):
+    """run_sequences, an Argoverse 2 file: the sample (built on the device), its one frame pair, and the rows of its two
+    frames -- two contiguous ranges.  -> (data, frame pairs, rows per frame)"""
+    data, fp = load_argo_sample(path, args, device)
+    m2, m = len(fp.points_dst), len(data["time_indice"])
+    if m != m2 + len(fp.points_src):
+        raise ValueError(f"{path}: the frame pair does not cover the sample's points")
+    ground["none"] = ground.get("none", 0) + 1
+    pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
+    rows = [torch.arange(0, m2, device=device), torch.arange(m2, m, device=device)]
+    return data, [fp], rows
+
+
+def run_sequences(args, paths, device, in_flight=1, dataset="pca"):
     """Evaluate sequence files by the reference's protocol (main.py:173-296) on one GPU.  Per file: the sample
     (`load_sequence_sample`) and its num_frames - 1 frame pairs (`load_sequence`), registered by the existing path
     (`register_frame_pair`, or `register_in_flight` with in_flight > 1); the flows are put into the sequence's flow ON THE
@@ -853,35 +927,28 @@ def run_sequences(args, paths, device, in_flight=1):
     sample's evaluation inputs resident beforehand like the loader's work), ms_eval_per_sequence, ground, pose_sources).
     With args.if_verbose (absent = False): after a sequence's evaluation the reference's per-frame lines and per-segment
     report of each of its frame pairs (utils_debug.debug_frame, utils_flow.flow_evaluation; printed as the reference prints
-    them), returned under `segments` and timed on their own as ms_report_per_sequence; the other two times keep their meaning."""
+    them), returned under `segments` and timed on their own as ms_report_per_sequence; the other two times keep their meaning.
+    dataset="argo" (main.py:156-159, `--dataset argo`): every file is one Argoverse 2 sample of two frames (`load_argo_sample`:
+    the sample and its labels built on the device), its one frame pair registered as above; no ground removal, whatever
+    args.ground says (dataset_argo.py:140)."""
     device = torch.device(device)
     F = int(args.num_frames)
+    if dataset not in ("pca", "argo"):
+        raise ValueError(f"dataset must be 'pca' or 'argo' (got {dataset!r})")
+    if dataset == "argo" and F != 2:
+        raise ValueError(f"an Argoverse 2 sample has two frames (num_frames {F})")
     metrics = utils_eval.new_metric_table(F)
     times, eval_times, n_pairs, ground, pose_sources = [], [], 0, {}, {}
     verbose = bool(getattr(args, "if_verbose", False))
     segments, report_times = [], []
     for path in paths:
-        sample = load_sequence_sample(path, args)
-        fps = load_sequence(path, args)
-        t = sample["time_indice"]
-        counts = [int((t == j).sum()) for j in range(F)]
-        if len(fps) != F - 1 or [len(fp.points_src) for fp in fps] != counts[1:] or (fps and len(fps[0].points_dst) != counts[0]):
-            raise ValueError(f"{path}: the frame pairs do not cover the sample's points (num_frames {F}, points per frame {counts})")
-        how = _sequence_ground(args, sample, fps)
-        ground[how] = ground.get(how, 0) + 1
-        for fp in fps:
-            pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
-        # resident before the clock starts: what the evaluation reads besides the flows, and where each frame's rows are
-        on = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device).to(dt)   # noqa: E731
-        data = dict(raw_points=on(sample["raw_points"][:, 0:3], torch.float64 if sample["raw_points"].dtype == np.float64 else torch.float32),
-                    time_indice=on(t, torch.int32), sd_labels=on(sample["sd_labels"], torch.int32),
-                    fb_labels=on(sample["fb_labels"], torch.int32), scene_flow=on(sample["scene_flow"], torch.float64))
-        if not (np.isin(sample["sd_labels"], (0, 1)).all() and np.isin(sample["fb_labels"], (0, 1)).all()):
-            data["sd_labels"], data["fb_labels"] = utils_eval._binary_labels(sample["sd_labels"], device), utils_eval._binary_labels(sample["fb_labels"], device)
-        rows = [on(np.flatnonzero(t == j), torch.int64) for j in range(F)]
+        if dataset == "argo":
+            data, fps, rows = _argo_inputs(args, path, device, ground, pose_sources)
+        else:
+            data, fps, rows = _pca_inputs(args, path, device, F, ground, pose_sources)
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
-        flow_seq = torch.zeros((len(t), 3), dtype=torch.float32, device=device)
+        flow_seq = torch.zeros((len(data["time_indice"]), 3), dtype=torch.float32, device=device)
         if int(in_flight) > 1:
             done = register_in_flight(args, fps, device, in_flight)
         else:
@@ -1005,7 +1072,11 @@ def main(argv=None):
                     help="with --pose-source estimate: sigma = X metres on every frame instead of the adaptive threshold (0 = adaptive)")
     ap.add_argument("--protocol", choices=("reference",), default=None,
                     help="reference: evaluate sequence files by the reference's table of 6 classes x (num_frames + 1) rows")
-    ap.add_argument("--num-frames", type=int, default=5, help="--protocol reference: frames per sequence (main.py:67)")
+    ap.add_argument("--dataset", choices=("pca", "argo"), default="pca",
+                    help="--protocol reference: pca = Waymo / nuScenes sequence files; argo = Argoverse 2 files as ZeroFlow exports "
+                         "them, one two-frame sample each (main.py:156-159)")
+    ap.add_argument("--num-frames", type=int, default=None,
+                    help="--protocol reference: frames per sequence (main.py:67; default 5, with --dataset argo 2 and nothing else)")
     ap.add_argument("--range-z", type=float, default=0.0, help="--protocol reference: ground <= range_z (main.py:73)")
     ap.add_argument("--ground-slack", type=float, default=0.3, help="--protocol reference (main.py:113)")
     ap.add_argument("--eval-ground", action="store_true", help="--protocol reference: evaluate ground points too (main.py:115)")
@@ -1018,6 +1089,12 @@ def main(argv=None):
                     help="--protocol reference: write a JSON list of the segments with EPE above --report-epe, worst first")
     ap.add_argument("--report-epe", type=float, default=2.0, help="threshold of --report in metres (utils_flow.py:112)")
     ns = ap.parse_args(argv)
+    if ns.dataset == "argo":
+        if ns.num_frames not in (None, 2):
+            raise SystemExit(f"--dataset argo: an Argoverse 2 sample has two frames (--num-frames {ns.num_frames})")
+        if ns.protocol != "reference":
+            raise SystemExit("--dataset argo goes with --protocol reference (without it every file is a plain frame pair already)")
+    num_frames = ns.num_frames if ns.num_frames is not None else 2 if ns.dataset == "argo" else 5
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1037,11 +1114,14 @@ def main(argv=None):
             raise SystemExit("--protocol reference is single-process (the table is not reduced across ranks)")
         if args.range_x is None or args.range_y is None:
             args.range_x, args.range_y = 32.0, 32.0                                    # main.py:69-72
-        args.num_frames, args.range_z, args.ground_slack, args.eval_ground = ns.num_frames, ns.range_z, ns.ground_slack, ns.eval_ground
+        args.num_frames, args.range_z, args.ground_slack, args.eval_ground = num_frames, ns.range_z, ns.ground_slack, ns.eval_ground
         args.ground = ns.ground
         if ns.if_verbose or ns.report:
             args.if_verbose = True
-        res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_sequence(p)], device, in_flight=ns.in_flight)
+        if ns.dataset == "argo":
+            res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_argo(p)], device, in_flight=ns.in_flight, dataset="argo")
+        else:
+            res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_sequence(p)], device, in_flight=ns.in_flight)
         reports = res.pop("segments", None)
         if ns.report:
             with open(ns.report, "w") as f:

@@ -1,6 +1,8 @@
 """Drop-in for the pose arithmetic of the reference's loader (utils_loading.py:21-48): the two functions that turn a
 Waymo / nuScenes sample's poses into its ground-truth scene flow (dataset_pca.py:66-69), computed by icpflow_seq_gt_flow
 (csrc/seqeval.hip) in fp64.  numpy arrays or device tensors in, the same kind out; there is no CPU path.
+`argo_sample` is the front of the other loader, dataset_argo.py:47-50, 66-71, 83-89 (icpflow_seq_argo_sample): the two-frame
+sample of an Argoverse 2 file with its static / dynamic and foreground / background labels, built on the device.
 
 Where this differs from numpy on purpose: a time index outside [0, n_frames) or an instance label outside [0, M) raises
 (numpy wraps a negative index around to the last pose, and checks only the combination inst * n_frames + t)."""
@@ -94,3 +96,79 @@ def reconstruct_sequence(points, time_indice, inst_labels, tsfm, n_frames):
 def scene_flow(raw_points, time_indice, inst_labels, ego_motion_gt, inst_motion_gt):
     """dataset_pca.py:66-69 in one launch: reconstruct_sequence(ego_motion_compensation(raw)) - raw, float64 [m,3]."""
     return _like(seq_transform(raw_points, time_indice, inst_labels, ego_motion_gt, inst_motion_gt, _lib.SEQ_OUT_FLOW), raw_points)
+
+
+# dataset_argo.py:23-25: the reference looks its six background categories up by POSITION in its id table sorted by id, and
+# that table starts at id -1 -- so these are the categories' ids + 1 (ids 4, 7, 8, 12, 20, 21), compared with the file's classes
+ARGO_BACKGROUND_IDXES = (5, 8, 9, 13, 21, 22)
+ARGO_DYNAMIC_THRESHOLD = 0.5 * 0.1            # dataset_argo.py:66-67: 10 Hz, more than 0.5 m/s is dynamic
+
+
+def _file_dtype(a, name):
+    """The type a file stores an array in -> (torch dtype, numpy type, ICPFLOW_DTYPE_*)"""
+    kind = str(a.dtype).replace("torch.", "")
+    if kind == "float32":
+        return torch.float32, np.float32, _lib.DTYPE_FLOAT32
+    if kind == "float64":
+        return torch.float64, np.float64, _lib.DTYPE_FLOAT64
+    raise TypeError(f"{name}: float32 or float64 expected, got {a.dtype}")
+
+
+def argo_sample(pc1, pc2, flow_0_1, classes1, valid1, valid2, background=None, device=None):
+    """dataset_argo.py:47-50, 66-71, 83-89 on the device (icpflow_seq_argo_sample): the arrays of one Argoverse 2 file --
+    pc1 [n1,3], pc2 [n2,3], gt_flow_0_1 [n1,3], pc1_classes [n1], the two *_flows_valid_idx (index lists, or boolean masks:
+    np.flatnonzero on the host first) -- as numpy arrays or device tensors -> the sample calculate_metrics reads, a dict of
+    device tensors of m = m2 + m1 rows, frame 0 (pc2's rows) first: raw_points (in the points' own dtype: the kernel's
+    float64 rows narrowed back, which is exact, so that the evaluation rounds its crop thresholds as numpy does for that
+    dtype), time_indice, sd_labels, fb_labels (int32), scene_flow (float64).  `background`: the class values that are not
+    foreground besides -1 (default ARGO_BACKGROUND_IDXES).  An index outside [0, n) raises IndexError (numpy's negative
+    wrap-around is not reproduced).  There is no CPU path."""
+    if device is None:
+        device = _device_for(pc1, pc2, flow_0_1, classes1)
+    device = torch.device(device)
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("icp_flow_amd: an Argoverse 2 sample is built on the GPU -- there is no CPU path")
+    p_t, _, p_code = _file_dtype(pc1, "pc1")
+    if _file_dtype(pc2, "pc2")[0] != p_t:
+        raise TypeError("pc1 and pc2 must be stored in one dtype")
+    f_t, f_np, f_code = _file_dtype(flow_0_1, "gt_flow_0_1")
+    p1, p2 = to_device(pc1, p_t, device), to_device(pc2, p_t, device)
+    flow = to_device(flow_0_1, f_t, device)
+    for name, a in (("pc1", p1), ("pc2", p2), ("gt_flow_0_1", flow)):
+        if a.dim() != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name}: expected [n,3], got {tuple(a.shape)}")
+    n1, n2 = p1.shape[0], p2.shape[0]
+    cls = to_device(classes1, torch.float64, device)
+    if flow.shape[0] != n1 or cls.shape != (n1,):
+        raise ValueError("gt_flow_0_1 and pc1_classes: one row per point of pc1 required")
+
+    def index_list(v, n, name):
+        if (isinstance(v, torch.Tensor) and v.dtype == torch.bool) or (not isinstance(v, torch.Tensor) and np.asarray(v).dtype == bool):
+            host = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            if host.shape != (n,):
+                raise IndexError(f"{name}: a boolean mask of {host.shape} for {n} points")
+            v = np.flatnonzero(host)
+        v = to_device(v, torch.int64, device)
+        if v.dim() != 1:
+            raise ValueError(f"{name}: a list of indices expected, got {tuple(v.shape)}")
+        return v
+
+    v1, v2 = index_list(valid1, n1, "pc1_flows_valid_idx"), index_list(valid2, n2, "pc2_flows_valid_idx")
+    m1, m2 = v1.shape[0], v2.shape[0]
+    m = m1 + m2
+    bg = np.ascontiguousarray(ARGO_BACKGROUND_IDXES if background is None else background, dtype=np.int32).reshape(-1)
+    pts = torch.empty((m, 3), dtype=torch.float64, device=device)
+    tim, sd, fb = (torch.empty(m, dtype=torch.int32, device=device) for _ in range(3))
+    out_flow = torch.empty((m, 3), dtype=torch.float64, device=device)
+    bad = torch.empty(1, dtype=torch.int64, device=device)
+    # the threshold as numpy compares it with a norm of the flow's dtype (utils_eval._threshold_for's idea)
+    threshold = float(np.asarray(ARGO_DYNAMIC_THRESHOLD, dtype=np.float64).astype(f_np))
+    with torch.cuda.device(device):
+        _lib.call("icpflow_seq_argo_sample", _lib.ptr(p1), n1, _lib.ptr(p2), n2, p_code, _lib.ptr(flow), f_code, _lib.ptr(cls),
+                  _lib.ptr(v1), m1, _lib.ptr(v2), m2, bg.ctypes.data_as(ctypes.c_void_p), len(bg), threshold, _lib.ptr(pts),
+                  _lib.ptr(tim), _lib.ptr(sd), _lib.ptr(fb), _lib.ptr(out_flow), _lib.ptr(bad), _lib.stream(device))
+    n_bad = int(bad.item())
+    if n_bad:
+        raise IndexError(f"{n_bad} of {m} valid indices lie outside their cloud ([0, {n1}) for pc1, [0, {n2}) for pc2; "
+                         "numpy's negative-index wrap-around is not reproduced)")
+    return dict(raw_points=pts.to(p_t), time_indice=tim, sd_labels=sd, fb_labels=fb, scene_flow=out_flow)

@@ -801,6 +801,25 @@ int icpflow_egomotion_register_frame_stamped(icpflow_ego_t *ego, const float *d_
  *   Counts are exact.  The sums of e are a function of the arguments alone -- not of the device, the stream or the
  *   scheduling: a fixed reduction order, no floating-point atomics (csrc/seqeval.hip).  F > ICPFLOW_SEQ_MAX_FRAMES is
  *   ICPFLOW_E_LIMIT (the table of a workgroup lives in LDS).
+ *
+ * icpflow_seq_argo_sample -- replaces dataset_argo.py:47-50 (the gathers), :66-71 (the two labels) and :83-89 (the
+ *   two-frame sample) for one Argoverse 2 file as ZeroFlow exports it, without the clouds or the flow crossing to the
+ *   host.  d_pc1 [n1,3], d_pc2 [n2,3] in points_dtype, d_flow_0_1 [n1,3] in flow_dtype (ICPFLOW_DTYPE_FLOAT32 or _FLOAT64:
+ *   the file's own types), d_classes1 float64 [n1] (widened by the caller: exact for every integer or float type an npz
+ *   holds, and == then decides as numpy does on the file's type), d_valid1 int64 [m1], d_valid2 int64 [m2]: the files'
+ *   pc*_flows_valid_idx (a boolean mask is the caller's np.flatnonzero).  Outputs of m = m2 + m1 rows:
+ *       rows [0, m2)   frame 0: d_points = pc2[valid2[i]] widened, d_time_indice 0, d_sd_labels 0, d_fb_labels 0, zero flow
+ *       rows [m2, m)   frame 1: d_points = pc1[valid1[k]] widened, d_time_indice 1, d_scene_flow = flow[valid1[k]] widened,
+ *                      sd = (|flow row| > sd_threshold), fb = 1 except where the class equals -1 or one of the
+ *                      n_background entries of h_background (HOST memory, read before the call returns), there 0
+ *   |flow row| is np.linalg.norm(flow, axis=-1) as numpy computes it IN flow_dtype: sqrt((x x + y y) + z z), every
+ *   operation rounded by itself, the square root correctly rounded; the caller passes sd_threshold as numpy compares it,
+ *   0.5 * 0.1 rounded to flow_dtype.  A NaN norm is not > threshold (sd = 0), a NaN class equals nothing (fb = 1).
+ *   An index outside [0, n) writes nothing for its row and is counted in d_bad_rows (int64 [1]); numpy's wrap-around of a
+ *   negative index is NOT reproduced.  Rows of the inputs that no index selects are never read (the files pad them with
+ *   non-finite values).  No workspace.  n_background > ICPFLOW_ARGO_MAX_BACKGROUND is ICPFLOW_E_LIMIT; a null pointer, a
+ *   negative size or an unknown dtype is ICPFLOW_E_ARG before any launch; m = 0 succeeds (*d_bad_rows = 0).  Asynchronous
+ *   on `stream`; the results are a function of the arguments alone.
  * ------------------------------------------------------------------------- */
 #define ICPFLOW_SEQ_MAX_FRAMES 16
 #define ICPFLOW_SEQ_OUT_FLOW 0
@@ -817,6 +836,14 @@ int icpflow_seq_metrics(const double *d_points, const int32_t *d_time_indice, co
                         const int32_t *d_fb_labels, const double *d_gt_flow, const float *d_pred_flow, int m, int F, int crop,
                         double range_x, double range_y, double z_min, int64_t *d_table, int64_t *d_info, void *d_ws,
                         size_t ws_bytes, icpflow_stream_t stream);
+#define ICPFLOW_DTYPE_FLOAT32 0
+#define ICPFLOW_DTYPE_FLOAT64 1
+#define ICPFLOW_ARGO_MAX_BACKGROUND 64
+int icpflow_seq_argo_sample(const void *d_pc1, int n1, const void *d_pc2, int n2, int points_dtype, const void *d_flow_0_1,
+                            int flow_dtype, const double *d_classes1, const int64_t *d_valid1, int m1, const int64_t *d_valid2,
+                            int m2, const int32_t *h_background, int n_background, double sd_threshold, double *d_points,
+                            int32_t *d_time_indice, int32_t *d_sd_labels, int32_t *d_fb_labels, double *d_scene_flow,
+                            int64_t *d_bad_rows, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * 8(f)  per-segment evaluation of one labelled cloud of one frame pair: the numbers behind the reference's verbose loop,
