@@ -73,6 +73,10 @@ SIGNATURES = {
     "icpflow_hdbscan_mst_workspace_bytes": (_sz, [_i]),
     "icpflow_hdbscan_mst": (_i, [_p, _i, _p, _i, _i, _d, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_hdbscan_labels": (_i, [_p, _p, _p, _i, _i, _p]),
+    "icpflow_cluster_default_params": (_i, [_p]),
+    "icpflow_cluster_pcd_workspace_bytes": (_sz, [_i, _i, _p]),
+    "icpflow_cluster_pcd": (_i, [_p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_track_frame_points": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p]),
     "icpflow_ego_default_params": (_i, [_p]),
     "icpflow_ego_state_bytes": (_sz, [_p]),
     "icpflow_ego_create": (_i, [_p, _p, _sz, _p, ctypes.POINTER(_p)]),
@@ -206,6 +210,25 @@ class FrameParams(ctypes.Structure):
     _fields_ = [("struct_size", _sz), ("seed", ctypes.c_uint64), ("generator", _p), ("max_points", _i), ("min_cluster_size", _i),
                 ("translation_frame", _f), ("thres_box", _f), ("thres_iou", _f), ("rot_limit_deg", _f), ("thres_error", _f),
                 ("tight_padding", _i), ("superset_width", _i)]
+
+
+CLUSTER_DBSCAN, CLUSTER_HDBSCAN = 0, 1
+
+
+class ClusterParams(ctypes.Structure):
+    """icpflow_cluster_params_t: what cluster_pcd reads of the reference's parser (icpflow_cluster_pcd, icpflow_track_frame_points)."""
+    _fields_ = [("struct_size", _sz), ("method", _i), ("min_cluster_size", _i), ("num_clusters", _i), ("reserved", _i),
+                ("eps", _d), ("cell", _d)]
+
+    @staticmethod
+    def defaults(**over):
+        p = ClusterParams()
+        call("icpflow_cluster_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise TypeError(f"icpflow_cluster_params_t has no field {k!r}")
+            setattr(p, k, v)
+        return p
 
 
 class EgoParams(ctypes.Structure):

@@ -29,6 +29,7 @@
 
 using icpflow::align256;
 using icpflow::Carver;
+using icpflow::Pinned;
 using icpflow::report_error;
 
 namespace {
@@ -360,29 +361,6 @@ struct PassRows {
         }
         for (int d = 0; d < D; ++d)
             if (nr[d] && pair_passes(st, dt, s, d, tf, tb)) visit(d);
-    }
-};
-
-struct Pinned {   // a pinned host buffer that grows (read in place by the kernels / target of the read-backs)
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    int device = -1;
-    Pinned() = default;
-    Pinned(const Pinned &) = delete;
-    Pinned &operator=(const Pinned &) = delete;
-    ~Pinned() { if (ptr != nullptr) (void)hipHostFree(ptr); }   // (thread_local: freed when the host thread ends)
-    char *need(size_t want)
-    {
-        int dev = -1;
-        (void)hipGetDevice(&dev);
-        if (ptr == nullptr || bytes < want || device != dev) {
-            if (ptr != nullptr) (void)hipHostFree(ptr);
-            ptr = nullptr;
-            bytes = std::max(want, (size_t)1 << 20);
-            if (hipHostMalloc(&ptr, bytes, hipHostMallocDefault) != hipSuccess) { ptr = nullptr; bytes = 0; }
-            device = dev;
-        }
-        return static_cast<char *>(ptr);
     }
 };
 

@@ -3,6 +3,8 @@
 #pragma once
 #include "carver.hpp"
 
+#include <algorithm>
+
 #include <hip/hip_runtime.h>
 
 #include "../../include/icpflow_hip.h"
@@ -24,6 +26,30 @@ inline int workspace_error(const char *fn, const char *query, const void *ws, si
 {
     return report_errorf(ICPFLOW_E_WORKSPACE, "%s: workspace of %zu bytes, %s says %zu", fn, ws ? have : (size_t)0, query, need);
 }
+
+// (frame.hip's staging and read-backs, clusterpcd.hip's download and upload: one per host thread each, thread_local)
+struct Pinned {   // a pinned host buffer that grows (read in place by the kernels / target of the read-backs)
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    int device = -1;
+    Pinned() = default;
+    Pinned(const Pinned &) = delete;
+    Pinned &operator=(const Pinned &) = delete;
+    ~Pinned() { if (ptr != nullptr) (void)hipHostFree(ptr); }   // (thread_local: freed when the host thread ends)
+    char *need(size_t want)
+    {
+        int dev = -1;
+        (void)hipGetDevice(&dev);
+        if (ptr == nullptr || bytes < want || device != dev) {
+            if (ptr != nullptr) (void)hipHostFree(ptr);
+            ptr = nullptr;
+            bytes = std::max(want, (size_t)1 << 20);
+            if (hipHostMalloc(&ptr, bytes, hipHostMallocDefault) != hipSuccess) { ptr = nullptr; bytes = 0; }
+            device = dev;
+        }
+        return static_cast<char *>(ptr);
+    }
+};
 
 }  // namespace icpflow
 

@@ -311,6 +311,10 @@ def cluster_frame_pair(args, ps, pd, nonground_src=None, nonground_dst=None):
     m_dst = ones(len(pd)) if nonground_dst is None else torch.as_tensor(nonground_dst, device=dev).bool()
     a = SimpleNamespace(epsilon=float(args.epsilon), min_cluster_size=int(args.min_cluster_size),
                         num_clusters=int(args.num_clusters), if_hdbscan=args.cluster == "hdbscan")
+    if getattr(args, "native_cluster", False):     # icpflow_cluster_pcd: both segments as they are, no stack, no numpy
+        l_dst, l_src = utils_cluster.cluster_pcd_native(a, pd, ps, None if nonground_dst is None else m_dst,
+                                                        None if nonground_src is None else m_src)
+        return l_src, l_dst
     labels = utils_cluster.cluster_pcd(a, torch.cat([pd, ps], dim=0), torch.cat([m_dst, m_src], dim=0)).float()
     return labels[len(pd):].contiguous(), labels[: len(pd)].contiguous()
 
@@ -502,13 +506,25 @@ def register_frame_pair_native(args, fp, device, gap=None):
     device = torch.device(device)
     ps = _input(fp, "points_src", device)
     pd = _input(fp, "points_dst", device)
+    pose = torch.from_numpy(fp.pose).to(device)
+    flow_src = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    if fp.labels_src is None and getattr(args, "native_cluster", False):
+        # points in: icpflow_track_frame_points clusters the stack itself.  A frame pair it cannot serve goes the way of every
+        # other one (the caller's register_frame_pair_steps, which clusters through cluster_frame_pair under the same switch)
+        if getattr(args, "cluster", None) not in ("dbscan", "hdbscan"):
+            raise ValueError("frame pair without cluster labels: pass precomputed labels_src / labels_dst or set "
+                             "args.cluster = 'hdbscan' | 'dbscan'")
+        from . import utils_cluster
+        par = utils_cluster.cluster_params(SimpleNamespace(epsilon=float(args.epsilon), min_cluster_size=int(args.min_cluster_size),
+                                                           num_clusters=int(args.num_clusters), if_hdbscan=args.cluster == "hdbscan"))
+        m_src = None if fp.nonground_src is None else torch.as_tensor(fp.nonground_src, device=device).bool()
+        m_dst = None if fp.nonground_dst is None else torch.as_tensor(fp.nonground_dst, device=device).bool()
+        return track_frame_native(a, ps, pd, None, None, pose, flow_src, cluster=par, mask_src=m_src, mask_dst=m_dst)
     if fp.labels_src is None:
         ls, ld = cluster_frame_pair(args, ps, pd, fp.nonground_src, fp.nonground_dst)
     else:
         ls = _input(fp, "labels_src", device)
         ld = _input(fp, "labels_dst", device)
-    pose = torch.from_numpy(fp.pose).to(device)
-    flow_src = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
     return track_frame_native(a, ps, pd, ls, ld, pose, flow_src)
 
 
@@ -546,11 +562,15 @@ def randperm_restatement_ok():
     return _randperm_ok
 
 
-def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, generator=None):
+def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, generator=None, cluster=None, mask_src=None,
+                       mask_dst=None):
     """icpflow_track_frame on device tensors: `track(a, ps, pd, ls, ld)` (+ `flow_estimation_torch` of `flow_points` under
     `pose` when given) with `a.translation_frame` set; the random subsamples of over-long clusters are torch.randperm's on a
     generator seeded with `seed` -- or on `generator` (a torch CPU generator, or "global" for torch's own: its state goes in,
     and comes back advanced when the call has served the frame pair).
+    cluster (an _lib.ClusterParams; ls / ld None): icpflow_track_frame_points -- the call clusters the stack of both clouds
+    itself (mask_src / mask_dst: uint8 or bool device tensors, the non-ground rows, or None) and leaves the labels it used in
+    the result under `if_verbose`.
     -> dict(pairs, transformations[, flow]), None (see register_frame_pair_native) or NEEDS_HOST_ASSOCIATION."""
     from . import _lib, utils_match
     import ctypes
@@ -563,15 +583,21 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
         return None
     if not randperm_restatement_ok():
         return None                     # (the caller's Python host draws with torch.randperm itself)
-    _lib.require_gpu(ps, pd, ls, ld)
+    _lib.require_gpu(ps, pd, ls, ld, mask_src, mask_dst)
     ps3, pd3 = ps[:, 0:3].contiguous().float(), pd[:, 0:3].contiguous().float()
-    ls, ld = ls.contiguous().float(), ld.contiguous().float()
+    if cluster is None:
+        ls, ld = ls.contiguous().float(), ld.contiguous().float()
+    else:
+        ls = torch.empty(len(ps3), dtype=torch.float32, device=device)
+        ld = torch.empty(len(pd3), dtype=torch.float32, device=device)
+        mask_src = None if mask_src is None else mask_src.to(torch.uint8).contiguous()
+        mask_dst = None if mask_dst is None else mask_dst.to(torch.uint8).contiguous()
     rows = torch.empty((1024, 10), dtype=torch.float32, device=device)
     T = torch.empty((1024, 4, 4), dtype=torch.float32, device=device)
     flow = f_pts = f_pose = None
     if flow_points is not None:
         f_pts = ps3 if flow_points is ps else flow_points[:, 0:3].contiguous().float()
-        assert len(f_pts) == len(ls)
+        assert len(f_pts) == len(ps3)
         f_pose = pose.to(device).contiguous().float()
         flow = torch.empty((len(ps3), 3), dtype=torch.float32, device=device)
     reg, keep_alive = utils_match._registration(a, device)
@@ -592,17 +618,20 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
                       no_stage_overlap=getattr(a, "stage_overlap", None) is False):
         opt = _lib.opt()
         for _ in range(5):   # (the scratch is sized in up to three parts -- fixed, stages, exact stage 2 --, each learnt from a refusal)
-            rc = _lib._L.icpflow_track_frame(_lib.ptr(ps3), _lib.ptr(ls), len(ps3), _lib.ptr(pd3), _lib.ptr(ld), len(pd3),
-                                             ctypes.byref(reg), ctypes.byref(par), _lib.ptr(rows), _lib.ptr(T), ctypes.byref(pairs),
-                                             _lib.ptr(f_pts), _lib.ptr(f_pose), _lib.ptr(flow), _lib.ptr(scratch), scratch.numel(),
-                                             ctypes.byref(need), _lib.stream(device), opt)
+            tail = (ctypes.byref(reg), ctypes.byref(par), _lib.ptr(rows), _lib.ptr(T), ctypes.byref(pairs), _lib.ptr(f_pts),
+                    _lib.ptr(f_pose), _lib.ptr(flow), _lib.ptr(scratch), scratch.numel(), ctypes.byref(need), _lib.stream(device), opt)
+            if cluster is None:
+                rc = _lib._L.icpflow_track_frame(_lib.ptr(ps3), _lib.ptr(ls), len(ps3), _lib.ptr(pd3), _lib.ptr(ld), len(pd3), *tail)
+            else:
+                rc = _lib._L.icpflow_track_frame_points(_lib.ptr(ps3), _lib.ptr(mask_src), len(ps3), _lib.ptr(pd3), _lib.ptr(mask_dst),
+                                                        len(pd3), ctypes.byref(cluster), _lib.ptr(ls), _lib.ptr(ld), *tail)
             if rc != -2:
                 break
             # (the scratch grows to what this frame pair needs, with some room: the next ones are alike)
             scratch = _frame_scratch[key] = torch.empty((int(need.value * 1.25),), dtype=torch.uint8, device=device)
     if rc != 0:
         msg = _lib._L.icpflow_last_error()
-        raise RuntimeError(f"icpflow_track_frame failed (code {rc}): {msg.decode() if msg else ''}")
+        raise RuntimeError(f"icpflow_track_frame{'_points' if cluster is not None else ''} failed (code {rc}): {msg.decode() if msg else ''}")
     P = int(pairs.value)
     if P == -3:
         return NEEDS_HOST_ASSOCIATION
@@ -1085,6 +1114,9 @@ def main(argv=None):
                          "Patchwork++ AND the threshold per frame on the GPU (utils_ground.py:16-23)")
     ap.add_argument("--if-verbose", action="store_true",
                     help="--protocol reference: print the per-frame and per-segment lines of the reference's --if_verbose (main.py:117)")
+    ap.add_argument("--native-cluster", action="store_true",
+                    help="with --cluster: frame pairs without labels are clustered inside the library (icpflow_cluster_pcd / "
+                         "icpflow_track_frame_points) instead of by the Python clustering; off by default")
     ap.add_argument("--report", metavar="FILE", default=None,
                     help="--protocol reference: write a JSON list of the segments with EPE above --report-epe, worst first")
     ap.add_argument("--report-epe", type=float, default=2.0, help="threshold of --report in metres (utils_flow.py:112)")
@@ -1107,6 +1139,8 @@ def main(argv=None):
     args.max_points, args.min_cluster_size, args.chunk_size = int(args.max_points), int(args.min_cluster_size), int(args.chunk_size)
     args.num_clusters = int(args.num_clusters)
     args.pose_source, args.save_poses = ns.pose_source, ns.save_poses
+    if ns.native_cluster:
+        args.native_cluster = True
     if ns.ego_deskew or ns.ego_fixed_threshold:
         args.ego_motion = dict(deskew=ns.ego_deskew, fixed_threshold=ns.ego_fixed_threshold)
     if ns.protocol == "reference":

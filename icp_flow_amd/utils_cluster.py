@@ -15,6 +15,10 @@ minimum spanning tree of the mutual-reachability graph -- runs in libicpflow_hip
 csrc/hdbscan.hip); the sequential remainder on the n - 1 tree edges (sort, dendrogram, condensed tree,
 excess-of-mass selection) is host C++ in the same library (`icpflow_hdbscan_labels`, csrc/hdbscan_tree.cpp),
 checked against scikit-learn's compiled routines for those steps.
+
+`args.native_cluster = True` (absent = False) with device tensors in: cluster_pcd as a whole in one call into the library
+(`cluster_pcd_native`, `icpflow_cluster_pcd`: the keep rule and the labels are kernels, for HDBSCAN host C++).
+The path above stays the default; among clusters of equal size at the cut the native call keeps the larger id.
 """
 import numpy as np
 import torch
@@ -100,6 +104,9 @@ def cluster_pcd(args, points, idxs_nonground):
         full = np.zeros(len(points), dtype=bool)
         full[np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask)] = True
         mask = full
+    if getattr(args, "native_cluster", False) and resident:
+        lab, _ = cluster_pcd_native(args, points, None, mask, None)
+        return lab.double()
     if getattr(args, "if_hdbscan", False):
         lab_h = cluster_hdbscan(args, points, mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
         out_h = np.where(lab_h == -2, -1e8, lab_h.astype(np.float64))
@@ -107,6 +114,61 @@ def cluster_pcd(args, points, idxs_nonground):
     lab = _cluster(args, points, mask)
     out = torch.where(lab == -2, torch.full((), -1e8, dtype=torch.float64, device=lab.device), lab.double())
     return out if resident else out.cpu().numpy()
+
+
+def cluster_params(args):
+    """icpflow_cluster_params_t of the flags cluster_pcd reads (utils_cluster.py:14, 35, 19-27)."""
+    return _lib.ClusterParams.defaults(method=_lib.CLUSTER_HDBSCAN if getattr(args, "if_hdbscan", False) else _lib.CLUSTER_DBSCAN,
+                                       eps=float(getattr(args, "epsilon", 0.25)), min_cluster_size=int(args.min_cluster_size),
+                                       num_clusters=int(args.num_clusters))
+
+
+def _native_segment(points, mask):
+    if points is None or len(points) == 0:
+        return None, None
+    _lib.require_gpu(points)
+    if points.dim() != 2 or points.shape[1] < 3:
+        raise RuntimeError(f"cluster_pcd: expected points [n, >=3], got {tuple(points.shape)}")
+    pts = points.float().contiguous()
+    m = None
+    if mask is not None:
+        m = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask))
+        m = m.to(pts.device).to(torch.uint8).contiguous()
+        if m.shape != (len(pts),):
+            raise RuntimeError(f"cluster_pcd: mask must have shape ({len(pts)},), got {tuple(m.shape)}")
+    return pts, m
+
+
+def cluster_pcd_native(args, dst, src=None, mask_dst=None, mask_src=None, check=True):
+    """cluster_pcd (utils_cluster.py:50-63) of the stack [dst; src] in one call into the library (icpflow_cluster_pcd): the keep
+    rule and the labels are kernels, nothing is concatenated.  Device tensors only.  -> (labels_dst, labels_src) float32 on the
+    GPU (labels_src None without src).  check: read the call's four info words back and raise IndexError where the reference's
+    expression does (nothing left to keep, utils_cluster.py:24 / :43)."""
+    import ctypes
+    d, md = _native_segment(dst, mask_dst)
+    s, ms = _native_segment(src, mask_src)
+    if d is None and s is None:
+        raise RuntimeError("cluster_pcd: no points")
+    if d is None or (s is not None and s.shape[1] != d.shape[1]):      # one stride for both segments
+        d = None if d is None else d[:, 0:3].contiguous()
+        s = None if s is None else s[:, 0:3].contiguous()
+    dev = (d if d is not None else s).device
+    nd, ns = (0 if d is None else len(d)), (0 if s is None else len(s))
+    par = cluster_params(args)
+    need = int(_lib._L.icpflow_cluster_pcd_workspace_bytes(nd, ns, ctypes.byref(par)))
+    if need == 0:
+        msg = _lib._L.icpflow_last_error()
+        raise RuntimeError(f"icpflow_cluster_pcd_workspace_bytes: {msg.decode() if msg else 'no size'}")
+    ws = _lib.workspace(dev, need)
+    ld = torch.empty(nd, dtype=torch.float32, device=dev)
+    ls = torch.empty(ns, dtype=torch.float32, device=dev)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    _lib.call("icpflow_cluster_pcd", _lib.ptr(d), nd, _lib.ptr(s), ns, (d if d is not None else s).shape[1], _lib.ptr(md), _lib.ptr(ms),
+              ctypes.byref(par), _lib.ptr(ld) if nd else None, _lib.ptr(ls) if ns else None, _lib.ptr(info), _lib.ptr(ws), ws.numel(),
+              _lib.stream(dev))
+    if check and int(info[1].item()) == 0:
+        raise IndexError("cluster_pcd: no cluster is left to keep (utils_cluster.py:24 / :43 index an empty array here)")
+    return ld, (ls if src is not None else None)
 
 
 def hdbscan_mst(points, min_samples, mask=None, cell=0.25):

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* (icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 214 /* (icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -597,7 +597,8 @@ int icpflow_flow_rigid_rows(const float *d_points, const float *d_labels, int N,
  * Outputs: d_labels int32 [n]: cluster id 0..C-1 in order of each cluster's smallest core-point row
  * (Open3D's numbering), -1 noise, -2 masked out;  d_counts int32 [n]: the first C entries are the
  * cluster sizes;  d_num_clusters int32 [1] = C.  Keeping only the num_clusters largest clusters
- * (utils_cluster.py:38-45) is host logic on d_counts (icp_flow_amd/utils_cluster.py).
+ * (utils_cluster.py:38-45) is not part of this call: icpflow_cluster_pcd below does it on the device (its keep-rule
+ * kernel reads d_counts); icp_flow_amd/utils_cluster.py's default path still does it in numpy.
  * ------------------------------------------------------------------------- */
 size_t icpflow_dbscan_workspace_bytes(int n);
 int icpflow_dbscan(const float *d_points, int stride, const uint8_t *d_mask, int n, double eps, int min_points,
@@ -613,8 +614,9 @@ int icpflow_dbscan(const float *d_points, int stride, const uint8_t *d_mask, int
  *     does not count the point (its boruvka_kdtree path queries k = min_samples + 1, _hdbscan_boruvka.pyx):
  *     pass its min_samples + 1 here -- icp_flow_amd/utils_cluster.py does, for the reference's
  *     HDBSCAN(min_cluster_size, min_samples=None) that is min_cluster_size + 1.
- * The dendrogram, condensed tree and cluster selection on the n - 1 edges are sequential host logic
- * (icp_flow_amd/utils_cluster.py).
+ * The dendrogram, condensed tree and cluster selection on the n - 1 edges are sequential host logic:
+ * icpflow_hdbscan_labels below, host C++.  icpflow_cluster_pcd chains the two with the rest of cluster_pcd (row mapping,
+ * label histogram, keep rule) inside the library; icp_flow_amd/utils_cluster.py's default path does that rest in numpy.
  *
  * d_points / stride / d_mask as icpflow_dbscan.  cell: edge of the uniform sort grid in metres (speed
  * only; 0.25 suits LiDAR frames).  Outputs: d_edge_a / d_edge_b int32 [n], d_edge_w2 float64 [n]: the
@@ -636,6 +638,69 @@ int icpflow_hdbscan_mst(const float *d_points, int stride, const uint8_t *d_mask
  * Returns ICPFLOW_E_ARG when the edges do not span the points or min_cluster_size < 2. */
 int icpflow_hdbscan_labels(const int32_t *h_edge_a, const int32_t *h_edge_b, const double *h_edge_w,
                            int n_points, int min_cluster_size, int32_t *h_labels);
+
+/* ---------------------------------------------------------------------------
+ * 8(f) row 10  cluster_pcd as a whole (utils_cluster.py:50-63 with cluster_dbscan :32-48 or hdbscan :10-29): the points of a
+ * frame pair in, the labels track() reads out.  The call clusters the STACK of two segments, dst first, as
+ * dataset_pca.py:175-182 and demo.py:210-212 stack them -- the caller concatenates nothing; n_src = 0 clusters one cloud.
+ *
+ * The fields of icpflow_cluster_params_t; icpflow_cluster_default_params fills it with main.py:77-82's defaults and DBSCAN:
+ *   method            ICPFLOW_CLUSTER_DBSCAN (utils_cluster.py:32-48) or ICPFLOW_CLUSTER_HDBSCAN (:10-29, --if_hdbscan)
+ *   eps               --epsilon: DBSCAN's radius (:35; HDBSCAN does not read it, :14 passes no epsilon)
+ *   min_cluster_size  --min_cluster_size: DBSCAN's min_points (:35); HDBSCAN's min_cluster_size (:14), with
+ *                     min_samples = min_cluster_size + 1 handed to icpflow_hdbscan_mst (the hdbscan package does not count
+ *                     the point itself, see there) -- at most 63
+ *   num_clusters      --num_clusters: how many of the largest clusters survive (:19-27, :39-46)
+ *   cell              HDBSCAN's sort grid (icpflow_hdbscan_mst), 0 = 0.25
+ *
+ * d_dst / d_src float32 rows of `stride` floats (x, y, z first); d_mask_dst / d_mask_src uint8 per row or NULL (all rows):
+ * rows with mask 0 are the ground rows of cluster_pcd's idxs_nonground (:52-53).
+ * Outputs: d_labels_dst [n_dst], d_labels_src [n_src] float32 in cluster_pcd's convention (:54-62): the cluster id, -1 for
+ * an unclustered row, -1e8 for a masked row;  d_info int32 [4] = {clusters found, clusters kept, noise rows, live (unmasked)
+ * rows}.  "clusters kept" = 0 is where the reference raises IndexError (:24 / :43: nothing left to sort); every label is
+ * then -1 or -1e8.
+ *
+ * The keep rule (:19-27, :39-46), quirks included: the FIRST unique label is dropped unseen -- -1 when at least one row is
+ * noise, otherwise cluster 0, which is then never kept; the num_clusters largest of the rest survive.  Named deviation: among
+ * clusters of EQUAL size at the cut the LARGER id wins (a stable ascending sort followed by the reference's [::-1]; numpy's
+ * default argsort is not stable and its tie order depends on the numpy build).
+ *
+ * DBSCAN: enqueued work only, like every other entry point -- the keep rule (rank of a cluster = the number of clusters that
+ * beat it) and the label finish are kernels.  HDBSCAN: BLOCKING on `stream`: spanning tree and the sort of its edges on the
+ * device, one download into host memory the library owns (ICPFLOW_E_HOSTMEM when it cannot be had), icpflow_hdbscan_labels,
+ * row mapping / label histogram / keep rule in host C++, one upload, the same finish kernel.  ICPFLOW_E_ARG when fewer than
+ * min_cluster_size + 1 rows can be clustered (the hdbscan package raises there).
+ * ICPFLOW_E_LIMIT: cluster ids must be exact in float32 -- any n = n_dst + n_src with ceil(n / min_cluster_size) > 2^24.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_CLUSTER_DBSCAN 0
+#define ICPFLOW_CLUSTER_HDBSCAN 1
+typedef struct icpflow_cluster_params {
+    size_t struct_size; /* sizeof(icpflow_cluster_params_t) */
+    int method;
+    int min_cluster_size;
+    int num_clusters;
+    int reserved;
+    double eps;
+    double cell;
+} icpflow_cluster_params_t;
+int icpflow_cluster_default_params(icpflow_cluster_params_t *params);
+size_t icpflow_cluster_pcd_workspace_bytes(int n_dst, int n_src, const icpflow_cluster_params_t *params);
+int icpflow_cluster_pcd(const float *d_dst, int n_dst, const float *d_src, int n_src, int stride, const uint8_t *d_mask_dst,
+                        const uint8_t *d_mask_src, const icpflow_cluster_params_t *params, float *d_labels_dst,
+                        float *d_labels_src, int32_t *d_info, void *d_ws, size_t ws_bytes, icpflow_stream_t stream);
+
+/* icpflow_track_frame from POINTS: icpflow_cluster_pcd of the stack (dst first; main.py:184-215 clusters, then tracks)
+ * followed by icpflow_track_frame on the labels it leaves in d_labels_src [n_src] / d_labels_dst [n_dst] (float32, the
+ * caller's: the verbose loop, main.py:236-259, reads them).  d_points_* float32 [n,3]; d_mask_* uint8 [n] or NULL.  Every
+ * other argument, the results and the scratch protocol (a refusal with *scratch_needed) are icpflow_track_frame's; the
+ * scratch holds the clustering's workspace in front of the frame's. */
+int icpflow_track_frame_points(const float *d_points_src, const uint8_t *d_mask_src, int n_src, const float *d_points_dst,
+                               const uint8_t *d_mask_dst, int n_dst, const icpflow_cluster_params_t *cluster,
+                               float *d_labels_src, float *d_labels_dst, const icpflow_registration_t *reg,
+                               const icpflow_frame_params_t *par, float *d_rows, float *d_T, int32_t *h_pairs,
+                               const float *d_flow_points, const float *d_pose, float *d_flow, void *d_scratch,
+                               size_t scratch_bytes, size_t *scratch_needed, icpflow_stream_t stream,
+                               const icpflow_options_t *opt);
 
 /* ---------------------------------------------------------------------------
  * 8(f)  ego motion of a LiDAR sequence that comes without poses: scan-to-map odometry resident on the GPU.
