@@ -3,10 +3,24 @@
 // sums per segment).  fp64 with numpy's operation order; the files that include this are compiled with -ffp-contract=off
 // (build.py: CFLAGS), so the squares, the two additions, the square root and the division are the separately rounded
 // operations numpy performs, the square root correctly rounded and the division IEEE.
+// crop_keep is the row test of the two kernels that walk a whole sample: seq_metrics_kernel and class_table_kernel
+// (classeval.hip: counts and sums per class, speed bucket and error split).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace icpflow {
+
+struct Crop {
+    int mode;                // ICPFLOW_SEQ_CROP_*
+    double rx, ry, zmin;
+};
+
+// crop_data, utils_eval.py:33-38 (a NaN coordinate fails every comparison there and here); mode 0 / 1 / 2 are
+// ICPFLOW_SEQ_CROP_NONE / _XY / _XYZ
+__device__ __forceinline__ bool crop_keep(const Crop &crop, double x, double y, double z)
+{
+    return crop.mode == 0 || (fabs(x) < crop.rx && fabs(y) < crop.ry && (crop.mode == 1 || z > crop.zmin));
+}
 
 struct RowError {
     double e, r;             // end point error, relative error

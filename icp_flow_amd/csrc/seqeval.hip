@@ -154,10 +154,7 @@ __global__ __launch_bounds__(kThreads) void seq_argo_sample_kernel(const P *__re
 }
 
 // ---- the table ---------------------------------------------------------------------------------------------------
-struct Crop {
-    int mode;
-    double rx, ry, zmin;
-};
+using icpflow::Crop;
 
 __global__ __launch_bounds__(kThreads) void seq_metrics_kernel(const double *__restrict__ pts, const int32_t *__restrict__ tim,
                                                                const int32_t *__restrict__ sd, const int32_t *__restrict__ fb,
@@ -188,8 +185,8 @@ __global__ __launch_bounds__(kThreads) void seq_metrics_kernel(const double *__r
         if (row) {
             t = tim[i];
             const double x = pts[3 * i + 0], y = pts[3 * i + 1], z = pts[3 * i + 2];
-            // crop_data, utils_eval.py:33-38 (a NaN coordinate fails every comparison there and here)
-            keep = crop.mode == ICPFLOW_SEQ_CROP_NONE || (fabs(x) < crop.rx && fabs(y) < crop.ry && (crop.mode == ICPFLOW_SEQ_CROP_XY || z > crop.zmin));
+            // crop_data, utils_eval.py:33-38 (rowerr.hpp)
+            keep = icpflow::crop_keep(crop, x, y, z);
             // compute_epe_test, utils_eval.py:163-168 (rowerr.hpp)
             q = icpflow::row_error(gt[3 * i + 0], gt[3 * i + 1], gt[3 * i + 2], pred[3 * i + 0], pred[3 * i + 1], pred[3 * i + 2]);
             s = sd[i], f = fb[i];

@@ -48,6 +48,13 @@ on the device (`load_argo_sample`, icpflow_seq_argo_sample).  main.sh:38's range
     python -m icp_flow_amd.frame_pairs DIR --protocol reference --dataset argo --range-x 10000 --range-y 10000
                                            --range-z -10000 --ground-slack 0 --cluster hdbscan --speed 1.67
 
+`--class-table meta|fine` (with `--dataset argo`) prints, after the reference's table, one line per meta category (fine: and per
+category) and speed bucket -- n, EPE, mean speed, the shares of the error splits -- and the three-way EPE, from one more pass
+(icpflow_seq_class_table) and one more small read-back; `--save-flows` writes every sequence's flow and poses next to its
+split (`flow_file`: <split>_icp_flow[_ego], main.py:265-284), `--save-metrics FILE` the reference's closing file
+(main.py:298-312).  Under more than one process the files are dealt round-robin, every rank keeps one record per file, and
+one all_gather and a replay in file order (`merge_sequence_records`) give every rank the single process's table bit for bit.
+
 `--if-verbose` is the reference's verbose loop (utils_debug.debug_frame, utils_flow.flow_evaluation): per frame pair three
 lines (overall, static, dynamic) and the per-segment evaluation, from one more pass over what is resident
 (icpflow_seq_segment_table) and a read-back of two small tables.
@@ -945,8 +952,92 @@ def _argo_inputs(args, path, device, ground, pose_sources):
     return data, [fp], rows
 
 
-def run_sequences(args, paths, device, in_flight=1, dataset="pca"):
-    """Evaluate sequence files by the reference's protocol (main.py:173-296) on one GPU.  Per file: the sample
+SPLITS = ("train", "val", "test")
+
+
+def flow_file(path, estimated_poses=False):
+    """Where a sequence's flow is saved, --if_save of the reference (main.py:265-280) by `_pose_file`'s idea instead of its
+    substring replacement: the LAST directory component that is a split (train / val / test) or starts with one plus "_"
+    (the Argoverse tree's val_zero_flow) gets "_icp_flow" (estimated ego poses) or "_icp_flow_ego" (ground-truth poses)
+    after the split's name: .../val/x.npz -> .../val_icp_flow_ego/x.npz, .../val_zero_flow/log/x.npz ->
+    .../val_icp_flow_ego_zero_flow/log/x.npz.  No such component: ValueError."""
+    parts = os.path.normpath(path).split(os.sep)
+    tag = "_icp_flow" if estimated_poses else "_icp_flow_ego"
+    for k in range(len(parts) - 2, -1, -1):
+        for split in SPLITS:
+            if parts[k] == split or parts[k].startswith(split + "_"):
+                return os.sep.join(parts[:k] + [split + tag + parts[k][len(split):]] + parts[k + 1:])
+    raise ValueError(f"{path}: no split directory (train / val / test, or one of them plus '_...') to put the saved flow next to")
+
+
+def save_sequence_flow(path, flow_seq, fps, F):
+    """np.savez_compressed to flow_file(path), the reference's keys (main.py:281-284): scene_flow float64 [m,3] (the float32
+    flows widened; zeros for frame 0; the rows of the sample as loaded), ego_motion float64 [F,4,4] (the poses the frame pairs
+    were registered with; identity for frame 0).  -> the file written"""
+    poses = np.stack([np.eye(4)] * F)
+    for fp in fps:
+        poses[fp.gap] = fp.pose_exact
+    estimated = any(fp.pose_source in ("pose_file", "ego_motion", "estimate") for fp in fps)
+    out = flow_file(path, estimated)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    np.savez_compressed(out, scene_flow=flow_seq.to(torch.float64).cpu().numpy(), ego_motion=poses)
+    return out
+
+
+RECORD_HEAD = 6     # file index, kept0, frame pairs, wall time, evaluation time, save time (the three in microseconds)
+
+
+def sequence_record(index, F, table, kept0, n_pairs, us, classes=None):
+    """One file's numbers as int64 words: RECORD_HEAD words, the F * 36 words of sequence_table (the sums of e as their bits),
+    then the class table's words when there is one.  `us`: (wall, evaluation, save) in microseconds."""
+    head = np.array([index, kept0, n_pairs] + [int(round(u)) for u in us], dtype=np.int64)
+    parts = [head, np.ascontiguousarray(table, dtype=np.int64).reshape(F * 36)]
+    if classes is not None:
+        parts.append(classes.words())
+    return np.concatenate(parts)
+
+
+def merge_sequence_records(args, records, total, rank=0, world=1, group=None, device=None, class_shape=None):
+    """The end of a sharded run_sequences, with no GPU work of its own: ONE all_gather of every rank's records (padded to
+    the largest share with rows whose file index is -1; on the device under NCCL, on the host under gloo, chosen as
+    run_stream chooses), then -- on every rank -- update_meters and ClassTable.add replayed IN FILE ORDER, which is what a
+    single process does: meters and class table are bit-identical to its, whatever the world size and however uneven the
+    shares.  records: this rank's sequence_record()s; total: files in all; class_shape: (G, S, E) when the records carry a
+    class table.  -> (metrics, ClassTable or None, rows [total, RECORD_HEAD] of the records' heads in file order)"""
+    F = int(args.num_frames)
+    words = RECORD_HEAD + F * 36 + (class_shape[0] * class_shape[1] * (class_shape[2] + 2) if class_shape else 0)
+    share = -(-total // world) if total else 0
+    local = np.full((share, words), -1, dtype=np.int64)
+    if len(records) > share or any(len(r) != words for r in records):
+        raise ValueError(f"rank {rank}: {len(records)} records for a share of {share}, or a record that is not {words} words")
+    for k, r in enumerate(records):
+        local[k] = r
+    if world > 1:
+        import torch.distributed as dist
+        on_gpu = dist.get_backend(group) == "nccl"
+        mine = torch.from_numpy(local).to(device if on_gpu else "cpu")
+        parts = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(parts, mine, group=group)
+        every = torch.cat(parts).cpu().numpy()
+    else:
+        every = local
+    every = every[every[:, 0] >= 0]
+    every = every[np.argsort(every[:, 0], kind="stable")]
+    if not np.array_equal(every[:, 0], np.arange(total)):
+        raise RuntimeError(f"the gathered records do not cover files 0 .. {total - 1} once each: {every[:, 0].tolist()}")
+    metrics = utils_eval.new_metric_table(F)
+    classes = utils_eval.ClassTable.zeros(*class_shape) if class_shape else None
+    for row in every:
+        table = np.ascontiguousarray(row[RECORD_HEAD:RECORD_HEAD + F * 36]).reshape(F, 6, 6)
+        esum = np.ascontiguousarray(table[:, :, 1]).view(np.float64)
+        utils_eval.update_meters(args, metrics, table, esum, int(row[1]))
+        if classes is not None:
+            classes.add(utils_eval.ClassTable.from_words(row[RECORD_HEAD + F * 36:], *class_shape, kept0=int(row[1])))
+    return metrics, classes, every[:, :RECORD_HEAD]
+
+
+def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world=1, group=None):
+    """Evaluate sequence files by the reference's protocol (main.py:173-296).  Per file: the sample
     (`load_sequence_sample`) and its num_frames - 1 frame pairs (`load_sequence`), registered by the existing path
     (`register_frame_pair`, or `register_in_flight` with in_flight > 1); the flows are put into the sequence's flow ON THE
     DEVICE (zeros for frame 0, main.py:217-260) and `utils_eval.calculate_metrics` takes it from there: one launch pair, one
@@ -959,18 +1050,36 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca"):
     them), returned under `segments` and timed on their own as ms_report_per_sequence; the other two times keep their meaning.
     dataset="argo" (main.py:156-159, `--dataset argo`): every file is one Argoverse 2 sample of two frames (`load_argo_sample`:
     the sample and its labels built on the device), its one frame pair registered as above; no ground removal, whatever
-    args.ground says (dataset_argo.py:140)."""
+    args.ground says (dataset_argo.py:140).
+    args.class_table (absent = off; dataset="argo" only): utils_eval.class_table per file, one more pass and one more small
+    read-back inside ms_eval_per_sequence, accumulated in file order -> `class_table` (a utils_eval.ClassTable) and `threeway`.
+    args.save_flows (absent = False): after a sequence's evaluation its flow and poses are written to `flow_file(path)`
+    (`save_sequence_flow`) -- outside the two times above, reported as ms_save_per_sequence.
+    rank / world / group: the files are dealt round-robin (`shard_round_robin`), every rank keeps one record per file and
+    `merge_sequence_records` gathers them once at the end and replays them in file order: `metrics`, `class_table`, the
+    counts and the times are those of the whole run on every rank, bit for bit the single process's; ground and pose_sources
+    are this rank's, every rank saves its own files, and if_verbose is refused (merging the reports is not built)."""
     device = torch.device(device)
     F = int(args.num_frames)
     if dataset not in ("pca", "argo"):
         raise ValueError(f"dataset must be 'pca' or 'argo' (got {dataset!r})")
     if dataset == "argo" and F != 2:
         raise ValueError(f"an Argoverse 2 sample has two frames (num_frames {F})")
-    metrics = utils_eval.new_metric_table(F)
-    times, eval_times, n_pairs, ground, pose_sources = [], [], 0, {}, {}
+    with_classes = bool(getattr(args, "class_table", None))
+    if with_classes and dataset != "argo":
+        raise ValueError("class_table goes with dataset='argo' (the other files' sem_labels have no names in the reference)")
+    saving = bool(getattr(args, "save_flows", False))
     verbose = bool(getattr(args, "if_verbose", False))
-    segments, report_times = [], []
-    for path in paths:
+    if world > 1 and verbose:
+        raise ValueError("if_verbose under more than one rank: merging the reports is not built")
+    paths = list(paths)
+    mine = shard_round_robin(list(enumerate(paths)), rank, world)        # (file index, path)
+    class_shape = (utils_eval.ARGO_CLASS_ROWS, len(utils_eval.ARGO_SPEED_EDGES) + 1, len(utils_eval.ARGO_ERROR_EDGES) + 1) if with_classes else None
+    metrics = utils_eval.new_metric_table(F)
+    classes = utils_eval.ClassTable.zeros(*class_shape) if with_classes else None
+    times, eval_times, save_times, n_pairs, ground, pose_sources = [], [], [], 0, {}, {}
+    segments, report_times, records = [], [], []
+    for index, path in mine:
         if dataset == "argo":
             data, fps, rows = _argo_inputs(args, path, device, ground, pose_sources)
         else:
@@ -982,26 +1091,49 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca"):
             done = register_in_flight(args, fps, device, in_flight)
         else:
             done = ((k, fp, register_frame_pair(args, fp, device)) for k, fp in enumerate(fps))
-        kept = []
+        kept, pairs_here = [], 0
         for _, fp, out in done:
             flow_seq.index_copy_(0, rows[fp.gap], out["flow"].to(torch.float32))
-            n_pairs += 1
+            pairs_here += 1
             if verbose:
                 kept.append((fp, out))
+        n_pairs += pairs_here
         torch.cuda.synchronize(device)
         t1 = time.perf_counter()
-        utils_eval.calculate_metrics(args, data, flow_seq, metrics)     # (its read-back of the table is the synchronisation)
+        if world == 1:
+            utils_eval.calculate_metrics(args, data, flow_seq, metrics)     # (its read-back of the table is the synchronisation)
+        else:                                                               # the same table, kept for the replay in file order
+            table, esum, kept0 = utils_eval.checked_sequence_table(args, data, flow_seq)
+        one = utils_eval.class_table(args, data, flow_seq) if with_classes else None
+        if world == 1 and with_classes:
+            classes.add(one)
         t2 = time.perf_counter()
         times.append((t2 - t0) * 1e3)
         eval_times.append((t2 - t1) * 1e3)
         if verbose:
             segments.extend(_sequence_reports(args, path, data, rows, kept))
             report_times.append((time.perf_counter() - t2) * 1e3)
+        if saving:
+            t3 = time.perf_counter()
+            save_sequence_flow(path, flow_seq, fps, F)
+            save_times.append((time.perf_counter() - t3) * 1e3)
+        if world > 1:
+            records.append(sequence_record(index, F, table, kept0, pairs_here,
+                                           (times[-1] * 1e3, eval_times[-1] * 1e3, save_times[-1] * 1e3 if saving else 0.0), one))
+    if world > 1:
+        metrics, classes, heads = merge_sequence_records(args, records, len(paths), rank, world, group, device, class_shape)
+        n_pairs = int(heads[:, 2].sum())
+        times, eval_times = (heads[:, 3] * 1e-3).tolist(), (heads[:, 4] * 1e-3).tolist()
+        save_times = (heads[:, 5] * 1e-3).tolist() if saving else []
     res = dict(metrics=metrics, sequences=len(times), frame_pairs=n_pairs, ms_per_sequence=sum(times) / max(len(times), 1),
                ms_eval_per_sequence=sum(eval_times) / max(len(eval_times), 1),
                ground="+".join(sorted(ground)) if ground else "none", pose_sources=pose_sources)
     if verbose:
         res.update(segments=segments, ms_report_per_sequence=sum(report_times) / max(len(report_times), 1))
+    if saving:
+        res.update(ms_save_per_sequence=sum(save_times) / max(len(save_times), 1))
+    if with_classes:
+        res.update(class_table=classes, threeway=classes.threeway(utils_eval.ARGO_META_GROUPS["BACKGROUND"]))
     return res
 
 
@@ -1120,7 +1252,18 @@ def main(argv=None):
     ap.add_argument("--report", metavar="FILE", default=None,
                     help="--protocol reference: write a JSON list of the segments with EPE above --report-epe, worst first")
     ap.add_argument("--report-epe", type=float, default=2.0, help="threshold of --report in metres (utils_flow.py:112)")
+    ap.add_argument("--class-table", choices=("meta", "fine"), default=None,
+                    help="--protocol reference --dataset argo: per meta category (fine: and per category) and speed bucket n, EPE, "
+                         "speed and the error splits, and the three-way EPE, after the reference's table")
+    ap.add_argument("--save-flows", action="store_true",
+                    help="--protocol reference: write every sequence's flow and poses next to its split (<split>_icp_flow[_ego], main.py:265-284)")
+    ap.add_argument("--save-metrics", metavar="FILE", default=None,
+                    help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
     ns = ap.parse_args(argv)
+    if ns.class_table and not (ns.protocol == "reference" and ns.dataset == "argo"):
+        raise SystemExit("--class-table goes with --protocol reference --dataset argo (the category names are Argoverse 2's)")
+    if (ns.save_flows or ns.save_metrics) and ns.protocol != "reference":
+        raise SystemExit("--save-flows and --save-metrics go with --protocol reference")
     if ns.dataset == "argo":
         if ns.num_frames not in (None, 2):
             raise SystemExit(f"--dataset argo: an Argoverse 2 sample has two frames (--num-frames {ns.num_frames})")
@@ -1144,24 +1287,41 @@ def main(argv=None):
     if ns.ego_deskew or ns.ego_fixed_threshold:
         args.ego_motion = dict(deskew=ns.ego_deskew, fixed_threshold=ns.ego_fixed_threshold)
     if ns.protocol == "reference":
-        if world > 1:
-            raise SystemExit("--protocol reference is single-process (the table is not reduced across ranks)")
+        if world > 1 and (ns.if_verbose or ns.report):
+            raise SystemExit("--if-verbose / --report under more than one rank: merging the reports is not built")
         if args.range_x is None or args.range_y is None:
             args.range_x, args.range_y = 32.0, 32.0                                    # main.py:69-72
         args.num_frames, args.range_z, args.ground_slack, args.eval_ground = num_frames, ns.range_z, ns.ground_slack, ns.eval_ground
         args.ground = ns.ground
         if ns.if_verbose or ns.report:
             args.if_verbose = True
+        if ns.class_table:
+            args.class_table = ns.class_table
+        if ns.save_flows:
+            args.save_flows = True
+        shard = dict(rank=rank, world=world) if world > 1 else {}
         if ns.dataset == "argo":
-            res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_argo(p)], device, in_flight=ns.in_flight, dataset="argo")
+            res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_argo(p)], device, in_flight=ns.in_flight, dataset="argo", **shard)
         else:
-            res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_sequence(p)], device, in_flight=ns.in_flight)
-        reports = res.pop("segments", None)
-        if ns.report:
-            with open(ns.report, "w") as f:
-                json.dump(worst_segments(reports, ns.report_epe), f, indent=1)
-        print(utils_eval.format_metric_table(res.pop("metrics"), args.num_frames))
-        print(json.dumps(res))
+            res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_sequence(p)], device, in_flight=ns.in_flight, **shard)
+        if rank == 0:
+            reports = res.pop("segments", None)
+            if ns.report:
+                with open(ns.report, "w") as f:
+                    json.dump(worst_segments(reports, ns.report_epe), f, indent=1)
+            metrics = res.pop("metrics")
+            print(utils_eval.format_metric_table(metrics, args.num_frames))
+            if ns.save_metrics:
+                utils_eval.save_metrics_file(ns.save_metrics, metrics, args.num_frames)
+            if ns.class_table:
+                table = res.pop("class_table")
+                print(utils_eval.format_class_table(table, fine=ns.class_table == "fine"))
+                shown = table if ns.class_table == "fine" else table.meta(utils_eval.ARGO_META_GROUPS)
+                res["class_table"] = dict(rows=list(shown.names or utils_eval.ARGO_ROW_NAMES), counts=shown.counts.tolist(),
+                                          esum=shown.esum.tolist(), ssum=shown.ssum.tolist())
+            print(json.dumps(res))
+        if world > 1:
+            dist.destroy_process_group()
         return
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:

@@ -3,7 +3,12 @@ host like the reference's.  Pinned by tests/golden/g9_ep
 
 The evaluation of a whole sequence -- crop_data / calculate_metrics, utils_eval.py:24-63 and 185-368 -- runs on the GPU
 (icpflow_seq_metrics, csrc/seqeval.hip): one pass over the points, one table of F x 6 x 6 numbers back, from which the
-reference's meters are updated row by row.  Pinned by tests/golden/g13_seqeval_*.npz."""
+reference's meters are updated row by row.  Pinned by tests/golden/g13_seqeval_*.npz.
+
+Per class, per speed bucket and per error split -- the Argoverse 2 way of reporting, for which the reference carries the
+tables (dataset_argo.py:145-217) and uses six names of them: `class_table` (icpflow_seq_class_table, csrc/classeval.hip), one
+more pass over the rows and one small table back; `ClassTable` adds, groups and prints it, `ClassTable.threeway` is the
+three-way EPE.  The names and groups below are pinned by tests/golden/g16_argo_classes.json."""
 import numpy as np
 
 METRIC_NAMES = ("epe", "accs", "accr", "outlier", "Routlier")
@@ -138,6 +143,15 @@ def _binary_labels(labels, device):
     return utils_loading.to_device(np.where(a == 0, 0, np.where(a == 1, 1, 2)).astype(np.int32), torch.int32, device)
 
 
+def _crop_arguments(args, raw):
+    """calculate_metrics' crop as the kernels take it -> (ICPFLOW_SEQ_CROP_*, range_x, range_y, z_min)"""
+    from . import _lib
+    if args.eval_ground:                 # utils_eval.py:186-189: no crop at all
+        return _lib.SEQ_CROP_NONE, 0.0, 0.0, 0.0
+    return (_lib.SEQ_CROP_XYZ, _threshold_for(args.range_x, raw), _threshold_for(args.range_y, raw),
+            _threshold_for(args.range_z + args.ground_slack, raw))
+
+
 def sequence_table(args, data, flow_seq):
     """icpflow_seq_metrics on one sequence -> (table int64 [F,6,6] numpy, sum of e float64 [F,6] numpy, kept points of
     frame 0, rows with a time index outside [0,F)).  Inputs may live on either side; with device tensors the only
@@ -157,12 +171,7 @@ def sequence_table(args, data, flow_seq):
     for name, t in (("time_indice", tim), ("sd_labels", sd), ("fb_labels", fb), ("scene_flow", gt), ("flow_seq", pred)):
         if t.shape[0] != m:
             raise ValueError(f"{name}: {t.shape[0]} rows for {m} points")
-    if args.eval_ground:                 # utils_eval.py:186-189: no crop at all
-        crop, rx, ry, zmin = _lib.SEQ_CROP_NONE, 0.0, 0.0, 0.0
-    else:
-        crop = _lib.SEQ_CROP_XYZ
-        rx, ry = _threshold_for(args.range_x, raw), _threshold_for(args.range_y, raw)
-        zmin = _threshold_for(args.range_z + args.ground_slack, raw)
+    crop, rx, ry, zmin = _crop_arguments(args, raw)
     out = torch.empty(F * 36 + 2, dtype=torch.int64, device=device)
     with torch.cuda.device(device):
         need = int(_lib._L.icpflow_seq_metrics_workspace_bytes(m, F))
@@ -203,13 +212,20 @@ def calculate_metrics(args, data, flow_seq, metrics_per_frame):
       * the weights keep the reference's types (len() is an int, sum(mask) a numpy integer): numpy's promotion of a float32 fraction
         times the weight follows from them.
     Not kept: the reference prints three lines per gap; pass args.if_verbose to get them."""
+    table, esum, kept0 = checked_sequence_table(args, data, flow_seq)
+    return update_meters(args, metrics_per_frame, table, esum, kept0)
+
+
+def checked_sequence_table(args, data, flow_seq):
+    """The device half of calculate_metrics with its refusals: sequence_table, no time index outside [0, F), every frame
+    present after the crop (utils_eval.py:197-198).  -> (table, esum, kept0) for update_meters"""
     F = int(args.num_frames)
     table, esum, kept0, outside = sequence_table(args, data, flow_seq)
     if outside:
         raise ValueError(f"{outside} points have a time index outside [0, {F})")
     present = int(kept0 > 0) + sum(int(table[j, 0, 0] > 0) for j in range(1, F))
     assert present == args.num_frames, f"{present} frames have points after the crop, args.num_frames is {args.num_frames}"   # utils_eval.py:197-198
-    return update_meters(args, metrics_per_frame, table, esum, kept0)
+    return table, esum, kept0
 
 
 def update_meters(args, metrics_per_frame, table, esum, kept0):
@@ -242,3 +258,196 @@ def _update_meters(args, metrics_per_frame, table, esum, kept0):
             w = 1 if per_scene else total if c == 0 else weight(n)
             metrics_per_frame[f"{metric}_{row:d}"].update(*vals, w)
     return metrics_per_frame
+
+
+# ---- per class, per speed bucket, per error split ---------------------------------------------------------------------
+# The public Argoverse 2 taxonomy in alphabetical order behind the name the reference's id table starts with (its id -1),
+# by the POSITION the reference compares a file's pc1_classes with (dataset_argo.py:23-25, 69-70: position = id + 1, so a file
+# value of 5 is BOLLARD to it).  A file value of -1 has no position: the row "UNLABELLED".
+ARGO_CATEGORY_NAMES = (
+    "BACKGROUND", "ANIMAL", "ARTICULATED_BUS", "BICYCLE", "BICYCLIST", "BOLLARD", "BOX_TRUCK", "BUS", "CONSTRUCTION_BARREL",
+    "CONSTRUCTION_CONE", "DOG", "LARGE_VEHICLE", "MESSAGE_BOARD_TRAILER", "MOBILE_PEDESTRIAN_CROSSING_SIGN", "MOTORCYCLE",
+    "MOTORCYCLIST", "OFFICIAL_SIGNALER", "PEDESTRIAN", "RAILED_VEHICLE", "REGULAR_VEHICLE", "SCHOOL_BUS", "SIGN", "STOP_SIGN",
+    "STROLLER", "TRAFFIC_LIGHT_TRAILER", "TRUCK", "TRUCK_CAB", "VEHICULAR_TRAILER", "WHEELCHAIR", "WHEELED_DEVICE", "WHEELED_RIDER")
+ARGO_CLASS_LO, ARGO_CLASS_ROWS = -1, 33             # rows: file values -1 .. 30, then everything else
+ARGO_ROW_NAMES = ("UNLABELLED",) + ARGO_CATEGORY_NAMES + ("OTHER",)
+# table rows (file value + 1) per meta category.  BACKGROUND is exactly what the reference's fb label makes background: file
+# values -1, 5, 8, 9, 13, 21, 22.  File value 0 ("BACKGROUND" by position), ANIMAL, DOG and the last row are foreground in
+# no named group.
+ARGO_META_GROUPS = {"BACKGROUND": (0, 6, 9, 10, 14, 22, 23),
+                    "PEDESTRIAN": (17, 18, 24, 29),
+                    "SMALL_MOVERS": (4, 5, 15, 16, 30, 31),
+                    "LARGE_MOVERS": (3, 7, 8, 12, 13, 19, 20, 21, 25, 26, 27, 28)}
+ARGO_SPEED_EDGES = (0.5 * 0.1, 2.0 * 0.1)           # metres per frame at 10 Hz: 0.5 and 2 m/s
+ARGO_ERROR_EDGES = (0.05, 0.1)                      # metres
+
+
+class ClassTable:
+    """icpflow_seq_class_table's numbers on the host: counts int64 [G,S,E] (class row, speed bucket, error split), esum and
+    ssum float64 [G,S] (sums of e and of |gt|), kept0 (kept rows of frame 0), names (one per row, or None)."""
+
+    def __init__(self, counts, esum, ssum, kept0=0, names=None):
+        self.counts = np.array(counts, dtype=np.int64)
+        self.esum, self.ssum = np.array(esum, dtype=np.float64), np.array(ssum, dtype=np.float64)
+        self.kept0 = int(kept0)
+        self.names = tuple(names) if names is not None else None
+        G, S, _ = self.counts.shape
+        assert self.esum.shape == (G, S) and self.ssum.shape == (G, S)
+
+    @classmethod
+    def zeros(cls, G, S, E):
+        return cls(np.zeros((G, S, E), np.int64), np.zeros((G, S)), np.zeros((G, S)))
+
+    @classmethod
+    def from_words(cls, words, G, S, E, kept0=0):
+        """the kernel's int64 [G][S][E + 2] -> ClassTable"""
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.int64).reshape(G, S, E + 2))
+        return cls(w[:, :, :E], np.ascontiguousarray(w[:, :, E]).view(np.float64), np.ascontiguousarray(w[:, :, E + 1]).view(np.float64), kept0)
+
+    def words(self):
+        """-> int64 [G * S * (E + 2)], the kernel's layout (the sums as their bits)"""
+        G, S, E = self.counts.shape
+        w = np.empty((G, S, E + 2), np.int64)
+        w[:, :, :E], w[:, :, E], w[:, :, E + 1] = self.counts, self.esum.view(np.int64), self.ssum.view(np.int64)
+        return w.reshape(-1)
+
+    def add(self, other):
+        """Accumulate another sample's table: integers add exactly, the sums add in call order.  -> self"""
+        if other.counts.shape != self.counts.shape:
+            raise ValueError(f"class tables of {other.counts.shape} and {self.counts.shape} do not add")
+        self.counts = self.counts + other.counts
+        self.esum, self.ssum = self.esum + other.esum, self.ssum + other.ssum
+        self.kept0 += other.kept0
+        return self
+
+    def _rows_sum(self, rows):
+        """the rows added in ascending row order -> (counts [S,E], esum [S], ssum [S])"""
+        _, S, E = self.counts.shape
+        counts, esum, ssum = np.zeros((S, E), np.int64), np.zeros(S), np.zeros(S)
+        for r in sorted(rows):
+            counts, esum, ssum = counts + self.counts[r], esum + self.esum[r], ssum + self.ssum[r]
+        return counts, esum, ssum
+
+    def meta(self, groups):
+        """Rows summed per named group ({name: rows}) in ascending row order; the rows in no group form OTHER, the last
+        row.  -> ClassTable of len(groups) + 1 rows with `names`"""
+        G = self.counts.shape[0]
+        used = [r for rows in groups.values() for r in rows]
+        if len(set(used)) != len(used) or any(not 0 <= r < G for r in used):
+            raise ValueError("meta: every row belongs to at most one group and lies in the table")
+        parts = [self._rows_sum(rows) for rows in groups.values()] + [self._rows_sum(set(range(G)) - set(used))]
+        return ClassTable(np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts]), np.stack([p[2] for p in parts]),
+                          self.kept0, tuple(groups) + ("OTHER",))
+
+    def threeway(self, background=ARGO_META_GROUPS["BACKGROUND"]):
+        """The three-way EPE over whatever was accumulated: FD = foreground rows (every row not in `background`) in a speed
+        bucket >= 1, FS = foreground rows in bucket 0, BS = background rows in bucket 0; each (sum of e) / (rows), rows in
+        ascending order, then buckets.  An empty component is NaN, and so is the mean then.  Dynamic background rows are in
+        no component (the reference's six classes have none for them): their count is `n_BD`.
+        -> dict(FD, FS, BS, mean, n_FD, n_FS, n_BS, n_BD)"""
+        G = self.counts.shape[0]
+        bg = sorted(set(background))
+        fg = [r for r in range(G) if r not in set(bg)]
+        n = self.counts.sum(axis=2)
+
+        def part(rows, buckets):
+            total, rows_n = 0.0, 0
+            for r in rows:
+                for s in buckets:
+                    total, rows_n = total + self.esum[r, s], rows_n + int(n[r, s])
+            return (total / rows_n if rows_n else float("nan")), rows_n
+
+        moving = range(1, self.counts.shape[1])
+        (fd, n_fd), (fs, n_fs), (bs, n_bs) = part(fg, moving), part(fg, (0,)), part(bg, (0,))
+        return dict(FD=float(fd), FS=float(fs), BS=float(bs), mean=float((fd + fs + bs) / 3.0), n_FD=n_fd, n_FS=n_fs, n_BS=n_bs,
+                    n_BD=int(n[bg][:, 1:].sum()))
+
+
+def class_table(args, data, flow_seq, classes=None, speed_edges=ARGO_SPEED_EDGES, error_edges=ARGO_ERROR_EDGES, class_lo=ARGO_CLASS_LO,
+                rows=ARGO_CLASS_ROWS):
+    """icpflow_seq_class_table on one sample -> ClassTable of `rows` class rows (values class_lo .. class_lo + rows - 2 of
+    `classes`, default data["classes"], one per point; everything else in the last row), len(speed_edges) + 1 speed buckets
+    (|scene_flow| in metres per frame, lower edge inclusive) and len(error_edges) + 1 error splits, over the rows
+    calculate_metrics counts: those that pass args' crop with a time index in [1, num_frames).  Inputs as for
+    sequence_table; the one device -> host copy is the table.  There is no CPU path."""
+    import ctypes
+    import torch
+    from . import _lib, utils_loading
+    device = utils_loading._device_for(flow_seq, data["raw_points"], data["scene_flow"])
+    F = int(args.num_frames)
+    raw = data["raw_points"]
+    pts = utils_loading.to_device(raw, torch.float64, device)[:, 0:3].contiguous()
+    m = pts.shape[0]
+    tim = utils_loading.to_device(data["time_indice"], torch.int32, device)
+    cls = utils_loading.to_device(data["classes"] if classes is None else classes, torch.float64, device)
+    gt = utils_loading.to_device(data["scene_flow"], torch.float64, device)[:, 0:3].contiguous()
+    pred = utils_loading.to_device(flow_seq, torch.float32, device)[:, 0:3].contiguous()
+    for name, t in (("time_indice", tim), ("classes", cls), ("scene_flow", gt), ("flow_seq", pred)):
+        if t.shape[0] != m or (name == "classes" and t.dim() != 1):
+            raise ValueError(f"{name}: {tuple(t.shape)} for {m} points")
+    crop, rx, ry, zmin = _crop_arguments(args, raw)
+    G = int(rows)
+    speed, error = np.ascontiguousarray(speed_edges, dtype=np.float64).reshape(-1), np.ascontiguousarray(error_edges, dtype=np.float64).reshape(-1)
+    S, E = len(speed) + 1, len(error) + 1
+    edge_ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if len(a) else None   # noqa: E731
+    words = G * S * (E + 2)
+    out = torch.empty(max(words, 0) + 2, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        need = int(_lib._L.icpflow_seq_class_table_workspace_bytes(m, G, S, E))
+        ws = _lib.workspace(device, need)
+        _lib.call("icpflow_seq_class_table", _lib.ptr(pts), _lib.ptr(tim), _lib.ptr(cls), _lib.ptr(gt), _lib.ptr(pred), m, F, crop, rx, ry,
+                  zmin, float(class_lo), G, edge_ptr(speed), S, edge_ptr(error), E, _lib.ptr(out),
+                  ctypes.c_void_p(out.data_ptr() + words * 8), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    host = out.cpu().numpy()             # the one read-back
+    if int(host[words + 1]):
+        raise ValueError(f"{int(host[words + 1])} points have a time index outside [0, {F})")
+    return ClassTable.from_words(host[:words], G, S, E, kept0=int(host[words]))
+
+
+def format_class_table(table, names=ARGO_ROW_NAMES, groups=ARGO_META_GROUPS, rate_hz=10.0, fine=False, speed_edges=ARGO_SPEED_EDGES,
+                       error_edges=ARGO_ERROR_EDGES):
+    """One line per non-empty (meta category, speed bucket): n, mean EPE, mean speed in m/s (|gt| per frame times rate_hz)
+    and the shares of the error splits; with `fine`, the non-empty rows of the table itself follow.  The last line is the
+    three-way EPE with the number of dynamic background rows, which are in none of its components."""
+    def bounds(edges, scale, unit):
+        e = [0.0] + [x * scale for x in edges] + [float("inf")]
+        return [f"[{a:g}, {b:g}) {unit}" for a, b in zip(e, e[1:])]
+
+    buckets = bounds(speed_edges, rate_hz, "m/s")
+    splits = "/".join(f"e<{x:g}" for x in error_edges) + "/rest"
+
+    def lines(t, row_names):
+        out = []
+        for g, name in enumerate(row_names):
+            for s in range(t.counts.shape[1]):
+                n = int(t.counts[g, s].sum())
+                if n:
+                    shares = " ".join(f"{c / n:.4f}" for c in t.counts[g, s])
+                    out.append(f"{name:>32}, {buckets[s]:>16}, n: {n:8d}, EPE3D: {t.esum[g, s] / n:.6f}, speed: {t.ssum[g, s] / n * rate_hz:.4f} m/s, "
+                               f"{splits}: {shares}")
+        return out
+
+    meta = table.meta(groups)
+    text = ["################# Per class and speed bucket ##########################################"] + lines(meta, meta.names)
+    if fine:
+        text += ["################# Per category ########################################################"] + lines(table, names)
+    tw = table.threeway(groups["BACKGROUND"]) if "BACKGROUND" in groups else table.threeway(())
+    text.append(f"three-way EPE: {tw['mean']:.6f}, FD: {tw['FD']:.6f} (n {tw['n_FD']}), FS: {tw['FS']:.6f} (n {tw['n_FS']}), "
+                f"BS: {tw['BS']:.6f} (n {tw['n_BS']}); dynamic background rows, in no component: {tw['n_BD']}")
+    return "\n".join(text)
+
+
+def save_metrics_file(path, metrics_per_frame, num_frames):
+    """The reference's closing file (main.py:298-312, np.savez): per meter <name> of the table the keys EPE3D<name> -- no
+    underscore, as the reference writes it -- ACC3DS_<name>, ACC3DR_<name>, OUTLIER_<name> and ROUTLIER_<name>, each the
+    meter's `*_data` list as an array of shape [1, n] (what the reference's trailing commas make of the lists).  -> the keys"""
+    prefixes = ("EPE3D", "ACC3DS_", "ACC3DR_", "OUTLIER_", "ROUTLIER_")
+    out = {}
+    for k in range(0, num_frames + 1):
+        for metric in METRIC_CLASSES:
+            name = metric + f"_{k:d}"
+            for prefix, field in zip(prefixes, METRIC_NAMES):
+                out[prefix + name] = np.asarray(getattr(metrics_per_frame[name], field + "_data"), dtype=np.float64).reshape(1, -1)
+    with open(path, "wb") as f:           # (np.savez would append ".npz" to a name without it)
+        np.savez(f, **out)
+    return list(out)

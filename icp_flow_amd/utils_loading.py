@@ -120,7 +120,8 @@ def argo_sample(pc1, pc2, flow_0_1, classes1, valid1, valid2, background=None, d
     np.flatnonzero on the host first) -- as numpy arrays or device tensors -> the sample calculate_metrics reads, a dict of
     device tensors of m = m2 + m1 rows, frame 0 (pc2's rows) first: raw_points (in the points' own dtype: the kernel's
     float64 rows narrowed back, which is exact, so that the evaluation rounds its crop thresholds as numpy does for that
-    dtype), time_indice, sd_labels, fb_labels (int32), scene_flow (float64).  `background`: the class values that are not
+    dtype), time_indice, sd_labels, fb_labels (int32), scene_flow (float64), classes (float64: pc1_classes of frame 1's rows, NaN
+    for frame 0's -- what utils_eval.class_table reads).  `background`: the class values that are not
     foreground besides -1 (default ARGO_BACKGROUND_IDXES).  An index outside [0, n) raises IndexError (numpy's negative
     wrap-around is not reproduced).  There is no CPU path."""
     if device is None:
@@ -171,4 +172,6 @@ def argo_sample(pc1, pc2, flow_0_1, classes1, valid1, valid2, background=None, d
     if n_bad:
         raise IndexError(f"{n_bad} of {m} valid indices lie outside their cloud ([0, {n1}) for pc1, [0, {n2}) for pc2; "
                          "numpy's negative-index wrap-around is not reproduced)")
-    return dict(raw_points=pts.to(p_t), time_indice=tim, sd_labels=sd, fb_labels=fb, scene_flow=out_flow)
+    # the class of every row for utils_eval.class_table: NaN for frame 0, whose rows are never counted (the indices are known good here)
+    classes = torch.cat([torch.full((m2,), float("nan"), dtype=torch.float64, device=device), cls.index_select(0, v1)])
+    return dict(raw_points=pts.to(p_t), time_indice=tim, sd_labels=sd, fb_labels=fb, scene_flow=out_flow, classes=classes)

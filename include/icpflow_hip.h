@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* (icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 214 /* (icpflow_seq_class_table, the per-class and per-speed table of a sample, icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -885,6 +885,31 @@ int icpflow_egomotion_register_frame_stamped(icpflow_ego_t *ego, const float *d_
  *   non-finite values).  No workspace.  n_background > ICPFLOW_ARGO_MAX_BACKGROUND is ICPFLOW_E_LIMIT; a null pointer, a
  *   negative size or an unknown dtype is ICPFLOW_E_ARG before any launch; m = 0 succeeds (*d_bad_rows = 0).  Asynchronous
  *   on `stream`; the results are a function of the arguments alone.
+ *
+ * icpflow_seq_class_table -- what everyone who reports on Argoverse 2 reports, and what the reference carries the tables for
+ *   without using them (dataset_argo.py:145-217: category names, meta categories, speed buckets, end-point-error splits):
+ *   counts and sums per class, speed bucket and error split, in one more pass over the rows of a sample.  d_points,
+ *   d_time_indice, d_gt_flow, d_pred_flow, m, F, crop, range_x, range_y, z_min: as for icpflow_seq_metrics, with the same row
+ *   test (one __device__ function, csrc/rowerr.hpp).  A row counts when it passes the crop and its time index is in [1, F);
+ *   there is no axis for gaps.  d_info int64 [2]: the kept rows of frame 0, and the rows with a time index outside [0, F).
+ *   Per counted row:
+ *       class row     g = v - class_lo when v = d_classes[row] (float64 [m]) is integer-valued and class_lo <= v <= class_lo + G - 2;
+ *                     everything else -- NaN, +-inf, 3.5, a value out of range -- is row G - 1, "other"
+ *       speed bucket  s = the number of h_speed_edges[k], k < S - 1, with |gt| >= edge: S buckets [lo, hi) from S - 1 interior
+ *                     edges in metres per frame; |gt| = sqrt((x x + y y) + z z) in fp64, every operation rounded by itself
+ *       error split   the same count of h_error_edges[k], k < E - 1, with e >= edge; e is icpflow_seq_metrics' per-row e
+ *   (a NaN is >= nothing: bucket / split 0).  The edge arrays live in HOST memory and are read before the call returns; they
+ *   must be finite and strictly ascending; NULL is accepted for a list of no edges (S = 1, E = 1).  class_lo is an integer value.
+ *   d_table int64 [G][S][E + 2]: words 0 .. E-1 the rows per error split, word E the BITS OF the float64 sum of e, word E + 1
+ *   the bits of the float64 sum of |gt|.
+ *   G <= ICPFLOW_CLASS_MAX_ROWS, S and E <= ICPFLOW_CLASS_MAX_BUCKETS and G * S * (E + 2) <= ICPFLOW_CLASS_MAX_WORDS, else
+ *   ICPFLOW_E_LIMIT (a wave keeps its own cells in LDS: four waves x 1024 words x 8 bytes = 32 KB; the Argoverse 2 call needs
+ *   33 x 3 x 5 = 495 words).  A null pointer, a negative size, F < 1, G < 2, S < 1, E < 1, unsorted or non-finite edges are
+ *   ICPFLOW_E_ARG before any launch.  The workspace is the caller's: icpflow_seq_class_table_workspace_bytes(m, G, S, E) bytes
+ *   (0 for arguments the call refuses), 8-byte aligned; nothing in it is read before it is written; fewer bytes are
+ *   ICPFLOW_E_WORKSPACE before anything is written.  m = 0 succeeds with a zero table.  Counts are exact; the two sums of a
+ *   cell are a function of the arguments alone -- fixed reduction order, no floating-point atomics (csrc/classeval.hip).
+ *   Asynchronous on `stream`.
  * ------------------------------------------------------------------------- */
 #define ICPFLOW_SEQ_MAX_FRAMES 16
 #define ICPFLOW_SEQ_OUT_FLOW 0
@@ -909,6 +934,15 @@ int icpflow_seq_argo_sample(const void *d_pc1, int n1, const void *d_pc2, int n2
                             int m2, const int32_t *h_background, int n_background, double sd_threshold, double *d_points,
                             int32_t *d_time_indice, int32_t *d_sd_labels, int32_t *d_fb_labels, double *d_scene_flow,
                             int64_t *d_bad_rows, icpflow_stream_t stream);
+#define ICPFLOW_CLASS_MAX_ROWS 64
+#define ICPFLOW_CLASS_MAX_BUCKETS 8
+#define ICPFLOW_CLASS_MAX_WORDS 1024
+size_t icpflow_seq_class_table_workspace_bytes(int m, int G, int S, int E);
+int icpflow_seq_class_table(const double *d_points, const int32_t *d_time_indice, const double *d_classes,
+                            const double *d_gt_flow, const float *d_pred_flow, int m, int F, int crop, double range_x,
+                            double range_y, double z_min, double class_lo, int G, const double *h_speed_edges, int S,
+                            const double *h_error_edges, int E, int64_t *d_table, int64_t *d_info, void *d_ws,
+                            size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * 8(f)  per-segment evaluation of one labelled cloud of one frame pair: the numbers behind the reference's verbose loop,
