@@ -164,7 +164,7 @@ struct Workspace {
     float *voteKey = nullptr;   // per-pair sort-key parameters of the vote (votekey.hpp)
     int *zcidx = nullptr;
     IcpTeam team{};
-    int32_t *icpSplit = nullptr;   // [B + 64] the pair list (and its count) of the second of two ICP launches (icp.hip: icp_split_kernel)
+    int32_t *icpSplit = nullptr;   // [B + 64] the pair list (and its count) of the second of two ICP launches (icp_epilogue.hip: icp_split_kernel)
     // host-side note of THIS call: score_pick_kernel has left the forward totals of the picked candidates in scoreAccum[0 .. B)
     // (the scoring ran as sweeps over the sort the check sweep will use): the roll-back check scans under the final pose only
     bool initSumValid = false;

@@ -1,75 +1,35 @@
-// icp.hip -- masked batched point-to-point ICP for gfx950 (a-5, a-6, a-7).
+// icp.hip -- masked batched point-to-point ICP for gfx950 (a-5, a-6, a-7): the loop (IcpParams, icp_pair, icp_kernel) and
+// its launch policy (launch_icp_variant, launch_icp_iters, launch_icp), nothing else.  What a registration prepares
+// beforehand is in icp_prep.hip, the team plan in icp_plan.hip, the kernels that read what the loop leaves behind in
+// icp_epilogue.hip, the debug variants' instruments (globals, stamps, accessors) in icp_instr.hip.
 //
 // Reference semantics: utils_icp_pytorch3d.py:100-225 (loop), :303-382 (Kabsch via SVD),
-// :385-396 (apply).  Design: one workgroup per cluster pair runs a whole ICP iteration --
-// NN scan of the moved source against the LDS-staged target (scan.hpp), inlier gate,
-// weighted centroids, centred 3x3 covariance, closed-form rotation, rmse -- so the 15-odd
-// torch kernels, the cuSOLVER call and the host sync of one reference iteration collapse
-// into one launch with ONE block reduction of 18 raw moments.  All sums and the 3x3 solve are
-// fp64 (fp32 inputs), i.e. at least as accurate as the reference's fp32 torch reductions.
+// :385-396 (apply).  Design: one workgroup per cluster pair (or a team of them, or a persistent grid drawing pairs by
+// ticket: icp_kernel) runs ALL iterations of a pair -- exact gated nearest neighbours of the moved source among the
+// fixed cloud (sorted sweep, hashed grid or all-pairs scan, scan.hpp), inlier gate, weighted centroids, centred 3x3
+// covariance, closed-form rotation (kabsch.hpp), rmse -- so the 15-odd torch kernels, the cuSOLVER call and the host sync
+// of one reference iteration collapse into one pass over the points with ONE block reduction of 18 raw moments.  All sums
+// and the 3x3 solve are fp64 (fp32 inputs), i.e. at least as accurate as the reference's fp32 torch reductions.
 //
-// Stopping: ICPFLOW_STOP_REFERENCE reproduces the batch-global rule (stop when every pair
-// has rel <= thr, :209) WITHOUT a host round trip: one launch per iteration is enqueued up
-// front; each pair that is not converged bumps ctrl->notconv[it]; the launch of iteration
-// it+1 returns immediately when notconv[it] == 0.  ICPFLOW_STOP_PER_PAIR loops inside one
-// launch and lets every pair stop on its own.
+// Stopping: ICPFLOW_STOP_REFERENCE reproduces the batch-global rule (stop when every pair has rel <= thr, :209) WITHOUT a
+// host round trip.  Up to kHistIters iterations ONE launch runs every pair speculatively: a pair writes (R, T, rmse) of
+// every iteration into the history and adds itself to that iteration's tally (pairs arrived, pairs not converged:
+// IcpCtrl::tally); it leaves when it sees an iteration at which the rule held, when its trajectory is periodic, or at the
+// cap, and the epilogue (icp_epilogue.hip, or the consumers themselves: posefuse.hpp) takes every pair's state at the
+// reference's stopping iteration.  Beyond kHistIters -- and with the speculative launch switched off -- the fallback: one
+// launch per iteration is enqueued up front, each pair that is not converged bumps ctrl->notconv[it], and the launch of
+// iteration it + 1 returns immediately when notconv[it] == 0.  ICPFLOW_STOP_PER_PAIR loops inside one launch and lets
+// every pair stop on its own.
 #include <atomic>
 #include <mutex>
-#include <vector>
 
 #include "scan.hpp"
 #include "sortdir.hpp"
 #include "kernels.hpp"
+#include "gridhash.hpp"
+#include "icp_instr.hip"   // ICPFLOW_STAMP, and the instruments of the debug variants (a part of this unit, not a source of its own)
+#include "kabsch.hpp"      // after ICPFLOW_STAMP: the solver carries the phase stamps of debug builds
 
-namespace icpflow {
-
-#ifdef ICPFLOW_PHASE_TIMING
-// debug builds only (tools/dbg/phase_timing.py): shader-clock stamps of workgroup 0
-__device__ long long g_phase_stamps[16];
-__device__ long long g_wave_stamps[16 * 16];   // [wave][k] of workgroup 0
-__device__ int g_stamp_block;                  // the workgroup that stamps (icpflow_debug_set_stamp_block)
-#define ICPFLOW_STAMP(k) do { if ((int)blockIdx.x == g_stamp_block && threadIdx.x == 0) g_phase_stamps[k] = clock64(); \
-    if ((int)blockIdx.x == g_stamp_block && (threadIdx.x & 63) == 0) g_wave_stamps[(threadIdx.x >> 6) * 16 + (k)] = clock64(); } while (0)
-#else
-#define ICPFLOW_STAMP(k) do { } while (0)
-#endif
-
-#ifdef ICPFLOW_TAIL_CLOCK
-// debug builds only (tools/dbg/tail_clock.py): per pair, shader clocks wave 0 spent between the block barrier and the
-// publication of (R, T) (the serial tail), in the rest of the loop, and the iterations it executed; and the tail split
-// at the phase stamps (accumulated in LDS by thread 0)
-__device__ long long g_tail_clock[1024 * 3];
-__device__ long long g_wg_wall[8192 * 4];
-__device__ int g_unit_pair = -1;                       // pair whose per-(iteration, pass, wave) clocks are recorded (owner, no helpers)
-__device__ long long g_unit_clk[64 * 8 * 16];
-__device__ int g_unit_win[64 * 8 * 16 * 2];   // per (iteration, pass, wave): targets in the scanned window, lanes that searched
-__device__ unsigned long long g_pair_help[1024];   // passes the pair's owner received from helpers
-__device__ unsigned long long g_pair_hclk[1024 * 4];   // per pair: helper pass clocks, helper passes, helper waits (100 MHz), owner waits (100 MHz)
-__device__ unsigned long long g_help_stats[8];   // helpers that joined a pair, passes the owners took from helpers, owner clocks spent waiting   // per pair: wall clock (100 MHz) at entry and exit of its workgroup, HW_ID, XCC_ID
-__device__ long long g_tail_split[1024 * 16];
-__shared__ long long g_tcSh[17];
-#ifdef ICPFLOW_TAIL_SPLIT   // (each stamp costs ~200 clocks: the totals above are measured without)
-#undef ICPFLOW_STAMP
-#define ICPFLOW_STAMP(k) do { if (threadIdx.x == 0) { const long long t_ = clock64(); g_tcSh[k] += t_ - g_tcSh[16]; g_tcSh[16] = t_; } } while (0)
-#endif
-#endif
-#ifdef ICPFLOW_DEBUG_SOLVE
-// debug builds only (tools/dbg/onestep_case.py): the 18 moments, H, lambda and R of one pair's FIRST iteration
-__device__ double g_dbg_solve[64];
-__device__ float g_dbg_xt[4096 * 3];   // the moved points of that iteration by ORIGINAL row
-__device__ int g_dbg_pair = 0;
-#endif
-#ifdef ICPFLOW_CERT_STATS
-// debug builds only (tools/dbg/cert_stats.py): per iteration, over the whole batch: waves that ran, waves that searched,
-// queries that searched, targets scanned (per wave)
-__device__ unsigned long long g_cert_stats[128 * 4];
-__device__ unsigned long long g_probe_stats[128 * 2];   // probes, conclusive probes
-__device__ unsigned long long g_occ_cert[128 * 4];      // per iteration: queries without a certificate; of those, queries whose cell of the fixed cloud's grid is empty (plane 1: nothing within 0.98 h > gate); queries with certificate (B); outliers among ALL live queries by the grid
-__device__ int g_stats_block = -1;                       // >= 0: only this workgroup counts
-#endif
-
-}  // namespace icpflow
-#include "kabsch.hpp"   // after ICPFLOW_STAMP: the solver carries the phase stamps of debug builds
 namespace icpflow {
 
 // ---------------------------------------------------------------------------------
@@ -138,228 +98,6 @@ struct IcpParams {
     int32_t *splitScratch;       // host side only: [B + 64] ints (the list, then count and floor)
 };
 
-
-// ---------------------------------------------------------------------------------
-// Exact nearest neighbour within the gate radius through a hashed uniform grid.
-//
-// The ICP loop consumes the NN search only through the gate d^2 <= thres^2 and the neighbour of
-// gated points (utils_icp_pytorch3d.py:160-164), and the fixed cloud never changes during a
-// registration.  So the fixed cloud is binned ONCE into cells of edge h = 1.01 * thres (hashed
-// into H = 2^k >= 2N buckets, counting sort); a query then evaluates only the points of the 27
-// cells around it.  Every point within the gate radius of the query lies in those cells
-// (|coordinate difference| <= thres < h  =>  cell index difference <= 1; the cell index is a
-// monotone function of the coordinate), distances are evaluated with the SAME fp32 instruction
-// sequence as the brute-force scan and ties go to the lowest original index, so gate decisions
-// and neighbours -- hence every transform -- are bit-identical to the all-pairs search, at
-// ~30 instead of n distance evaluations per query.
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ int grid_cell(float v, float o, float invh)
-{
-    return (int)floorf((v - o) * invh);
-}
-
-__device__ __forceinline__ unsigned grid_hash(int cx, int cy, int cz, unsigned mask)
-{
-    return ((unsigned)cx * 73856093u ^ (unsigned)cy * 19349663u ^ (unsigned)cz * 83492791u) & mask;
-}
-
-constexpr int kGridBlock = 256;
-
-int grid_buckets(int N)
-{
-    int H = 64;
-    while (H < 2 * N) H <<= 1;
-    return H;
-}
-
-// One workgroup per pair.  counts/starts live in global scratch (L2 resident).
-__global__ __launch_bounds__(kGridBlock) void grid_build_kernel(
-    const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ lenX,
-    const int32_t *__restrict__ lenY, const uint8_t *__restrict__ swap, int N, int H, float invh,
-    float *__restrict__ origin, int32_t *__restrict__ start, int32_t *__restrict__ cursor,
-    float4 *__restrict__ pts)
-{
-    __shared__ int part[kGridBlock];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const bool sw = swap != nullptr && swap[b] != 0;
-    const float4 *yb = reinterpret_cast<const float4 *>(sw ? X : Y) + (size_t)b * N;
-    const int n = (sw ? lenX : lenY)[b];
-    int32_t *st = start + (size_t)b * (H + 1);
-    int32_t *cu = cursor + (size_t)b * H;
-    float4 *out = pts + (size_t)b * N;
-    const unsigned mask = (unsigned)H - 1u;
-    float4 o4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n > 0) o4 = yb[0];
-    if (tid == 0) { origin[b * 4 + 0] = o4.x; origin[b * 4 + 1] = o4.y; origin[b * 4 + 2] = o4.z; origin[b * 4 + 3] = 0.f; }
-    for (int k = tid; k <= H; k += kGridBlock) st[k] = 0;
-    __syncthreads();
-    for (int j = tid; j < n; j += kGridBlock) {
-        const float4 q = yb[j];
-        const unsigned h = grid_hash(grid_cell(q.x, o4.x, invh), grid_cell(q.y, o4.y, invh),
-                                     grid_cell(q.z, o4.z, invh), mask);
-        atomicAdd(&st[h + 1], 1);
-    }
-    __syncthreads();
-    // exclusive scan of st[1..H] in place: thread t owns a contiguous slice
-    const int per = (H + kGridBlock - 1) / kGridBlock;
-    const int lo = 1 + tid * per, hi = min(1 + (tid + 1) * per, H + 1);
-    int sum = 0;
-    for (int k = lo; k < hi; ++k) sum += st[k];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int k = 0; k < kGridBlock; ++k) { const int v = part[k]; part[k] = run; run += v; }
-    }
-    __syncthreads();
-    int run = part[tid];
-    for (int k = lo; k < hi; ++k) { run += st[k]; st[k] = run; }   // st[k] = #points in buckets < k
-    __syncthreads();
-    for (int k = tid; k < H; k += kGridBlock) cu[k] = st[k];
-    __syncthreads();
-    for (int j = tid; j < n; j += kGridBlock) {
-        const float4 q = yb[j];
-        const unsigned h = grid_hash(grid_cell(q.x, o4.x, invh), grid_cell(q.y, o4.y, invh),
-                                     grid_cell(q.z, o4.z, invh), mask);
-        const int pos = atomicAdd(&cu[h], 1);
-        out[pos] = make_float4(q.x, q.y, q.z, __int_as_float(j));
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// Sorted sweep: exact gated nearest neighbour with BROADCAST target reads.
-//
-// Both clouds are sorted once per registration along the longest axis a of the fixed cloud.
-// In every iteration a wave (64 consecutive sorted queries) computes the span [lo, hi] of its
-// CURRENT query coordinates along a (exact, from the moved points) and scans only the fixed
-// points with coordinate in [lo - m, hi + m], m = 1.01 * thres: a contiguous range of the sorted
-// array, read through LDS at one address for the whole wave (the same broadcast scan core as the
-// all-pairs search, just over ~1/10 of the targets).  A point outside that window is farther than
-// the gate radius from every query of the wave, so gate decisions and gated neighbours are the
-// ones of the all-pairs search; equal-distance ties are resolved to the lowest ORIGINAL index.
-// ---------------------------------------------------------------------------------
-constexpr int kSortBlock = 1024;
-static std::atomic<unsigned long long> g_sortAttr{0ull};   // devices on which sort_clouds_kernel has its dynamic-LDS opt-in
-
-// grid (B, 2): blockIdx.y == 0 sorts the fixed cloud, 1 the moving cloud (pre-pose applied)
-__global__ __launch_bounds__(kSortBlock) void sort_clouds_kernel(
-    const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ lenX,
-    const int32_t *__restrict__ lenY, const uint8_t *__restrict__ swap, const float *__restrict__ prePose,
-    int N, int NP2, int32_t *__restrict__ axisOut, float4 *__restrict__ Xs, float4 *__restrict__ Ys,
-    float *__restrict__ Ysoa, float *__restrict__ Xsoa, int selfCount, int dirKeys)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char dynLds[];
-    unsigned long long *kv = reinterpret_cast<unsigned long long *>(dynLds);   // (sort key, row) pairs, NP2 of them
-    __shared__ float bb[6 * (kSortBlock / kWave)];
-    __shared__ int axisSh;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const bool moving = blockIdx.y == 1;
-    int cX, cY;
-    bool sw;
-    if (selfCount) {
-        // hist_icp on the side stream, forked before anything has counted: the lengths (rows with a positive flag) and
-        // the smaller-cloud-first flag exactly as count_pair_kernel / zsort_kernel form them; lenX / lenY / swap unread
-        __shared__ int cntScratch[2 * (kSortBlock / kWave)];
-        const float4 *px = reinterpret_cast<const float4 *>(X) + (size_t)b * N;
-        const float4 *py = reinterpret_cast<const float4 *>(Y) + (size_t)b * N;
-        int c[2] = {0, 0};
-        for (int i = tid; i < N; i += kSortBlock) {
-            c[0] += (px[i].w > 0.0f) ? 1 : 0;
-            c[1] += (py[i].w > 0.0f) ? 1 : 0;
-        }
-        block_sum<2, int>(c, cntScratch);
-        cX = c[0]; cY = c[1];
-        sw = selfCount == 2 && cX > cY;
-    } else {
-        cX = lenX[b]; cY = lenY[b];
-        sw = swap != nullptr && swap[b] != 0;
-    }
-    const float4 *xb = reinterpret_cast<const float4 *>(sw ? Y : X) + (size_t)b * N;  // moving role
-    const float4 *yb = reinterpret_cast<const float4 *>(sw ? X : Y) + (size_t)b * N;  // fixed role
-    const int nx = sw ? cY : cX, ny = sw ? cX : cY;
-    // axis of largest extent of the fixed cloud (both blocks compute it the same way)
-    float mn[3] = {kInf, kInf, kInf}, mx[3] = {-kInf, -kInf, -kInf};
-    for (int j = tid; j < ny; j += kSortBlock) {
-        const float4 q = yb[j];
-        mn[0] = fminf(mn[0], q.x); mn[1] = fminf(mn[1], q.y); mn[2] = fminf(mn[2], q.z);
-        mx[0] = fmaxf(mx[0], q.x); mx[1] = fmaxf(mx[1], q.y); mx[2] = fmaxf(mx[2], q.z);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o, kWave));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o, kWave));
-        }
-    if ((tid & (kWave - 1)) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { bb[(tid >> 6) * 6 + k] = mn[k]; bb[(tid >> 6) * 6 + 3 + k] = mx[k]; }
-    }
-    __syncthreads();
-    __shared__ float boxSh[6];
-    if (tid == 0) {
-        float e[3];
-        for (int k = 0; k < 3; ++k) {
-            float lo = bb[k], hi = bb[3 + k];
-            for (int w = 1; w < kSortBlock / kWave; ++w) { lo = fminf(lo, bb[w * 6 + k]); hi = fmaxf(hi, bb[w * 6 + 3 + k]); }
-            e[k] = hi - lo;
-            boxSh[k] = lo; boxSh[3 + k] = hi;
-        }
-        const int a = (e[0] >= e[1] && e[0] >= e[2]) ? 0 : (e[1] >= e[2] ? 1 : 2);
-        axisSh = a;
-    }
-    __syncthreads();
-    // The key that spreads the fixed cloud best (sortdir.hpp): among the three axes and kSortDirs horizontal directions, the one
-    // with the smallest sum of squared populations of 0.1 m key bins -- the longest axis, as before, unless another key is at
-    // least a tenth better (clouds of a thousand points and more: below that every window is short anyway).  Integer counts,
-    // the same on both blocks of the pair.
-    if (dirKeys && ny >= kSortDirMinN && nx >= kSortDirMinMoving) {
-        __shared__ unsigned int scoreSh[kSortCodes];
-        // (the sort has not started: its key array -- NP2 >= 2048 entries of 8 bytes here -- holds the counters)
-        (void)choose_sort_code<kSortBlock>(yb, ny, boxSh, axisSh, reinterpret_cast<unsigned int *>(dynLds), scoreSh, &axisSh);
-    }
-    if (tid == 0 && !moving) axisOut[b] = axisSh;
-    const int axis = axisSh;
-    float dirX = 0.f, dirY = 0.f;
-    if (axis >= 3) sort_dir(axis, dirX, dirY);
-    const int n = moving ? nx : ny;
-    const float4 *cloud = moving ? xb : yb;
-    PointXf pre;
-    pre.kind = (moving && prePose) ? XF_AFFINE : XF_NONE;
-    pre.a = (moving && prePose) ? affine_from_pose(prePose + (size_t)b * 16) : affine_identity();
-    // the sorting network only has to hold THIS cloud: next power of two >= n (ragged batches are
-    // padded to the largest cluster, most clusters are far smaller)
-    int np2 = kWave;
-    while (np2 < n) np2 <<= 1;
-    np2 = min(np2, NP2);
-    for (int j = tid; j < np2; j += kSortBlock) {
-        float k = kInf;
-        if (j < n) {
-            const float4 q = cloud[j];
-            float px, py, pz;
-            xf_apply(pre, q.x, q.y, q.z, px, py, pz);
-            k = sort_key_of(axis, dirX, dirY, px, py, pz);
-        }
-        kv[j] = sort_pack(k, j);
-    }
-    __syncthreads();
-    bitonic_sort_lds(kv, np2);
-    float4 *out = (moving ? Xs : Ys) + (size_t)b * N;
-    const int NP16 = (N + kChunk - 1) / kChunk * kChunk;
-    // structure-of-arrays image (x[], y[], z[], padded with +inf to a multiple of 16): always for the
-    // fixed cloud, for the moving cloud when the caller wants to sweep in both directions (Xsoa)
-    float *soa = moving ? (Xsoa ? Xsoa + (size_t)b * 3 * NP16 : nullptr) : Ysoa + (size_t)b * 3 * NP16;
-    for (int r = tid; r < (soa ? NP16 : n); r += kSortBlock) {
-        float px = kInf, py = kInf, pz = kInf;
-        if (r < n) {
-            const int j = sort_index_of(kv[r]);
-            const float4 q = cloud[j];
-            xf_apply(pre, q.x, q.y, q.z, px, py, pz);
-            out[r] = make_float4(px, py, pz, __int_as_float(j));
-        }
-        if (soa) { soa[r] = px; soa[NP16 + r] = py; soa[2 * NP16 + r] = pz; }
-    }
-}
 
 // Moments accumulated per iteration (one block reduction, fp64).  With x' = x0 - o and
 // y' = y_nn - o for a per-pair origin o (the first source point; keeps |x'|,|y'| at the cluster
@@ -2387,360 +2125,17 @@ void icp_kernel(IcpParams p, int itBegin, int itEnd)
     }
 }
 
-// speculative mode epilogue: the reference's stopping iteration is the first one at which every
-// pair had arrived and none was unconverged; every pair's state is taken from its history there.
-__global__ void icp_resolve_history_kernel(IcpState *__restrict__ st, IcpCtrl *__restrict__ ctrl,
-                                           const float *__restrict__ history, int B, int maxIter)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    int n = maxIter;
-    for (int s = 0; s < maxIter; ++s) {
-        const unsigned long long t = ctrl->tally[s];
-        if ((int)(t & 0xffffffffull) == B && (t >> 32) == 0ull) { n = s + 1; break; }
-    }
-    const float *h = history + ((size_t)(n - 1) * B + b) * kHistStride;
-    for (int k = 0; k < 9; ++k) st[b].R[k] = h[k];
-    for (int k = 0; k < 3; ++k) st[b].T[k] = h[9 + k];
-    st[b].rmse = h[12];
-    st[b].s = h[13];
-#ifdef ICPFLOW_DEBUG_EXECUTED
-    st[b].rmse = (float)st[b].iters;   // developer builds: iterations this pair actually executed
-#endif
-    st[b].iters = n;
-    if (ctrl->error) st[b].R[0] = __int_as_float(0x7fc00000);   // a team gave up waiting: poison
-    if (b == 0) {
-        ctrl->iters = n;
-        // same convention as the per-iteration path: notconv[n-1] == 0 <=> converged
-        ctrl->notconv[n - 1] = (int)(ctrl->tally[n - 1] >> 32);
-    }
-}
-
-hipError_t launch_icp_resolve_history(IcpState *state, IcpCtrl *ctrl, const float *history, int B, int maxIter,
-                                      hipStream_t s)
-{
-    hipLaunchKernelGGL(icp_resolve_history_kernel, dim3((B + 127) / 128), dim3(128), 0, s, state, ctrl, history, B,
-                       maxIter);
-    return hipGetLastError();
-}
-
-__global__ void icp_export_kernel(const IcpState *__restrict__ st, const IcpCtrl *__restrict__ ctrl,
-                                  int B, int stopMode, float *__restrict__ R, float *__restrict__ T,
-                                  float *__restrict__ rmse, int32_t *__restrict__ iters,
-                                  int32_t *__restrict__ converged, float *__restrict__ scale)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) {
-        if (R) for (int k = 0; k < 9; ++k) R[(size_t)b * 9 + k] = ctrl->error ? __int_as_float(0x7fc00000) : st[b].R[k];
-        if (T) for (int k = 0; k < 3; ++k) T[(size_t)b * 3 + k] = st[b].T[k];
-        if (rmse) rmse[b] = st[b].rmse;
-        if (scale) scale[b] = st[b].s;
-    }
-    if (b == 0) {
-        const int n = ctrl->iters;
-        if (iters) *iters = ctrl->error ? -1 : n;
-        if (converged) {
-            if (stopMode == ICPFLOW_STOP_REFERENCE_) *converged = (n > 0 && ctrl->notconv[n - 1] == 0) ? 1 : 0;
-            else *converged = (ctrl->notconv[0] == 0) ? 1 : 0;
-        }
-    }
-}
-
-// Team plan for one launch (one block of 256 threads; B <= 256).  Round 4: sizes by PASS BOUNDARIES.
-//
-// A member's waves take one unit (64 consecutive sorted queries) per pass, so an iteration of a member lasts
-// passes x (its slowest unit), passes = ceil(units per member / 12) for the 768-thread team kernel: a fifth workgroup on
-// a pair of 73 units (19 -> 15 units per member) shortens nothing, the seventh (11 units: one pass) halves the iteration.
-// So team sizes move from one level of "units per member" to the next -- ..., 36, 24, 12 (passes 3, 2, 1), then 8 and 4
-// (fewer waves sharing a SIMD: the early iterations, where every unit scans its window, are VALU issue) -- and the spare
-// workgroups go, one level at a time, to the pair whose estimated iteration is the longest (levels x a weight that grows
-// with the length of the fixed cloud: what a unit costs follows the targets in its window).
-//   * A pair first gets the team that lets its members keep the per-query RECORDS (neighbour certificates: a member's
-//     share of the queries must fit `recCap`): a 2200-query pair served by ONE workgroup of a batch padded to 10000
-//     searched every window in every iteration (90 k clocks per iteration against 25 k; ragged real-shape batch).
-//   * Pairs of a single pass (<= 768 queries) are CHAINED: up to kTeamChain of them are served one after the other by one
-//     workgroup (t.next), when the large pairs can use the workgroups that frees.  They finish within a few per cent
-//     of the launch (nobody waits for anybody under the speculative batch rule; a chained pair only arrives later at
-//     the tallies), and a workgroup that has finished its one small pair would idle for the rest of the launch.
-// The sums of a team are added in member order: the plan decides the rounding of a registration's moment sums, so it
-// depends on the batch's lengths alone (never on timing).
-#ifndef ICPFLOW_TEAM_CHAIN
-#define ICPFLOW_TEAM_CHAIN 4
-#endif
-constexpr int kTeamChain = ICPFLOW_TEAM_CHAIN;
-#ifndef ICPFLOW_TEAM_MIN_SHARE
-#define ICPFLOW_TEAM_MIN_SHARE 256
-#endif
-constexpr int kTeamMinShare = ICPFLOW_TEAM_MIN_SHARE;   // queries per member, at least
-constexpr int kTeamWaves = 768 / kWave;   // units per pass of a member
-
-// units per member at the level below `u`
-__device__ __forceinline__ int team_next_level(int u)
-{
-    if (u > kTeamWaves) return (u - 1) / kTeamWaves * kTeamWaves;   // one pass fewer
-    return u > 8 ? 8 : (u > 4 ? 4 : 0);
-}
-// relative length of an iteration at u units per member
-__device__ __forceinline__ float team_level_cost(int u)
-{
-    if (u >= kTeamWaves) return (float)((u + kTeamWaves - 1) / kTeamWaves);
-    return u > 8 ? 1.0f : (u > 4 ? 0.85f : 0.7f);
-}
-
-__global__ __launch_bounds__(256) void icp_team_plan_kernel(const int32_t *__restrict__ lenX,
-                                                            const int32_t *__restrict__ lenY,
-                                                            const uint8_t *__restrict__ swap, int B, IcpTeam t, int recCap,
-                                                            const uint8_t *__restrict__ active)
-{
-    __shared__ int size[256];
-    __shared__ int first[257];
-    __shared__ int part[4];
-    __shared__ int sh[8];        // [0] small pairs, [1] sum of minimum teams, [2] sum of wishes, [3] chain length, [4] slots for the large pairs
-    __shared__ int teamList[256];
-    __shared__ int xcdUsed[8];
-    const int b = threadIdx.x, lane = b & (kWave - 1), wv = b >> 6;
-    int n = 0, nf = 0;
-    if (b < B) {
-        const bool sw = swap != nullptr && swap[b] != 0;
-        n = sw ? lenY[b] : lenX[b];
-        nf = sw ? lenX[b] : lenY[b];
-        // a pair that is not in the batch (options.d_pair_active) counts as the two EMPTY clouds a caller who knew the mask
-        // beforehand hands over: the plan -- hence the order of every team's sums -- is the same whether the pair's clouds are
-        // there or not (a frame pair's stage 2 on the whole superset, api.hip, against the serial path's empty clouds)
-        if (active != nullptr && active[b] == 0) { n = 0; nf = 0; }
-    }
-    const int units = (n + kWave - 1) / kWave;
-    const bool small = b < B && units <= kTeamWaves;
-    const bool big = b < B && !small;
-    // smallest team whose members keep their records; the team of one pass
-    int gMin = 1;
-    if (big && recCap > 0) {
-        const int capUnits = max(recCap / kWave, 1);
-        gMin = min(kMaxTeam, (units + capUnits - 1) / capUnits);
-    }
-    const int gWish = small ? 1 : min(kMaxTeam, (units + kTeamWaves - 1) / kTeamWaves);
-    // (the square root: between no weight and the full ratio of the fixed clouds' lengths, measured in round 3)
-    const float weight = big ? sqrtf((float)max(nf, 1024) / 1024.0f) : 0.f;
-    for (int w = threadIdx.x; w < t.maxWG; w += blockDim.x) { t.wgPair[w] = -1; t.wgRank[w] = 0; }
-    if (b < 8) sh[b] = 0;
-    __syncthreads();
-    // block-wide sum of one int per thread (all threads call it)
-    auto block_sum_int = [&](int v) -> int {
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-        __syncthreads();
-        if (lane == 0) part[wv] = v;
-        __syncthreads();
-        return part[0] + part[1] + part[2] + part[3];
-    };
-    // block-wide exclusive prefix sum of one int per thread, in thread order (all threads call it)
-    auto block_prefix_int = [&](int v) -> int {
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const int up = __shfl_up(inc, o, kWave);
-            if (lane >= o) inc += up;
-        }
-        __syncthreads();
-        if (lane == kWave - 1) part[wv] = inc;
-        __syncthreads();
-        int base = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) base += (k < wv) ? part[k] : 0;
-        return base + inc - v;
-    };
-    const int nSmall = block_sum_int(small ? 1 : 0), nBig = B - nSmall;
-    const int sumMin = block_sum_int(big ? gMin : 0);
-    const int sumWish = block_sum_int(big ? max(gWish, gMin) : 0);
-    // chain the single-pass pairs only as far as the large pairs can use the workgroups: chain length c frees
-    // nSmall - ceil(nSmall / c) of them
-    int chain = 1;
-    while (chain < kTeamChain && nBig > 0 && t.maxWG - (nSmall + chain - 1) / chain < sumWish) ++chain;
-    int slots = t.maxWG - (nSmall + chain - 1) / chain;     // workgroups for the large pairs
-    const bool fits = slots >= sumMin;       // not even the minimum teams: every pair one workgroup, no chains (B <= maxWG)
-    if (!fits) { chain = 1; slots = t.maxWG - nSmall; }
-    // The levels this pair's team can take: (workgroups, estimated length of an iteration), from its minimum team down the
-    // levels of units per member.  The spare workgroups go where they shorten the LONGEST estimated iteration: the
-    // smallest bound tau such that every pair brought down to tau (or as far as it can go) still fits, by bisection
-    // over the levels' costs (a block-wide sum per step), then what is left over to the pairs just above, in pair order.
-    constexpr int kLevels = 8;
-    int lvG[kLevels];          // (every loop over the levels is fully unrolled: the tables stay in registers)
-    float lvC[kLevels];
-    int gLast = 0;
-    {
-        int G = fits ? gMin : 1;
-        int u = (units + G - 1) / G;
-        bool open = big;
-#pragma unroll
-        for (int k = 0; k < kLevels; ++k) {
-            lvG[k] = G; lvC[k] = open ? team_level_cost(u) * weight : 3.0e38f;
-            if (open) gLast = G;
-            const int uNext = team_next_level(u);
-            const int gNext = uNext > 0 ? (units + uNext - 1) / uNext : 0;
-            open = open && uNext > 0 && gNext <= kMaxTeam && gNext > G && n / max(gNext, 1) >= kTeamMinShare;
-            if (open) { G = gNext; u = (units + G - 1) / G; }
-        }
-    }
-    auto teams_at = [&](float tau) -> int {      // this pair's team under the bound tau: the first level that meets it, or its last
-        int G = gLast;
-#pragma unroll
-        for (int k = kLevels - 1; k >= 0; --k)
-            if (lvC[k] <= tau) G = lvG[k];
-        return big ? G : 0;
-    };
-    int G = b < B ? 1 : 0;
-    if (nBig > 0) {
-        // bisection on tau between 0 (everybody at its last level) and the largest first-level cost
-        float hiC = big ? lvC[0] : 0.f;
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) hiC = fmaxf(hiC, __shfl_xor(hiC, o, kWave));
-        __syncthreads();
-        if (lane == 0) part[wv] = __float_as_int(hiC);
-        __syncthreads();
-        float hi = fmaxf(fmaxf(__int_as_float(part[0]), __int_as_float(part[1])), fmaxf(__int_as_float(part[2]), __int_as_float(part[3])));
-        float lo = 0.f;
-        // (hi always fits: every pair at its first level is sumMin <= slots, or one workgroup each)
-        for (int step = 0; step < 14; ++step) {
-            const float mid = 0.5f * (lo + hi);
-            if (block_sum_int(teams_at(mid)) <= slots) hi = mid; else lo = mid;
-        }
-        G = big ? teams_at(hi) : G;
-        // left-over workgroups: one more level for the pairs that can take one, in pair order
-        int left = slots - block_sum_int(big ? G : 0);
-        if (left > 0) {
-            int want = 0;
-#pragma unroll
-            for (int k = 0; k + 1 < kLevels; ++k)
-                if (big && lvG[k] == G && lvC[k + 1] < 3.0e38f && want == 0) want = lvG[k + 1] - G;
-            const int before = block_prefix_int(want);
-            if (want > 0 && before + want <= left) G += want;
-        }
-    }
-    // a chain of single-pass pairs is one workgroup: its first pair carries the slot, the others hang on t.next
-    {
-        const int seq = block_prefix_int(small ? 1 : 0);   // this small pair's number among the small pairs (in pair order)
-        if (small) first[seq] = b;      // (first[] is scratch here: small pair number -> pair)
-        __syncthreads();
-        const bool head = small && (seq % chain) == 0;
-        if (b < B) t.next[b] = (small && seq + 1 < nSmall && (seq + 1) % chain != 0) ? first[seq + 1] : -1;
-        __syncthreads();
-        size[b] = (b < B) ? (small ? (head ? 1 : 0) : G) : 0;
-    }
-    __syncthreads();
-    // Workgroup w is dispatched to XCD w % 8, so slot k = (w % 8) * per + w / 8 enumerates the
-    // workgroups XCD by XCD (per = maxWG / 8 of them each).  A team takes consecutive slots of ONE
-    // XCD (its exchange stays inside one L2); teams go to the XCD with the most free slots, which
-    // spreads the launch over all eight L2s.  Only the teams of several members go through that (serial) loop; the
-    // single workgroups then fill what is left, XCD by XCD.
-    const int per = (t.maxWG % 8 == 0) ? t.maxWG / 8 : t.maxWG;
-    const int nx = (per == t.maxWG) ? 1 : 8;
-    // this pair's number among the teams / the single workgroups (in pair order; both counts in one word)
-    const int numbers = block_prefix_int((b < B && size[b] > 1 ? 1 << 16 : 0) + (b < B && size[b] == 1 ? 1 : 0));
-    const int teamNo = numbers >> 16, singleNo = numbers & 0xffff;
-    if (b < B && size[b] > 1) teamList[teamNo] = b;
-    const int nTeams = block_sum_int((b < B && size[b] > 1) ? 1 : 0);
-    if (b == 0) {
-        int used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        bool ok = true;
-        for (int k = 0; k < nTeams && ok; ++k) {
-            // (the least-used XCD, first one on ties; the counters stay in registers: no indexing by a variable)
-            int x = 0, ux = used[0];
-#pragma unroll
-            for (int c = 1; c < 8; ++c)
-                if (c < nx && used[c] < ux) { x = c; ux = used[c]; }
-            const int sz = size[teamList[k]];
-            if (ux + sz > per) ok = false;
-            first[teamList[k]] = x * per + ux;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) used[c] += (c == x) ? sz : 0;
-        }
-        if (!ok) {   // does not fit XCD by XCD: plain packing (teams may span two XCDs)
-            int acc = 0;
-            for (int k = 0; k < nTeams; ++k) { first[teamList[k]] = acc; acc += size[teamList[k]]; }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) used[c] = 0;
-            for (int c = 0; c < 8; ++c) { const int take = min(max(acc - c * per, 0), per); xcdUsed[c] = (c < nx) ? take : per; }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) xcdUsed[c] = (c < nx) ? used[c] : per;
-        }
-    }
-    __syncthreads();
-    if (b < B && size[b] == 1) {
-        // the singleNo-th single workgroup: the singleNo-th free slot, XCD by XCD
-        int skip = singleNo, slot = -1;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int freeC = per - xcdUsed[c];
-            if (slot < 0 && c < nx) {
-                if (skip < freeC) slot = c * per + xcdUsed[c] + skip;
-                else skip -= freeC;
-            }
-        }
-        first[b] = slot;    // (>= 0: the plan never hands out more workgroups than there are)
-    }
-    __syncthreads();
-    if (b < B) {
-        t.teamSize[b] = G;
-        t.arrived[b] = 0u;
-        for (int r = 0; r < size[b]; ++r) {
-            const int k = first[b] + r;
-            const int w = (per == t.maxWG) ? k : (k % per) * 8 + k / per;
-            if (first[b] >= 0 && w < t.maxWG) { t.wgPair[w] = b; t.wgRank[w] = r; }
-        }
-    }
-}
-
-// Two launches for batches of a few rounds (round 6).  A persistent grid deals its pairs in index order, and which pairs
-// are the long ones is not known beforehand (tools/dbg/order_predictor.py): config 4's shard (1024 pairs x 2048 points, two
-// 512-thread workgroups per CU) keeps its 512 slots full for the first half of the launch and spends the second half on a
-// thinning set of long pairs, each on HALF a CU (tools/dbg/help_timeline.py: 498 owners at 50 % of the span, 227 at 70 %, 55 at
-// 85 %; 30-40 us per iteration while the CU is shared, ~20 us with helpers once it is not).  So the launch is DRAINED as soon as
-// at most `drainAt` (the number of CUs) pairs are unfinished: every pair still iterating leaves behind its current iteration,
-// still moving (IcpState: state, rmse, iterations; its history rows and tallies are in place).  This kernel, between the two
-// launches, looks for the batch rule among the tallies (found: nobody goes on), finds the first iteration some pair has not
-// reached yet (the floor of the second launch's search for the rule) and lists the pairs that left still moving; the SECOND launch
-// gives each of them a whole CU -- one 1024-thread workgroup, two passes instead of four -- and resumes it at ITS iteration.
-// What makes that bit-identical (ICPFLOW_OPT_TWO_LAUNCH against the default; tests/test_gpu_fullsize.py): the first launch keeps its moment sums
-// per (pass, wave) and adds them in that order (redPasses, the helpers' bookkeeping) -- i.e. in the order of the UNITS of 64
-// consecutive sorted queries, which is the same order whether 8 waves take 4 passes or 16 waves take 2; everything else of an
-// iteration is a function of (R, T).  The neighbour certificates are rebuilt in a pair's first iteration of the second launch,
-// the cycle detection and the own-convergence bits are restored from the pair's history rows (icp_pair).
+// two launches (described at icp_split_kernel, icp_epilogue.hip): the persistent grid is drained once at most this many
+// pairs are unfinished
 #ifndef ICPFLOW_DRAIN_AT
 #define ICPFLOW_DRAIN_AT 0   // 0: the number of CUs
 #endif
-__global__ __launch_bounds__(1024) void icp_split_kernel(const IcpCtrl *__restrict__ ctrl, const IcpState *__restrict__ st, int B, int maxIter,
-                                                         int32_t *__restrict__ list, int32_t *__restrict__ meta)
+// a kernel's opt-in to the dynamic LDS a launch needs above the default limit: once per instantiation and device
+template <auto KERN>
+static void allow_dynamic_lds(size_t dyn)
 {
-    __shared__ int foundSh, floorSh, waveCnt[16];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-    if (tid == 0) { foundSh = 0; floorSh = maxIter; }
-    __syncthreads();
-    for (int s0 = tid; s0 < maxIter; s0 += 1024) {
-        const unsigned long long t = ctrl->tally[s0];
-        if ((int)(t & 0xffffffffull) >= B) { if ((t >> 32) == 0ull) foundSh = 1; }
-        else atomicMin(&floorSh, s0);
-    }
-    __syncthreads();
-    if (foundSh) {   // the batch rule holds at an iteration every pair has reached: nobody goes on
-        if (tid == 0) { meta[0] = 0; meta[1] = 0; }
-        return;
-    }
-    int total = 0;   // (workgroup-uniform)
-    for (int b0 = 0; b0 < B; b0 += 1024) {
-        const int b = b0 + tid;
-        const bool on = b < B && st[b].active != 0 && st[b].iters < maxIter;
-        const unsigned long long m = __ballot(on);
-        if (lane == 0) waveCnt[wave] = __builtin_popcountll(m);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) { const int c = waveCnt[w]; before += w < wave ? c : 0; all += c; }
-        if (on) list[total + before + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = b;
-        total += all;
-        __syncthreads();
-    }
-    if (tid == 0) { meta[0] = total; meta[1] = floorSh; }
+    static std::atomic<unsigned long long> raised{0ull};
+    if (dyn > 48 * 1024) ensure_dynamic_lds(reinterpret_cast<const void *>(KERN), 156 * 1024, &raised);
 }
 
 template <int BLOCK, int Q, int TS, int GRID, bool TEAM = false, bool SCALE = false>
@@ -2791,10 +2186,7 @@ static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd
     if constexpr (!TEAM && !SCALE && GRID == 4 && Q == 1) {
         constexpr auto kernH = &icp_kernel<BLOCK, Q, TS, GRID, false, false, true, true>;
         const int passes = (p.N + BLOCK - 1) / BLOCK;
-        if (p.N <= kRecMaxN && passes >= 3 && dynBytes(passes) > 48 * 1024) {   // (before the occupancy is asked for)
-            static std::atomic<unsigned long long> raisedH{0ull};
-            ensure_dynamic_lds(reinterpret_cast<const void *>(kernH), 156 * 1024, &raisedH);
-        }
+        if (p.N <= kRecMaxN && passes >= 3) allow_dynamic_lds<kernH>(dynBytes(passes));   // (before the occupancy is asked for)
         const long long capH = (p.N <= kRecMaxN && passes >= 3) ? capacity(reinterpret_cast<const void *>(kernH), dynBytes(passes)) : 0;
         const bool eligible = capH > 0 && (long long)B > capH && (long long)B <= 4 * capH && capH <= kHelpMaxWG;
         if (eligible) {
@@ -2814,7 +2206,7 @@ static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd
                         constexpr auto kern2 = &icp_kernel<1024, 1, 1, 4, false, false>;
                         q.drainAt = drainAt;
                         hipLaunchKernelGGL(kernH, dim3((int)capH), dim3(BLOCK), dyn, s, q, itBegin, itEnd);
-                        hipLaunchKernelGGL(icp_split_kernel, dim3(1), dim3(1024), 0, s, q.ctrl, q.state, B, q.maxIter, q.splitScratch, q.splitScratch + B);
+                        launch_icp_split(q.ctrl, q.state, B, q.maxIter, q.splitScratch, q.splitScratch + B, s);
                         IcpParams q2 = q;
                         q2.persistent = 0; q2.helpOn = 0; q2.drainAt = 0; q2.halfCu = 0;
                         q2.pairList = q.splitScratch;
@@ -2823,10 +2215,7 @@ static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd
                         const size_t red2 = (size_t)q2.redPasses * 16 * kMoments * sizeof(double), img = (size_t)((p.N + kChunk - 1) / kChunk * kChunk) * 12;
                         q2.x0Cache = (p.recCap > 0 && red2 + img + (size_t)p.recCap * 32 <= (size_t)152 * 1024) ? 1 : 0;
                         const size_t dyn2 = red2 + img + (size_t)p.recCap * (q2.x0Cache ? 32 : 20);
-                        if (dyn2 > 48 * 1024) {
-                            static std::atomic<unsigned long long> raised2{0ull};
-                            ensure_dynamic_lds(reinterpret_cast<const void *>(kern2), 156 * 1024, &raised2);
-                        }
+                        allow_dynamic_lds<kern2>(dyn2);
                         hipLaunchKernelGGL(kern2, dim3(drainAt), dim3(1024), dyn2, s, q2, 0, itEnd);
                         return;
                     }
@@ -2840,10 +2229,7 @@ static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd
     if constexpr (!TEAM && !SCALE && GRID >= 3) {
         if (p.persistent && q.redPasses == 0) {
             constexpr auto kern = &icp_kernel<BLOCK, Q, TS, GRID, false, false, true, false>;
-            if (dyn > 48 * 1024) {
-                static std::atomic<unsigned long long> raisedP{0ull};
-                ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 156 * 1024, &raisedP);
-            }
+            allow_dynamic_lds<kern>(dyn);
             const long long cap = capacity(reinterpret_cast<const void *>(kern), dyn);
             if ((long long)B > cap) {
                 q.persistent = 1;
@@ -2858,25 +2244,16 @@ static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd
         // config 2's kernel.  (Its pairList is NULL: only the second of two launches, kern2 above, has one.)
         if (!dirKeys && q.redPasses == 0) {
             constexpr auto kernA = &icp_kernel<BLOCK, Q, TS, GRID, false, false, false, false, false>;
-            if (dyn > 48 * 1024) {
-                static std::atomic<unsigned long long> raisedA{0ull};
-                ensure_dynamic_lds(reinterpret_cast<const void *>(kernA), 156 * 1024, &raisedA);
-            }
+            allow_dynamic_lds<kernA>(dyn);
             hipLaunchKernelGGL(kernA, dim3(B), dim3(BLOCK), dyn, s, q, itBegin, itEnd);
             return;
         }
     }
-    if (dyn > 48 * 1024) {   // above the default dynamic-LDS limit: opt in once per instantiation and device
-        static std::atomic<unsigned long long> raised{0ull};
-        ensure_dynamic_lds(reinterpret_cast<const void *>(&icp_kernel<BLOCK, Q, TS, GRID, TEAM, SCALE>), 156 * 1024, &raised);
-    }
+    allow_dynamic_lds<&icp_kernel<BLOCK, Q, TS, GRID, TEAM, SCALE>>(dyn);
     const int wgs = TEAM ? p.team.maxWG : B;
     if constexpr (TEAM && GRID == 4) {
         if (p.shareScans) {   // the instantiation with shared window scans (icp_pair: SHAREK)
-            if (dyn > 48 * 1024) {
-                static std::atomic<unsigned long long> raisedS{0ull};
-                ensure_dynamic_lds(reinterpret_cast<const void *>(&icp_kernel<BLOCK, Q, TS, GRID, TEAM, SCALE, false, true>), 156 * 1024, &raisedS);
-            }
+            allow_dynamic_lds<&icp_kernel<BLOCK, Q, TS, GRID, TEAM, SCALE, false, true>>(dyn);
             hipLaunchKernelGGL((icp_kernel<BLOCK, Q, TS, GRID, TEAM, SCALE, false, true>), dim3(wgs), dim3(BLOCK), dyn, s, q, itBegin, itEnd);
             return;
         }
@@ -2884,180 +2261,9 @@ static void launch_icp_variant(const IcpParams &p, int B, int itBegin, int itEnd
     hipLaunchKernelGGL((icp_kernel<BLOCK, Q, TS, GRID, TEAM, SCALE>), dim3(wgs), dim3(BLOCK), dyn, s, q, itBegin, itEnd);
 }
 
-// ---- optional per-launch timing of this (dominant) kernel with HIP events ---------------------
-// bench.py needs the average launch duration of the dominant kernel measured on the stream it
-// runs on; the events are recorded by the library because only it sees the individual launches.
-// The recorder is an object the caller owns (icpflow_profile_t) and passes with the call's options.
-struct LaunchProfile {
-    std::vector<hipEvent_t> start, stop;
-    int used = 0;
-};
-
-#ifdef ICPFLOW_TAIL_CLOCK
-extern "C" int icpflow_debug_tail_clock(long long *out3072)
-{
-    return (int)hipMemcpyFromSymbol(out3072, HIP_SYMBOL(g_tail_clock), sizeof(long long) * 3072);
-}
-extern "C" int icpflow_debug_pair_hclk(unsigned long long *out4096, int reset)
-{
-    int rc = (int)hipMemcpyFromSymbol(out4096, HIP_SYMBOL(g_pair_hclk), sizeof(unsigned long long) * 4096);
-    if (reset) { static unsigned long long z[4096]; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_hclk), z, sizeof(z)); }
-    return rc;
-}
-extern "C" int icpflow_debug_unit_win(int *out16384)
-{
-    return (int)hipMemcpyFromSymbol(out16384, HIP_SYMBOL(g_unit_win), sizeof(int) * 16384);
-}
-extern "C" int icpflow_debug_unit_clk(long long *out8192, int pair)
-{
-    int rc = (int)hipMemcpyFromSymbol(out8192, HIP_SYMBOL(g_unit_clk), sizeof(long long) * 8192);
-    rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_unit_pair), &pair, sizeof(int));
-    return rc;
-}
-extern "C" int icpflow_debug_pair_help(unsigned long long *out1024, int reset)
-{
-    int rc = (int)hipMemcpyFromSymbol(out1024, HIP_SYMBOL(g_pair_help), sizeof(unsigned long long) * 1024);
-    if (reset) { static unsigned long long z[1024]; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_help), z, sizeof(z)); }
-    return rc;
-}
-extern "C" int icpflow_debug_wg_wall(long long *out32768)
-{
-    return (int)hipMemcpyFromSymbol(out32768, HIP_SYMBOL(g_wg_wall), sizeof(long long) * 32768);
-}
-extern "C" int icpflow_debug_help_stats(unsigned long long *out8, int reset)
-{
-    int rc = (int)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_help_stats), sizeof(unsigned long long) * 8);
-    if (reset) { static unsigned long long z[8]; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_help_stats), z, sizeof(z)); }
-    return rc;
-}
-extern "C" int icpflow_debug_tail_split(long long *out16384)
-{
-    return (int)hipMemcpyFromSymbol(out16384, HIP_SYMBOL(g_tail_split), sizeof(long long) * 16384);
-}
-#endif
-#ifdef ICPFLOW_DEBUG_SOLVE
-extern "C" int icpflow_debug_solve(int pair, double *out64)
-{
-    if (out64 == nullptr) return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_pair), &pair, sizeof(int));
-    return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_dbg_solve), sizeof(double) * 64);
-}
-extern "C" int icpflow_debug_xt(float *out12288)
-{
-    return (int)hipMemcpyFromSymbol(out12288, HIP_SYMBOL(g_dbg_xt), sizeof(float) * 12288);
-}
-#endif
-#ifdef ICPFLOW_CERT_STATS
-extern "C" int icpflow_debug_set_stats_block(int b)
-{
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stats_block), &b, sizeof(int));
-}
-extern "C" int icpflow_debug_cert_stats(unsigned long long *out512, int reset)
-{
-    int rc = (int)hipMemcpyFromSymbol(out512, HIP_SYMBOL(g_cert_stats), sizeof(unsigned long long) * 512);
-    rc |= (int)hipMemcpyFromSymbol(out512 + 512, HIP_SYMBOL(g_probe_stats), sizeof(unsigned long long) * 256);
-    if (reset) {
-        static unsigned long long zeros4[512];
-        rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_occ_cert), zeros4, sizeof(zeros4));
-        static unsigned long long zeros[512];
-        rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_cert_stats), zeros, sizeof(zeros));
-        rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_probe_stats), zeros, sizeof(unsigned long long) * 256);
-    }
-    return rc;
-}
-#endif
-#ifdef ICPFLOW_CERT_STATS
-extern "C" int icpflow_debug_occ_cert(unsigned long long *out512)
-{
-    return (int)hipMemcpyFromSymbol(out512, HIP_SYMBOL(g_occ_cert), sizeof(unsigned long long) * 512);
-}
-#endif
-#ifdef ICPFLOW_PHASE_TIMING
-extern "C" int icpflow_debug_set_stamp_block(int b)
-{
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_block), &b, sizeof(int));
-}
-extern "C" int icpflow_debug_phase_stamps(long long *out16)
-{
-    return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_stamps), sizeof(long long) * 16);
-}
-extern "C" int icpflow_debug_wave_stamps(long long *out256)
-{
-    return (int)hipMemcpyFromSymbol(out256, HIP_SYMBOL(g_wave_stamps), sizeof(long long) * 256);
-}
-#endif
-
-LaunchProfile *profile_create(int capacity, hipError_t *err)
-{
-    LaunchProfile *p = new LaunchProfile;
-    *err = hipSuccess;
-    for (int i = 0; i < capacity; ++i) {
-        hipEvent_t a, b;
-        hipError_t e = hipEventCreate(&a);
-        if (e == hipSuccess) {
-            e = hipEventCreate(&b);
-            if (e != hipSuccess) (void)hipEventDestroy(a);
-        }
-        if (e != hipSuccess) { *err = e; profile_destroy(p); return nullptr; }
-        p->start.push_back(a); p->stop.push_back(b);
-    }
-    return p;
-}
-
-void profile_destroy(LaunchProfile *p)
-{
-    if (p == nullptr) return;
-    for (hipEvent_t e : p->start) (void)hipEventDestroy(e);
-    for (hipEvent_t e : p->stop) (void)hipEventDestroy(e);
-    delete p;
-}
-
-hipError_t profile_collect(LaunchProfile *p, double *total_ms, int *launches)
-{
-    double sum = 0.0;
-    for (int i = 0; i < p->used; ++i) {
-        hipError_t e = hipEventSynchronize(p->stop[i]);
-        if (e != hipSuccess) return e;
-        float ms = 0.f;
-        e = hipEventElapsedTime(&ms, p->start[i], p->stop[i]);
-        if (e != hipSuccess) return e;
-        sum += ms;
-    }
-    if (total_ms) *total_ms = sum;
-    if (launches) *launches = p->used;
-    p->used = 0;
-    return hipSuccess;
-}
-
-int device_cus()
-{
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-    int c = cache[dev].load(std::memory_order_relaxed);
-    if (c == 0) {
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 1;
-        cache[dev].store(c, std::memory_order_relaxed);
-    }
-    return c;
-}
-
-void ensure_dynamic_lds(const void *func, int bytes, std::atomic<unsigned long long> *mask)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (dev < 64 && (mask->load(std::memory_order_acquire) & bit)) return;
-    // never more than the CU's 160 KiB less the kernel's static LDS (the request fails as a whole otherwise)
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, func) == hipSuccess) bytes = min(bytes, 160 * 1024 - (int)fa.sharedSizeBytes);
-    (void)hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (dev < 64) mask->fetch_or(bit, std::memory_order_release);
-}
-
 static void launch_icp_iters(const IcpParams &p, bool dirKeys, int B, int itBegin, int itEnd, LaunchProfile *prof, hipStream_t s)
 {
-    const bool timed = prof != nullptr && prof->used < (int)prof->start.size();
-    if (timed) (void)hipEventRecord(prof->start[prof->used], s);
+    const bool timed = profile_start(prof, s);
     if (p.sortY != nullptr) {    // sorted sweep
         // one query per lane (Q = 1; two per lane on 8 waves measured 25 % slower at n = 1024): a wave's 64
         // consecutive sorted queries span the narrowest window;
@@ -3129,7 +2335,7 @@ static void launch_icp_iters(const IcpParams &p, bool dirKeys, int B, int itBegi
         else if (p.N <= 1024) launch_icp_variant<1024, 4, 4, 0>(p, B, itBegin, itEnd, s);  // 1024
         else launch_icp_variant<1024, 4, 2, 0>(p, B, itBegin, itEnd, s);                   // 2048 per pass
     }
-    if (timed) (void)hipEventRecord(prof->stop[prof->used++], s);
+    if (timed) profile_stop(prof, s);
 }
 
 // Teams: with at most half of the CUs taken by one workgroup per pair, the spare CUs join the pairs
@@ -3145,34 +2351,6 @@ bool icp_teams_wanted(const IcpTeam *team, const IcpOpts &opts, const GridScratc
            (speculative || stopMode == ICPFLOW_STOP_PER_PAIR_);
     // (B <= the workgroups the plan really gets: with teamsHalfGpu on a part whose CUs / 2 is not a multiple of eight --
     // 104, 110, 120 CUs -- the plan has fewer slots than CUs / 2, and a pair without a slot would never be served)
-}
-
-// dynamic LDS of a team member with the LDS image (image + records): the CU's 160 KiB less the team kernel's static LDS
-// (~16 KiB with the accumulators of the shared window scans: 143 KiB; ~6.7 KiB without: 152 KiB)
-// workgroups of a team launch: one per CU, or one per CU of HALF the GPU (a multiple of the eight XCDs either way)
-// Shared window scans (icp_pair, SHAREK): from this padded width on -- below, windows of 256 targets are rare.
-#ifndef ICPFLOW_SHARE_LAUNCH_MIN_N
-#define ICPFLOW_SHARE_LAUNCH_MIN_N 5000
-#endif
-bool icp_team_shares(const IcpOpts &opts, int N) { return opts.sharedScans && opts.adaptiveWindows && N >= ICPFLOW_SHARE_LAUNCH_MIN_N && N <= 12288; }
-size_t icp_team_room(const IcpOpts &opts, int N) { return icp_team_shares(opts, N) ? (size_t)143 * 1024 : (size_t)152 * 1024; }
-int icp_team_workgroups(const IcpOpts &opts)
-{
-    const int cus = device_cus();
-    return opts.teamsHalfGpu ? max(8, cus / 2 / 8 * 8) : cus;
-}
-
-// the plan of a team launch (icp_team_plan_kernel): depends on the pairs' lengths and roles only
-void launch_icp_team_plan(const IcpTeam *team, const int32_t *lenX, const int32_t *lenY, const uint8_t *swap, int B, int N,
-                          const IcpOpts &opts, hipStream_t s)
-{
-    IcpTeam t = *team;
-    t.maxWG = min(icp_team_workgroups(opts), team->maxWG);
-    // (records behind the LDS image of the padded length: what a member's share of the queries has to fit, see launch_icp)
-    const size_t imgT = (size_t)((N + kChunk - 1) / kChunk * kChunk) * 12;
-    const size_t roomT = icp_team_room(opts, N);
-    const int recCapT = (opts.adaptiveWindows && N <= 12288 && imgT + 64 * 20 <= roomT) ? (int)((roomT - imgT) / 20 / 64 * 64) : 0;
-    hipLaunchKernelGGL(icp_team_plan_kernel, dim3(1), dim3(256), 0, s, lenX, lenY, swap, B, t, recCapT, opts.pairActive);
 }
 
 hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
@@ -3217,18 +2395,8 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
         p.sortedRaw = 1;
         recWanted = opts.adaptiveWindows;
     } else if (grid != nullptr && grid->mode == 3) {
-        int NP2 = 64;
-        while (NP2 < N) NP2 <<= 1;
-        if ((size_t)NP2 * 8 > 64 * 1024)   // dynamic LDS above 64 KiB needs the attribute (N > 8192)
-            ensure_dynamic_lds(reinterpret_cast<const void *>(&sort_clouds_kernel), 128 * 1024, &g_sortAttr);
-        if (N > kChunkSortMinN && grid->ckey != nullptr) {   // long clouds: several workgroups per sort
-            e = launch_sort_clouds_chunked(X, Y, lenX, lenY, swap, prePose, B, N, grid->axis, grid->sortX, grid->pts,
-                                           grid->sortYsoa, nullptr, grid->ckey, grid->cidx, s, nullptr, grid->dirKeys);
-            if (e != hipSuccess) return e;
-        } else
-        hipLaunchKernelGGL(sort_clouds_kernel, dim3(B, 2), dim3(kSortBlock), (size_t)NP2 * 8, s, X, Y, lenX, lenY,
-                           swap, prePose, N, NP2, grid->axis, (float4 *)grid->sortX, (float4 *)grid->pts, grid->sortYsoa,
-                           (float *)nullptr, 0, grid->dirKeys);
+        e = launch_sort_clouds(X, Y, lenX, lenY, swap, prePose, B, N, grid, false, nullptr, 0, s);   // (icp_prep.hip)
+        if (e != hipSuccess) return e;
         p.sortX = (const float4 *)grid->sortX; p.sortY = (const float4 *)grid->pts; p.sortAxis = grid->axis;
         dirKeys = grid->dirKeys && N >= kSortDirMinN;   // (the sort above chooses a direction only for such clouds, sortdir.hpp)
         p.sortYsoa = grid->sortYsoa;
@@ -3237,8 +2405,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
     } else if (grid != nullptr) {
         // bin the fixed cloud once: cell edge 1 % above the gate radius (rounding head-room)
         const float invh = (float)(1.0 / (1.01 * thres));
-        hipLaunchKernelGGL(grid_build_kernel, dim3(B), dim3(kGridBlock), 0, s, X, Y, lenX, lenY, swap, N,
-                           grid->H, invh, grid->origin, grid->start, grid->cursor, (float4 *)grid->pts);
+        launch_grid_build(X, Y, lenX, lenY, swap, B, N, invh, grid, s);
         p.gridPts = (const float4 *)grid->pts; p.gridStart = grid->start; p.gridOrigin = grid->origin;
         p.gridH = grid->H; p.gridInvH = invh;
     }
@@ -3256,7 +2423,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
         // room for the per-query records behind the LDS image: every query of a pair when one workgroup serves it,
         // the member's own share of the queries in a team (the image of a 10^4-point cloud leaves room for ~1800)
         const size_t img = (size_t)((N + kChunk - 1) / kChunk * kChunk) * 12;
-        const size_t room = p.team.wgPair != nullptr ? icp_team_room(opts, N) : (size_t)152 * 1024;   // dynamic LDS next to the kernel's static LDS (~3 KiB; teams: see kTeamRoom)
+        const size_t room = p.team.wgPair != nullptr ? icp_team_room(opts, N) : (size_t)152 * 1024;   // dynamic LDS next to the kernel's static LDS (~3 KiB; teams: icp_team_room, icp_plan.hip)
         int recCap = 0;
         if (p.team.wgPair != nullptr) {
             if (N <= 12288 && img + 64 * 20 <= room) recCap = (int)((room - img) / 20 / 64 * 64);
@@ -3324,92 +2491,6 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
         p.helpOn = (opts.helpers && maxIter <= kHelpMaxEpoch - 2) ? 1 : 0;
         launch_icp_iters(p, dirKeys, B, 0, maxIter, opts.profile, s);
     }
-    return hipGetLastError();
-}
-
-// both clouds of every pair sorted along the fixed cloud's longest axis, without a pre-pose, with
-// structure-of-arrays images of BOTH: input of the scoring sweep (nn.hip)
-// selfCount (single-workgroup sorts only, N <= kChunkSortMinN): 1 = the kernel counts the valid rows itself, 2 = and
-// forms the smaller-cloud-first flag itself (X = src); lenX / lenY / swap are then not read
-hipError_t launch_sort_clouds_soa(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
-                                  const uint8_t *swap, int B, int N, const GridScratch *grid, hipStream_t s, int selfCount)
-{
-    if (selfCount != 0 && N > kChunkSortMinN) return hipErrorInvalidValue;
-    int NP2 = 64;
-    while (NP2 < N) NP2 <<= 1;
-    if ((size_t)NP2 * 8 > 64 * 1024)
-        ensure_dynamic_lds(reinterpret_cast<const void *>(&sort_clouds_kernel), 128 * 1024, &g_sortAttr);
-    if (N > kChunkSortMinN && grid->ckey != nullptr)   // long clouds: several workgroups per sort (sort.hip)
-        return launch_sort_clouds_chunked(X, Y, lenX, lenY, swap, nullptr, B, N, grid->axis, grid->sortX, grid->pts,
-                                          grid->sortYsoa, grid->sortXsoa, grid->ckey, grid->cidx, s, grid->pairBox, grid->dirKeys);
-    hipLaunchKernelGGL(sort_clouds_kernel, dim3(B, 2), dim3(kSortBlock), (size_t)NP2 * 8, s, X, Y, lenX, lenY, swap,
-                       (const float *)nullptr, N, NP2, grid->axis, (float4 *)grid->sortX, (float4 *)grid->pts,
-                       grid->sortYsoa, grid->sortXsoa, selfCount, grid->dirKeys);
-    return hipGetLastError();
-}
-
-// The batch rule over a SUBSET of the pairs, after the fact (round 5: a frame pair's stage 2 iterates all the candidates of its
-// superset beside stage 1, before it is known which of them are in the batch).  The speculative launch has left every pair's
-// (R, T, rmse) of every iteration in the history and the tallies of the rule over ALL pairs; every pair has rows up to the first
-// iteration s_all at which that rule held (a pair leaves only when it has seen such an iteration, when its trajectory is
-// periodic -- it then writes all remaining rows -- or at the cap), and the rule over a subset holds no later.  This kernel
-// recomputes, per iteration s <= s_all, "every ACTIVE pair converged" from the history's rmse values with the loop's own test
-// (:195-198, :209: rel = (prev - rmse) / prev <= thr, false at iteration 0 and on a NaN) and REWRITES the tallies so that their
-// readers (posefuse.hpp) find the subset's stopping iteration: exactly what a launch with options.d_pair_active would have left.
-__global__ __launch_bounds__(1024) void icp_retally_kernel(IcpCtrl *__restrict__ ctrl, const float *__restrict__ history,
-                                                           const uint8_t *__restrict__ active, int B, int maxIter, float relThr)
-{
-    __shared__ unsigned int bad[4];       // bit s: some active pair is not converged at iteration s
-    __shared__ int limitSh;
-    const int tid = threadIdx.x;
-    if (tid < 4) bad[tid] = tid == 0 ? 1u : 0u;      // (iteration 0: rel = 1, nobody is converged)
-    if (tid < kWave) {                               // the first iteration at which the rule over ALL pairs held (wave 0, 64 tallies a round)
-        int lim = maxIter - 1;
-        for (int s0 = 0; s0 < maxIter; s0 += kWave) {
-            const int s = s0 + tid;
-            bool hit = false;
-            if (s < maxIter) {
-                const unsigned long long t = ctrl->tally[s];
-                hit = (int)(t & 0xffffffffull) == B && (t >> 32) == 0ull;
-            }
-            const unsigned long long m = __ballot(hit);
-            if (m != 0ull) { lim = s0 + __builtin_ctzll(m); break; }
-        }
-        if (tid == 0) limitSh = lim;
-    }
-    __syncthreads();
-    const int lim = limitSh;
-    // one (pair, iteration) per thread and round, pairs fastest (neighbouring threads read neighbouring rows): every test reads
-    // the two rmse values it compares -- no chain through the iterations
-    for (int i = tid; i < B * lim; i += 1024) {
-        const int b = i % B, s = i / B + 1;
-        if (active[b] == 0) continue;
-        const float prev = history[((size_t)(s - 1) * B + b) * kHistStride + 12];
-        const float rm = history[((size_t)s * B + b) * kHistStride + 12];
-        const float rel = (prev - rm) / prev;
-        if (!(rel <= relThr)) atomicOr(&bad[s >> 5], 1u << (s & 31));
-    }
-    __syncthreads();
-    for (int s = tid; s < maxIter; s += 1024) {
-        unsigned long long t = 0ull;                              // beyond s_all: "not everybody has arrived"
-        if (s <= lim) t = (unsigned long long)(unsigned)B | (((bad[s >> 5] >> (s & 31)) & 1u) ? (1ull << 32) : 0ull);
-        ctrl->tally[s] = t;
-    }
-}
-
-hipError_t launch_icp_retally(IcpCtrl *ctrl, const float *history, const uint8_t *active, int B, int maxIter, double relThr,
-                              hipStream_t s)
-{
-    if (maxIter > kHistIters) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(icp_retally_kernel, dim3(1), dim3(1024), 0, s, ctrl, history, active, B, maxIter, (float)relThr);
-    return hipGetLastError();
-}
-
-hipError_t launch_icp_export(IcpState *state, IcpCtrl *ctrl, int B, int stopMode, float *R,
-                             float *T, float *rmse, int32_t *iters, int32_t *converged, hipStream_t s, float *scale)
-{
-    hipLaunchKernelGGL(icp_export_kernel, dim3((B + 127) / 128), dim3(128), 0, s, state, ctrl, B,
-                       stopMode, R, T, rmse, iters, converged, scale);
     return hipGetLastError();
 }
 

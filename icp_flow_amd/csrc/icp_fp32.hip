@@ -20,7 +20,7 @@
 //   rmse         = sqrt(sum w |Xt - y|^2 / clamp(sum w, 1e-9))       :191-192
 // everything fp32 except the 3x3 solve.  Search: the all-pairs LDS scan (same gate decisions and
 // neighbours as every other search).  One workgroup per pair runs all iterations and records
-// (R, T, rmse) per iteration; the epilogue of the speculative mode (icp_resolve_history_kernel)
+// (R, T, rmse) per iteration; the epilogue of the speculative mode (icp_epilogue.hip: icp_resolve_history_kernel)
 // then applies the batch-global rule.  Trajectories of different pairs are independent, so this is
 // exactly the reference's control flow.
 #include "scan.hpp"

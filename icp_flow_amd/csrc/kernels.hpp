@@ -67,7 +67,7 @@ struct IcpHelp {
 // bytes of the control block + everything cleared with it (IcpCtrl, HelpPair[B], tag, owner)
 inline size_t icp_ctrl_bytes(int B);
 
-// Teams (icp.hip): several workgroups share one LARGE pair.  Every member owns a contiguous range
+// Teams (icp.hip; planned by icp_plan.hip): several workgroups share one LARGE pair.  Every member owns a contiguous range
 // of the sorted moving cloud, the 18 moments of an iteration are exchanged through `mom`, and each
 // member solves for the same (R, T) redundantly -- one exchange per iteration, nobody broadcasts.
 #ifndef ICPFLOW_MAX_TEAM
@@ -128,7 +128,7 @@ hipError_t launch_hist_vote_sorted(const float *X, const float *Y, int32_t *nX, 
                                    const PairCountFuse *fuse = nullptr, bool sideBusy = false, const float *boxes = nullptr,
                                    int32_t *work = nullptr, size_t workCap = 0, int32_t *orderOut = nullptr, bool *planned = nullptr);   // work: scratch of the vote's work list (ints), or NULL
 size_t vote_work_capacity(int B, int N);   // ints the work list of a batch can take (0: such batches never use one)
-// sort.hip: several workgroups per long cloud; same outputs as zsort_kernel / sort_clouds_kernel
+// sort.hip: several workgroups per long cloud; same outputs as zsort_kernel (hist.hip) / sort_clouds_kernel (icp_prep.hip)
 constexpr int kChunkSortMinN = 4096;
 constexpr int kPairBoxStride = 24;   // floats per pair of count_pair's boxes (votekey.hpp)
 int chunk_sort_length(int N);
@@ -191,14 +191,14 @@ hipError_t launch_scan_nn(const float *Qp, const float *Tp, int B, int NQ, int N
                           int strideT, const int32_t *lenQ, const int32_t *lenT, int sqrt_dist,
                           int64_t *idx, float *dist, hipStream_t s);
 
-// icp.hip
+// the scratch and the per-call switches of a registration (icp.hip and the files around it)
 constexpr int kOccWords = 1024;   // 32 768 cells per (pair, role) occupancy grid (nn.hip)
 #ifndef ICPFLOW_OCC_RINGS
 #define ICPFLOW_OCC_RINGS 3
 #endif
 constexpr int kOccRings = ICPFLOW_OCC_RINGS;   // ... in that many planes: the cloud dilated once, twice, ...
 constexpr int kSweepShareSlots = 16;   // (query blocks x shares) of a job whose blocks split ALL targets between them (nn.hip)
-struct GridScratch {   // scratch of the exact gated NN searches of the ICP loop (see icp.hip)
+struct GridScratch {   // scratch of the exact gated NN searches of the ICP loop (filled by icp_prep.hip, searched by icp.hip)
     int mode;          // 2 = hashed grid, 3 = sorted sweep
     int H;             // grid: buckets per pair, power of two >= 2N
     float *origin;     // grid: [B,4]
@@ -234,9 +234,8 @@ struct GridScratch {   // scratch of the exact gated NN searches of the ICP loop
     int presorted;     // sortX / pts / sortYsoa / axis already hold both clouds sorted WITHOUT the pre-pose
                        // (scoring sweep ran on this batch): the ICP applies the pre-pose when it loads
 };
-int grid_buckets(int N);
 // per-call switches of the ICP launch (icpflow_options_t, include/icpflow_hip.h); nothing process-global
-struct LaunchProfile;   // icp.hip: HIP-event recorder behind icpflow_profile_t
+struct LaunchProfile;   // device.hip: HIP-event recorder behind icpflow_profile_t
 struct IcpOpts {
     int arith = 0;                 // ICPFLOW_ARITH_*
     bool teams = true;             // several workgroups per large pair when the batch leaves CUs idle
@@ -262,38 +261,59 @@ struct IcpOpts {
     bool twoLaunch = false;        // persistent grids with helpers: drained for a second launch of whole-CU workgroups (ICPFLOW_OPT_TWO_LAUNCH)
     int32_t *splitScratch = nullptr;   // [B + 64] ints: the second launch's pair list, its count and the floor of its rule search (NULL: one launch)
 };
-bool icp_teams_wanted(const IcpTeam *team, const IcpOpts &opts, const GridScratch *grid, int B, int N, int maxIter,
-                      int stopMode, const float *history);
+
+// device.hip: per-device caches (a process may drive several GPUs) -- CU count, and the opt-in of a kernel to more
+// than the default dynamic LDS, which HIP keeps per device -- and the recorder of launch times
+int device_cus();
+void ensure_dynamic_lds(const void *func, int bytes, std::atomic<unsigned long long> *doneMask);
+LaunchProfile *profile_create(int capacity, hipError_t *err);
+void profile_destroy(LaunchProfile *p);
+hipError_t profile_collect(LaunchProfile *p, double *total_ms, int *launches);
+bool profile_start(LaunchProfile *p, hipStream_t s);   // -> false: nothing recorded (no recorder, or it is full)
+void profile_stop(LaunchProfile *p, hipStream_t s);    // after a profile_start that returned true
+
+// icp_prep.hip: the fixed cloud binned, or both clouds sorted, once per registration
+int grid_buckets(int N);
+void launch_grid_build(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY, const uint8_t *swap, int B,
+                       int N, float invh, const GridScratch *grid, hipStream_t s);
+hipError_t launch_sort_clouds(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY, const uint8_t *swap,
+                              const float *prePose, int B, int N, const GridScratch *grid, bool wantXsoa, const float *boxes,
+                              int selfCount, hipStream_t s);
+hipError_t launch_sort_clouds_soa(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
+                                  const uint8_t *swap, int B, int N, const GridScratch *grid, hipStream_t s, int selfCount = 0);
+
+// icp_plan.hip: the plan of a team launch and the host's figures of it
 int icp_team_workgroups(const IcpOpts &opts);
+bool icp_team_shares(const IcpOpts &opts, int N);   // the team kernel with shared window scans
+size_t icp_team_room(const IcpOpts &opts, int N);   // dynamic LDS of a team member (image + records)
 void launch_icp_team_plan(const IcpTeam *team, const int32_t *lenX, const int32_t *lenY, const uint8_t *swap, int B, int N,
                           const IcpOpts &opts, hipStream_t s);
-// icp_fp32.hip: the reference's fp32 operation order (study mode), batch-global stop via the history epilogue
-hipError_t launch_icp_fp32ref(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
-                              const uint8_t *swap, const float *prePose, int B, int N, double thres, int maxIter,
-                              double relThr, IcpState *state, IcpCtrl *ctrl, float *history, float *nnScratch,
-                              hipStream_t s);
+
+// icp.hip: the loop and its launch policy
+bool icp_teams_wanted(const IcpTeam *team, const IcpOpts &opts, const GridScratch *grid, int B, int N, int maxIter,
+                      int stopMode, const float *history);
 hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
                       const uint8_t *swap, const float *prePose, int B, int N, double thres,
                       int maxIter, double relThr, int stopMode, IcpState *state, IcpCtrl *ctrl,
                       const GridScratch *grid, float *history, const IcpTeam *team, const IcpOpts &opts,
                       hipStream_t s);
-hipError_t launch_sort_clouds_soa(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
-                                  const uint8_t *swap, int B, int N, const GridScratch *grid, hipStream_t s, int selfCount = 0);
-LaunchProfile *profile_create(int capacity, hipError_t *err);
-void profile_destroy(LaunchProfile *p);
-hipError_t profile_collect(LaunchProfile *p, double *total_ms, int *launches);
-// per-device caches (a process may drive several GPUs): CU count, and the opt-in of a kernel to more
-// than the default dynamic LDS, which HIP keeps per device
-int device_cus();
-void ensure_dynamic_lds(const void *func, int bytes, std::atomic<unsigned long long> *doneMask);
+// icp_fp32.hip: the reference's fp32 operation order (study mode), batch-global stop via the history epilogue
+hipError_t launch_icp_fp32ref(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
+                              const uint8_t *swap, const float *prePose, int B, int N, double thres, int maxIter,
+                              double relThr, IcpState *state, IcpCtrl *ctrl, float *history, float *nnScratch,
+                              hipStream_t s);
+
+// icp_epilogue.hip: readers of IcpState / IcpCtrl / the history
+hipError_t launch_icp_resolve_history(IcpState *state, IcpCtrl *ctrl, const float *history, int B, int maxIter,
+                                      hipStream_t s);
 hipError_t launch_icp_export(IcpState *state, IcpCtrl *ctrl, int B, int stopMode, float *R,
                              float *T, float *rmse, int32_t *iters, int32_t *converged, hipStream_t s,
                              float *scale = nullptr);
+// between the two launches of a drained grid: the pairs that left still moving (list, meta[0] of them; meta[1]: the floor)
+void launch_icp_split(const IcpCtrl *ctrl, const IcpState *state, int B, int maxIter, int32_t *list, int32_t *meta, hipStream_t s);
 // the batch rule over the pairs flagged in `active`, from the history of a launch that iterated all of them: rewrites the tallies
 hipError_t launch_icp_retally(IcpCtrl *ctrl, const float *history, const uint8_t *active, int B, int maxIter, double relThr,
                               hipStream_t s);
-hipError_t launch_icp_resolve_history(IcpState *state, IcpCtrl *ctrl, const float *history, int B, int maxIter,
-                                      hipStream_t s);
 
 // pose.hip
 hipError_t launch_score_pick(const double *partial, int qblocks, const int32_t *lenA,

@@ -1,5 +1,5 @@
 // posefuse.hpp -- the final pose of a pair straight from what the ICP launch left behind, for the kernels that
-// consume it (roll-back check, select): no icp_resolve_history / compose launches in between.
+// consume it (roll-back check, select): no icp_resolve_history (icp_epilogue.hip) / compose launches in between.
 //
 // After the speculative single launch (icp.hip) every pair has its (R, T, rmse) of every iteration in `history`
 // and the per-iteration tallies say where the reference's batch-global rule stops (the first iteration at which

@@ -1,7 +1,7 @@
 // sort.hip -- sorting LONG clouds (N > 4096) with several workgroups per cloud.
 //
 // The per-pair sorts of the path (by z for the vote, along the fixed cloud's longest axis for the
-// sweeps) run as one bitonic network in the LDS of one workgroup (hist.hip: zsort_kernel, icp.hip:
+// sweeps) run as one bitonic network in the LDS of one workgroup (hist.hip: zsort_kernel, icp_prep.hip:
 // sort_clouds_kernel).  That is the right shape for vehicle-sized clusters, but a 16 384-key network
 // has 105 stages of 8 dependent LDS exchanges per thread (~240 us) and a frame with one wall-sized
 // cluster waits for it twice.  Here a long cloud is cut into chunks of 2048 keys; every chunk is sorted

@@ -141,7 +141,7 @@ const char *icpflow_build_info(void);
 /* (a bit-identity switch, OFF by default: it does not pay -- DESIGN.md 8) ICP of a batch of two to four rounds of half-CU workgroups
  * under the reference's batch-global stop (utils_icp_pytorch3d.py:153-213): the persistent grid is DRAINED once the unfinished pairs
  * fit one CU each (they leave behind their current iteration, still moving), and a second launch gives each of them a 1024-thread
- * workgroup and resumes it at its own iteration from its history rows (icp.hip: icp_split_kernel).  Same sums (added in the order of
+ * workgroup and resumes it at its own iteration from its history rows (icp_epilogue.hip: icp_split_kernel).  Same sums (added in the order of
  * the 64-query units in either kernel), same history: transforms and iteration counts are those of one launch, bit for bit. */
 #define ICPFLOW_OPT_TWO_LAUNCH (1u << 17)
 /* (NOT strictly a bit-identity switch: same neighbours, gate decisions, iteration counts and picks; the queries of a pair are visited in

@@ -41,7 +41,7 @@ def test_tool_is_in_step_with_the_package(path):
             if node.value.id == "_lib" and node.attr == "_L":
                 continue
             assert hasattr(mods[node.value.id], node.attr), f"{os.path.basename(path)}: icp_flow_amd.{node.value.id}.{node.attr} does not exist"
-    # the debug exports a tool calls are the ones the instrumented builds define (icp.hip / nn.hip, #ifdef ICPFLOW_*)
-    csrc = "".join(open(f).read() for f in glob.glob(os.path.join(REPO, "icp_flow_amd", "csrc", "*.hip")))
+    # the debug exports a tool calls are the ones the instrumented builds define (icp_instr.hip / nn.hip, #ifdef ICPFLOW_*)
+    csrc = "".join(open(f).read() for ext in ("*.hip", "*.hpp") for f in glob.glob(os.path.join(REPO, "icp_flow_amd", "csrc", ext)))
     for name in set(re.findall(r"_L\.(icpflow_debug_\w+)", src)):
         assert re.search(r"\b" + name + r"\s*\(", csrc), f"{os.path.basename(path)}: {name} is not defined by any debug build"

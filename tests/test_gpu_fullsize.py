@@ -316,7 +316,7 @@ def test_ticket_dispatch_changes_nothing(shape):
 def test_two_icp_launches_change_nothing(shape):
     """Batches of a few rounds under the reference's batch-global stop (utils_icp_pytorch3d.py:153-213): the persistent grid of
     half-CU workgroups is DRAINED once the unfinished pairs fit one CU each -- they leave behind their current iteration, still
-    moving -- and a second launch (icp.hip icp_split_kernel: the batch rule among the tallies, the list of those pairs) gives each
+    moving -- and a second launch (icp_epilogue.hip icp_split_kernel: the batch rule among the tallies, the list of those pairs) gives each
     a 1024-thread workgroup and resumes it at its own iteration from IcpState and its history rows.  Which iteration a pair is cut
     at depends on timing; nothing else does: the moment sums are added in the order of the 64-query units in either kernel, so
     transforms and iteration count are bit-identical to ONE launch (the default; ICPFLOW_OPT_TWO_LAUNCH switches the two launches on -- it is off because it does not pay), with and without helpers, and

@@ -56,7 +56,7 @@ cp /tmp/tl.txt profiles/${TAG}_frame_pair_native_timeline.txt
   echo "dir_keys_fuzz.py (what differs: the order of the fp64 moment sums); one MI355X, build $B"
   grep -v amdgpu.ids $E/dir_keys_ab.txt; grep -v amdgpu.ids $E/dir_keys_diff.txt; grep -v amdgpu.ids $E/dir_keys_fuzz.txt | tail -3; } > profiles/${TAG}_direction_keys.txt
 { echo "The ICP of batches of a few rounds in ONE launch (default) against two (ICPFLOW_OPT_TWO_LAUNCH: the grid of half-CU workgroups drained once the"
-  echo "unfinished pairs fit one CU each, the rest resumed on whole CUs; icp.hip icp_split_kernel): tools/dbg/two_launch_ab.py, then -- library built with"
+  echo "unfinished pairs fit one CU each, the rest resumed on whole CUs; icp_epilogue.hip icp_split_kernel): tools/dbg/two_launch_ab.py, then -- library built with"
   echo "-DICPFLOW_TAIL_CLOCK -- tools/dbg/help_timeline.py (the one launch: resident owners over its span, the pairs that end it) and"
   echo "tools/dbg/two_launch_stats.py (when the drain happens, what the second launch's pairs take); config 4's shard, one MI355X, build $B"
   grep -v amdgpu.ids $E/two_launch_ab.txt; grep -v amdgpu.ids $E/help_timeline.txt; grep -v amdgpu.ids $E/two_launch_stats.txt; } > profiles/${TAG}_two_launch.txt

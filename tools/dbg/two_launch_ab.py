@@ -1,5 +1,5 @@
 """Developer tool: the ICP of batches larger than the GPU in ONE launch (the default; ICPFLOW_OPT_TWO_LAUNCH switches the two launches on) against two (all pairs to
-iteration kSplitIter, then the pairs still moving; icp.hip icp_split_kernel) -- ICP launch(es) and step per shape, and that
+iteration kSplitIter, then the pairs still moving; icp_epilogue.hip icp_split_kernel) -- ICP launch(es) and step per shape, and that
 transforms and iteration count are the same bits.  SHAPES="1024x2048,8192x2048" REPS=8 python tools/dbg/two_launch_ab.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -1,4 +1,4 @@
-"""Developer tool (library built with -DICPFLOW_TAIL_CLOCK): the ICP of a batch of a few rounds in ONE launch and in two (icp.hip
+"""Developer tool (library built with -DICPFLOW_TAIL_CLOCK): the ICP of a batch of a few rounds in ONE launch and in two (icp_epilogue.hip
 icp_split_kernel: the grid of half-CU workgroups drained, the rest on whole CUs) -- when the drain happens, how many pairs the second
 launch serves, how long they take there against the same pairs in one launch.  B=1024 N=2048 python tools/dbg/two_launch_stats.py"""
 import ctypes, os, sys
