@@ -35,20 +35,11 @@ static_assert(ICPFLOW_SEQ_CROP_NONE == 0 && ICPFLOW_SEQ_CROP_XY == 1 && ICPFLOW_
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = icpflow::kTableThreads;        // the grid: rowerr.hpp's table_grid (icpflow_seq_metrics' rule)
 constexpr int kWaves = kThreads / kWave;
-constexpr int kRowsPerThread = 8;                       // rows a workgroup is sized for: kThreads * kRowsPerThread
-constexpr int kMaxGrid = 256;                           // workgroups at most (a CU each) -- icpflow_seq_metrics' grid
 constexpr int kMaxWords = ICPFLOW_CLASS_MAX_WORDS;      // 64-bit words of a wave's table in LDS: 4 waves x 1024 x 8 B = 32 KB
 constexpr int kMaxClasses = ICPFLOW_CLASS_MAX_ROWS, kMaxBuckets = ICPFLOW_CLASS_MAX_BUCKETS;
 constexpr int kInfo = 2;                                // kept rows of frame 0, rows whose time index is outside [0, F)
-
-int grid_for(int m)
-{
-    const long long per = (long long)kThreads * kRowsPerThread;
-    const long long g = ((long long)m + per - 1) / per;
-    return (int)(g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g);
-}
 
 // what travels with the launch: the rows' classes and the two lists of interior edges
 struct Split {
@@ -88,14 +79,10 @@ __global__ __launch_bounds__(kThreads) void class_table_kernel(const double *__r
             keep = icpflow::crop_keep(crop, pts[3 * i + 0], pts[3 * i + 1], pts[3 * i + 2]);
             const double gx = gt[3 * i + 0], gy = gt[3 * i + 1], gz = gt[3 * i + 2];
             e = icpflow::row_error(gx, gy, gz, pred[3 * i + 0], pred[3 * i + 1], pred[3 * i + 2]).e;
-            speed = sqrt((gx * gx + gy * gy) + gz * gz);
-            // the class row: an integer value of [class_lo, class_lo + G - 2], else the last row (NaN fails every comparison)
-            const double v = cls[i];
-            int g = sp.G - 1;
-            if (v == floor(v) && v >= sp.class_lo && v <= sp.class_lo + (double)(sp.G - 2)) g = (int)(v - sp.class_lo);
-            int s = 0;
-            for (int k = 0; k < sp.S - 1; ++k) s += speed >= sp.speed[k] ? 1 : 0;      // lower edge inclusive; a NaN is bucket 0
-            for (int k = 0; k < sp.E - 1; ++k) split += e >= sp.error[k] ? 1 : 0;
+            speed = icpflow::row_speed(gx, gy, gz);
+            const int g = icpflow::class_row(cls[i], sp.class_lo, sp.G);
+            const int s = icpflow::edge_bucket(speed, sp.speed, sp.S - 1);
+            split = icpflow::edge_bucket(e, sp.error, sp.E - 1);
             c = g * sp.S + s;
         }
         outside += __popcll(__ballot(row && (t < 0 || t >= F)));
@@ -163,14 +150,6 @@ bool within_limits(int G, int S, int E)
     return G <= kMaxClasses && S <= kMaxBuckets && E <= kMaxBuckets && (long long)G * S * (E + 2) <= kMaxWords;
 }
 
-// n interior edges: finite and strictly ascending
-bool edges_ok(const double *h, int n)
-{
-    for (int k = 0; k < n; ++k)
-        if (!std::isfinite(h[k]) || (k > 0 && !(h[k] > h[k - 1]))) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -178,7 +157,7 @@ extern "C" {
 size_t icpflow_seq_class_table_workspace_bytes(int m, int G, int S, int E)
 {
     if (m < 0 || G < 2 || S < 1 || E < 1 || !within_limits(G, S, E)) return 0;
-    return align256((size_t)grid_for(m) * ((size_t)G * S * (E + 2) + kInfo) * sizeof(unsigned long long));
+    return align256((size_t)icpflow::table_grid(m) * ((size_t)G * S * (E + 2) + kInfo) * sizeof(unsigned long long));
 }
 
 int icpflow_seq_class_table(const double *d_points, const int32_t *d_time_indice, const double *d_classes, const double *d_gt_flow,
@@ -203,7 +182,7 @@ int icpflow_seq_class_table(const double *d_points, const int32_t *d_time_indice
     if (!d_table || !d_info || (S > 1 && !h_speed_edges) || (E > 1 && !h_error_edges) ||
         (m > 0 && (!d_points || !d_time_indice || !d_classes || !d_gt_flow || !d_pred_flow)))
         return pointer_error(fn);
-    if (!edges_ok(h_speed_edges, S - 1) || !edges_ok(h_error_edges, E - 1))
+    if (!icpflow::edges_ok(h_speed_edges, S - 1) || !icpflow::edges_ok(h_error_edges, E - 1))
         return report_error(ICPFLOW_E_ARG, "icpflow_seq_class_table: the edges must be finite and strictly ascending");
     const size_t need = icpflow_seq_class_table_workspace_bytes(m, G, S, E);
     if (!d_ws || ws_bytes < need) return workspace_error(fn, "icpflow_seq_class_table_workspace_bytes", d_ws, ws_bytes, need);
@@ -215,7 +194,7 @@ int icpflow_seq_class_table(const double *d_points, const int32_t *d_time_indice
         sp.speed[k] = k < S - 1 ? h_speed_edges[k] : 0.0;
         sp.error[k] = k < E - 1 ? h_error_edges[k] : 0.0;
     }
-    const int grid = grid_for(m);
+    const int grid = icpflow::table_grid(m);
     unsigned long long *partial = (unsigned long long *)d_ws;
     const Crop c = {crop, range_x, range_y, z_min};
     class_table_kernel<<<grid, kThreads, 0, st>>>(d_points, d_time_indice, d_classes, d_gt_flow, d_pred_flow, m, F, c, sp, partial);

@@ -4,6 +4,7 @@
 #include "carver.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,14 @@ inline int pointer_error(const char *fn) { return report_errorf(ICPFLOW_E_ARG, "
 inline int workspace_error(const char *fn, const char *query, const void *ws, size_t have, size_t need)
 {
     return report_errorf(ICPFLOW_E_WORKSPACE, "%s: workspace of %zu bytes, %s says %zu", fn, ws ? have : (size_t)0, query, need);
+}
+
+// n interior edges of a list of buckets (HOST memory): finite and strictly ascending
+inline bool edges_ok(const double *h, int n)
+{
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(h[k]) || (k > 0 && !(h[k] > h[k - 1]))) return false;
+    return true;
 }
 
 // (frame.hip's staging and read-backs, clusterpcd.hip's download and upload: one per host thread each, thread_local)

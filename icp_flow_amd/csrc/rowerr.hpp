@@ -3,8 +3,10 @@
 // sums per segment).  fp64 with numpy's operation order; the files that include this are compiled with -ffp-contract=off
 // (build.py: CFLAGS), so the squares, the two additions, the square root and the division are the separately rounded
 // operations numpy performs, the square root correctly rounded and the division IEEE.
-// crop_keep is the row test of the two kernels that walk a whole sample: seq_metrics_kernel and class_table_kernel
-// (classeval.hip: counts and sums per class, speed bucket and error split).
+// crop_keep is the row test of the kernels that walk a whole sample: seq_metrics_kernel, class_table_kernel (classeval.hip:
+// counts and sums per class, speed bucket and error split) and bucket_table_kernel (bucketeval.hip: per class and speed bucket,
+// with a table per workgroup).  The last two also share the rules below it: a row's speed, its class row, its bucket, and the
+// grid that follows from the number of rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +43,40 @@ __device__ __forceinline__ RowError row_error(double gx, double gy, double gz, f
     const double e = sqrt((dx * dx + dy * dy) + dz * dz);
     const double r = e / (sqrt((gx * gx + gy * gy) + gz * gz) + 1e-20);
     return row_predicates(e, r);
+}
+
+// |gt| in metres per frame: numpy's norm, every operation rounded by itself
+__device__ __forceinline__ double row_speed(double gx, double gy, double gz)
+{
+    return sqrt((gx * gx + gy * gy) + gz * gz);
+}
+
+// the class row of a value: an integer value of [class_lo, class_lo + G - 2], else the last row (NaN fails every comparison)
+__device__ __forceinline__ int class_row(double v, double class_lo, int G)
+{
+    int g = G - 1;
+    if (v == floor(v) && v >= class_lo && v <= class_lo + (double)(G - 2)) g = (int)(v - class_lo);
+    return g;
+}
+
+// the bucket of a value among n ascending interior edges: the number of edges <= v (lower edge inclusive; a NaN is bucket 0)
+__device__ __forceinline__ int edge_bucket(double v, const double *edge, int n)
+{
+    int s = 0;
+    for (int k = 0; k < n; ++k) s += v >= edge[k] ? 1 : 0;
+    return s;
+}
+
+// the grid of the two table kernels: a workgroup of kTableThreads threads per kTableThreads * kTableRowsPerThread rows, at
+// least one and at most kTableMaxGrid (a CU each) -- a function of m alone, never of the device
+constexpr int kTableThreads = 256;
+constexpr int kTableRowsPerThread = 8;
+constexpr int kTableMaxGrid = 256;
+inline int table_grid(int m)
+{
+    const long long per = (long long)kTableThreads * kTableRowsPerThread;
+    const long long g = ((long long)m + per - 1) / per;
+    return (int)(g < 1 ? 1 : g > kTableMaxGrid ? kTableMaxGrid : g);
 }
 
 }  // namespace icpflow

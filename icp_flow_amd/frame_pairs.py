@@ -55,6 +55,11 @@ split (`flow_file`: <split>_icp_flow[_ego], main.py:265-284), `--save-metrics FI
 (main.py:298-312).  Under more than one process the files are dealt round-robin, every rank keeps one record per file, and
 one all_gather and a replay in file order (`merge_sequence_records`) give every rank the single process's table bit for bit.
 
+`--bucketed-epe` (with `--dataset argo`, independent of `--class-table`) prints the bucket-normalised EPE of the Argoverse 2
+2024 challenge: per class a static EPE and a speed-normalised dynamic EPE over 51 speed buckets, and their means, from one more
+pass (icpflow_seq_bucket_table) and one more small read-back; the table rides the same records under more than one process.
+The challenge evaluates the 70 m x 70 m box, `--range-x 35 --range-y 35`.
+
 `--if-verbose` is the reference's verbose loop (utils_debug.debug_frame, utils_flow.flow_evaluation): per frame pair three
 lines (overall, static, dynamic) and the per-segment evaluation, from one more pass over what is resident
 (icpflow_seq_segment_table) and a read-back of two small tables.
@@ -987,25 +992,31 @@ def save_sequence_flow(path, flow_seq, fps, F):
 RECORD_HEAD = 6     # file index, kept0, frame pairs, wall time, evaluation time, save time (the three in microseconds)
 
 
-def sequence_record(index, F, table, kept0, n_pairs, us, classes=None):
+def sequence_record(index, F, table, kept0, n_pairs, us, classes=None, *, buckets=None):
     """One file's numbers as int64 words: RECORD_HEAD words, the F * 36 words of sequence_table (the sums of e as their bits),
-    then the class table's words when there is one.  `us`: (wall, evaluation, save) in microseconds."""
+    then the class table's words when there is one, then the bucket table's (`buckets`, a utils_eval.BucketTable) when there
+    is one.  `us`: (wall, evaluation, save) in microseconds."""
     head = np.array([index, kept0, n_pairs] + [int(round(u)) for u in us], dtype=np.int64)
     parts = [head, np.ascontiguousarray(table, dtype=np.int64).reshape(F * 36)]
     if classes is not None:
         parts.append(classes.words())
+    if buckets is not None:
+        parts.append(buckets.words())
     return np.concatenate(parts)
 
 
-def merge_sequence_records(args, records, total, rank=0, world=1, group=None, device=None, class_shape=None):
+def merge_sequence_records(args, records, total, rank=0, world=1, group=None, device=None, class_shape=None, *, bucket_shape=None):
     """The end of a sharded run_sequences, with no GPU work of its own: ONE all_gather of every rank's records (padded to
     the largest share with rows whose file index is -1; on the device under NCCL, on the host under gloo, chosen as
     run_stream chooses), then -- on every rank -- update_meters and ClassTable.add replayed IN FILE ORDER, which is what a
     single process does: meters and class table are bit-identical to its, whatever the world size and however uneven the
     shares.  records: this rank's sequence_record()s; total: files in all; class_shape: (G, S, E) when the records carry a
-    class table.  -> (metrics, ClassTable or None, rows [total, RECORD_HEAD] of the records' heads in file order)"""
+    class table.  -> (metrics, ClassTable or None, rows [total, RECORD_HEAD] of the records' heads in file order).
+    bucket_shape: (G, S) when the records carry a bucket table behind that; BucketTable.add is replayed in file order like the
+    rest, and the result has a fourth entry, the BucketTable."""
     F = int(args.num_frames)
-    words = RECORD_HEAD + F * 36 + (class_shape[0] * class_shape[1] * (class_shape[2] + 2) if class_shape else 0)
+    class_words = class_shape[0] * class_shape[1] * (class_shape[2] + 2) if class_shape else 0
+    words = RECORD_HEAD + F * 36 + class_words + (bucket_shape[0] * bucket_shape[1] * 3 if bucket_shape else 0)
     share = -(-total // world) if total else 0
     local = np.full((share, words), -1, dtype=np.int64)
     if len(records) > share or any(len(r) != words for r in records):
@@ -1027,12 +1038,17 @@ def merge_sequence_records(args, records, total, rank=0, world=1, group=None, de
         raise RuntimeError(f"the gathered records do not cover files 0 .. {total - 1} once each: {every[:, 0].tolist()}")
     metrics = utils_eval.new_metric_table(F)
     classes = utils_eval.ClassTable.zeros(*class_shape) if class_shape else None
+    buckets = utils_eval.BucketTable.zeros(*bucket_shape) if bucket_shape else None
     for row in every:
         table = np.ascontiguousarray(row[RECORD_HEAD:RECORD_HEAD + F * 36]).reshape(F, 6, 6)
         esum = np.ascontiguousarray(table[:, :, 1]).view(np.float64)
         utils_eval.update_meters(args, metrics, table, esum, int(row[1]))
         if classes is not None:
-            classes.add(utils_eval.ClassTable.from_words(row[RECORD_HEAD + F * 36:], *class_shape, kept0=int(row[1])))
+            classes.add(utils_eval.ClassTable.from_words(row[RECORD_HEAD + F * 36:RECORD_HEAD + F * 36 + class_words], *class_shape, kept0=int(row[1])))
+        if buckets is not None:
+            buckets.add(utils_eval.BucketTable.from_words(row[RECORD_HEAD + F * 36 + class_words:], *bucket_shape, kept0=int(row[1])))
+    if bucket_shape:
+        return metrics, classes, every[:, :RECORD_HEAD], buckets
     return metrics, classes, every[:, :RECORD_HEAD]
 
 
@@ -1053,6 +1069,9 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
     args.ground says (dataset_argo.py:140).
     args.class_table (absent = off; dataset="argo" only): utils_eval.class_table per file, one more pass and one more small
     read-back inside ms_eval_per_sequence, accumulated in file order -> `class_table` (a utils_eval.ClassTable) and `threeway`.
+    args.bucket_table (absent = off; dataset="argo" only): utils_eval.bucket_table per file, one more pass and one more small
+    read-back inside ms_eval_per_sequence, accumulated in file order -> `bucket_table` (a utils_eval.BucketTable) and
+    `bucketed_epe` (utils_eval.bucketed_epe of it); independent of args.class_table.
     args.save_flows (absent = False): after a sequence's evaluation its flow and poses are written to `flow_file(path)`
     (`save_sequence_flow`) -- outside the two times above, reported as ms_save_per_sequence.
     rank / world / group: the files are dealt round-robin (`shard_round_robin`), every rank keeps one record per file and
@@ -1068,6 +1087,9 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
     with_classes = bool(getattr(args, "class_table", None))
     if with_classes and dataset != "argo":
         raise ValueError("class_table goes with dataset='argo' (the other files' sem_labels have no names in the reference)")
+    with_buckets = bool(getattr(args, "bucket_table", None))
+    if with_buckets and dataset != "argo":
+        raise ValueError("bucket_table goes with dataset='argo' (the classes and the buckets are Argoverse 2's)")
     saving = bool(getattr(args, "save_flows", False))
     verbose = bool(getattr(args, "if_verbose", False))
     if world > 1 and verbose:
@@ -1077,6 +1099,8 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
     class_shape = (utils_eval.ARGO_CLASS_ROWS, len(utils_eval.ARGO_SPEED_EDGES) + 1, len(utils_eval.ARGO_ERROR_EDGES) + 1) if with_classes else None
     metrics = utils_eval.new_metric_table(F)
     classes = utils_eval.ClassTable.zeros(*class_shape) if with_classes else None
+    bucket_shape = (utils_eval.ARGO_CLASS_ROWS, len(utils_eval.ARGO_BUCKET_EDGES) + 1) if with_buckets else None
+    buckets = utils_eval.BucketTable.zeros(*bucket_shape) if with_buckets else None
     times, eval_times, save_times, n_pairs, ground, pose_sources = [], [], [], 0, {}, {}
     segments, report_times, records = [], [], []
     for index, path in mine:
@@ -1107,6 +1131,9 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
         one = utils_eval.class_table(args, data, flow_seq) if with_classes else None
         if world == 1 and with_classes:
             classes.add(one)
+        one_b = utils_eval.bucket_table(args, data, flow_seq) if with_buckets else None
+        if world == 1 and with_buckets:
+            buckets.add(one_b)
         t2 = time.perf_counter()
         times.append((t2 - t0) * 1e3)
         eval_times.append((t2 - t1) * 1e3)
@@ -1119,9 +1146,11 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
             save_times.append((time.perf_counter() - t3) * 1e3)
         if world > 1:
             records.append(sequence_record(index, F, table, kept0, pairs_here,
-                                           (times[-1] * 1e3, eval_times[-1] * 1e3, save_times[-1] * 1e3 if saving else 0.0), one))
+                                           (times[-1] * 1e3, eval_times[-1] * 1e3, save_times[-1] * 1e3 if saving else 0.0), one, buckets=one_b))
     if world > 1:
-        metrics, classes, heads = merge_sequence_records(args, records, len(paths), rank, world, group, device, class_shape)
+        merged = merge_sequence_records(args, records, len(paths), rank, world, group, device, class_shape, bucket_shape=bucket_shape)
+        metrics, classes, heads = merged[:3]
+        buckets = merged[3] if with_buckets else None
         n_pairs = int(heads[:, 2].sum())
         times, eval_times = (heads[:, 3] * 1e-3).tolist(), (heads[:, 4] * 1e-3).tolist()
         save_times = (heads[:, 5] * 1e-3).tolist() if saving else []
@@ -1134,6 +1163,8 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
         res.update(ms_save_per_sequence=sum(save_times) / max(len(save_times), 1))
     if with_classes:
         res.update(class_table=classes, threeway=classes.threeway(utils_eval.ARGO_META_GROUPS["BACKGROUND"]))
+    if with_buckets:
+        res.update(bucket_table=buckets, bucketed_epe=utils_eval.bucketed_epe(buckets))
     return res
 
 
@@ -1255,6 +1286,10 @@ def main(argv=None):
     ap.add_argument("--class-table", choices=("meta", "fine"), default=None,
                     help="--protocol reference --dataset argo: per meta category (fine: and per category) and speed bucket n, EPE, "
                          "speed and the error splits, and the three-way EPE, after the reference's table")
+    ap.add_argument("--bucketed-epe", action="store_true",
+                    help="--protocol reference --dataset argo: the bucket-normalised EPE per class of the Argoverse 2 2024 challenge "
+                         "(static EPE and speed-normalised dynamic EPE over 51 speed buckets), after the reference's table; the "
+                         "challenge's region is --range-x 35 --range-y 35")
     ap.add_argument("--save-flows", action="store_true",
                     help="--protocol reference: write every sequence's flow and poses next to its split (<split>_icp_flow[_ego], main.py:265-284)")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
@@ -1262,6 +1297,8 @@ def main(argv=None):
     ns = ap.parse_args(argv)
     if ns.class_table and not (ns.protocol == "reference" and ns.dataset == "argo"):
         raise SystemExit("--class-table goes with --protocol reference --dataset argo (the category names are Argoverse 2's)")
+    if ns.bucketed_epe and not (ns.protocol == "reference" and ns.dataset == "argo"):
+        raise SystemExit("--bucketed-epe goes with --protocol reference --dataset argo (the classes and the buckets are Argoverse 2's)")
     if (ns.save_flows or ns.save_metrics) and ns.protocol != "reference":
         raise SystemExit("--save-flows and --save-metrics go with --protocol reference")
     if ns.dataset == "argo":
@@ -1297,6 +1334,8 @@ def main(argv=None):
             args.if_verbose = True
         if ns.class_table:
             args.class_table = ns.class_table
+        if ns.bucketed_epe:
+            args.bucket_table = True
         if ns.save_flows:
             args.save_flows = True
         shard = dict(rank=rank, world=world) if world > 1 else {}
@@ -1319,6 +1358,9 @@ def main(argv=None):
                 shown = table if ns.class_table == "fine" else table.meta(utils_eval.ARGO_META_GROUPS)
                 res["class_table"] = dict(rows=list(shown.names or utils_eval.ARGO_ROW_NAMES), counts=shown.counts.tolist(),
                                           esum=shown.esum.tolist(), ssum=shown.ssum.tolist())
+            if ns.bucketed_epe:
+                res.pop("bucket_table")
+                print(utils_eval.format_bucketed_epe(res["bucketed_epe"]))
             print(json.dumps(res))
         if world > 1:
             dist.destroy_process_group()

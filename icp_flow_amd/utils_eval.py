@@ -8,7 +8,12 @@ reference's meters are updated row by row.  Pinned by tests/golden/g13_seqeval_*
 Per class, per speed bucket and per error split -- the Argoverse 2 way of reporting, for which the reference carries the
 tables (dataset_argo.py:145-217) and uses six names of them: `class_table` (icpflow_seq_class_table, csrc/classeval.hip), one
 more pass over the rows and one small table back; `ClassTable` adds, groups and prints it, `ClassTable.threeway` is the
-three-way EPE.  The names and groups below are pinned by tests/golden/g16_argo_classes.json."""
+three-way EPE.  The names and groups below are pinned by tests/golden/g16_argo_classes.json.
+
+The bucket-normalised EPE Argoverse 2 has been ranked by since its 2024 challenge (Khatri et al., ECCV 2024): `bucket_table`
+(icpflow_seq_bucket_table, csrc/bucketeval.hip) is one more pass and one table of 33 rows x 51 speed buckets back; `BucketTable`
+adds and groups it, `bucketed_epe` is the metric per challenge class.  A restatement of the published method, unpinned
+against the `bucketed_scene_flow_eval` package (COVERAGE.md, named deviations)."""
 import numpy as np
 
 METRIC_NAMES = ("epe", "accs", "accr", "outlier", "Routlier")
@@ -434,6 +439,161 @@ def format_class_table(table, names=ARGO_ROW_NAMES, groups=ARGO_META_GROUPS, rat
     tw = table.threeway(groups["BACKGROUND"]) if "BACKGROUND" in groups else table.threeway(())
     text.append(f"three-way EPE: {tw['mean']:.6f}, FD: {tw['FD']:.6f} (n {tw['n_FD']}), FS: {tw['FS']:.6f} (n {tw['n_FS']}), "
                 f"BS: {tw['BS']:.6f} (n {tw['n_BS']}); dynamic background rows, in no component: {tw['n_BD']}")
+    return "\n".join(text)
+
+
+# ---- bucket-normalised EPE per class (Argoverse 2, 2024 challenge) ---------------------------------------------------------
+# 51 speed buckets from 50 interior edges in metres per frame: 0.04, ..., 2.0 (0.4 ... 20 m/s at 10 Hz), lower edge
+# inclusive; bucket 0 = [0, 0.04) is "static", bucket 50 = [2.0, inf).  The doubles numpy produces, handed over as they are.
+ARGO_BUCKET_EDGES = tuple(float(x) for x in np.linspace(0.0, 2.0, 51)[1:])
+# the challenge's five classes BY NAME (the publication's taxonomy); rows in no group -- ANIMAL, DOG, OTHER -- are reported
+# as OTHER and enter neither mean
+_ARGO_CHALLENGE_NAMES = {
+    "BACKGROUND": ("UNLABELLED", "BACKGROUND", "BOLLARD", "CONSTRUCTION_BARREL", "CONSTRUCTION_CONE", "MOBILE_PEDESTRIAN_CROSSING_SIGN",
+                   "SIGN", "STOP_SIGN"),
+    "CAR": ("REGULAR_VEHICLE",),
+    "OTHER_VEHICLES": ("ARTICULATED_BUS", "BOX_TRUCK", "BUS", "LARGE_VEHICLE", "MESSAGE_BOARD_TRAILER", "RAILED_VEHICLE", "SCHOOL_BUS",
+                       "TRAFFIC_LIGHT_TRAILER", "TRUCK", "TRUCK_CAB", "VEHICULAR_TRAILER"),
+    "PEDESTRIAN": ("OFFICIAL_SIGNALER", "PEDESTRIAN", "STROLLER", "WHEELCHAIR"),
+    "WHEELED_VRU": ("BICYCLE", "BICYCLIST", "MOTORCYCLE", "MOTORCYCLIST", "WHEELED_DEVICE", "WHEELED_RIDER")}
+assert all(n in ARGO_ROW_NAMES for names in _ARGO_CHALLENGE_NAMES.values() for n in names), "a challenge class names a row that does not exist"
+ARGO_CHALLENGE_GROUPS = {group: tuple(sorted(ARGO_ROW_NAMES.index(n) for n in names)) for group, names in _ARGO_CHALLENGE_NAMES.items()}
+
+
+class BucketTable:
+    """icpflow_seq_bucket_table's numbers on the host: counts int64 [G,S] (class row, speed bucket), esum and ssum float64
+    [G,S] (sums of e and of |gt|), kept0 (kept rows of frame 0), names (one per row, or None)."""
+
+    def __init__(self, counts, esum, ssum, kept0=0, names=None):
+        self.counts = np.array(counts, dtype=np.int64)
+        self.esum, self.ssum = np.array(esum, dtype=np.float64), np.array(ssum, dtype=np.float64)
+        self.kept0 = int(kept0)
+        self.names = tuple(names) if names is not None else None
+        assert self.counts.ndim == 2 and self.esum.shape == self.counts.shape and self.ssum.shape == self.counts.shape
+
+    @classmethod
+    def zeros(cls, G, S):
+        return cls(np.zeros((G, S), np.int64), np.zeros((G, S)), np.zeros((G, S)))
+
+    @classmethod
+    def from_words(cls, words, G, S, kept0=0):
+        """the kernel's int64 [G][S][3] -> BucketTable"""
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.int64).reshape(G, S, 3))
+        return cls(w[:, :, 0], np.ascontiguousarray(w[:, :, 1]).view(np.float64), np.ascontiguousarray(w[:, :, 2]).view(np.float64), kept0)
+
+    def words(self):
+        """-> int64 [G * S * 3], the kernel's layout (the sums as their bits)"""
+        G, S = self.counts.shape
+        w = np.empty((G, S, 3), np.int64)
+        w[:, :, 0], w[:, :, 1], w[:, :, 2] = self.counts, self.esum.view(np.int64), self.ssum.view(np.int64)
+        return w.reshape(-1)
+
+    def add(self, other):
+        """Accumulate another sample's table: integers add exactly, the sums add in call order.  -> self"""
+        if other.counts.shape != self.counts.shape:
+            raise ValueError(f"bucket tables of {other.counts.shape} and {self.counts.shape} do not add")
+        self.counts = self.counts + other.counts
+        self.esum, self.ssum = self.esum + other.esum, self.ssum + other.ssum
+        self.kept0 += other.kept0
+        return self
+
+    def _rows_sum(self, rows):
+        """the rows added in ascending row order -> (counts [S], esum [S], ssum [S])"""
+        S = self.counts.shape[1]
+        counts, esum, ssum = np.zeros(S, np.int64), np.zeros(S), np.zeros(S)
+        for r in sorted(rows):
+            counts, esum, ssum = counts + self.counts[r], esum + self.esum[r], ssum + self.ssum[r]
+        return counts, esum, ssum
+
+    def meta(self, groups):
+        """Rows summed per named group ({name: rows}) in ascending row order; the rows in no group form OTHER, the last
+        row.  -> BucketTable of len(groups) + 1 rows with `names`"""
+        G = self.counts.shape[0]
+        used = [r for rows in groups.values() for r in rows]
+        if len(set(used)) != len(used) or any(not 0 <= r < G for r in used):
+            raise ValueError("meta: every row belongs to at most one group and lies in the table")
+        parts = [self._rows_sum(rows) for rows in groups.values()] + [self._rows_sum(set(range(G)) - set(used))]
+        return BucketTable(np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts]), np.stack([p[2] for p in parts]),
+                           self.kept0, tuple(groups) + ("OTHER",))
+
+
+def bucket_table(args, data, flow_seq, classes=None, speed_edges=ARGO_BUCKET_EDGES, class_lo=ARGO_CLASS_LO, rows=ARGO_CLASS_ROWS):
+    """icpflow_seq_bucket_table on one sample -> BucketTable of `rows` class rows (as for class_table) and len(speed_edges) + 1
+    speed buckets (|scene_flow| in metres per frame, lower edge inclusive), over the rows calculate_metrics counts.  Inputs as
+    for sequence_table; one call, and the one device -> host copy is the table.  There is no CPU path."""
+    import ctypes
+    import torch
+    from . import _lib, utils_loading
+    device = utils_loading._device_for(flow_seq, data["raw_points"], data["scene_flow"])
+    F = int(args.num_frames)
+    raw = data["raw_points"]
+    pts = utils_loading.to_device(raw, torch.float64, device)[:, 0:3].contiguous()
+    m = pts.shape[0]
+    tim = utils_loading.to_device(data["time_indice"], torch.int32, device)
+    cls = utils_loading.to_device(data["classes"] if classes is None else classes, torch.float64, device)
+    gt = utils_loading.to_device(data["scene_flow"], torch.float64, device)[:, 0:3].contiguous()
+    pred = utils_loading.to_device(flow_seq, torch.float32, device)[:, 0:3].contiguous()
+    for name, t in (("time_indice", tim), ("classes", cls), ("scene_flow", gt), ("flow_seq", pred)):
+        if t.shape[0] != m or (name == "classes" and t.dim() != 1):
+            raise ValueError(f"{name}: {tuple(t.shape)} for {m} points")
+    crop, rx, ry, zmin = _crop_arguments(args, raw)
+    G = int(rows)
+    speed = np.ascontiguousarray(speed_edges, dtype=np.float64).reshape(-1)
+    S = len(speed) + 1
+    words = G * S * 3
+    out = torch.empty(max(words, 0) + 2, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        need = int(_lib._L.icpflow_seq_bucket_table_workspace_bytes(m, G, S))
+        ws = _lib.workspace(device, need)
+        _lib.call("icpflow_seq_bucket_table", _lib.ptr(pts), _lib.ptr(tim), _lib.ptr(cls), _lib.ptr(gt), _lib.ptr(pred), m, F, crop, rx, ry,
+                  zmin, float(class_lo), G, speed.ctypes.data_as(ctypes.c_void_p) if len(speed) else None, S, _lib.ptr(out),
+                  ctypes.c_void_p(out.data_ptr() + words * 8), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    host = out.cpu().numpy()             # the one read-back
+    if int(host[words + 1]):
+        raise ValueError(f"{int(host[words + 1])} points have a time index outside [0, {F})")
+    return BucketTable.from_words(host[:words], G, S, kept0=int(host[words]))
+
+
+def bucketed_epe(table, groups=ARGO_CHALLENGE_GROUPS):
+    """The bucket-normalised EPE over whatever was accumulated.  Per class (the groups, then OTHER = the rows in none):
+    `static` = (sum of e) / n of bucket 0, NaN when it is empty; `dynamic` = the plain mean over the non-empty buckets b >= 1 of
+    (sum of e)_b / (sum of |gt|)_b -- the bucket's mean EPE over its mean speed -- NaN when there is none; n_static, n_dynamic
+    (rows) and buckets_used.  `mean_static` and `mean_dynamic` are the means over the groups' classes, a NaN skipped (NaN when
+    every class is NaN); OTHER enters neither.  -> {name: {...} for every class, "mean_static": x, "mean_dynamic": y}"""
+    meta = table.meta(groups)
+    classes = {}
+    with np.errstate(all="ignore"):
+        for k, name in enumerate(meta.names):
+            n, es, ss = meta.counts[k], meta.esum[k], meta.ssum[k]
+            static = float(es[0] / n[0]) if n[0] else float("nan")
+            used = [b for b in range(1, len(n)) if n[b]]
+            ratios = [float(es[b] / ss[b]) for b in used]
+            total = 0.0
+            for r in ratios:
+                total += r
+            dynamic = total / len(ratios) if ratios else float("nan")
+            classes[name] = dict(static=static, dynamic=float(dynamic), n_static=int(n[0]), n_dynamic=int(n[1:].sum()), buckets_used=len(used))
+
+    def mean(key):
+        total, k = 0.0, 0
+        for name in groups:
+            v = classes[name][key]
+            if v == v:
+                total, k = total + v, k + 1
+        return total / k if k else float("nan")
+
+    return dict(classes, mean_static=mean("static"), mean_dynamic=mean("dynamic"))
+
+
+def format_bucketed_epe(result):
+    """bucketed_epe's dict as lines: one per class, then the two means."""
+    text = ["################# Bucket-normalised EPE per class #####################################"]
+    for name, c in result.items():
+        if not isinstance(c, dict):
+            continue
+        text.append(f"{name:>16}, static EPE: {c['static']:.6f} (n {c['n_static']}), dynamic normalised EPE: {c['dynamic']:.6f} "
+                    f"(n {c['n_dynamic']}, {c['buckets_used']} buckets)")
+    text.append(f"mean static EPE: {result['mean_static']:.6f}, mean dynamic normalised EPE: {result['mean_dynamic']:.6f}")
     return "\n".join(text)
 
 

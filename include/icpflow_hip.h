@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* (icpflow_seq_class_table, the per-class and per-speed table of a sample, icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 214 /* (icpflow_seq_bucket_table, the cells of the bucket-normalised EPE per class, icpflow_seq_class_table, the per-class and per-speed table of a sample, icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -910,6 +910,27 @@ int icpflow_egomotion_register_frame_stamped(icpflow_ego_t *ego, const float *d_
  *   ICPFLOW_E_WORKSPACE before anything is written.  m = 0 succeeds with a zero table.  Counts are exact; the two sums of a
  *   cell are a function of the arguments alone -- fixed reduction order, no floating-point atomics (csrc/classeval.hip).
  *   Asynchronous on `stream`.
+ *
+ * icpflow_seq_bucket_table -- the cells behind the bucket-normalised EPE Argoverse 2 has been ranked by since its 2024
+ *   challenge (Khatri et al., "I Can't Believe It's Not Scene Flow!", ECCV 2024), which the reference has no code for: per
+ *   class row and speed bucket the rows, the sum of e and the sum of |gt|, in one more pass over the rows of a sample.  Every
+ *   argument it shares with icpflow_seq_class_table means what it means there, word for word: the row test, the rows that
+ *   count (crop passed, time index in [1, F)), d_info, the class row of a value (not integer-valued or outside
+ *   [class_lo, class_lo + G - 2]: row G - 1) and the speed bucket (the number of h_speed_edges[k], k < S - 1, with
+ *   |gt| >= edge; a NaN is bucket 0) are the same __device__ functions (csrc/rowerr.hpp).  There is no error split.
+ *   d_table int64 [G][S][3]: word 0 the rows of the cell, word 1 the BITS OF the float64 sum of e, word 2 the bits of the
+ *   float64 sum of |gt|.  The metric itself -- per class the static EPE of bucket 0 and the mean over the non-empty buckets
+ *   b >= 1 of (sum of e) / (sum of |gt|) -- is host arithmetic on the table, as are the protocol's 50 edges and its grouping
+ *   of the rows into classes (icp_flow_amd/utils_eval.py: bucketed_epe, ARGO_BUCKET_EDGES, ARGO_CHALLENGE_GROUPS).
+ *   G <= ICPFLOW_BUCKET_MAX_ROWS and S <= ICPFLOW_BUCKET_MAX_BUCKETS, else ICPFLOW_E_LIMIT: a WORKGROUP keeps one table in
+ *   dynamic LDS, 64 x 64 x 3 words = 96 KB at the limits (the Argoverse 2 call needs 33 x 51 x 3 = 5049 words, beyond what
+ *   icpflow_seq_class_table's table per wave holds).  A null pointer, a negative size, F < 1, G < 2, S < 1, a class_lo that is
+ *   no integer value, unsorted or non-finite edges are ICPFLOW_E_ARG before any launch.  The workspace is the caller's:
+ *   icpflow_seq_bucket_table_workspace_bytes(m, G, S) = grid(m) * (G * S * 3 + 2) * 8 bytes rounded up to a multiple of 256,
+ *   grid(m) = ceil(m / 2048) clamped to [1, 256] (0 for arguments the call refuses), 8-byte aligned; nothing in it is read
+ *   before it is written; fewer bytes are ICPFLOW_E_WORKSPACE before anything is written.  m = 0 succeeds with a zero table.
+ *   Counts are exact; the two sums of a cell are a function of the arguments alone -- fixed reduction order, no
+ *   floating-point atomics (csrc/bucketeval.hip).  Asynchronous on `stream`, no host synchronisation, no allocation.
  * ------------------------------------------------------------------------- */
 #define ICPFLOW_SEQ_MAX_FRAMES 16
 #define ICPFLOW_SEQ_OUT_FLOW 0
@@ -943,6 +964,13 @@ int icpflow_seq_class_table(const double *d_points, const int32_t *d_time_indice
                             double range_y, double z_min, double class_lo, int G, const double *h_speed_edges, int S,
                             const double *h_error_edges, int E, int64_t *d_table, int64_t *d_info, void *d_ws,
                             size_t ws_bytes, icpflow_stream_t stream);
+#define ICPFLOW_BUCKET_MAX_ROWS 64
+#define ICPFLOW_BUCKET_MAX_BUCKETS 64
+size_t icpflow_seq_bucket_table_workspace_bytes(int m, int G, int S);
+int icpflow_seq_bucket_table(const double *d_points, const int32_t *d_time_indice, const double *d_classes,
+                             const double *d_gt_flow, const float *d_pred_flow, int m, int F, int crop, double range_x,
+                             double range_y, double z_min, double class_lo, int G, const double *h_speed_edges, int S,
+                             int64_t *d_table, int64_t *d_info, void *d_ws, size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * 8(f)  per-segment evaluation of one labelled cloud of one frame pair: the numbers behind the reference's verbose loop,
