@@ -1102,10 +1102,20 @@ static int hist_icp_core(const float *d_src, const float *d_dst, int B, int N, c
         // from here on the side stream belongs to the caller's stream order (and capture): a failed
         // launch still records the join so that the fork never dangles.  With the counting folded into the sorts
         // nothing on the side stream waits for a kernel of this call: the axis sort counts for itself (selfCount).
-        hipError_t se = launch_sort_clouds_soa(d_src, d_dst, w.lenA, w.lenC, w.swap, B, N, &w.grid, side->stream,
-                                               countInSort ? 2 : 0);
-        // ... and, behind it, the occupancy grids of the two sorted clouds for the scoring's pre-bound (nn.hip)
-        if (se == hipSuccess && score_by_sweep(N, true, o) && o.on(ICPFLOW_OPT_NO_SCORE_PRUNE) && o.on(ICPFLOW_OPT_NO_SCORE_PREBOUND)) {
+        // The occupancy grids of the two clouds for the scoring's pre-bound (nn.hip).  A grid is a function of the cloud's points as
+        // a set, so where one workgroup sorts a cloud (it takes the first n rows as they come) the grids are built from the raw
+        // clouds IN FRONT of the sort, beside the z sort: behind the sort -- which runs starved beside the vote and ends with it --
+        // they were the last 14 us in front of the join that the scoring waits for.  Long clouds: from the sorted images, behind it.
+        const bool wantOcc = score_by_sweep(N, true, o) && o.on(ICPFLOW_OPT_NO_SCORE_PRUNE) && o.on(ICPFLOW_OPT_NO_SCORE_PREBOUND);
+        const bool occFirst = wantOcc && N <= kChunkSortMinN;
+        hipError_t se = hipSuccess;
+        if (occFirst) {
+            se = launch_occupancy_raw(d_src, d_dst, w.lenA, w.lenC, w.swap, B, N, &w.grid, countInSort ? 2 : 0, side->stream);
+            if (se == hipSuccess) w.grid.occReady = 1;
+        }
+        if (se == hipSuccess)
+            se = launch_sort_clouds_soa(d_src, d_dst, w.lenA, w.lenC, w.swap, B, N, &w.grid, side->stream, countInSort ? 2 : 0);
+        if (se == hipSuccess && wantOcc && !occFirst) {
             se = launch_occupancy(&w.grid, B, N, side->stream);
             if (se == hipSuccess) w.grid.occReady = 1;
         }

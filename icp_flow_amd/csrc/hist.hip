@@ -835,13 +835,22 @@ hipError_t launch_u32_to_f32(const uint32_t *in, float *out, size_t n, hipStream
 }
 
 // ---------------------------------------------------------------------------------
-// peaks: separable (z, y, x) running maximum through two scratch volumes, then k
-// rounds of block-wide arg-max on the key (vote << 32 | ~index).
-// One workgroup per pair; the volumes live in global scratch (L2 resident: a demo
-// histogram is 20 KiB, the largest Waymo one 868 KiB) so every size takes the same path.
+// peaks: separable (z, y, x) window maximum through two scratch volumes, then the k
+// largest keys (vote << 32 | ~index) of the bins that equal their window's maximum.
+// One workgroup per pair.  Volumes up to 150 KiB live in LDS (a demo histogram is
+// 20 KiB): votes and z maxima in one step, y and x as running maxima along lines, the
+// top k from a list of the positive survivors.  Larger ones (the largest Waymo one is
+// 868 KiB) live in global scratch, L2 resident: a window read per bin, k rounds of
+// block-wide arg-max.  DESIGN.md 3.20.
 // ---------------------------------------------------------------------------------
 constexpr int kPeakBlock = 1024;
 constexpr int kPeakMaxK = 8;
+constexpr int kPeakList = 512;   // LDS volumes: room for the keys of so many positive survivors (a demo histogram has a few dozen)
+// The three parts of the LDS form that can be left out of a build on their own (developer A/B, -DICPFLOW_PEAK_PARTS=<bits>):
+// 1 fill and z pass in one step, 2 y and x passes as running maxima along lines, 4 top k from the compacted survivors
+#ifndef ICPFLOW_PEAK_PARTS
+#define ICPFLOW_PEAK_PARTS 7
+#endif
 
 // max of V over the window |q - c| <= R along one axis (extent n, `stride` words per step), around flat position f.  With the
 // radius known at compile time the 2R + 1 reads are independent and in flight together -- positions beyond the volume are
@@ -860,6 +869,29 @@ __device__ __forceinline__ uint32_t peak_window_max(const uint32_t *__restrict__
     return m;
 }
 
+// Running maxima along one line (extent n, `stride` words per step, first word `base`): the 2R + 1 outputs s0 .. s0 + 2R from the
+// 4R + 1 inputs s0 - R .. s0 + 3R, every input read once (positions beyond the line clamped onto its edge, as above).  Suffix
+// maxima of the first 2R + 1 inputs towards the middle one, prefix maxima of the last 2R + 1 away from it (van Herk / Gil-Werman):
+// output i is max(suffix i, prefix i) -- 6R + 1 maxima for 2R + 1 outputs instead of 2R each, and one clamp per input.
+template <int R>
+__device__ __forceinline__ void peak_line_max(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, int base, int stride,
+                                              int n, int s0)
+{
+    uint32_t v[4 * R + 1];
+#pragma unroll
+    for (int j = 0; j <= 4 * R; ++j) v[j] = src[base + min(max(s0 - R + j, 0), n - 1) * stride];
+    uint32_t suf[2 * R + 1], pre[2 * R + 1];
+    suf[2 * R] = v[2 * R];
+#pragma unroll
+    for (int j = 2 * R - 1; j >= 0; --j) suf[j] = max(v[j], suf[j + 1]);
+    pre[0] = v[2 * R];
+#pragma unroll
+    for (int j = 1; j <= 2 * R; ++j) pre[j] = max(pre[j - 1], v[2 * R + j]);
+#pragma unroll
+    for (int i = 0; i <= 2 * R; ++i)
+        if (s0 + i < n) dst[base + (s0 + i) * stride] = max(suf[i], pre[i]);
+}
+
 #ifdef ICPFLOW_PEAK_CLOCK
 __device__ unsigned long long g_peakClock[1024][8];
 #define PEAK_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_peakClock[blockIdx.x][k] = wall_clock64(); } while (0)
@@ -874,9 +906,14 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
     uint32_t *__restrict__ wsA, uint32_t *__restrict__ wsB, float *__restrict__ votes,
     int64_t *__restrict__ idx_out, PeakDecode dec)
 {
+    constexpr bool kFillZ = MEM != 0 && (ICPFLOW_PEAK_PARTS & 1) != 0, kLines = MEM != 0 && (ICPFLOW_PEAK_PARTS & 2) != 0,
+                   kList = MEM != 0 && (ICPFLOW_PEAK_PARTS & 4) != 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ unsigned long long red[(kPeakBlock / kWave) * kPeakMaxK];   // the waves' k largest keys
+    // the waves' k largest keys; before them, in the same words, the list of the positive survivors' keys
+    __shared__ unsigned long long red[kList ? kPeakList : (kPeakBlock / kWave) * kPeakMaxK];
     __shared__ unsigned long long chosen[kPeakMaxK];
+    __shared__ unsigned int nSurvivors;
+    static_assert(kPeakList >= (kPeakBlock / kWave) * kPeakMaxK, "the waves' keys reuse the list");
     const int b = blockIdx.x;
     const int L = Lx * Ly * Lz;
     const BinT *h = bins + (size_t)b * L;
@@ -885,7 +922,33 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
     uint32_t *Bv = MEM ? H0 + 2 * (size_t)L : wsB + (size_t)b * L;
     const int tid = threadIdx.x;
     PEAK_STAMP(0);
-    if (MEM) {
+    if (kList && tid == 0) nSurvivors = 0u;
+    if (kFillZ) {
+        // fill and pass z in one step: whoever loads a z column (Lz consecutive words) writes the votes to H0 and the column's
+        // windowed maxima to A -- no barrier and no trip through LDS between the two
+        const int nCol = Lx * Ly;
+        for (int c = tid; c < nCol; c += kPeakBlock) {
+            const int f0 = c * Lz;
+            if (Lz == 3 && radius >= 2) {                         // (the demo's column, the window is all of it)
+                const uint32_t v0 = (uint32_t)h[f0], v1 = (uint32_t)h[f0 + 1], v2 = (uint32_t)h[f0 + 2];
+                const uint32_t m = max(max(v0, v1), v2);
+                H0[f0] = v0; H0[f0 + 1] = v1; H0[f0 + 2] = v2;
+                A[f0] = m; A[f0 + 1] = m; A[f0 + 2] = m;
+            } else if (Lz <= 2 * radius + 1) {                    // the window is the whole column
+                uint32_t m = 0;
+                for (int z = 0; z < Lz; ++z) { const uint32_t v = (uint32_t)h[f0 + z]; H0[f0 + z] = v; m = max(m, v); }
+                for (int z = 0; z < Lz; ++z) A[f0 + z] = m;
+            } else {
+                for (int z = 0; z < Lz; ++z) H0[f0 + z] = (uint32_t)h[f0 + z];
+                for (int z = 0; z < Lz; ++z) {                    // (this thread's own writes: no barrier)
+                    const int lo = max(0, z - radius), hi = min(Lz - 1, z + radius);
+                    uint32_t m = 0;
+                    for (int q = lo; q <= hi; ++q) m = max(m, H0[f0 + q]);
+                    A[f0 + z] = m;
+                }
+            }
+        }
+    } else if (MEM) {
         for (int f = tid; f < L; f += kPeakBlock) H0[f] = (uint32_t)h[f];
         __syncthreads();
     }
@@ -902,7 +965,7 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
         if (y >= Ly) { y -= Ly; ++x; }                           \
     } while (0)
     // pass z: A = max over |dz| <= r of h   (-inf padding == ignore out of range)
-    {
+    if (!kFillZ) {
         int x = x0, y = y0, z = z0;
         for (int f = tid; f < L; f += kPeakBlock) {
             (void)x;
@@ -918,8 +981,31 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
     }
     __syncthreads();
     PEAK_STAMP(2);
+    // passes y and x as running maxima along lines (kernel_size 11): a thread takes one segment of 2r + 1 outputs of one line
+    // (peak_line_max); lines are the fastest index over the threads, which for the x pass means consecutive LDS words.
+    // 41 x 41 x 3: 123 lines of 4 segments, 492 threads busy per pass, 21 reads and 11 writes each
+    const bool lines = kLines && radius == 5;
+    if (lines) {
+        constexpr int W = 2 * 5 + 1;
+        {   // pass y: B = max over |dy| <= r of A; line (x, z) starts at x Ly Lz + z, Lz words per step
+            const int nLines = Lx * Lz, items = nLines * ((Ly + W - 1) / W);
+            for (int it = tid; it < items; it += kPeakBlock) {
+                const int seg = it / nLines, line = it - seg * nLines, x = line / Lz, z = line - x * Lz;
+                peak_line_max<5>(A, Bv, x * LyLz + z, Lz, Ly, seg * W);
+            }
+        }
+        __syncthreads();
+        PEAK_STAMP(3);
+        {   // pass x: A = max over |dx| <= r of B; line (y, z) starts at y Lz + z, Ly Lz words per step
+            const int items = LyLz * ((Lx + W - 1) / W);
+            for (int it = tid; it < items; it += kPeakBlock) {
+                const int seg = it / LyLz, line = it - seg * LyLz;
+                peak_line_max<5>(Bv, A, line, LyLz, Lx, seg * W);
+            }
+        }
+    }
     // pass y: B = max over |dy| <= r of A
-    {
+    if (!lines) {
         int x = x0, y = y0, z = z0;
         for (int f = tid; f < L; f += kPeakBlock) {
             (void)x;
@@ -933,10 +1019,12 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
             ICPFLOW_PEAK_ADVANCE();
         }
     }
-    __syncthreads();
-    PEAK_STAMP(3);
+    if (!lines) {
+        __syncthreads();
+        PEAK_STAMP(3);
+    }
     // pass x: A = max over |dx| <= r of B  -> full 3-D window maximum
-    {
+    if (!lines) {
         int x = x0, y = y0, z = z0;
         for (int f = tid; f < L; f += kPeakBlock) {
             uint32_t m = 0;
@@ -957,9 +1045,62 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
     // global top k is a subset of the union of the waves' top k); one barrier; wave 0 then picks the k largest of those
     // 16 k keys -- one barrier instead of two per round.  A thread's keys are distinct, so when its best one was taken
     // its next one is the largest below it.
+    //
+    // LDS volumes: only a local maximum can have a positive surviving vote, and there are a few dozen.  One pass appends the
+    // keys of the positive survivors to a list (a wave's survivors take their places by ballot and popcount, one LDS atomic
+    // per wave and 64 bins); wave 0 takes the k largest of the list -- by key, so the list's order does not matter -- and,
+    // with fewer than k of them, gives the remaining places to the lowest flat indices that are not positive survivors (their
+    // surviving vote is 0: among the first k + n bins there are k of them).  More positive survivors than the list holds (a
+    // plateau: every bin survives) take the waves' path below; the count decides for the whole workgroup.
     const int lane = tid & (kWave - 1), wave = tid >> 6;
+    bool listed = false;
+    if constexpr (kList) {
+        for (int f0 = wave * kWave; f0 < L; f0 += kPeakBlock) {    // (wave-uniform trips: the ballot sees whole waves)
+            const int f = f0 + lane;
+            uint32_t v = 0u;
+            bool surv = false;
+            if (f < L) { v = H0[f]; surv = v != 0u && v == A[f]; }
+            const unsigned long long mask = __ballot(surv);
+            if (mask != 0ull) {
+                unsigned int at = 0u;
+                if (lane == 0) at = atomicAdd(&nSurvivors, (unsigned int)__popcll(mask));
+                at = (unsigned int)__builtin_amdgcn_readfirstlane((int)at) + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
+                if (surv && at < (unsigned int)kPeakList)
+                    red[at] = ((unsigned long long)v << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)f);
+            }
+        }
+        __syncthreads();
+        PEAK_STAMP(5);
+        const int n = (int)nSurvivors;
+        listed = n <= kPeakList;
+        if (listed && wave == 0) {
+            unsigned long long below = ~0ull, best = 0ull;
+            bool stale = true;
+            const int top = min(n, k);
+            for (int r = 0; r < top; ++r) {
+                if (stale) {
+                    best = 0ull;
+                    for (int j = lane; j < n; j += kWave) {
+                        const unsigned long long key = red[j];
+                        if (key < below && key > best) best = key;
+                    }
+                    stale = false;
+                }
+                const unsigned long long w = wave_max_u64_dpp(best);
+                if (lane == 0) chosen[r] = w;
+                if (w == best && w != 0ull) { below = best; stale = true; }
+            }
+            if (n < k) {
+                bool zero = false;
+                if (lane < L) { const uint32_t v = H0[lane]; zero = !(v != 0u && v == A[lane]); }
+                const unsigned long long mask = __ballot(zero);
+                const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+                if (zero && rank < k - n) chosen[n + rank] = (unsigned long long)(0xFFFFFFFFu - (uint32_t)lane);
+            }
+        }
+    }
     unsigned long long *wtop = reinterpret_cast<unsigned long long *>(red);   // [waves][kPeakMaxK], see the declaration
-    {
+    if (!listed) {
         unsigned long long below = ~0ull, best = 0ull;
         bool stale = true;
         for (int r = 0; r < k; ++r) {
@@ -979,9 +1120,9 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
             if (w == best && w != 0ull) { below = best; stale = true; }   // mine was taken: look for my next one
         }
     }
-    __syncthreads();
-    PEAK_STAMP(5);
-    if (wave == 0) {
+    if (!listed) __syncthreads();
+    if (!kList) PEAK_STAMP(5);
+    if (!listed && wave == 0) {
         constexpr int kWaves = kPeakBlock / kWave;
         // candidate c = lane, lane + 64, ... of the kWaves * k keys (at most two per lane)
         unsigned long long c0 = 0ull, c1 = 0ull;

@@ -170,6 +170,10 @@ hipError_t launch_sweep_check(const GridScratch *grid, const float *X, const flo
                               const uint8_t *active = nullptr, const double *initSum = nullptr);
 // after launch_sort_clouds_soa on the same stream: the occupancy grids of both sorted clouds (GridScratch.occHdr / occBits)
 hipError_t launch_occupancy(const GridScratch *grid, int B, int N, hipStream_t s);
+// ... the same grids from the clouds as they come in (X src, Y dst, lengths / roles / selfCount as launch_sort_clouds_soa takes them), for
+// clouds that ONE workgroup sorts (N <= kChunkSortMinN): independent of the sort, to be launched in front of it
+hipError_t launch_occupancy_raw(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY, const uint8_t *swap, int B, int N,
+                                const GridScratch *grid, int selfCount, hipStream_t s);
 hipError_t launch_sweep_score(const GridScratch *grid, const int32_t *lenA, const int32_t *lenC, const uint8_t *swap,
                               int B, int N, const float *cand, double *partial, hipStream_t s);
 hipError_t launch_sweep_score_pruned(const GridScratch *grid, const int32_t *lenA, const int32_t *lenC,

@@ -1284,18 +1284,54 @@ __device__ __forceinline__ uint32_t occ_shifted(const uint32_t *in, int w, int s
     return r == 0 ? hi : ((hi >> r) | (hi1 << (32 - r)));
 }
 
+//
+// RAW: the same grids from the clouds as they come in ([B, N, 4] rows, X the src and Y the dst cloud), for a launch that must not wait
+// for the sort: the rows the sort takes (the first n of the role's cloud: sort_clouds_kernel, lengths and roles formed the same way,
+// selfCount as there) are the points of its image, and the grid is a function of the SET of points -- minima, maxima and bits set
+// by atomicOr -- so it is the same grid, bit for bit.
+template <bool RAW>
 __global__ __launch_bounds__(kOccBlock) void occ_build_kernel(const float *__restrict__ Xsoa, const float *__restrict__ Ysoa,
-                                                            int NP16, float *__restrict__ hdrOut, uint32_t *__restrict__ bitsOut)
+                                                            int NP16, float *__restrict__ hdrOut, uint32_t *__restrict__ bitsOut,
+                                                            const int32_t *__restrict__ lenX, const int32_t *__restrict__ lenY,
+                                                            const uint8_t *__restrict__ swap, int selfCount)
 {
     __shared__ uint32_t bitsA[kOccWords], bitsB[kOccWords];
     __shared__ float red[6 * (kOccBlock / kWave)];
     __shared__ float hd[8];
     const int b = blockIdx.x, which = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-    const float *px = (which == 0 ? Xsoa : Ysoa) + (size_t)b * 3 * NP16, *py = px + NP16, *pz = py + NP16;
+    // SoA image: NP16 rows per coordinate; raw rows: the first `rows` float4 of the role's cloud (NP16 is N then), 4 floats apart
+    const float *px, *py, *pz;
+    int rows = NP16;
+    constexpr int kStep = RAW ? 4 : 1;
+    if (RAW) {
+        int cX, cY;
+        bool sw;
+        if (selfCount) {
+            __shared__ int cntScratch[2 * (kOccBlock / kWave)];
+            const float4 *qx = reinterpret_cast<const float4 *>(Xsoa) + (size_t)b * NP16;
+            const float4 *qy = reinterpret_cast<const float4 *>(Ysoa) + (size_t)b * NP16;
+            int c[2] = {0, 0};
+            for (int i = tid; i < NP16; i += kOccBlock) {
+                c[0] += (qx[i].w > 0.0f) ? 1 : 0;
+                c[1] += (qy[i].w > 0.0f) ? 1 : 0;
+            }
+            block_sum<2, int>(c, cntScratch);
+            cX = c[0]; cY = c[1];
+            sw = selfCount == 2 && cX > cY;
+        } else {
+            cX = lenX[b]; cY = lenY[b];
+            sw = swap != nullptr && swap[b] != 0;
+        }
+        const bool fromY = (which == 0) == sw;   // which 0: the moving role's cloud (X unless swapped), 1: the fixed role's
+        px = (fromY ? Ysoa : Xsoa) + (size_t)b * NP16 * 4; py = px + 1; pz = px + 2;
+        rows = fromY ? cY : cX;
+    } else {
+        px = (which == 0 ? Xsoa : Ysoa) + (size_t)b * 3 * NP16; py = px + NP16; pz = py + NP16;
+    }
     for (int k = tid; k < kOccWords; k += kOccBlock) bitsA[k] = 0u;
     float mn[3] = {kInf, kInf, kInf}, mx[3] = {-kInf, -kInf, -kInf};
-    for (int i = tid; i < NP16; i += kOccBlock) {
-        const float x = px[i], y = py[i], z = pz[i];
+    for (int i = tid; i < rows; i += kOccBlock) {
+        const float x = px[i * kStep], y = py[i * kStep], z = pz[i * kStep];
         if (fabsf(x) < 1e30f && fabsf(y) < 1e30f && fabsf(z) < 1e30f) {   // (pads are +inf; NaN rows fail too: they are no target anybody is near)
             mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
             mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
@@ -1347,8 +1383,8 @@ __global__ __launch_bounds__(kOccBlock) void occ_build_kernel(const float *__res
     const float gox = hd[0], goy = hd[1], goz = hd[2], ginv = hd[3];
     const int gnx = __float_as_int(hd[5]), gny = __float_as_int(hd[6]), gnz = __float_as_int(hd[7]);
     if (gnx > 0) {
-        for (int i = tid; i < NP16; i += kOccBlock) {
-            const float x = px[i], y = py[i], z = pz[i];
+        for (int i = tid; i < rows; i += kOccBlock) {
+            const float x = px[i * kStep], y = py[i * kStep], z = pz[i * kStep];
             if (!(fabsf(x) < 1e30f && fabsf(y) < 1e30f && fabsf(z) < 1e30f)) continue;
             // the cell, kept kOccRings cells inside the grid (rounding at the box's faces): every dilation stays inside, and a
             // shift of the bit array by one cell along any axis never carries a bit across a face
@@ -1382,7 +1418,17 @@ hipError_t launch_occupancy(const GridScratch *grid, int B, int N, hipStream_t s
 {
     if (grid->occHdr == nullptr || grid->occBits == nullptr || grid->sortXsoa == nullptr || grid->sortYsoa == nullptr) return hipSuccess;
     const int NP16 = (N + kChunk - 1) / kChunk * kChunk;
-    hipLaunchKernelGGL(occ_build_kernel, dim3(B, 2), dim3(kOccBlock), 0, s, grid->sortXsoa, grid->sortYsoa, NP16, grid->occHdr, grid->occBits);
+    hipLaunchKernelGGL(occ_build_kernel<false>, dim3(B, 2), dim3(kOccBlock), 0, s, grid->sortXsoa, grid->sortYsoa, NP16, grid->occHdr, grid->occBits,
+                       (const int32_t *)nullptr, (const int32_t *)nullptr, (const uint8_t *)nullptr, 0);
+    return hipGetLastError();
+}
+
+// ... of the clouds as they come in (X src, Y dst: the arguments of launch_sort_clouds_soa, whose sort it need not wait for)
+hipError_t launch_occupancy_raw(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY, const uint8_t *swap, int B, int N,
+                                const GridScratch *grid, int selfCount, hipStream_t s)
+{
+    if (grid->occHdr == nullptr || grid->occBits == nullptr || grid->sortXsoa == nullptr || grid->sortYsoa == nullptr) return hipSuccess;
+    hipLaunchKernelGGL(occ_build_kernel<true>, dim3(B, 2), dim3(kOccBlock), 0, s, X, Y, N, grid->occHdr, grid->occBits, lenX, lenY, swap, selfCount);
     return hipGetLastError();
 }
 

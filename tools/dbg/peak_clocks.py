@@ -17,7 +17,9 @@ assert _lib._L.icpflow_debug_peak_clock(buf.ctypes.data) == 0
 c = buf[:256].astype(np.int64)
 t0 = c[:, 0].min()
 print("blocks start %.1f .. %.1f us; end %.1f .. %.1f us after the first" % ((c[:, 0].min() - t0) / 100, (c[:, 0].max() - t0) / 100, (c[:, 6].min() - t0) / 100, (c[:, 6].max() - t0) / 100))
-names = ["fill", "pass z", "pass y", "pass x", "waves' top k", "wave 0's pick"]
-for k, n in enumerate(names):
-    dt = (c[:, k + 1] - c[:, k]) / 100
-    print(f"  {n:14s} median {np.median(dt):6.2f} us   max {dt.max():6.2f}")
+# stamps: 0 start, 2 the votes in LDS and the z maxima (one step; stamp 1 is thread 0 through with its own columns), 3 pass y, 4 pass x,
+# 5 the survivors' list, 6 wave 0's selection (or, past the list's capacity, the waves' top k and wave 0's pick)
+names = [("fill + pass z", 0, 2), ("pass y", 2, 3), ("pass x", 3, 4), ("survivors' list", 4, 5), ("selection", 5, 6)]
+for n, a, b in names:
+    dt = (c[:, b] - c[:, a]) / 100
+    print(f"  {n:16s} median {np.median(dt):6.2f} us   max {dt.max():6.2f}")
