@@ -153,6 +153,11 @@ OPT_FLAGS = {"no_sorted_vote": 1 << 0, "no_side_stream": 1 << 1, "no_eval_sweep"
              "two_launch": 1 << 17,
              # the sweeps' clouds sorted along the fixed cloud's longest axis only (no direction keys: csrc/sortdir.hpp)
              "no_dir_keys": 1 << 18}
+# the switches added under ABI 214 since that table was pinned (same use: `options(no_front_roles=True)`, ICPFLOW_NO_FRONT_ROLES=1)
+OPT_FLAGS_214 = {
+    # hist_icp: axis sort and occupancy grids on the side stream instead of in the vote's own launch (csrc/hist.hip front_roles_kernel)
+    "no_front_roles": 1 << 19}
+_ALL_FLAGS = {**OPT_FLAGS, **OPT_FLAGS_214}
 
 
 class Options(ctypes.Structure):
@@ -311,7 +316,7 @@ def _env_default_flags():
     """Developer convenience: ICPFLOW_<SWITCH>=1 in the environment turns that optimisation off for every call
     that does not say otherwise (parsed here, on the Python side; the library itself reads no environment)."""
     f = 0
-    for name, bit in OPT_FLAGS.items():
+    for name, bit in _ALL_FLAGS.items():
         if os.environ.get("ICPFLOW_" + name.upper(), "0") not in ("0", ""):
             f |= bit
     return f
@@ -355,7 +360,7 @@ def options(search=None, arith=None, profile=None, vote_bins=None, icp_init=None
     if pair_active is not None:     # uint8 [B] device tensor: pairs flagged 0 are not in the batch (hist_icp / hist_icp_eval)
         cur["pair_active"] = pair_active
     for k, v in switches.items():
-        cur["flags"] = (cur["flags"] | OPT_FLAGS[k]) if v else (cur["flags"] & ~OPT_FLAGS[k])
+        cur["flags"] = (cur["flags"] | _ALL_FLAGS[k]) if v else (cur["flags"] & ~_ALL_FLAGS[k])
     stack = getattr(_tls, "stack", None)
     if stack is None:
         stack = _tls.stack = []

@@ -275,7 +275,7 @@ int parse_options(const char *fn, const icpflow_options_t *opt, Opts &o)
         return report_errorf(ICPFLOW_E_ARG, "%s: options.icp_search must be 0..3 (got %d)", fn, opt->icp_search);
     if (opt->icp_arith != ICPFLOW_ARITH_FP64 && opt->icp_arith != ICPFLOW_ARITH_FP32_REFERENCE)
         return report_errorf(ICPFLOW_E_ARG, "%s: options.icp_arith must be 0 or 1 (got %d)", fn, opt->icp_arith);
-    if (opt->flags >> 19) return report_errorf(ICPFLOW_E_ARG, "%s: unknown option flags 0x%x", fn, opt->flags);
+    if (opt->flags >> 20) return report_errorf(ICPFLOW_E_ARG, "%s: unknown option flags 0x%x", fn, opt->flags);
     o.search = opt->icp_search;
     o.arith = opt->icp_arith;
     o.flags = opt->flags;
@@ -468,10 +468,11 @@ int run_icp_and_select(const float *src, const float *dst, Workspace &w, const u
 }
 
 // joinBefore (hist_icp): event after which the side stream has both clouds sorted (w.grid.presorted)
+// roles (hist_icp): the vote's launch sorts them itself and builds the grids (hist.hip front_roles_kernel): nothing to wait for
 int run_init_pose(const float *src, const float *dst, Workspace &w, const uint8_t *swap, int B,
                   int N, const float *ex, int lx, const float *ey, int ly, const float *ez, int lz,
                   float shift, float *Tout, const Opts &o, hipStream_t s, hipEvent_t joinBefore = nullptr,
-                  const PairCountFuse *countFuse = nullptr, bool sideBusy = false)
+                  const PairCountFuse *countFuse = nullptr, bool sideBusy = false, const FrontRoles *roles = nullptr)
 {
     const int lens[3] = {lx, ly, lz};
     // vote with X = dst role, Y = src role (utils_hist.py:69); z-sorted sweep while the sort fits LDS
@@ -481,7 +482,7 @@ int run_init_pose(const float *src, const float *dst, Workspace &w, const uint8_
         ICPFLOW_TRY(launch_hist_vote_sorted(dst, src, w.lenC, w.lenA, B, N, lens, ex, ey, ez, swap, w.zsortC,
                                             w.zsortA, w.bins, w.zckey, w.zcidx, w.voteKey, s, countFuse, sideBusy,
                                             w.grid.pairBox, o.on(ICPFLOW_OPT_NO_VOTE_LIST) ? w.voteWork : nullptr, w.voteWorkCap,
-                                            w.pairOrder, &planned));
+                                            w.pairOrder, &planned, roles));
         if (planned) w.grid.pairOrder = w.pairOrder;   // (the sweeps of this call take the pairs largest first)
     } else
         ICPFLOW_TRY(launch_hist_vote(dst, src, B, N, N, nullptr, nullptr, lens, ex, ey, ez, swap, w.bins, s));
@@ -1092,7 +1093,19 @@ static int hist_icp_core(const float *d_src, const float *d_dst, int B, int N, c
     JoinGuard guard;   // every return below leaves the side stream joined into s
     const GridScratch *search = search_scratch(w, N, o);
     SideStream *side = nullptr;
-    if (search != nullptr && search->mode == 3 && N >= 64 && o.on(ICPFLOW_OPT_NO_SIDE_STREAM)) {
+    // Where the vote takes its <512, 4> form and ONE workgroup sorts a cloud, the axis sort and the grids are workgroups of the vote's
+    // own launch, in front of the vote's (hist.hip front_roles_kernel): no side stream, no fork, no join -- the scoring follows
+    // the peak search on the same queue.  Every other batch keeps the side stream.
+    const int lens[3] = {len_x, len_y, len_z};
+    const bool sideWanted = search != nullptr && search->mode == 3 && N >= 64 && o.on(ICPFLOW_OPT_NO_SIDE_STREAM);
+    const bool frontRoles = sideWanted && countInSort && o.on(ICPFLOW_OPT_NO_FRONT_ROLES) && vote_front_roles_fit(B, N, lens);
+    FrontRoles roles{};
+    if (frontRoles) {
+        roles.src = d_src; roles.dst = d_dst; roles.lenSrc = w.lenA; roles.lenDst = w.lenC; roles.grid = &w.grid;
+        roles.occ = score_by_sweep(N, true, o) && o.on(ICPFLOW_OPT_NO_SCORE_PRUNE) && o.on(ICPFLOW_OPT_NO_SCORE_PREBOUND);
+        w.grid.presorted = 1;
+        if (roles.occ) w.grid.occReady = 1;
+    } else if (sideWanted) {
         side = &side_stream(s);
         if (!side->ok) side = nullptr;
     }
@@ -1142,10 +1155,10 @@ static int hist_icp_core(const float *d_src, const float *d_dst, int B, int N, c
     }
     w.grid.shareCountClean = 1;   // (cleared with scoreAccum either way; the sweep launches of this call skip their memsets)
     w.grid.sweepTicket = w.ticketScratch;   // (cleared with it as well: the pruned scoring's count of listed scans)
-    const bool sweepScore = score_by_sweep(N, join != nullptr, o);
+    const bool sweepScore = score_by_sweep(N, join != nullptr || frontRoles, o);
     if (int r = run_init_pose(d_src, d_dst, w, w.swap, B, N, d_edges_x, len_x, d_edges_y, len_y, d_edges_z,
                               len_z, decode_shift, w.Tinit, o, s, sweepScore ? join : nullptr,
-                              countInSort ? &fuse : nullptr, join != nullptr))
+                              countInSort ? &fuse : nullptr, join != nullptr, frontRoles ? &roles : nullptr))
         return r;
     if (join != nullptr && !sweepScore) ICPFLOW_TRY(hipStreamWaitEvent(s, join, 0));
     guard.joined();

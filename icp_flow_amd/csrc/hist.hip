@@ -9,6 +9,8 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "votekey.hpp"
+#include "sortclouds.hpp"
+#include "occgrid.hpp"
 
 namespace icpflow {
 
@@ -457,31 +459,32 @@ __global__ __launch_bounds__(kZsortBlock) void zsort_kernel(const float4 *__rest
 // workgroup however idle the SIMD is.  With SPLIT = 2 a workgroup of BLOCK threads holds BLOCK / 2 rows and two waves
 // share each 64 rows, half of the window each: twice the waves per CU (the LDS counters allow four workgroups per CU
 // whatever their size), half the serial chain per wave.
-template <int BLOCK, int SPLIT = 1>
-__global__ __launch_bounds__(BLOCK) void hist_vote_sorted_kernel(
+// (the body of a vote workgroup: block (bx, by) of hist_vote_sorted_kernel's grid, `smem` its dynamic LDS)
+template <int BLOCK, int SPLIT>
+__device__ __forceinline__ void hist_vote_sorted_body(
+    unsigned char *smem, int bx, int by,
     const float4 *__restrict__ Xs, const float4 *__restrict__ Ys, const int32_t *__restrict__ nXv,
     const int32_t *__restrict__ nYv, int N, int len_x, int len_y, int len_z,
     const float *__restrict__ ex, const float *__restrict__ ey, const float *__restrict__ ez,
     const uint8_t *__restrict__ swap, int useLds, uint32_t *__restrict__ bins_u32,
     const float *__restrict__ keyRec, int span, const int32_t *__restrict__ work, int nPairs)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float4 *tile = reinterpret_cast<float4 *>(smem);
     uint32_t *lhist = reinterpret_cast<uint32_t *>(smem + sizeof(float4) * kVoteTile);
     // work list (vote_plan_kernel; a 1-D grid): this workgroup's (pair, row block, share of the Y rows), the workgroups
     // WITH rows first and the largest pairs first -- or nothing at all
     int item = 0;
     if (work != nullptr) {
-        item = work[blockIdx.x];
+        item = work[bx];
         if (item < 0) return;
     }
-    const int b = work != nullptr ? (item & 1023) : (int)blockIdx.y;
+    const int b = work != nullptr ? (item & 1023) : by;
     const VoteKey vk = vote_key_load(keyRec + (size_t)b * kVoteKeyStride);
     const bool sw = swap != nullptr && swap[b] != 0;
     const float4 *xb = (sw ? Ys : Xs) + (size_t)b * N;
     const float4 *yb = (sw ? Xs : Ys) + (size_t)b * N;
     const int nx = (sw ? nYv : nXv)[b], ny = (sw ? nXv : nYv)[b];
-    // blockIdx.x = row block * tsplit + share: on long clouds the Y tiles are dealt to `tsplit` workgroups
+    // bx = row block * tsplit + share: on long clouds the Y tiles are dealt to `tsplit` workgroups
     // per row block (`span` sorted Y rows each), so that one huge pair does not pace the launch
     const int tsplit = (N + span - 1) / span;
     // The rows are sorted by z and a wave's work grows with the number of targets inside its z window: the slabs in the
@@ -492,8 +495,8 @@ __global__ __launch_bounds__(BLOCK) void hist_vote_sorted_kernel(
     constexpr int kRowWaves = kRows / kWave;
     // (with a work list the waves are dealt over the row blocks the pair HAS, not over those of the padded width)
     const int rowBlocks = work != nullptr ? (nx + kRows - 1) / kRows : (N + kRows - 1) / kRows;
-    const int rb = work != nullptr ? ((item >> 10) & 255) : (int)blockIdx.x / tsplit;
-    const int jBegin = (work != nullptr ? (item >> 18) : (int)blockIdx.x % tsplit) * span;
+    const int rb = work != nullptr ? ((item >> 10) & 255) : bx / tsplit;
+    const int jBegin = (work != nullptr ? (item >> 18) : bx % tsplit) * span;
     if (rb * kWave >= nx || jBegin >= ny) return;  // sorted: valid rows first (rb * 64: the first row of wave 0)
     const float min_x = ex[0], max_x = ex[len_x - 1];
     const float min_y = ey[0], max_y = ey[len_y - 1];
@@ -605,6 +608,19 @@ __global__ __launch_bounds__(BLOCK) void hist_vote_sorted_kernel(
     }
 }
 
+template <int BLOCK, int SPLIT = 1>
+__global__ __launch_bounds__(BLOCK) void hist_vote_sorted_kernel(
+    const float4 *__restrict__ Xs, const float4 *__restrict__ Ys, const int32_t *__restrict__ nXv,
+    const int32_t *__restrict__ nYv, int N, int len_x, int len_y, int len_z,
+    const float *__restrict__ ex, const float *__restrict__ ey, const float *__restrict__ ez,
+    const uint8_t *__restrict__ swap, int useLds, uint32_t *__restrict__ bins_u32,
+    const float *__restrict__ keyRec, int span, const int32_t *__restrict__ work, int nPairs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    hist_vote_sorted_body<BLOCK, SPLIT>(smem, (int)blockIdx.x, (int)blockIdx.y, Xs, Ys, nXv, nYv, N, len_x, len_y, len_z, ex, ey, ez,
+                                        swap, useLds, bins_u32, keyRec, span, work, nPairs);
+}
+
 // Work list of the sorted vote on batches of few, wide, RAGGED pairs (a frame's clusters padded to their longest, the ragged
 // real-shape batch): the grid (row blocks of the padded width) x (shares of the padded Y rows) x pairs is 87 % workgroups
 // without rows there -- 50 560 workgroups for 6 000 with work, each holding 36 KiB of LDS and eight waves while it finds that
@@ -661,6 +677,102 @@ __global__ __launch_bounds__(1024) void vote_plan_kernel(const int32_t *__restri
     work[e] = item;
 }
 
+#ifndef ICPFLOW_VOTE_WIDE_N
+#define ICPFLOW_VOTE_WIDE_N 1023
+#endif
+#ifndef ICPFLOW_VOTE_LIST_MIN_N
+#define ICPFLOW_VOTE_LIST_MIN_N 4097
+#endif
+#ifndef ICPFLOW_VOTE_LIST_SPAN
+#define ICPFLOW_VOTE_LIST_SPAN 2048
+#endif
+#ifndef ICPFLOW_VOTE_WIDE_B
+#define ICPFLOW_VOTE_WIDE_B 2
+#endif
+// (launch_hist_vote_sorted's workgroup shapes: the comments there)
+constexpr int kVoteListSpan = ICPFLOW_VOTE_LIST_SPAN;
+constexpr int kVoteWideB = ICPFLOW_VOTE_WIDE_B;   // ... on batches of at most that many pairs per CU
+constexpr int kVoteWideN = ICPFLOW_VOTE_WIDE_N;   // widths above it take the four-waves-per-64-rows variant on small batches
+
+// The vote launch with the workgroups of hist_icp's former side stream in front of its own: ONE grid of 512-thread workgroups,
+// told apart by their place in dispatch order (x runs fastest).  The first `rows` rows of the grid hold, one after the other,
+//   nOcc (B or 0) GRID workgroups: both occupancy grids of one pair's raw clouds (occgrid.hpp), one in waves 0 .. 3, the other
+//       in waves 4 .. 7 -- a workgroup holds one of a CU's four places in LDS whatever it does, and with four of its waves gone
+//       (one grid per workgroup) the place was half used: config 2 0.6050 -> 0.6031 ms per step (profiles/front_roles_ab.txt);
+//   2 B SORT workgroups: one cloud sorted along the fixed cloud's key (sortclouds.hpp), one exchange per thread at 1024 rows;
+//   padding up to the end of the row, which leaves at once;
+// the rows behind them are hist_vote_sorted_kernel<512, 4>'s grid, unchanged.  Lengths and roles come from the z sort, which has
+// finished on the same stream.  The workgroups in front start at once -- beside a vote on a stream of its own the sort's
+// 1024-thread workgroups waited for sixteen free wave slots on CUs that the vote keeps full -- and are long over when the vote
+// is: no second stream, no fork, no join, and the scoring follows the peak search on the same queue.  What they cost is their
+// places: the vote keeps every CU's four full, so the launch is longer than the vote alone by about the places' time (config 2:
+// 98 -> 112 us, against 10 us of join in front of the scoring and 8 us of fork between two steps).  Role rows dealt evenly
+// among the vote's rows instead of in front of them measured the same launch (113 us).  Every role carves the ONE dynamic
+// buffer, sized for the vote.
+struct FrontRoleArgs {
+    const float *X, *Y;                 // the raw clouds [B, N, 4]: X the src, Y the dst cloud (launch_sort_clouds_soa's)
+    const int32_t *lenX, *lenY;
+    int32_t *axisOut;
+    float4 *Xs, *Ys;
+    float *Ysoa, *Xsoa;
+    float *occHdr;
+    uint32_t *occBits;
+    int NP2, dirKeys, nOcc, nSort, rows;
+};
+constexpr int kFrontBlock = 512;
+
+__global__ __launch_bounds__(kFrontBlock) void front_roles_kernel(
+    const float4 *__restrict__ Xs, const float4 *__restrict__ Ys, const int32_t *__restrict__ nXv,
+    const int32_t *__restrict__ nYv, int N, int len_x, int len_y, int len_z,
+    const float *__restrict__ ex, const float *__restrict__ ey, const float *__restrict__ ez,
+    const uint8_t *__restrict__ swap, int useLds, uint32_t *__restrict__ bins_u32,
+    const float *__restrict__ keyRec, int span, int nPairs, FrontRoleArgs r)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if ((int)blockIdx.y < r.rows) {
+        const int id = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+        if (id < r.nOcc) {
+            // both grids of pair `id`: waves 0 .. 3 the moving role's cloud, waves 4 .. 7 the fixed role's, each half with arrays
+            // of its own (the two halves run the same code, hence meet at the same barriers)
+            const int which = (int)threadIdx.x / kOccBlock;
+            uint32_t *bits = reinterpret_cast<uint32_t *>(smem + which * kOccLdsBytes);
+            float *red = reinterpret_cast<float *>(bits + 2 * kOccWords);
+            const OccLds lds{bits, bits + kOccWords, red, red + 6 * (kOccBlock / kWave), nullptr};
+            occ_build_body<true>(lds, id, which, (int)threadIdx.x % kOccBlock, r.X, r.Y, N, r.occHdr, r.occBits, r.lenX, r.lenY, swap, 0);
+        } else if (id < r.nOcc + r.nSort) {
+            const int job = id - r.nOcc;
+            unsigned long long *kv = reinterpret_cast<unsigned long long *>(smem);
+            float *bb = reinterpret_cast<float *>(kv + r.NP2);
+            float *box = bb + 6 * (kFrontBlock / kWave);
+            int *axis = reinterpret_cast<int *>(box + 6);
+            const SortLds lds{kv, bb, box, axis, reinterpret_cast<unsigned int *>(axis + 1), nullptr};
+            sort_clouds_body<kFrontBlock>(lds, job >> 1, (job & 1) != 0, (int)threadIdx.x, r.X, r.Y, r.lenX, r.lenY, swap, nullptr, N,
+                                          r.NP2, r.axisOut, r.Xs, r.Ys, r.Ysoa, r.Xsoa, 0, r.dirKeys);
+        }
+        return;
+    }
+    hist_vote_sorted_body<kFrontBlock, 4>(smem, (int)blockIdx.x, (int)blockIdx.y - r.rows, Xs, Ys, nXv, nYv, N, len_x, len_y, len_z, ex,
+                                          ey, ez, swap, useLds, bins_u32, keyRec, span, nullptr, nPairs);
+}
+
+static size_t vote_lds_bytes(const int lens[3])
+{
+    const size_t L = (size_t)lens[0] * lens[1] * lens[2];
+    return sizeof(float4) * kVoteTile + sizeof(uint32_t) * (L + (size_t)vote_overflow_bins(lens[1], lens[2]));
+}
+
+// the batches whose vote takes the <512, 4> form without a work list, with its counters in LDS, whose clouds ONE workgroup
+// sorts, and whose vote buffer holds the sort's keys and the grids' bit arrays
+bool vote_front_roles_fit(int B, int N, const int lens[3])
+{
+    const size_t lds = vote_lds_bytes(lens);
+    if (lds > 64 * 1024 || N <= kVoteWideN || N > kChunkSortMinN || N >= ICPFLOW_VOTE_LIST_MIN_N || B > kVoteWideB * device_cus())
+        return false;
+    int NP2 = 64;
+    while (NP2 < N) NP2 <<= 1;
+    return (size_t)NP2 * 8 + (size_t)sort_lds_small_bytes(kFrontBlock) <= lds && 2 * (size_t)kOccLdsBytes <= lds;
+}
+
 size_t vote_work_capacity(int B, int N)
 {
     if (N <= 1023 || B > 1024) return 0;   // (the work list serves the four-waves-per-64-rows variant: ICPFLOW_VOTE_WIDE_N)
@@ -673,9 +785,10 @@ hipError_t launch_hist_vote_sorted(const float *X, const float *Y, int32_t *nX, 
                                    const float *ez, const uint8_t *swap, float *sortX, float *sortY,
                                    uint32_t *bins_u32, float *ckey, int *cidx, float *keyRec, hipStream_t s,
                                    const PairCountFuse *fuse, bool sideBusy, const float *boxes, int32_t *work, size_t workCap,
-                                   int32_t *orderOut, bool *planned)
+                                   int32_t *orderOut, bool *planned, const FrontRoles *roles)
 {
     if (planned != nullptr) *planned = false;
+    if (roles != nullptr && !vote_front_roles_fit(B, N, lens)) return hipErrorInvalidValue;   // (the caller asks first)
     if (fuse != nullptr && N > kChunkSortMinN) return hipErrorInvalidValue;   // only zsort_kernel counts
     const size_t L = (size_t)lens[0] * lens[1] * lens[2];
     int NP2 = 64;
@@ -708,21 +821,6 @@ hipError_t launch_hist_vote_sorted(const float *X, const float *Y, int32_t *nX, 
     // small to give every SIMD two waves (a frame's candidate pairs) deal the sorted Y rows of a pair to several
     // workgroups of 1024 rows, `span` Y rows each (64 x 1024: -5 % per registration; on a batch that fills the GPU the extra window
     // searches and counter flushes cost 13 %).
-#ifndef ICPFLOW_VOTE_WIDE_N
-#define ICPFLOW_VOTE_WIDE_N 1023
-#endif
-#ifndef ICPFLOW_VOTE_LIST_MIN_N
-#define ICPFLOW_VOTE_LIST_MIN_N 4097
-#endif
-#ifndef ICPFLOW_VOTE_LIST_SPAN
-#define ICPFLOW_VOTE_LIST_SPAN 2048
-#endif
-    constexpr int kVoteListSpan = ICPFLOW_VOTE_LIST_SPAN;
-#ifndef ICPFLOW_VOTE_WIDE_B
-#define ICPFLOW_VOTE_WIDE_B 2
-#endif
-    constexpr int kVoteWideB = ICPFLOW_VOTE_WIDE_B;   // ... on batches of at most that many pairs per CU
-    constexpr int kVoteWideN = ICPFLOW_VOTE_WIDE_N;   // widths above it take the four-waves-per-64-rows variant on small batches
     const int cus = device_cus();
     const long long wgs256 = (long long)((N + kVoteBlock - 1) / kVoteBlock) * ((N + kVoteSpan * kVoteTile - 1) / (kVoteSpan * kVoteTile)) * B;
     int block = wgs256 >= 4LL * cus ? 512 : kVoteBlock;
@@ -761,6 +859,20 @@ hipError_t launch_hist_vote_sorted(const float *X, const float *Y, int32_t *nX, 
                                (int)U, work, orderOut);
             if (planned != nullptr) *planned = orderOut != nullptr;
             grid = dim3((unsigned)U, 1);
+        }
+        if (roles != nullptr) {   // (never listed: vote_front_roles_fit) the grids and the axis sort in front, in the same launch
+            const GridScratch *g = roles->grid;
+            const bool occ = roles->occ && g->occHdr != nullptr && g->occBits != nullptr && g->sortXsoa != nullptr && g->sortYsoa != nullptr;
+            FrontRoleArgs r{};
+            r.X = roles->src; r.Y = roles->dst; r.lenX = roles->lenSrc; r.lenY = roles->lenDst;
+            r.axisOut = g->axis; r.Xs = (float4 *)g->sortX; r.Ys = (float4 *)g->pts; r.Ysoa = g->sortYsoa; r.Xsoa = g->sortXsoa;
+            r.occHdr = g->occHdr; r.occBits = g->occBits;
+            r.NP2 = NP2; r.dirKeys = g->dirKeys; r.nOcc = occ ? B : 0; r.nSort = 2 * B;
+            r.rows = (r.nOcc + r.nSort + (int)grid.x - 1) / (int)grid.x;
+            hipLaunchKernelGGL(front_roles_kernel, dim3(grid.x, (unsigned)(r.rows + B)), dim3(kFrontBlock), lds_hist, s,
+                               (const float4 *)sortX, (const float4 *)sortY, nX, nY, N, lens[0], lens[1], lens[2], ex, ey,
+                               ez, swap, useLds, bins_u32, keyRec, span, B, r);
+            return hipGetLastError();
         }
         hipLaunchKernelGGL((hist_vote_sorted_kernel<512, 4>), grid, dim3(512), lds_hist, s,
                            (const float4 *)sortX, (const float4 *)sortY, nX, nY, N, lens[0], lens[1], lens[2], ex, ey,

@@ -6,6 +6,7 @@
 // (sort_clouds_kernel is not in sort.hip: beside it, sort.hip's own kernels compile to other code.)
 #include "scan.hpp"
 #include "sortdir.hpp"
+#include "sortclouds.hpp"
 #include "kernels.hpp"
 #include "gridhash.hpp"
 
@@ -97,7 +98,7 @@ void launch_grid_build(const float *X, const float *Y, const int32_t *lenX, cons
 constexpr int kSortBlock = 1024;
 static std::atomic<unsigned long long> g_sortAttr{0ull};   // devices on which sort_clouds_kernel has its dynamic-LDS opt-in
 
-// grid (B, 2): blockIdx.y == 0 sorts the fixed cloud, 1 the moving cloud (pre-pose applied)
+// grid (B, 2): blockIdx.y == 0 sorts the fixed cloud, 1 the moving cloud (pre-pose applied); the body: sortclouds.hpp
 __global__ __launch_bounds__(kSortBlock) void sort_clouds_kernel(
     const float *__restrict__ X, const float *__restrict__ Y, const int32_t *__restrict__ lenX,
     const int32_t *__restrict__ lenY, const uint8_t *__restrict__ swap, const float *__restrict__ prePose,
@@ -105,116 +106,14 @@ __global__ __launch_bounds__(kSortBlock) void sort_clouds_kernel(
     float *__restrict__ Ysoa, float *__restrict__ Xsoa, int selfCount, int dirKeys)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char dynLds[];
-    unsigned long long *kv = reinterpret_cast<unsigned long long *>(dynLds);   // (sort key, row) pairs, NP2 of them
     __shared__ float bb[6 * (kSortBlock / kWave)];
-    __shared__ int axisSh;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const bool moving = blockIdx.y == 1;
-    int cX, cY;
-    bool sw;
-    if (selfCount) {
-        // hist_icp on the side stream, forked before anything has counted: the lengths (rows with a positive flag) and
-        // the smaller-cloud-first flag exactly as count_pair_kernel / zsort_kernel form them; lenX / lenY / swap unread
-        __shared__ int cntScratch[2 * (kSortBlock / kWave)];
-        const float4 *px = reinterpret_cast<const float4 *>(X) + (size_t)b * N;
-        const float4 *py = reinterpret_cast<const float4 *>(Y) + (size_t)b * N;
-        int c[2] = {0, 0};
-        for (int i = tid; i < N; i += kSortBlock) {
-            c[0] += (px[i].w > 0.0f) ? 1 : 0;
-            c[1] += (py[i].w > 0.0f) ? 1 : 0;
-        }
-        block_sum<2, int>(c, cntScratch);
-        cX = c[0]; cY = c[1];
-        sw = selfCount == 2 && cX > cY;
-    } else {
-        cX = lenX[b]; cY = lenY[b];
-        sw = swap != nullptr && swap[b] != 0;
-    }
-    const float4 *xb = reinterpret_cast<const float4 *>(sw ? Y : X) + (size_t)b * N;  // moving role
-    const float4 *yb = reinterpret_cast<const float4 *>(sw ? X : Y) + (size_t)b * N;  // fixed role
-    const int nx = sw ? cY : cX, ny = sw ? cX : cY;
-    // axis of largest extent of the fixed cloud (both blocks compute it the same way)
-    float mn[3] = {kInf, kInf, kInf}, mx[3] = {-kInf, -kInf, -kInf};
-    for (int j = tid; j < ny; j += kSortBlock) {
-        const float4 q = yb[j];
-        mn[0] = fminf(mn[0], q.x); mn[1] = fminf(mn[1], q.y); mn[2] = fminf(mn[2], q.z);
-        mx[0] = fmaxf(mx[0], q.x); mx[1] = fmaxf(mx[1], q.y); mx[2] = fmaxf(mx[2], q.z);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-            mn[k] = fminf(mn[k], __shfl_xor(mn[k], o, kWave));
-            mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o, kWave));
-        }
-    if ((tid & (kWave - 1)) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { bb[(tid >> 6) * 6 + k] = mn[k]; bb[(tid >> 6) * 6 + 3 + k] = mx[k]; }
-    }
-    __syncthreads();
     __shared__ float boxSh[6];
-    if (tid == 0) {
-        float e[3];
-        for (int k = 0; k < 3; ++k) {
-            float lo = bb[k], hi = bb[3 + k];
-            for (int w = 1; w < kSortBlock / kWave; ++w) { lo = fminf(lo, bb[w * 6 + k]); hi = fmaxf(hi, bb[w * 6 + 3 + k]); }
-            e[k] = hi - lo;
-            boxSh[k] = lo; boxSh[3 + k] = hi;
-        }
-        const int a = (e[0] >= e[1] && e[0] >= e[2]) ? 0 : (e[1] >= e[2] ? 1 : 2);
-        axisSh = a;
-    }
-    __syncthreads();
-    // The key that spreads the fixed cloud best (sortdir.hpp): among the three axes and kSortDirs horizontal directions, the one
-    // with the smallest sum of squared populations of 0.1 m key bins -- the longest axis, as before, unless another key is at
-    // least a tenth better (clouds of a thousand points and more: below that every window is short anyway).  Integer counts,
-    // the same on both blocks of the pair.
-    if (dirKeys && ny >= kSortDirMinN && nx >= kSortDirMinMoving) {
-        __shared__ unsigned int scoreSh[kSortCodes];
-        // (the sort has not started: its key array -- NP2 >= 2048 entries of 8 bytes here -- holds the counters)
-        (void)choose_sort_code<kSortBlock>(yb, ny, boxSh, axisSh, reinterpret_cast<unsigned int *>(dynLds), scoreSh, &axisSh);
-    }
-    if (tid == 0 && !moving) axisOut[b] = axisSh;
-    const int axis = axisSh;
-    float dirX = 0.f, dirY = 0.f;
-    if (axis >= 3) sort_dir(axis, dirX, dirY);
-    const int n = moving ? nx : ny;
-    const float4 *cloud = moving ? xb : yb;
-    PointXf pre;
-    pre.kind = (moving && prePose) ? XF_AFFINE : XF_NONE;
-    pre.a = (moving && prePose) ? affine_from_pose(prePose + (size_t)b * 16) : affine_identity();
-    // the sorting network only has to hold THIS cloud: next power of two >= n (ragged batches are
-    // padded to the largest cluster, most clusters are far smaller)
-    int np2 = kWave;
-    while (np2 < n) np2 <<= 1;
-    np2 = min(np2, NP2);
-    for (int j = tid; j < np2; j += kSortBlock) {
-        float k = kInf;
-        if (j < n) {
-            const float4 q = cloud[j];
-            float px, py, pz;
-            xf_apply(pre, q.x, q.y, q.z, px, py, pz);
-            k = sort_key_of(axis, dirX, dirY, px, py, pz);
-        }
-        kv[j] = sort_pack(k, j);
-    }
-    __syncthreads();
-    bitonic_sort_lds(kv, np2);
-    float4 *out = (moving ? Xs : Ys) + (size_t)b * N;
-    const int NP16 = (N + kChunk - 1) / kChunk * kChunk;
-    // structure-of-arrays image (x[], y[], z[], padded with +inf to a multiple of 16): always for the
-    // fixed cloud, for the moving cloud when the caller wants to sweep in both directions (Xsoa)
-    float *soa = moving ? (Xsoa ? Xsoa + (size_t)b * 3 * NP16 : nullptr) : Ysoa + (size_t)b * 3 * NP16;
-    for (int r = tid; r < (soa ? NP16 : n); r += kSortBlock) {
-        float px = kInf, py = kInf, pz = kInf;
-        if (r < n) {
-            const int j = sort_index_of(kv[r]);
-            const float4 q = cloud[j];
-            xf_apply(pre, q.x, q.y, q.z, px, py, pz);
-            out[r] = make_float4(px, py, pz, __int_as_float(j));
-        }
-        if (soa) { soa[r] = px; soa[NP16 + r] = py; soa[2 * NP16 + r] = pz; }
-    }
+    __shared__ int axisSh;
+    __shared__ unsigned int scoreSh[kSortCodes];
+    __shared__ int cntScratch[2 * (kSortBlock / kWave)];
+    const SortLds lds{reinterpret_cast<unsigned long long *>(dynLds), bb, boxSh, &axisSh, scoreSh, cntScratch};
+    sort_clouds_body<kSortBlock>(lds, blockIdx.x, blockIdx.y == 1, threadIdx.x, X, Y, lenX, lenY, swap, prePose, N, NP2, axisOut, Xs,
+                                 Ys, Ysoa, Xsoa, selfCount, dirKeys);
 }
 
 // long clouds, where the scratch has the chunk arrays: several workgroups per sort (sort.hip)

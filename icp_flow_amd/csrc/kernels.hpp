@@ -121,12 +121,26 @@ struct PairCountFuse {
     void *zero0; size_t bytes0;
     void *zero1; size_t bytes1;
 };
+// hist_icp's front in ONE launch (hist.hip front_roles_kernel): the occupancy grids of the raw clouds and the axis sort of
+// launch_sort_clouds_soa(src, dst, lenSrc, lenDst, swap, ...) as workgroups of the vote's launch, in front of the vote's own.
+// lenSrc / lenDst / swap are read on the device behind the z sort (which may be what writes them: PairCountFuse).  Only for
+// batches that vote_front_roles_fit() accepts; leaves grid->sortX / pts / sortYsoa / sortXsoa / axis (and occHdr / occBits with `occ`)
+// as the two launches it replaces do.
+struct GridScratch;
+struct FrontRoles {
+    const float *src, *dst;
+    const int32_t *lenSrc, *lenDst;
+    const GridScratch *grid;
+    bool occ;
+};
+bool vote_front_roles_fit(int B, int N, const int lens[3]);
 hipError_t launch_hist_vote_sorted(const float *X, const float *Y, int32_t *nX, int32_t *nY,
                                    int B, int N, const int lens[3], const float *ex, const float *ey,
                                    const float *ez, const uint8_t *swap, float *sortX, float *sortY,
                                    uint32_t *bins_u32, float *ckey, int *cidx, float *keyRec, hipStream_t s,
                                    const PairCountFuse *fuse = nullptr, bool sideBusy = false, const float *boxes = nullptr,
-                                   int32_t *work = nullptr, size_t workCap = 0, int32_t *orderOut = nullptr, bool *planned = nullptr);   // work: scratch of the vote's work list (ints), or NULL
+                                   int32_t *work = nullptr, size_t workCap = 0, int32_t *orderOut = nullptr, bool *planned = nullptr,
+                                   const FrontRoles *roles = nullptr);   // work: scratch of the vote's work list (ints), or NULL
 size_t vote_work_capacity(int B, int N);   // ints the work list of a batch can take (0: such batches never use one)
 // sort.hip: several workgroups per long cloud; same outputs as zsort_kernel (hist.hip) / sort_clouds_kernel (icp_prep.hip)
 constexpr int kChunkSortMinN = 4096;

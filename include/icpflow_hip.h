@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* (icpflow_seq_bucket_table, the cells of the bucket-normalised EPE per class, icpflow_seq_class_table, the per-class and per-speed table of a sample, icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 214 /* (icpflow_seq_bucket_table, the cells of the bucket-normalised EPE per class, icpflow_seq_class_table, the per-class and per-speed table of a sample, icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed; so is ICPFLOW_OPT_NO_FRONT_ROLES, the axis sort and the occupancy grids as workgroups of the vote's launch) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -151,6 +151,10 @@ const char *icpflow_build_info(void);
  * directions -- that spreads the fixed cloud best (a vehicle heading along an axis shows a face across it: a third of its points on
  * one key).  The searches are exact under any such key: same neighbours, same sums (utils_icp_pytorch3d.py:153-168, utils_hist.py:86-101) */
 #define ICPFLOW_OPT_NO_DIR_KEYS (1u << 18)
+/* (a bit-identity switch) icpflow_hist_icp and the entry points built on it: the axis sort of both clouds and the occupancy grids
+ * run beside the vote on a second stream, forked from and joined into the caller's, instead of as workgroups of the vote's own
+ * launch, in front of the vote's (batches of up to 4096 points per cloud whose vote gives four waves to every 64 rows) */
+#define ICPFLOW_OPT_NO_FRONT_ROLES (1u << 19)
 
 typedef struct icpflow_profile icpflow_profile_t; /* opaque */
 
