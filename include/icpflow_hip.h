@@ -407,9 +407,10 @@ int icpflow_gather_pad(const float *d_points, const int32_t *d_rows, int B, int 
  *
  * icpflow_assoc_collect: the pair rows of both stages, stage 1 first, each in ascending source row: d_rows float32 [cap,10]
  * (source label, destination label, errors, inliers, ratios, ious: utils_match.py:120-131), d_T float32 [cap,16]; rows beyond
- * the matches carry the label -3e38 (no point has it) and the identity.  d_count int32: the number of matches, or -1 when a
- * stage reported an abandoned batch (iteration count < 0).  Labels: float64 tables with `label_stride` doubles per row (the
- * d_table of icpflow_cluster_table).  Stage 2 may be absent (K2 = 0). */
+ * the matches carry the label -3e38 (no point has it) and the identity.  d_count int32: the number of matches written, at most
+ * `cap` (matches beyond the first `cap`, in that order, are dropped), or -1 when a stage reported an abandoned batch
+ * (iteration count < 0).  Labels: float64 tables with `label_stride` doubles per row (the d_table of icpflow_cluster_table).
+ * Stage 2 may be absent (K2 = 0). */
 int icpflow_assoc_assign(const float *d_result, const int32_t *d_si, const int32_t *d_di, int K, const uint8_t *d_active,
                          int S, int D, float translation_frame, float thres_iou, float rot_limit_deg, float thres_error,
                          int32_t *d_best, int K2, const int32_t *d_si2, const int32_t *d_di2, int64_t *d_seg2,
