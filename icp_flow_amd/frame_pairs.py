@@ -30,6 +30,12 @@ independent, main.py:184), and reports ms / frame pair and the reference's accur
 
     python -m icp_flow_amd.frame_pairs DIR [--max-points 10000] [--speed 1.0] [--repeat 3]
 
+`--residual [R]` judges every frame pair WITHOUT ground truth as well: the nearest-neighbour residual of the warped source
+against the destination, truncated at R metres (2.0 when given bare), before and after the registration, both directions
+(`frame_residual`, icpflow_nn_residual); the summary gains a `residual` block and `ms_residual_per_frame_pair`.
+
+    python -m icp_flow_amd.frame_pairs DIR --residual [R] [--in-flight 4]
+
 `run_sequences` (`--protocol reference`) evaluates whole sequence files by the reference's metric protocol instead
 (utils_eval.py:185-368, main.py:173-181, 285-296): the frame pairs of a file as above, their flows assembled on the device
 into the sequence's flow (zeros for frame 0, main.py:217-260), one pass of icpflow_seq_metrics over it and ONE small
@@ -396,7 +402,7 @@ def register_frame_pair_steps(args, fp, device, gap=None, asynchronous=False):
     else:
         flow = utils_flow.flow_estimation_torch(a, flow_src, pd, ls, ld, pairs, T, pose)
     out = dict(pairs=pairs, transformations=T, flow=flow, translation_frame=a.translation_frame, association=a.association_path or "host")
-    if getattr(args, "if_verbose", False):      # what the per-segment report reads besides the flow (run_sequences)
+    if getattr(args, "if_verbose", False) or getattr(args, "residual", None):   # what the per-segment report (run_sequences) and the residual (run_stream) read besides the flow
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -657,7 +663,7 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
     out = dict(pairs=rows[:P], transformations=T[:P], translation_frame=a.translation_frame, association="device")
     if flow is not None:
         out["flow"] = flow
-    if getattr(a, "if_verbose", False):         # what the per-segment report reads besides the flow (run_sequences)
+    if getattr(a, "if_verbose", False) or getattr(a, "residual", None):   # what the per-segment report (run_sequences) and the residual (run_stream) read besides the flow
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -1168,6 +1174,90 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
     return res
 
 
+def residual_groups(labels_src, pairs):
+    """The group of every source row for the residual's table (utils_eval.RESIDUAL_GROUPS): 0 ground (label -1e8), 1 unclustered
+    (-1), 2 clustered but unmatched, 3 matched -- its label is the source label of a row of `pairs` ([P,10], column 0).  Device
+    tensors in, int32 [Ns] on the device out."""
+    matched = torch.isin(labels_src, pairs[:, 0].to(labels_src.dtype)) if pairs.shape[0] else torch.zeros_like(labels_src, dtype=torch.bool)
+    g = torch.where(matched, 3, 2).to(torch.int32)
+    g = torch.where(labels_src == -1.0, torch.ones_like(g), g)
+    return torch.where(labels_src == -1e8, torch.zeros_like(g), g).contiguous()
+
+
+def frame_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
+    """The four residual calls of one registered frame pair and their one read-back: AFTER (the flow's source points -- raw when
+    the pair carries them -- plus the predicted flow against the destination, and the destination against that warped cloud) and
+    BEFORE (the ego-compensated source against the destination with no flow, and back).  The source's rows are grouped by
+    `residual_groups`, the destination's form one group.  -> [after forward, after backward, before forward, before backward],
+    ResidualTables."""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    ls = out.get("labels_src")
+    if ls is None and fp.labels_src is not None:
+        ls = _input(fp, "labels_src", device)
+    if ls is None:
+        raise ValueError("the residual groups the source rows by their cluster labels: the registration must leave labels_src in its result")
+    groups = residual_groups(ls.to(device).float(), out["pairs"].to(device))
+    flow = out["flow"].to(device).float()
+    G = len(utils_eval.RESIDUAL_GROUPS)
+    calls = ((raw, pd, flow, groups, G), (pd, raw[:, 0:3] + flow[:, 0:3], None, None, 1), (ps, pd, None, groups, G), (pd, ps, None, None, 1))
+    words = [utils_eval.nn_residual_device(q, t, f, radius, g, n, edges, per_row=False)[2] for q, t, f, g, n in calls]
+    host = torch.cat(words).cpu().numpy()             # the one read-back
+    tables, at = [], 0
+    for _, _, _, _, n in calls:
+        size = n * (len(edges) + 4)
+        tables.append(utils_eval.ResidualTable.from_words(host[at: at + size], n, tuple(edges), radius, bad=int(host[at + size])))
+        at += size + 4
+    return tables
+
+
+def _residual_flat(tables):
+    """the four tables as one list of numbers for the closing all_reduce (counts are exact in a float64), and back"""
+    flat = []
+    for t in tables:
+        flat += t.rows.tolist() + t.hits.tolist() + t.under.reshape(-1).tolist() + t.dsum.tolist() + t.ddsum.tolist() + [t.bad]
+    return [float(v) for v in flat]
+
+
+def _residual_unflat(flat, like):
+    tables, at = [], 0
+    for t in like:
+        G, E = len(t.rows), len(t.edges)
+        take = lambda k: [flat[at + j] for j in range(k)]   # noqa: E731
+        rows = take(G); at += G
+        hits = take(G); at += G
+        under = take(G * E); at += G * E
+        dsum = take(G); at += G
+        ddsum = take(G); at += G
+        tables.append(utils_eval.ResidualTable(np.rint(rows), np.rint(hits), np.rint(under), dsum, ddsum, t.edges, t.radius, bad=int(round(flat[at]))))
+        at += 1
+    return tables
+
+
+def _residual_zero(radius, edges=utils_eval.RESIDUAL_EDGES):
+    G = len(utils_eval.RESIDUAL_GROUPS)
+    return [utils_eval.ResidualTable.zeros(n, tuple(edges), radius) for n in (G, 1, G, 1)]
+
+
+def residual_block(tables):
+    """[after forward, after backward, before forward, before backward] -> the summary's `residual` block"""
+    af, ab, bf, bb = tables
+    side = lambda f, b: dict(forward=f.summary(utils_eval.RESIDUAL_GROUPS), backward=b.summary(("all",)), chamfer=f.mean() + b.mean())   # noqa: E731
+    words = dict(after_forward=af.words().tolist(), after_backward=ab.words().tolist(), before_forward=bf.words().tolist(),
+                 before_backward=bb.words().tolist())      # the tables themselves (ResidualTable.from_words): runs can be added
+    return dict(radius=af.radius, edges=list(af.edges), groups=list(utils_eval.RESIDUAL_GROUPS), before=side(bf, bb), after=side(af, ab),
+                words=words)
+
+
+def residual_tables(block):
+    """the summary's `residual` block -> (before, after), each dict(forward, backward: ResidualTable), what format_residual takes"""
+    edges, r, G = tuple(block["edges"]), block["radius"], len(block["groups"])
+    table = lambda key, n: utils_eval.ResidualTable.from_words(block["words"][key], n, edges, r)   # noqa: E731
+    return (dict(forward=table("before_forward", G), backward=table("before_backward", 1)),
+            dict(forward=table("after_forward", G), backward=table("after_backward", 1)))
+
+
 def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, register_fn=None, in_flight=1):
     """Register this rank's share of `paths`; -> summary dict (identical on every rank).
     ms / frame pair is the mean wall time per pair, host -> device upload of the clouds included
@@ -1176,7 +1266,12 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     (`register_frame_pair`); the CPU tests of the sharding logic pass the oracle here.
     in_flight > 1 (HIP path only): that many frame pairs at once (`register_in_flight`: one stream and one host thread each, a
     blocking call into the library per frame pair; or the one-thread scheduler with asynchronous hand-overs); ms / frame pair is then the wall time of the whole share over its frame pairs --
-    throughput of the stream, not the latency of one pair."""
+    throughput of the stream, not the latency of one pair.
+    args.residual = r (metres; `--residual [R]`): every frame pair is also judged WITHOUT ground truth -- `frame_residual`, after
+    the pair is registered (and, in flight, delivered) and outside the timed region of one pair at a time; the tables are added
+    in the order of the frame pairs whatever order they complete in, ride the closing all_reduce, and the summary gains a
+    `residual` block and `ms_residual_per_frame_pair` (device-synchronised around the four calls and their read-back).  In flight,
+    ms / frame pair is the wall time of the share and then includes this work."""
     import torch.distributed as dist
     device = torch.device(device)
     pipelined = int(in_flight) > 1 and register_fn is None
@@ -1190,9 +1285,17 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     meter = utils_eval.AverageMeter()
     times, matched = [], 0
     pose_sources = {}
+    radius = getattr(args, "residual", None)
+    residuals, residual_ms = {}, []              # frame pair (its number in this rank's share) -> its four tables
 
-    def account(fp, out):
+    def account(fp, out, index=None):
         nonlocal matched
+        if radius:
+            sync()
+            t0 = time.perf_counter()
+            residuals[len(residuals) if index is None else index] = frame_residual(fp, out, device, float(radius))
+            sync()
+            residual_ms.append((time.perf_counter() - t0) * 1e3)
         pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
         matched += int(out["pairs"].shape[0])
         if fp.gt_flow is not None:
@@ -1205,8 +1308,8 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
         sync()
         t0 = time.perf_counter()
         n = 0
-        for _, fp, out in register_in_flight(args, every, device, in_flight):
-            account(fp, out)
+        for index, fp, out in register_in_flight(args, every, device, in_flight):
+            account(fp, out, index)
             n += 1
         sync()
         times = [(time.perf_counter() - t0) * 1e3 / max(n, 1)] * n
@@ -1223,6 +1326,12 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             account(fp, out)
     # five weighted sums + point count + time + frame pairs + matches: one small all_reduce
     local = [getattr(meter, m + "_sum") for m in utils_eval.METRIC_NAMES] + [meter.num, sum(times), len(times), matched]
+    if radius:
+        total = _residual_zero(float(radius))
+        for index in sorted(residuals):
+            for acc, t in zip(total, residuals[index]):
+                acc.add(t)
+        local = local + [sum(residual_ms)] + _residual_flat(total)
     on_gpu = world > 1 and dist.get_backend(group) == "nccl"
     tot = torch.tensor(local, dtype=torch.float64, device=device if on_gpu else "cpu")
     tmax = torch.tensor([sum(times)], dtype=torch.float64, device=tot.device)
@@ -1238,10 +1347,13 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
            "pose_sources": pose_sources}     # (this rank's frame pairs: "ego_motion_gt" = ground-truth ego poses were used)
     if n_pts > 0:
         out.update({m: tot[k] / n_pts for k, m in enumerate(utils_eval.METRIC_NAMES)})
+    if radius:
+        out["ms_residual_per_frame_pair"] = tot[9] / max(n_fp, 1)
+        out["residual"] = residual_block(_residual_unflat(tot[10:], total) if world > 1 else total)
     return out
 
 
-def main(argv=None):
+def argument_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("directory")
     ap.add_argument("--repeat", type=int, default=1)
@@ -1292,13 +1404,23 @@ def main(argv=None):
                          "challenge's region is --range-x 35 --range-y 35")
     ap.add_argument("--save-flows", action="store_true",
                     help="--protocol reference: write every sequence's flow and poses next to its split (<split>_icp_flow[_ego], main.py:265-284)")
+    ap.add_argument("--residual", type=float, nargs="?", const=2.0, default=None, metavar="R",
+                    help="judge the flow without ground truth: the nearest-neighbour residual of the warped source against the "
+                         "destination, truncated at R metres (2.0 when given bare), before and after the registration, both "
+                         "directions (Chamfer); not with --protocol reference")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
                     help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
-    ns = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    ns = argument_parser().parse_args(argv)
     if ns.class_table and not (ns.protocol == "reference" and ns.dataset == "argo"):
         raise SystemExit("--class-table goes with --protocol reference --dataset argo (the category names are Argoverse 2's)")
     if ns.bucketed_epe and not (ns.protocol == "reference" and ns.dataset == "argo"):
         raise SystemExit("--bucketed-epe goes with --protocol reference --dataset argo (the classes and the buckets are Argoverse 2's)")
+    if ns.residual is not None and ns.protocol == "reference":
+        raise SystemExit("--residual is not built into --protocol reference (COVERAGE.md row 13): run the frame pairs without --protocol")
     if (ns.save_flows or ns.save_metrics) and ns.protocol != "reference":
         raise SystemExit("--save-flows and --save-metrics go with --protocol reference")
     if ns.dataset == "argo":
@@ -1365,8 +1487,12 @@ def main(argv=None):
         if world > 1:
             dist.destroy_process_group()
         return
+    if ns.residual is not None:
+        args.residual = ns.residual
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
+        if ns.residual is not None:
+            print(utils_eval.format_residual(*residual_tables(summary["residual"])))
         print(json.dumps(summary))
     if world > 1:
         dist.destroy_process_group()

@@ -13,7 +13,12 @@ three-way EPE.  The names and groups below are pinned by tests/golden/g16_argo_c
 The bucket-normalised EPE Argoverse 2 has been ranked by since its 2024 challenge (Khatri et al., ECCV 2024): `bucket_table`
 (icpflow_seq_bucket_table, csrc/bucketeval.hip) is one more pass and one table of 33 rows x 51 speed buckets back; `BucketTable`
 adds and groups it, `bucketed_epe` is the metric per challenge class.  A restatement of the published method, unpinned
-against the `bucketed_scene_flow_eval` package (COVERAGE.md, named deviations)."""
+against the `bucketed_scene_flow_eval` package (COVERAGE.md, named deviations).
+
+Without ground truth: `nn_residual` (icpflow_nn_residual, csrc/nnresid.hip) is the truncated nearest-neighbour residual of a
+warped cloud against the next one -- a hashed grid over the whole frame and an exact radius-bounded search on the GPU;
+`ResidualTable` adds and prints it, `chamfer` is the two directions.  A label-free proxy, not a metric of the reference
+(COVERAGE.md, named deviations)."""
 import numpy as np
 
 METRIC_NAMES = ("epe", "accs", "accr", "outlier", "Routlier")
@@ -611,3 +616,180 @@ def save_metrics_file(path, metrics_per_frame, num_frames):
     with open(path, "wb") as f:           # (np.savez would append ".npz" to a name without it)
         np.savez(f, **out)
     return list(out)
+
+
+# ---- judged without ground truth: the truncated nearest-neighbour residual (icpflow_nn_residual, csrc/nnresid.hip) ----------
+RESIDUAL_EDGES = (0.05, 0.1)           # metres: the reference's AccS / AccR distances (utils_eval.py:65-182)
+RESIDUAL_GROUPS = ("ground", "unclustered", "unmatched", "matched")   # run_stream's groups of the source rows
+
+
+class ResidualTable:
+    """icpflow_nn_residual's table on the host, per group of query rows: rows int64 [G] (good rows), hits int64 [G] (rows with
+    a neighbour within the radius), under int64 [G,E] (rows with d <= edge), dsum and ddsum float64 [G] (sums of d and of d * d,
+    d truncated at the radius); edges (metres), radius, bad (rows the call refused: bad coordinates or group)."""
+
+    def __init__(self, rows, hits, under, dsum, ddsum, edges=(), radius=None, bad=0):
+        self.rows, self.hits = np.array(rows, dtype=np.int64).reshape(-1), np.array(hits, dtype=np.int64).reshape(-1)
+        G = len(self.rows)
+        self.edges = tuple(float(e) for e in edges)
+        self.under = np.array(under, dtype=np.int64).reshape(G, len(self.edges))
+        self.dsum, self.ddsum = np.array(dsum, dtype=np.float64).reshape(-1), np.array(ddsum, dtype=np.float64).reshape(-1)
+        self.radius = None if radius is None else float(radius)
+        self.bad = int(bad)
+        assert len(self.hits) == G and len(self.dsum) == G and len(self.ddsum) == G
+
+    @classmethod
+    def zeros(cls, G, edges=RESIDUAL_EDGES, radius=None):
+        return cls(np.zeros(G, np.int64), np.zeros(G, np.int64), np.zeros((G, len(edges)), np.int64), np.zeros(G), np.zeros(G), edges, radius)
+
+    @classmethod
+    def from_words(cls, words, G, edges=RESIDUAL_EDGES, radius=None, bad=0):
+        """the kernel's int64 [G][E + 4] -> ResidualTable"""
+        E = len(edges)
+        w = np.ascontiguousarray(np.asarray(words, dtype=np.int64).reshape(G, E + 4))
+        return cls(w[:, 0], w[:, 1], w[:, 2:2 + E], np.ascontiguousarray(w[:, 2 + E]).view(np.float64),
+                   np.ascontiguousarray(w[:, 3 + E]).view(np.float64), edges, radius, bad)
+
+    def words(self):
+        """-> int64 [G * (E + 4)], the kernel's layout (the sums as their bits)"""
+        G, E = len(self.rows), len(self.edges)
+        w = np.empty((G, E + 4), np.int64)
+        w[:, 0], w[:, 1], w[:, 2:2 + E] = self.rows, self.hits, self.under
+        w[:, 2 + E], w[:, 3 + E] = self.dsum.view(np.int64), self.ddsum.view(np.int64)
+        return w.reshape(-1)
+
+    def add(self, other):
+        """Accumulate another call's table: integers add exactly, the sums add in call order.  -> self"""
+        if other.under.shape != self.under.shape or other.edges != self.edges:
+            raise ValueError(f"residual tables of {other.under.shape} {other.edges} and {self.under.shape} {self.edges} do not add")
+        self.rows, self.hits, self.under = self.rows + other.rows, self.hits + other.hits, self.under + other.under
+        self.dsum, self.ddsum = self.dsum + other.dsum, self.ddsum + other.ddsum
+        self.bad += other.bad
+        return self
+
+    def _pick(self, v, group):
+        """one group's value, or (group None) the groups' values added in ascending order"""
+        if group is not None:
+            return v[group]
+        total = v[0] * 0
+        for g in range(len(v)):
+            total = total + v[g]
+        return total
+
+    def n(self, group=None):
+        return int(self._pick(self.rows, group))
+
+    def hit_rate(self, group=None):
+        n = self.n(group)
+        return float(self._pick(self.hits, group)) / n if n else float("nan")
+
+    def mean(self, group=None):
+        """the mean truncated distance in metres (NaN for an empty group)"""
+        n = self.n(group)
+        return float(self._pick(self.dsum, group)) / n if n else float("nan")
+
+    def rms(self, group=None):
+        n = self.n(group)
+        return float(np.sqrt(float(self._pick(self.ddsum, group)) / n)) if n else float("nan")
+
+    def shares(self, group=None):
+        """per edge the share of the rows with d <= edge"""
+        n = self.n(group)
+        under = self._pick(self.under, group)
+        return tuple(float(u) / n if n else float("nan") for u in under)
+
+    def summary(self, names=None):
+        """-> JSON-ready: the whole table and one entry per group"""
+        def entry(g):
+            return dict(n=self.n(g), hit_rate=self.hit_rate(g), mean=self.mean(g), rms=self.rms(g), shares=list(self.shares(g)))
+        G = len(self.rows)
+        names = list(names) if names is not None else [str(g) for g in range(G)]
+        return dict(all=entry(None), groups={names[g]: entry(g) for g in range(G)}, bad_rows=self.bad)
+
+
+def _cloud3(t, name):
+    import torch
+    from . import _lib
+    _lib.require_gpu(t)
+    if t.dim() != 2 or t.shape[1] < 3:
+        raise ValueError(f"{name}: expected [n, 3], got {tuple(t.shape)}")
+    return t[:, 0:3].to(torch.float32).contiguous()
+
+
+def nn_residual_device(query, target, flow=None, radius=2.0, groups=None, n_groups=1, edges=RESIDUAL_EDGES, per_row=True):
+    """icpflow_nn_residual enqueued on the current stream, nothing read back.  -> (d2 float32 [n], idx int32 [n], words): words is
+    an int64 device tensor [n_groups * (len(edges) + 4) + 4], the table followed by d_info (bad queries, bad targets, occupied
+    buckets, longest bucket).  per_row False: d2 and idx are None (the call keeps them in its workspace)."""
+    import ctypes
+    import torch
+    from . import _lib
+    q, t = _cloud3(query, "query"), _cloud3(target, "target")
+    device = q.device
+    n, m, G = q.shape[0], t.shape[0], int(n_groups)
+    f = g = None
+    if flow is not None:
+        f = _cloud3(flow, "flow")
+        if f.shape[0] != n:
+            raise ValueError(f"flow: {tuple(f.shape)} for {n} query rows")
+    if groups is not None:
+        _lib.require_gpu(groups)
+        g = groups.to(torch.int32).contiguous()
+        if g.shape != (n,):
+            raise ValueError(f"groups: {tuple(g.shape)} for {n} query rows")
+    if t.device != device or (f is not None and f.device != device) or (g is not None and g.device != device):
+        raise ValueError("nn_residual: every tensor on the same device")
+    ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    E = len(ed)
+    words = max(G, 0) * (E + 4)
+    out = torch.empty(words + 4, dtype=torch.int64, device=device)
+    d2 = torch.empty(n, dtype=torch.float32, device=device) if per_row else None
+    idx = torch.empty(n, dtype=torch.int32, device=device) if per_row else None
+    with torch.cuda.device(device):
+        need = int(_lib._L.icpflow_nn_residual_workspace_bytes(n, m, G, E))
+        ws = _lib.workspace(device, need)
+        _lib.call("icpflow_nn_residual", _lib.ptr(q), _lib.ptr(f), n, _lib.ptr(t), m, float(radius), _lib.ptr(g), G,
+                  ed.ctypes.data_as(ctypes.c_void_p) if E else None, E, _lib.ptr(d2), _lib.ptr(idx), _lib.ptr(out),
+                  ctypes.c_void_p(out.data_ptr() + words * 8), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    return d2, idx, out
+
+
+def nn_residual(query, target, flow=None, radius=2.0, groups=None, n_groups=1, edges=RESIDUAL_EDGES):
+    """The truncated nearest-neighbour residual of `query` (+ `flow`) against `target`: per query row the squared distance to
+    the nearest target within `radius` metres (radius^2 without one) and that target's row (-1 without one, -2 for a bad row:
+    non-finite, beyond 1e6 m, or a group outside [0, n_groups)), and the table per group of rows (`groups` int [n], None: one
+    group).  float32 [n,3] tensors on the GPU; there is no CPU path.  -> (d2 float32 [n], idx int32 [n], ResidualTable); one
+    small read-back, the table."""
+    d2, idx, out = nn_residual_device(query, target, flow, radius, groups, n_groups, edges)
+    host = out.cpu().numpy()
+    words = len(host) - 4
+    table = ResidualTable.from_words(host[:words], int(n_groups), tuple(float(e) for e in edges), radius, bad=int(host[words]))
+    table.info = dict(bad_queries=int(host[words]), bad_targets=int(host[words + 1]), occupied_buckets=int(host[words + 2]),
+                      longest_bucket=int(host[words + 3]))
+    return d2, idx, table
+
+
+def chamfer(a, b, radius=2.0, edges=RESIDUAL_EDGES):
+    """The truncated Chamfer distance of two clouds through two calls: a against b, b against a.  -> dict(forward, backward:
+    ResidualTable, chamfer: the sum of the two mean truncated distances in metres)"""
+    _, _, fwd = nn_residual(a, b, radius=radius, edges=edges)
+    _, _, bwd = nn_residual(b, a, radius=radius, edges=edges)
+    return dict(forward=fwd, backward=bwd, chamfer=fwd.mean() + bwd.mean())
+
+
+def format_residual(before, after, names=RESIDUAL_GROUPS):
+    """The residual lines of a run.  `before` and `after`: dict(forward, backward: ResidualTable) -- the source under the ego
+    pose alone and under the predicted flow against the destination, and the destination against either."""
+    fb, fa = before["forward"], after["forward"]
+    text = [f"################# Nearest-neighbour residual, truncated at {fa.radius:g} m (no ground truth) ##############"]
+
+    def line(name, g):
+        shares = ", ".join(f"<= {e:g} m: {b:.4f} -> {a:.4f}" for e, b, a in zip(fa.edges, fb.shares(g), fa.shares(g)))
+        return (f"{name:>12}, n {fa.n(g)}, mean: {fb.mean(g):.6f} -> {fa.mean(g):.6f}, rms: {fb.rms(g):.6f} -> {fa.rms(g):.6f}, "
+                f"hit rate: {fb.hit_rate(g):.4f} -> {fa.hit_rate(g):.4f}" + (", " + shares if shares else ""))
+
+    for g in range(len(fa.rows)):
+        text.append(line(names[g] if names is not None and g < len(names) else str(g), g))
+    text.append(line("all", None))
+    cb, ca = fb.mean() + before["backward"].mean(), fa.mean() + after["backward"].mean()
+    text.append(f"truncated Chamfer distance (source -> destination + destination -> source): {cb:.6f} -> {ca:.6f}")
+    return "\n".join(text)

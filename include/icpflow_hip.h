@@ -1013,6 +1013,47 @@ int icpflow_seq_segment_table(const double *d_points, const float *d_labels, int
                               size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(g)  nearest-neighbour residual: flow judged without ground truth.  No counterpart in the reference: the truncated
+ * nearest-neighbour (Chamfer) distance of label-free scene-flow work (COVERAGE.md, named deviations).
+ *
+ * icpflow_nn_residual -- one direction.  Queries d_query float32 [n,3], optional d_flow float32 [n,3] (NULL: no warp),
+ *   targets d_target float32 [m,3], radius r in metres, in [1e-3, 1e3] (else ICPFLOW_E_ARG).
+ *   Arithmetic, every operation rounded by itself (the library is built with -ffp-contract=off): q = p + f, one fp32 addition
+ *   per coordinate; r2 = (float)r * (float)r, rounded once on the host; d2(q, t) = (dx dx + dy dy) + dz dz in fp32 with
+ *   dx = q.x - t.x; a target is a HIT iff d2 <= r2.  Per query d_d2_out float32 [n] is the minimum d2 over the hits and
+ *   d_idx_out int32 [n] its target row, the LOWEST row on equal d2; with no hit idx = -1 and d2 = r2.
+ *   Bad rows: a target with a non-finite coordinate or one beyond +-1e6 m (the pad rows (1e8, 1e8, 1e8) among them) is never a
+ *   neighbour; a query whose q has such a coordinate, or whose group lies outside [0, G), gets idx = -2, d2 = r2 and enters
+ *   no cell of the table.
+ *   The search is exact: a hashed uniform grid of cell edge 1.01 r over the targets (cell = floor((double)v / h) in fp64,
+ *   H = 2^k >= 2 m buckets), built by count / exclusive scan / scatter over several workgroups, and the 27 cells around q
+ *   (csrc/nnresid.hip states why no hit lies outside them); the queries are binned by the same cells, so that a wave's lanes
+ *   walk the same buckets.  Every output is a function of the arguments alone, whatever order the scatter leaves inside a
+ *   bucket.
+ *   d_group int32 [n] (NULL: every row in group 0), 1 <= G <= ICPFLOW_NNR_MAX_GROUPS; h_edges (HOST) E <= ICPFLOW_NNR_MAX_EDGES
+ *   distances in metres: finite, positive, strictly ascending, at most r.  d_table int64 [G][E + 4], per group: word 0 the good
+ *   rows, word 1 the hits, words 2 .. E + 1 the rows with d <= edge, word E + 2 the BITS OF the float64 sum of d, word E + 3
+ *   the bits of the float64 sum of d * d; d = sqrtf(d2_out) in fp32, correctly rounded, then widened (a miss counts with
+ *   d = sqrtf(r2): the distance is truncated at the radius), the edge test compares the widened d with the fp64 edge, d * d is
+ *   the exact fp64 product.  Counts are exact; the sums have a fixed order and no floating-point atomics.
+ *   d_info int64 [4], required: bad queries, bad targets, occupied buckets, the longest bucket (the last two are diagnostics).
+ *   d_d2_out, d_idx_out and d_table may each be NULL, not all three.  A null pointer, a negative size, r, G or E outside
+ *   their ranges, bad edges are ICPFLOW_E_ARG, n or m > 2^29 is ICPFLOW_E_LIMIT, before any launch.  The workspace is the
+ *   caller's, 16-byte aligned: icpflow_nn_residual_workspace_bytes(n, m, G, E) =
+ *       table(m) + table(n) + 2 a(4 n) + a(8 grid(n) G (E + 4)),   table(k) = 2 a(4 H) + 4 a(4 ceil(H / 1024)) + 256 + a(16 k)
+ *   bytes, a(x) = x rounded up to a multiple of 256, H the smallest power of two >= max(2 k, 1), grid(n) = ceil(n / 2048)
+ *   clamped to [1, 256] (0 for sizes the call refuses).  Nothing in it is read before it is written; fewer bytes are
+ *   ICPFLOW_E_WORKSPACE before anything is written.  n = 0 and m = 0 succeed (m = 0: every good query is a miss).
+ *   Asynchronous on `stream`, no host synchronisation, no allocation.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_NNR_MAX_GROUPS 64
+#define ICPFLOW_NNR_MAX_EDGES 4
+size_t icpflow_nn_residual_workspace_bytes(int n, int m, int G, int E);
+int icpflow_nn_residual(const float *d_query, const float *d_flow, int n, const float *d_target, int m, double radius,
+                        const int32_t *d_group, int G, const double *h_edges, int E, float *d_d2_out, int32_t *d_idx_out,
+                        int64_t *d_table, int64_t *d_info, void *d_ws, size_t ws_bytes, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
