@@ -165,7 +165,9 @@ __global__ __launch_bounds__(kBlock) void dbscan_hook_kernel(const float4 *__res
 }
 
 // every point points at the root of its tree; per chunk of 64 sorted rows: the root shared by all its core
-// points (-1: none at all, -2: several) -- the union step skips such chunks without reading them
+// points (-1: none at all, -2: several) -- the union step skips such chunks without reading them.
+// The walk only loads (uf_root): every store to parent[] in this launch is then the root of the slot's own tree,
+// whoever lands last (see dbscan_first_row_kernel).
 __global__ __launch_bounds__(kBlock) void dbscan_flatten_kernel(int n, const uint8_t *__restrict__ core,
                                                                 int *__restrict__ parent,
                                                                 int *__restrict__ chunkRoot)
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void dbscan_flatten_kernel(int n, const uin
     int root = -1;
     bool isCore = false;
     if (j < n) {
-        root = uf_find(parent, j);
+        root = uf_root(parent, j);
         parent[j] = root;
         isCore = core[j] != 0;
     }
@@ -217,7 +219,14 @@ __global__ __launch_bounds__(kBlock) void dbscan_union_kernel(const float4 *__re
     }
 }
 
-// smallest caller row of every component (Open3D numbers the clusters by it), one atomic per (wave, root)
+// smallest caller row of every component (Open3D numbers the clusters by it), one atomic per (wave, root).
+// dbscan_assign_kernel indexes firstRow[] with parent[j], so after this launch parent[j] must be the ROOT of every
+// core j under any interleaving.  No union runs here, so the trees are fixed.  The walk is uf_root, loads only:
+// the one store to slot j is its owner's `parent[j] = root`, and every value a walker can load from a slot is the
+// slot's old ancestor or its root -- both lead to the same root.  With uf_find's path splitting it was not so: a
+// walker that had loaded parent[a] = b and parent[b] = c on the chain a -> b -> c -> d could land its split store
+// parent[a] = c AFTER a's owner had written parent[a] = d; c is no root, firstRow[c] is still 0x7fffffff, and
+// the label kernel would index rank[] with it.  (Found by reading; never observed in a run.)
 __global__ __launch_bounds__(kBlock) void dbscan_first_row_kernel(const float4 *__restrict__ sorted,
                                                                   const uint8_t *__restrict__ core, int n,
                                                                   int *__restrict__ parent,
@@ -227,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void dbscan_first_row_kernel(const float4 *
     const int lane = threadIdx.x & 63;
     int root = -1, row = 0x7fffffff;
     if (j < n && core[j]) {
-        root = uf_find(parent, j);
+        root = uf_root(parent, j);
         parent[j] = root;
         row = __float_as_int(sorted[j].w);
     }

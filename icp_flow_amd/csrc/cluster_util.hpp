@@ -42,6 +42,18 @@ __device__ inline int uf_find(int *parent, int i)
     return i;
 }
 
+// the root of i by loads alone: for kernels that publish roots into parent[] while no union runs.  A split store
+// of uf_find may land AFTER the owner of that slot has written its root there and put an inner node back.
+__device__ inline int uf_root(const int *parent, int i)
+{
+    int p = uf_load(parent, i);
+    while (p != i) {
+        i = p;
+        p = uf_load(parent, i);
+    }
+    return i;
+}
+
 // roots only ever move to SMALLER indices, so the root of a finished component is its smallest member
 __device__ inline void uf_union(int *parent, int a, int b)
 {

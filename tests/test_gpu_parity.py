@@ -1234,7 +1234,8 @@ def test_frame_pairs_in_flight_equal_one_after_the_other(tmp_path):
 
 
 def test_cluster_table_chain_equals_the_torch_ops():
-    """icpflow_cluster_table (key kernel, radix sort, boundaries, rows, statistics: one chain of launches) against the
+    """icpflow_cluster_table (a stable counting sort by label -- dictionary, counts, scan, scatter -- and the statistics kernel:
+    one chain of five launches, table.hip) against the
     chain of torch ops it replaces (stable argsort, unique_consecutive, cumsum + icpflow_cluster_stats): the same row
     order, labels, counts, starts, centroids and extents, bit for bit; float labels of either sign, a cloud with more
     distinct labels than the device table holds (falls back to the torch ops), a single-cluster cloud."""
@@ -1261,8 +1262,8 @@ def test_cluster_table_chain_equals_the_torch_ops():
 
 
 def test_cluster_table_pair_chain_equals_two_single_chains():
-    """icpflow_cluster_table_pair (both clouds of a frame pair through ONE sort with the cloud's number above the label's
-    bits) against two icpflow_cluster_table calls: row order, labels, counts, starts, centroids, extents and the number of
+    """icpflow_cluster_table_pair (both clouds of a frame pair through ONE chain of launches of the counting sort: every
+    kernel takes its cloud from the block index, each cloud keeps a dictionary and a table of its own) against two icpflow_cluster_table calls: row order, labels, counts, starts, centroids, extents and the number of
     clusters bit for bit -- clouds of different sizes, labels of either sign shared and not shared between the two, one
     cloud overflowing the device table (its table falls back to the torch ops, the other one stays), single-row clouds."""
     from icp_flow_amd.utils_check import ClusterTable, TABLE_ROWS
