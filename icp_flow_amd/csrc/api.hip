@@ -593,6 +593,23 @@ int icpflow_selftest_kabsch(const double *d_H, const double *d_gsum, int n, int 
     return 0;
 }
 
+// host only: the carve of the fused entry points on a null base, as the size queries build it (order: icpflow_hip.h)
+int icpflow_selftest_workspace_layout(int B, int N, int Lx, int Ly, int Lz, size_t *h_offsets, int count)
+{
+    if (!h_offsets) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_workspace_layout: null pointer");
+    if (B <= 0 || N <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_workspace_layout: B (%d) and N (%d) must be positive", B, N);
+    if (count != ICPFLOW_WORKSPACE_LAYOUT_COUNT)
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_workspace_layout: count must be %d (got %d)", ICPFLOW_WORKSPACE_LAYOUT_COUNT, count);
+    const size_t L = (size_t)(Lx > 0 ? Lx : 0) * (size_t)(Ly > 0 ? Ly : 0) * (size_t)(Lz > 0 ? Lz : 0);
+    // (a null base carves null pointers -- carver.hpp --, so the same constructor runs on a nominal base that nothing dereferences)
+    const uintptr_t base = (uintptr_t)1 << 40;
+    const Workspace w(reinterpret_cast<void *>(base), B, N, L);
+    const void *const at[ICPFLOW_WORKSPACE_LAYOUT_COUNT] = {w.lenA, w.lenC, w.swap, w.grid.pts, w.grid.sortX, w.grid.sortYsoa, w.grid.sortXsoa,
+                                                            w.grid.axis, w.zsortA, w.zsortC, w.voteKey};
+    for (int k = 0; k < ICPFLOW_WORKSPACE_LAYOUT_COUNT; ++k) h_offsets[k] = (size_t)(reinterpret_cast<uintptr_t>(at[k]) - base);
+    return 0;
+}
+
 int icpflow_hist_vote(const float *d_X, const float *d_Y, int B, int NX, int NY, float min_x,
                       float min_y, float min_z, float max_x, float max_y, float max_z, int len_x,
                       int len_y, int len_z, float *d_bins, icpflow_stream_t stream)

@@ -24,6 +24,9 @@
  *   then pads -- because, like pytorch3d's `lengths`, they scan the first
  *   n = count(flag > 0) rows.  icpflow_hist_vote accepts arbitrary flag patterns
  *   (the reference's own hist_cuda/test.py uses random flags).
+ *   The first n rows of a cloud must be finite: the sorts pad their networks with +inf keys, a NaN
+ *   key orders behind that padding, and a sorted row r < n could then name a padding index instead of
+ *   a row of the cloud (csrc/sortclouds.hpp, DESIGN.md "The sorts").
  *
  * All citations `file:line` are into the reference repository
  * (yanconglin/ICP-Flow).
@@ -1136,6 +1139,26 @@ int icpflow_selftest_vote_quotient(const float *d_a, int n, float min_v, float m
  * ------------------------------------------------------------------------- */
 int icpflow_selftest_kabsch(const double *d_H, const double *d_gsum, int n, int mode, double *d_R, double *d_lam,
                             int32_t *d_path, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Diagnostics, host only (no launch, no device access): byte offsets, from the d_ws a fused entry point
+ * (icpflow_estimate_init_pose, icpflow_hist_icp, icpflow_icp, icpflow_apply_icp; the same B, N and histogram
+ * lengths, 0 0 0 for the two without a histogram) was given, of the arrays its sorts leave there.  Once the call
+ * has returned and the stream is synchronised the arrays are still in the caller's workspace.  h_offsets [count],
+ * count = ICPFLOW_WORKSPACE_LAYOUT_COUNT (anything else is ICPFLOW_E_ARG), in this order:
+ *    0 lenA      int32 [B]   valid rows of the src cloud          1 lenC   int32 [B]   ... of the dst cloud
+ *    2 swap      uint8 [B]   1: the src cloud is the longer one and takes the fixed role (icpflow_hist_icp only)
+ *    3 grid.pts  float [B,N,4]  the fixed role's cloud sorted along the pair's key: (x, y, z, row as int bits)
+ *    4 grid.sortX float [B,N,4] the moving role's cloud (pre-pose applied), the same key and layout
+ *    5 grid.sortYsoa float [B,3,NP16]  x[], y[], z[] of 3, +inf behind the valid rows; NP16 = N rounded up to 16
+ *    6 grid.sortXsoa float [B,3,NP16]  the same of 4 (where the call sorts for the scoring sweeps)
+ *    7 grid.axis int32 [B]   the pair's key code: 0 1 2 = x y z, 3 .. 8 = a horizontal direction (csrc/sortdir.hpp)
+ *    8 zsortA    float [B,N,4]  the src cloud's flagged rows by the vote's key, the key in w
+ *    9 zsortC    float [B,N,4]  ... the dst cloud's             10 voteKey float [B,8]  wide, uaxis, u0, z0, h (csrc/votekey.hpp)
+ * icpflow_hist_icp_eval reuses zsortA behind the registration.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_WORKSPACE_LAYOUT_COUNT 11
+int icpflow_selftest_workspace_layout(int B, int N, int Lx, int Ly, int Lz, size_t *h_offsets, int count);
 
 /* ---------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): per-launch timing of the dominant kernel, the ICP
