@@ -21,9 +21,9 @@ namespace {
 constexpr int kRowsBlock = 1024;
 constexpr int kTableCols = 9;   // label, count, start, mean (3), sorted bbox extents (3)
 
-// float -> uint32 whose unsigned order is the float order (-0.0 < +0.0 as bit patterns; labels are never -0.0 in
-// practice and torch.argsort would keep them adjacent as equals -- they stay distinct clusters here only if the
-// caller really passes both)
+// float -> uint32 whose unsigned order is the float order.  As bit patterns -0.0 < +0.0, where torch.argsort and
+// torch.unique -- and every `==` on labels downstream -- see one label: label_key below maps -0.0 to +0.0 first, so
+// the two are ONE cluster, reported as 0.0, its rows in original order.
 __device__ __forceinline__ uint32_t sortable(float f)
 {
     const uint32_t u = (uint32_t)__float_as_int(f);
@@ -70,7 +70,9 @@ constexpr uint32_t kEmpty = 0xffffffffu;
 
 __device__ __forceinline__ uint32_t label_key(float f)
 {
-    const uint32_t k = sortable(f);
+    // both zeros are one label (a select, not sort_pack's f + 0.0f: an add would quiet a signalling NaN, and NaN labels are
+    // kept apart by their bits)
+    const uint32_t k = sortable(f == 0.0f ? 0.0f : f);
     return k == kEmpty ? kEmpty - 1u : k;    // (one NaN payload shares the empty mark's pattern)
 }
 

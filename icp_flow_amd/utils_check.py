@@ -28,6 +28,8 @@ class ClusterTable:
     host:    h_labels (float32), h_count, h_start (int64), h_mean, h_extent (float32) -- the same numbers
     mean     centroid (utils_check.py:34-35);  extent: sorted bbox extents (get_bbox_tensor,
              utils_helper.py:166-170); both zero for negative labels (ground, noise: never candidates, :32)
+    -0.0 and +0.0 are one label, as torch.unique has them: the device table reports it as 0.0, the fallback below as whichever
+    zero comes first, and `find` matches either.
     """
 
     def __init__(self, points, labels, fetch=True, _buffer=None, _launch=True):

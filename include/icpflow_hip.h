@@ -573,7 +573,9 @@ int icpflow_cluster_stats(const float *d_points, const int64_t *d_order, const i
  * the per-pair masks (:81-86) and sanity_check (utils_check.py:34-43, get_bbox_tensor utils_helper.py:166-170) compute
  * cluster by cluster; centroid and extents are zero for negative labels (ground, noise: never candidates,
  * utils_check.py:32).  d_num int32 [1]: the number of distinct labels, or its negative when it exceeds Lmax (<= 4096;
- * the table then holds nothing usable).  float64 carries the float32 statistics and the counts exactly. */
+ * the table then holds nothing usable).  float64 carries the float32 statistics and the counts exactly.  -0.0 and +0.0
+ * are one label, reported as 0.0 (as torch.unique and every `==` on labels see them); NaN labels are one cluster per bit
+ * pattern, positive NaNs after +inf and negative NaNs before -inf, with statistics. */
 size_t icpflow_cluster_table_workspace_bytes(int M, int Lmax);
 int icpflow_cluster_table(const float *d_points, const float *d_labels, int M, int64_t *d_order, double *d_table, int Lmax,
                           int32_t *d_num, void *d_ws, size_t ws_bytes, icpflow_stream_t stream);

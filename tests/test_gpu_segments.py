@@ -138,6 +138,15 @@ def test_shapes_where_the_reduction_can_go_wrong(dtype):
         against_restatement(pts, labels, None, None, z_min)
 
 
+def test_both_zeros_are_one_segment():
+    """-0.0 and +0.0 are one label (table.hip's label_key, whose dictionary and order the segments reuse; np.unique in the
+    restatement): one segment of all their rows, reported as 0.0"""
+    labels = sg.interleaved_labels([300, 200, 100], [0.0, -0.0, 5.0], seed=9)
+    pts, gt, pred = sg.random_cloud(labels, seed=10)
+    got, _ = against_restatement(pts, labels, pred, gt, None)
+    assert got.shape[0] == 2 and got[0, 1] == 500 and got[0, 0] == 0 and not np.signbit(got[0, 0])
+
+
 def test_single_segment_lmax_exact_overflow_and_empty():
     from icp_flow_amd import _lib
     # one segment covering the whole cloud: 2 C + 100 rows, three chunks
