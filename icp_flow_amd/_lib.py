@@ -106,6 +106,8 @@ SIGNATURES = {
     "icpflow_seq_segment_table": (_i, [_p, _p, _i, _p, _p, _d, _p, _i, _p, _p, _sz, _p]),
     "icpflow_nn_residual_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "icpflow_nn_residual": (_i, [_p, _p, _i, _p, _i, _d, _p, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_nn_residual_segments_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "icpflow_nn_residual_segments": (_i, [_p, _p, _p, _p, _i, _p, _i, _d, _p, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -143,6 +145,7 @@ ARGO_MAX_BACKGROUND = 64
 CLASS_MAX_ROWS, CLASS_MAX_BUCKETS, CLASS_MAX_WORDS = 64, 8, 1024   # icpflow_seq_class_table: G, S and E, G * S * (E + 2)
 BUCKET_MAX_ROWS, BUCKET_MAX_BUCKETS = 64, 64     # icpflow_seq_bucket_table: G and S (a workgroup's table of G * S * 3 words in LDS)
 NNR_MAX_GROUPS, NNR_MAX_EDGES = 64, 4            # icpflow_nn_residual: G and E
+NNRS_COLS, NNRS_MAX_SEGMENTS = 18, 4096           # icpflow_nn_residual_segments: columns of a row; Lmax at most
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical

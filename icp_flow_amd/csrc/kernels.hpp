@@ -379,6 +379,14 @@ constexpr int kLabelOrderCols = 9;
 hipError_t launch_label_order(const float *labels, int M, int64_t *order, double *table, int Lmax, int32_t *num, void *ws,
                               size_t wsBytes, bool *wsTooSmall, hipStream_t s);
 
+// segeval.hip: a labelled cloud's segments cut into chunks of kSegmentChunk rows of the stable order (a workgroup per chunk,
+// whichever segment it belongs to).  segment_max_chunks: the chunks n rows in at most Lmax segments can make;
+// launch_segment_plan: chunkStart int [Lmax + 1] = the first chunk of every segment of launch_label_order's table, then the
+// number of chunks (nothing is written when *num <= 0)
+constexpr int kSegmentChunk = 1024;
+int segment_max_chunks(int n, int Lmax);
+hipError_t launch_segment_plan(const double *ctable, const int32_t *num, int *chunkStart, hipStream_t s);
+
 // cluster.hip: DBSCAN of a frame pair's points (labels int32 [n]: cluster id, -1 noise, -2 masked out)
 hipError_t dbscan_workspace_bytes(int n, size_t *bytes);
 hipError_t launch_dbscan(const float *pts, int stride, const uint8_t *mask, int n, double eps, int minPoints,

@@ -68,6 +68,7 @@
 #include "common.hpp"
 #include "gridhash.hpp"
 #include "host.hpp"
+#include "nnresid.hpp"
 #include "rowerr.hpp"
 
 using icpflow::align256;
@@ -77,6 +78,13 @@ using icpflow::pointer_error;
 using icpflow::report_error;
 using icpflow::report_errorf;
 using icpflow::workspace_error;
+using icpflow::nnr::Cloud;
+using icpflow::nnr::Edges;
+using icpflow::nnr::Grid;
+using icpflow::nnr::kMaxEdges;
+using icpflow::nnr::kMaxRows;
+using icpflow::nnr::kMaxRadius;
+using icpflow::nnr::kMinRadius;
 
 namespace {
 
@@ -84,15 +92,8 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kTile = 1024;                         // buckets per scan tile: four per thread
 constexpr int kPerThread = kTile / kThreads;
-constexpr int kMaxGroups = ICPFLOW_NNR_MAX_GROUPS, kMaxEdges = ICPFLOW_NNR_MAX_EDGES;
-constexpr int kMaxRows = 1 << 29;                   // of either cloud: 2^k >= 2 rows buckets stay an int
+constexpr int kMaxGroups = ICPFLOW_NNR_MAX_GROUPS;  // (the limits both entry points share: nnresid.hpp)
 constexpr float kFar = 1e6f;                        // a coordinate beyond it is a bad row
-constexpr double kMinRadius = 1e-3, kMaxRadius = 1e3;
-
-struct Edges {
-    int E;
-    double edge[kMaxEdges];
-};
 
 __device__ __forceinline__ bool good_coord(float x, float y, float z)   // (a NaN fails every comparison)
 {
@@ -100,13 +101,6 @@ __device__ __forceinline__ bool good_coord(float x, float y, float z)   // (a Na
 }
 
 __device__ __forceinline__ int cell_of(float v, double h) { return (int)floor((double)v / h); }
-
-// a cloud as the binning kernels see it: the targets (no flow, no groups) or the queries (q = p + f, a group per row)
-struct Cloud {
-    const float *pts, *flow;
-    const int32_t *group;
-    int rows, G;
-};
 
 // row j of the cloud -> its coordinates; false for a bad row
 __device__ __forceinline__ bool load_row(const Cloud &c, size_t j, float &x, float &y, float &z)
@@ -479,13 +473,13 @@ int buckets_for(int m)   // H = 2^k >= 2 m (1 for an empty cloud)
     return H;
 }
 
-// a hashed grid over one cloud in the workspace: H buckets (cursor: counts, then running ends; start), the scan's words per
-// tile of 1024 buckets, the number of rows in the table, the records
-struct Grid {
-    unsigned *cursor, *start, *tile_sum, *tile_occupied, *tile_longest, *tile_offset, *rows;
-    float4 *records;
-    int H, tiles;
-};
+inline unsigned blocks_for(int rows) { return (unsigned)(((size_t)rows + kThreads - 1) / kThreads); }
+
+}  // namespace
+
+// what segresid.hip calls as well (nnresid.hpp)
+namespace icpflow {
+namespace nnr {
 
 Grid carve_grid(Carver &ws, int rows)
 {
@@ -502,6 +496,41 @@ Grid carve_grid(Carver &ws, int rows)
     g.records = ws.take<float4>((size_t)rows * sizeof(float4));
     return g;
 }
+
+hipError_t bin_cloud(const Cloud &cloud, const Grid &g, double h, unsigned long long *bad_rows, unsigned long long *d_info, float r2,
+                     float *d2, int32_t *idx, hipStream_t st)
+{
+    const unsigned mask = (unsigned)g.H - 1u;
+    hipError_t e = hipMemsetAsync(g.cursor, 0, (size_t)g.H * sizeof(unsigned), st);
+    if (e != hipSuccess) return e;
+    if (cloud.rows > 0) nnr_count_kernel<<<blocks_for(cloud.rows), kThreads, 0, st>>>(cloud, h, mask, g.cursor, bad_rows);
+    nnr_tile_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_sum, g.tile_occupied, g.tile_longest);
+    nnr_offsets_kernel<<<1, kThreads, 0, st>>>(g.tile_sum, g.tile_occupied, g.tile_longest, g.tiles, g.tile_offset, g.rows, d_info);
+    nnr_starts_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_offset, g.start);
+    if (cloud.rows > 0) nnr_scatter_kernel<<<blocks_for(cloud.rows), kThreads, 0, st>>>(cloud, h, mask, g.cursor, g.records, r2, d2, idx);
+    return hipGetLastError();
+}
+
+// the queries binned by the same cells (a table of their own size), then a workgroup per 64 of them in bucket order
+hipError_t launch_binned_query(const Grid &queries, const Grid &targets, int n, float r2, double h, float *d2, int32_t *idx, hipStream_t st)
+{
+#ifndef ICPFLOW_NNR_LANE_QUERY
+    if (n <= 0) return hipSuccess;
+    nnr_query_kernel<<<(unsigned)(((size_t)n + kWave - 1) / kWave), kQueryWaves * kWave, 0, st>>>(queries.records, queries.rows, r2, h, (unsigned)targets.H - 1u,
+                                                                                             targets.start, targets.cursor, targets.records, d2, idx);
+    return hipGetLastError();
+#else
+    return hipErrorNotSupported;                    // (the timing variant has the lane-per-query kernel only)
+#endif
+}
+
+}  // namespace nnr
+}  // namespace icpflow
+
+namespace {
+
+using icpflow::nnr::bin_cloud;
+using icpflow::nnr::carve_grid;
 
 // what the call carves out of its workspace, in this order (the size query runs it on a null base): the targets' grid, the
 // queries' grid, the per-row outputs the caller did not take, the table's partials
@@ -526,25 +555,6 @@ Carve carve(void *base, int n, int m, int G, int E)
     c.partial = ws.take<unsigned long long>((size_t)c.grid * G * (E + 4) * sizeof(unsigned long long));
     c.total = ws.total();
     return c;
-}
-
-inline unsigned blocks_for(int rows) { return (unsigned)(((size_t)rows + kThreads - 1) / kThreads); }
-
-// count / scan / scatter of one cloud into its grid, enqueued on `st`; `bad_rows`: the word of d_info the bad rows are counted
-// into; d_info (the targets' grid only): the occupied buckets and the longest one; d2 / idx (the queries only): the outputs of
-// the bad rows
-hipError_t bin_cloud(const Cloud &cloud, const Grid &g, double h, unsigned long long *bad_rows, unsigned long long *d_info, float r2,
-                     float *d2, int32_t *idx, hipStream_t st)
-{
-    const unsigned mask = (unsigned)g.H - 1u;
-    hipError_t e = hipMemsetAsync(g.cursor, 0, (size_t)g.H * sizeof(unsigned), st);
-    if (e != hipSuccess) return e;
-    if (cloud.rows > 0) nnr_count_kernel<<<blocks_for(cloud.rows), kThreads, 0, st>>>(cloud, h, mask, g.cursor, bad_rows);
-    nnr_tile_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_sum, g.tile_occupied, g.tile_longest);
-    nnr_offsets_kernel<<<1, kThreads, 0, st>>>(g.tile_sum, g.tile_occupied, g.tile_longest, g.tiles, g.tile_offset, g.rows, d_info);
-    nnr_starts_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_offset, g.start);
-    if (cloud.rows > 0) nnr_scatter_kernel<<<blocks_for(cloud.rows), kThreads, 0, st>>>(cloud, h, mask, g.cursor, g.records, r2, d2, idx);
-    return hipGetLastError();
 }
 
 bool sizes_ok(int n, int m, int G, int E) { return n >= 0 && m >= 0 && n <= kMaxRows && m <= kMaxRows && G >= 1 && G <= kMaxGroups && E >= 0 && E <= kMaxEdges; }
@@ -583,7 +593,9 @@ int icpflow_nn_residual(const float *d_query, const float *d_flow, int n, const 
     const Carve c = carve(d_ws, n, m, G, E);
     const float rf = (float)radius, r2 = rf * rf;
     const double h = 1.01 * radius;
+#ifdef ICPFLOW_NNR_LANE_QUERY
     const unsigned mask = (unsigned)c.targets.H - 1u;
+#endif
     unsigned long long *info = (unsigned long long *)d_info;
     float *d2 = d_d2_out ? d_d2_out : c.d2;
     int32_t *idx = d_idx_out ? d_idx_out : c.idx;
@@ -593,13 +605,8 @@ int icpflow_nn_residual(const float *d_query, const float *d_flow, int n, const 
     ICPFLOW_TRY(hipMemsetAsync(info, 0, 4 * sizeof(unsigned long long), st));
     ICPFLOW_TRY(bin_cloud(targets, c.targets, h, info + 1, info, r2, nullptr, nullptr, st));
 #ifndef ICPFLOW_NNR_LANE_QUERY
-    // the queries binned by the same cells (a table of their own size), then a wave per 64 of them in bucket order
     ICPFLOW_TRY(bin_cloud(queries, c.queries, h, info + 0, nullptr, r2, d2, idx, st));
-    if (n > 0) {
-        nnr_query_kernel<<<(unsigned)(((size_t)n + kWave - 1) / kWave), kQueryWaves * kWave, 0, st>>>(c.queries.records, c.queries.rows, r2, h, mask, c.targets.start, c.targets.cursor,
-                                                             c.targets.records, d2, idx);
-        ICPFLOW_TRY(hipGetLastError());
-    }
+    ICPFLOW_TRY(icpflow::nnr::launch_binned_query(c.queries, c.targets, n, r2, h, d2, idx, st));
 #else
     if (n > 0) {
         nnr_query_kernel<<<blocks_for(n), kThreads, 0, st>>>(d_query, d_flow, n, d_group, G, r2, h, mask, c.targets.start, c.targets.cursor,

@@ -35,6 +35,7 @@ using icpflow::workspace_error;
 namespace {
 
 constexpr int kChunk = 1024;                          // C: rows of a chunk
+static_assert(kChunk == icpflow::kSegmentChunk, "the chunk the plan below is shared for (kernels.hpp)");
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kPerThread = kChunk / kThreads;
@@ -183,6 +184,19 @@ __global__ __launch_bounds__(kThreads) void seg_final_kernel(const double *__res
 }
 
 }  // namespace
+
+// the chunk plan, for segresid.hip as well (kernels.hpp)
+namespace icpflow {
+
+int segment_max_chunks(int n, int Lmax) { return max_chunks(n, Lmax); }
+
+hipError_t launch_segment_plan(const double *ctable, const int32_t *num, int *chunkStart, hipStream_t s)
+{
+    seg_plan_kernel<<<1, 1024, 0, s>>>(ctable, num, chunkStart);
+    return hipGetLastError();
+}
+
+}  // namespace icpflow
 
 extern "C" {
 

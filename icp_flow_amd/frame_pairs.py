@@ -1193,12 +1193,7 @@ def frame_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
     device = torch.device(device)
     ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
     raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
-    ls = out.get("labels_src")
-    if ls is None and fp.labels_src is not None:
-        ls = _input(fp, "labels_src", device)
-    if ls is None:
-        raise ValueError("the residual groups the source rows by their cluster labels: the registration must leave labels_src in its result")
-    groups = residual_groups(ls.to(device).float(), out["pairs"].to(device))
+    groups = residual_groups(_source_labels(fp, out, device), out["pairs"].to(device))
     flow = out["flow"].to(device).float()
     G = len(utils_eval.RESIDUAL_GROUPS)
     calls = ((raw, pd, flow, groups, G), (pd, raw[:, 0:3] + flow[:, 0:3], None, None, 1), (ps, pd, None, groups, G), (pd, ps, None, None, 1))
@@ -1210,6 +1205,28 @@ def frame_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
         tables.append(utils_eval.ResidualTable.from_words(host[at: at + size], n, tuple(edges), radius, bad=int(host[at + size])))
         at += size + 4
     return tables
+
+
+def _source_labels(fp, out, device):
+    ls = out.get("labels_src")
+    if ls is None and fp.labels_src is not None:
+        ls = _input(fp, "labels_src", device)
+    if ls is None:
+        raise ValueError("the residual groups the source rows by their cluster labels: the registration must leave labels_src in its result")
+    return ls.to(device).float()
+
+
+def frame_segment_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
+    """The residual of one registered frame pair PER SEGMENT of the source (utils_eval.segment_residual: one call, one
+    read-back): BEFORE the ego-compensated source, AFTER the flow's source points -- raw when the pair carries them -- plus the
+    predicted flow, both against the destination; the source labels as `frame_residual` finds them.  -> SegmentResidual"""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    return utils_eval.segment_residual(ps, raw, out["flow"].to(device).float(), _source_labels(fp, out, device), pd, radius, edges)
+
+
+RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
 
 
 def _residual_flat(tables):
@@ -1271,7 +1288,14 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     the pair is registered (and, in flight, delivered) and outside the timed region of one pair at a time; the tables are added
     in the order of the frame pairs whatever order they complete in, ride the closing all_reduce, and the summary gains a
     `residual` block and `ms_residual_per_frame_pair` (device-synchronised around the four calls and their read-back).  In flight,
-    ms / frame pair is the wall time of the share and then includes this work."""
+    ms / frame pair is the wall time of the share and then includes this work.
+    args.residual_segments = True or a file name (`--residual-segments [FILE]`; needs args.residual, whose radius it shares; one
+    process only): every frame pair is judged PER SEGMENT of its source as well -- `frame_segment_residual`, next to
+    `frame_residual` and like it outside the timed region of one pair at a time -- and the segments whose mean distance under the
+    flow exceeds utils_eval.RESIDUAL_EDGES[1] metres are collected, worst first.  The summary gains `residual_segments` (above,
+    segments_judged, segments_listed, worst: at most RESIDUAL_SEGMENTS_SHOWN entries, each with its frame pair's number and
+    path), `ms_segment_residual_per_frame_pair` (device-synchronised around the call and its read-back) and, with a file name,
+    `residual_segments_file`: the whole list written there as JSON."""
     import torch.distributed as dist
     device = torch.device(device)
     pipelined = int(in_flight) > 1 and register_fn is None
@@ -1287,15 +1311,30 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     pose_sources = {}
     radius = getattr(args, "residual", None)
     residuals, residual_ms = {}, []              # frame pair (its number in this rank's share) -> its four tables
+    per_segment = getattr(args, "residual_segments", None)
+    if per_segment and not radius:
+        raise ValueError("args.residual_segments needs args.residual: the two share the radius")
+    if per_segment and world > 1:
+        raise ValueError("args.residual_segments under more than one rank: merging the lists is not built")
+    segment_lists, segment_ms, segments_judged = {}, [], 0     # frame pair -> its listed segments
 
     def account(fp, out, index=None):
-        nonlocal matched
+        nonlocal matched, segments_judged
         if radius:
             sync()
             t0 = time.perf_counter()
             residuals[len(residuals) if index is None else index] = frame_residual(fp, out, device, float(radius))
             sync()
             residual_ms.append((time.perf_counter() - t0) * 1e3)
+        if per_segment:
+            k = len(segment_lists) if index is None else index
+            sync()
+            t0 = time.perf_counter()
+            report = frame_segment_residual(fp, out, device, float(radius))
+            sync()
+            segment_ms.append((time.perf_counter() - t0) * 1e3)
+            segments_judged += sum(1 for v in report.labels.tolist() if v not in utils_eval.RESIDUAL_SKIP_LABELS)
+            segment_lists[k] = [dict(frame_pair=k, path=fp.name, **e) for e in report.worst(pairs=out["pairs"])]
         pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
         matched += int(out["pairs"].shape[0])
         if fp.gt_flow is not None:
@@ -1350,6 +1389,16 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     if radius:
         out["ms_residual_per_frame_pair"] = tot[9] / max(n_fp, 1)
         out["residual"] = residual_block(_residual_unflat(tot[10:], total) if world > 1 else total)
+    if per_segment:
+        listed = [e for k in sorted(segment_lists) for e in segment_lists[k]]
+        listed.sort(key=lambda e: (-e["after_mean"], e["frame_pair"], e["label"]))
+        out["residual_segments"] = dict(above=utils_eval.RESIDUAL_EDGES[1], segments_judged=segments_judged, segments_listed=len(listed),
+                                        worst=listed[:RESIDUAL_SEGMENTS_SHOWN])
+        out["ms_segment_residual_per_frame_pair"] = sum(segment_ms) / max(len(segment_ms), 1)
+        if isinstance(per_segment, str):
+            with open(per_segment, "w") as f:
+                json.dump(listed, f, indent=1)
+            out["residual_segments_file"] = per_segment
     return out
 
 
@@ -1408,6 +1457,10 @@ def argument_parser():
                     help="judge the flow without ground truth: the nearest-neighbour residual of the warped source against the "
                          "destination, truncated at R metres (2.0 when given bare), before and after the registration, both "
                          "directions (Chamfer); not with --protocol reference")
+    ap.add_argument("--residual-segments", nargs="?", const=True, default=None, metavar="FILE",
+                    help="with --residual: the residual per segment (cluster) of every frame pair's source, before and after the "
+                         "flow; lists the segments whose mean distance under the flow exceeds 0.1 m, worst first (FILE: the "
+                         "whole list as JSON); one process only")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
                     help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
     return ap
@@ -1421,6 +1474,8 @@ def main(argv=None):
         raise SystemExit("--bucketed-epe goes with --protocol reference --dataset argo (the classes and the buckets are Argoverse 2's)")
     if ns.residual is not None and ns.protocol == "reference":
         raise SystemExit("--residual is not built into --protocol reference (COVERAGE.md row 13): run the frame pairs without --protocol")
+    if ns.residual_segments is not None and ns.residual is None:
+        raise SystemExit("--residual-segments goes with --residual (the two share the radius)")
     if (ns.save_flows or ns.save_metrics) and ns.protocol != "reference":
         raise SystemExit("--save-flows and --save-metrics go with --protocol reference")
     if ns.dataset == "argo":
@@ -1489,10 +1544,16 @@ def main(argv=None):
         return
     if ns.residual is not None:
         args.residual = ns.residual
+    if ns.residual_segments is not None:
+        if world > 1:
+            raise SystemExit("--residual-segments under more than one rank: merging the lists is not built")
+        args.residual_segments = ns.residual_segments
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         if ns.residual is not None:
             print(utils_eval.format_residual(*residual_tables(summary["residual"])))
+        if ns.residual_segments is not None:
+            print("\n".join(utils_eval.format_segment_residual(summary["residual_segments"]["worst"])))
         print(json.dumps(summary))
     if world > 1:
         dist.destroy_process_group()

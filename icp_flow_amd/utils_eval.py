@@ -18,7 +18,8 @@ against the `bucketed_scene_flow_eval` package (COVERAGE.md, named deviations).
 Without ground truth: `nn_residual` (icpflow_nn_residual, csrc/nnresid.hip) is the truncated nearest-neighbour residual of a
 warped cloud against the next one -- a hashed grid over the whole frame and an exact radius-bounded search on the GPU;
 `ResidualTable` adds and prints it, `chamfer` is the two directions.  A label-free proxy, not a metric of the reference
-(COVERAGE.md, named deviations)."""
+(COVERAGE.md, named deviations).  `segment_residual` (icpflow_nn_residual_segments, csrc/segresid.hip) is the same residual per
+segment of the source, before and after the flow, against one grid: `SegmentResidual.worst` names the clusters that fit badly."""
 import numpy as np
 
 METRIC_NAMES = ("epe", "accs", "accr", "outlier", "Routlier")
@@ -793,3 +794,129 @@ def format_residual(before, after, names=RESIDUAL_GROUPS):
     cb, ca = fb.mean() + before["backward"].mean(), fa.mean() + after["backward"].mean()
     text.append(f"truncated Chamfer distance (source -> destination + destination -> source): {cb:.6f} -> {ca:.6f}")
     return "\n".join(text)
+
+
+# ---- ... per segment, before and after the flow (icpflow_nn_residual_segments, csrc/segresid.hip) -----------------------------
+RESIDUAL_SKIP_LABELS = (-1e8, -1.0)    # the ground and the unclustered rows: segments no registration moved
+
+
+class SegmentResidual:
+    """icpflow_nn_residual_segments' table on the host: labels float64 [L] ascending, rows int64 [L] (rows of the segment, the
+    bad ones included), and per side -- `before`: the ego-compensated source, `after`: the cloud under the predicted flow, both
+    against the destination -- a ResidualTable with one group per segment; info: the call's d_info."""
+
+    def __init__(self, labels, rows, before, after, info=None):
+        self.labels, self.rows = np.array(labels, dtype=np.float64).reshape(-1), np.array(rows, dtype=np.int64).reshape(-1)
+        self.before, self.after = before, after
+        self.info = dict(info or {})
+        assert len(self.rows) == len(self.labels) == len(before.rows) == len(after.rows)
+
+    @classmethod
+    def from_table(cls, table, edges=RESIDUAL_EDGES, radius=None, info=None):
+        """the kernel's float64 [L][18] -> SegmentResidual"""
+        t = np.asarray(table, dtype=np.float64).reshape(-1, 18)
+        E = len(edges)
+        info = dict(info or {})
+
+        def side(at, bad):
+            return ResidualTable(np.rint(t[:, at]), np.rint(t[:, at + 1]), np.rint(t[:, at + 2: at + 2 + E]), t[:, at + 6], t[:, at + 7],
+                                 edges, radius, bad)
+
+        return cls(t[:, 0], np.rint(t[:, 1]), side(2, info.get("bad_queries_before", 0)), side(10, info.get("bad_queries_after", 0)), info)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def gain(self):
+        """per segment the mean truncated distance the flow took away, in metres: before.mean - after.mean (negative: the flow
+        made the segment fit worse; NaN for a segment without a good row on either side)"""
+        return np.array([self.before.mean(k) - self.after.mean(k) for k in range(len(self))], dtype=np.float64)
+
+    def worst(self, pairs=None, above=RESIDUAL_EDGES[1], skip=RESIDUAL_SKIP_LABELS):
+        """The segments whose AFTER mean exceeds `above` metres, worst first, equal means by ascending label; the labels of
+        `skip` are left out.  pairs ([P, >= 2], column 0 the source label, column 1 the destination's): `matched` says whether
+        the segment is a source of one, `pair` is that row's [src, dst] (None without one).  -> [dict(label, rows, after_mean,
+        before_mean, gain, hit_rate_after, matched, pair)]"""
+        by_src = {}
+        if pairs is not None:
+            p = pairs.detach().cpu().numpy() if hasattr(pairs, "detach") else np.asarray(pairs)
+            for row in np.asarray(p, dtype=np.float64).reshape(len(p), -1):
+                by_src.setdefault(float(row[0]), [float(row[0]), float(row[1])])
+        left_out = set(float(s) for s in skip)
+        out = []
+        for k in range(len(self)):
+            label, after = float(self.labels[k]), self.after.mean(k)
+            if label in left_out or not after > above:       # (a NaN mean -- no good row -- is not listed)
+                continue
+            before = self.before.mean(k)
+            out.append(dict(label=label, rows=int(self.rows[k]), after_mean=after, before_mean=before, gain=before - after,
+                            hit_rate_after=self.after.hit_rate(k), matched=label in by_src, pair=by_src.get(label)))
+        return sorted(out, key=lambda e: (-e["after_mean"], e["label"]))
+
+
+def segment_residual_device(before, after, flow, labels, target, radius=2.0, edges=RESIDUAL_EDGES, Lmax=4096, per_row=False):
+    """icpflow_nn_residual_segments enqueued on the current stream, nothing read back.  before, after [n, 3], flow [n, 3] or None,
+    labels [n], target [m, 3]: device tensors (`after` may be `before`).  -> (table float64 [Lmax, 18], num int32 [1], info
+    int64 [6], d2_before, d2_after): device tensors; the last two float32 [n] with per_row, else None (the call keeps them in
+    its workspace).  Rows of the table from num on are not written."""
+    import ctypes
+    import torch
+    from . import _lib
+    b, t = _cloud3(before, "before"), _cloud3(target, "target")
+    a = b if after is before else _cloud3(after, "after")
+    device = b.device
+    n, m, Lmax = b.shape[0], t.shape[0], int(Lmax)
+    f = None
+    if flow is not None:
+        f = _cloud3(flow, "flow")
+    _lib.require_gpu(labels)
+    lab = labels.to(torch.float32).contiguous()
+    if a.shape[0] != n or (f is not None and f.shape[0] != n) or lab.shape != (n,):
+        raise ValueError(f"segment_residual: after {tuple(a.shape)}, flow {None if f is None else tuple(f.shape)}, labels {tuple(lab.shape)} for {n} rows")
+    if any(x is not None and x.device != device for x in (a, f, lab, t)):
+        raise ValueError("segment_residual: every tensor on the same device")
+    ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    E = len(ed)
+    table = torch.empty((max(Lmax, 0), _lib.NNRS_COLS), dtype=torch.float64, device=device)
+    num = torch.empty(1, dtype=torch.int32, device=device)
+    info = torch.empty(6, dtype=torch.int64, device=device)
+    d2b = torch.empty(n, dtype=torch.float32, device=device) if per_row else None
+    d2a = torch.empty(n, dtype=torch.float32, device=device) if per_row else None
+    with torch.cuda.device(device):
+        need = int(_lib._L.icpflow_nn_residual_segments_workspace_bytes(n, m, Lmax, E))
+        ws = _lib.workspace(device, need)
+        _lib.call("icpflow_nn_residual_segments", _lib.ptr(b), _lib.ptr(a), _lib.ptr(f), _lib.ptr(lab), n, _lib.ptr(t), m, float(radius),
+                  ed.ctypes.data_as(ctypes.c_void_p) if E else None, E, _lib.ptr(table), Lmax, _lib.ptr(num), _lib.ptr(d2b), _lib.ptr(d2a),
+                  _lib.ptr(info), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    return table, num, info, d2b, d2a
+
+
+SEGMENT_INFO_NAMES = ("bad_queries_before", "bad_queries_after", "bad_targets", "occupied_buckets", "longest_bucket")
+
+
+def segment_residual(before, after, flow, labels, target, radius=2.0, edges=RESIDUAL_EDGES, Lmax=4096):
+    """The truncated nearest-neighbour residual of every segment (distinct label) of a source cloud against `target`, BEFORE
+    (`before` as it is) and AFTER (`after` + `flow`): one grid over the target, two queries, one table.  Tensors on the GPU;
+    there is no CPU path.  -> SegmentResidual; one read-back (the table, the number of segments and the info in one tensor).
+    More distinct labels than Lmax is a ValueError."""
+    import torch
+    table, num, info, _, _ = segment_residual_device(before, after, flow, labels, target, radius, edges, Lmax)
+    host = torch.cat([num.to(torch.float64), info.to(torch.float64), table.reshape(-1)]).cpu().numpy()     # the one read-back
+    L = int(host[0])
+    if L < 0:
+        raise ValueError(f"segment_residual: {-L} distinct labels, Lmax = {int(Lmax)}")
+    facts = {name: int(host[1 + k]) for k, name in enumerate(SEGMENT_INFO_NAMES)}
+    return SegmentResidual.from_table(host[7: 7 + L * 18], tuple(float(e) for e in edges), radius, facts)
+
+
+def format_segment_residual(report):
+    """One line per listed segment (SegmentResidual.worst's entries, or run_stream's, which carry `frame_pair` too), in the
+    shape of flow_evaluation's `eval segment:` line."""
+    lines = []
+    for e in report:
+        where = f"frame pair: {e['frame_pair']:4d}, " if "frame_pair" in e else ""
+        pair = e.get("pair")
+        ij = f"i: {int(pair[0]):3d}, j: {int(pair[1]):3d}" if pair else "unmatched"
+        lines.append(f"residual segment: {where}{e['label']:3g}, after: {e['after_mean']:.4f}, before: {e['before_mean']:.4f}, "
+                     f"gain: {e['gain']:.4f}, {ij}; len_i: {e['rows']:6d}, hit rate: {e['hit_rate_after']:.4f}")
+    return lines

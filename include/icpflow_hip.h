@@ -1059,6 +1059,53 @@ int icpflow_nn_residual(const float *d_query, const float *d_flow, int n, const 
                         int64_t *d_table, int64_t *d_info, void *d_ws, size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(g)  the residual per segment, before and after the flow: which cluster was registered wrongly, without ground truth.
+ *
+ * icpflow_nn_residual_segments -- two queries against ONE grid.  d_before float32 [n,3] (the ego-compensated source), d_after
+ *   float32 [n,3] (the cloud the flow applies to; may be the same pointer as d_before), d_flow float32 [n,3] or NULL: the AFTER
+ *   query is q = d_after + d_flow, one fp32 addition per coordinate (NULL: q = d_after); the BEFORE query is d_before as it
+ *   is.  d_target float32 [m,3], d_labels float32 [n], radius in [1e-3, 1e3], h_edges (HOST) E <= ICPFLOW_NNR_MAX_EDGES edges:
+ *   finite, positive, strictly ascending, at most the radius.
+ *   The arithmetic, the hit rule (d2 <= r2), the bad-row rule and the exact search are icpflow_nn_residual's, word for word:
+ *   the same device functions (csrc/nnresid.hpp), no copy.  The grid over the target is built once; each side's queries are
+ *   binned and run through the binned query kernel.  d_d2_before and d_d2_after float32 [n] may each be NULL; where given they
+ *   equal, bit for bit, what two icpflow_nn_residual calls write to d_d2_out.
+ *   A segment is one distinct value of d_labels, in ascending order, exactly as icpflow_cluster_table defines it (its dictionary
+ *   and stable order are reused: -0.0 and +0.0 are one label, NaN labels one segment per bit pattern); Lmax <= 4096 (else
+ *   ICPFLOW_E_LIMIT); *d_num (int32) is the number of segments, or the NEGATIVE count when there are more distinct labels than
+ *   Lmax (nothing of the table is written then).
+ *   d_table double [Lmax][ICPFLOW_NNRS_COLS], row c = the c-th label (rows from *d_num on are not written):
+ *       0        label                                1        rows of the segment
+ *       2 - 9    BEFORE: good rows, hits, rows with d <= edge[k] (k < 4; zero for k >= E), sum of d, sum of d * d
+ *       10 - 17  AFTER: the same eight
+ *   d = sqrtf(d2) widened to fp64, the edge test and d * d as in icpflow_nn_residual's table; a miss counts with sqrtf(r2); a
+ *   bad query enters nothing on its side.  Counts are exact in a double.
+ *   Every number is a function of the arguments alone, by icpflow_seq_segment_table's scheme: segments cut into chunks of 1024
+ *   rows of the stable order, a workgroup of 256 threads per chunk, thread t takes rows t, t + 256, t + 512, t + 768 in that
+ *   order, counts by ballot and popcount, sums through one fixed butterfly with the waves added in wave order, the chunks added
+ *   in ascending order; no floating-point atomics (csrc/segresid.hip).
+ *   d_info int64 [6], required: bad queries before, bad queries after, bad targets, occupied buckets, the longest bucket, 0.
+ *   Refusals, all before any launch: a null required pointer, a negative size, Lmax < 1, a radius, E or edges outside their
+ *   ranges are ICPFLOW_E_ARG; n or m > 2^29 or Lmax > 4096 are ICPFLOW_E_LIMIT; fewer workspace bytes than the query says are
+ *   ICPFLOW_E_WORKSPACE before anything is written; a workspace that is not 16-byte aligned is ICPFLOW_E_ARG.  n = 0 succeeds
+ *   with *d_num = 0; m = 0 succeeds (every good query is a miss).
+ *   The workspace is the caller's: icpflow_nn_residual_segments_workspace_bytes(n, m, Lmax, E) =
+ *       table(m) + table(n) + 3 a(4 n) + a(8 n) + a(72 Lmax) + a(4 (Lmax + 1)) + a(128 chunks) + a(T)
+ *   bytes: table(k) and a(x) as for icpflow_nn_residual (ONE query grid, table(n): the AFTER side is binned into it once the
+ *   BEFORE side's query is through), two d2 arrays and one idx array, the stable order, the segments' (label, count, start)
+ *   rows, the first chunk of every segment, chunks = floor(n / 1024) + min(n, Lmax) + 1 partials of 2 x 8 doubles, and
+ *   T = icpflow_cluster_table_workspace_bytes(max(n, 1), Lmax), the label order's own workspace.  E does not enter; 0 for
+ *   arguments the call refuses.  Nothing in it is read before it is written.  Asynchronous on `stream`, no host
+ *   synchronisation, no allocation.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_NNRS_COLS 18
+size_t icpflow_nn_residual_segments_workspace_bytes(int n, int m, int Lmax, int E);
+int icpflow_nn_residual_segments(const float *d_before, const float *d_after, const float *d_flow, const float *d_labels, int n,
+                                 const float *d_target, int m, double radius, const double *h_edges, int E, double *d_table,
+                                 int Lmax, int32_t *d_num, float *d_d2_before, float *d_d2_after, int64_t *d_info, void *d_ws,
+                                 size_t ws_bytes, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
