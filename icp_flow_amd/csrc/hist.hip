@@ -200,9 +200,10 @@ constexpr int kVoteSpan = 2;     // sorted vote: Y tiles per workgroup (at most)
 
 // The votes of one X row (per lane) against the staged targets [r0, r1) (wave-uniform bounds): the exact
 // box test and bin arithmetic of hist_cuda_core.cuh:44-60.  FAST: all three quotients take the hoisted
-// division and the bin index fits 24-bit multiplies (decided once per launch); LDS_HIST: counters in LDS.  Four targets per round, all four LDS
-// reads issued before the first test: with one workgroup per CU (a frame-level batch) nothing else hides
-// the LDS latency of a one-target loop.
+// division and the bin index fits 24-bit multiplies (decided once per launch); LDS_HIST: counters in LDS.  Four targets are in flight at any time
+// (a ring, see the loop): with one workgroup per CU (a frame-level batch) nothing else hides the LDS latency
+// of a one-target loop, and with eight waves per SIMD the waits of a loop that drains per round still
+// took two thirds of a wave's life.
 // The quotient (v - min) / (max - min) of a difference one float below max can round to 1.0, i.e. p = len (the
 // reference does not clamp, hist_cuda_core.cuh:52-58): with p_x = len_x the flat bin index runs past the pair's
 // L bins into the next pair's (bins are one [B, L] allocation, hist_cuda.cu:59) -- or, for the last pair, past the
@@ -222,6 +223,24 @@ extern "C" int icpflow_debug_vote_stats(unsigned long long *out4, int reset)
 }
 #endif
 
+// The byte offset of an LDS object inside the workgroup's LDS (what a ds_* instruction takes as its address).
+__device__ __forceinline__ uint32_t lds_byte_offset(const void *p)
+{
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
+}
+
+// One vote per lane of `mask` into the LDS counter at byte offset `addr`: ds_add_u32 under the exec mask, no skip branch around
+// it.  Written by hand because the compiler branches around any LDS operation of a conditional block (s_cbranch_execz) and then
+// cannot count it: it waited for lgkmcnt(0) -- every read in flight AND the votes before, whose result nobody needs -- in front of
+// the next target.  The compiler does not know of this operation at all: its own counts for the reads around it ask for too much
+// rather than too little (LDS operations of a wave return in order), and whoever reads the counters drains first (vote_range's end).
+__device__ __forceinline__ void lds_vote(uint32_t addr, unsigned long long mask)
+{
+    unsigned long long saved;
+    asm volatile("s_and_saveexec_b64 %0, %1\n\tds_add_u32 %2, %3\n\ts_mov_b64 exec, %0"
+                 : "=&s"(saved) : "s"(mask), "v"(addr), "v"(1u) : "memory", "scc");
+}
+
 template <bool FAST, bool LDS_HIST, bool P2 = false>
 __device__ __forceinline__ void vote_range(const float4 *__restrict__ tile, int r0, int r1, const float4 &xi,
                                            const VoteBox &box, const AxisQuot &dqx, const AxisQuot &dqy,
@@ -236,47 +255,81 @@ __device__ __forceinline__ void vote_range(const float4 *__restrict__ tile, int 
     const float hx = nextafterf(box.max_x, -INFINITY), hy = nextafterf(box.max_y, -INFINITY),
                 hz = nextafterf(box.max_z, -INFINITY);
     [[maybe_unused]] const float p2x = dqx.y1 * flx, p2y = dqy.y1 * fly;   // (P2: exact products of a power of two and an integer below 2^23)
-    for (int k = r0; k < r1; k += 4) {
-        float4 t4[4];
+    if (r1 <= r0) return;
+    [[maybe_unused]] const uint32_t lbase = LDS_HIST ? lds_byte_offset(counters) : 0u;
+    // one target against this lane's row, from their difference (vx, vy, vz)
+    auto vote = [&](const float vx, const float vy, const float vz) {
+        // min <= v < max  <=>  the median of (v, min, pred(max)) is v: one v_med3 + one compare per axis
+        // instead of two compares and a scalar AND (NaN fails both forms)
+        const bool inx = __builtin_amdgcn_fmed3f(vx, box.min_x, hx) == vx, iny = __builtin_amdgcn_fmed3f(vy, box.min_y, hy) == vy,
+                   inz = __builtin_amdgcn_fmed3f(vz, box.min_z, hz) == vz;
+        [[maybe_unused]] const bool in = inx && iny && inz;
+#ifdef ICPFLOW_VOTE_STATS
+        {
+            const unsigned long long m = __ballot(in);
+            if ((threadIdx.x & 63) == __builtin_ctzll(__ballot(true))) atomicAdd(&g_vote_stats[1], (unsigned long long)__popcll(m));
+        }
+#endif
+        // LDS counters: the bin of EVERY lane, the vote under the mask of the lanes inside the box (lds_vote).  A wave step without a
+        // voting lane is rare (tools/dbg/vote_stats.py), so the arithmetic of the lanes outside costs no issue slot that a skip would
+        // have saved; their bin is garbage and never used.  Global counters: the plain branch, their atomics need no wait.
+        if (LDS_HIST || in) {
+            // (P2: the x and y extents of the box are powers of two -- the quotient is one exact product, see axis_quot_make)
+            // ... and with it the quotient's product with float(len): (a 2^-k) len rounds once, like a (2^-k len) -- 2^-k len is exact
+            // for any length the 24-bit fast path admits
+            const int px = P2 ? (int)((vx - box.min_x) * p2x) : (int)(axis_quot<FAST>(vx - box.min_x, dqx) * flx);   // >= 0: truncation == floor
+            const int py = P2 ? (int)((vy - box.min_y) * p2y) : (int)(axis_quot<FAST>(vy - box.min_y, dqy) * fly);
+            const int pz = (int)(axis_quot<FAST>(vz - box.min_z, dqz) * flz);
+            // FAST also promises len_x * len_y and len_z below 2^23: 24-bit multiplies (full rate) are exact
+            int bin;
+            if (FAST) {   // v_mad_i32_i24 is full rate (the compiler picks the quarter-rate v_mad_u64_u32 here)
+                int row;
+                asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(row) : "v"(px), "s"(box.len_y), "v"(py));
+                asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(bin) : "v"(row), "s"(box.len_z), "v"(pz));
+            } else {
+                // (unsigned: with LDS counters the lanes outside the box come through here with any px, py, pz)
+                bin = (int)(((uint32_t)px * (uint32_t)box.len_y + (uint32_t)py) * (uint32_t)box.len_z + (uint32_t)pz);
+            }
+            // (the mask from the three compares' own: the ballot of their conjunction goes through a register and back)
+            if (LDS_HIST) lds_vote(lbase + ((uint32_t)bin << 2), __builtin_amdgcn_ballot_w64(inx) & __builtin_amdgcn_ballot_w64(iny) & __builtin_amdgcn_ballot_w64(inz));
+            else if (bin < limit) atomicAdd(&counters[bin], 1u);   // (last pair: nothing past the allocation)
+        }
+    };
+    // A ring of four targets in registers: the read of target k + 4 is issued into the registers target k has just left, in front
+    // of target k's vote, so a wave always has reads outstanding while it evaluates and waits for none that was issued less than two
+    // targets ago.  Full trips with a full trip behind them read without a clamp; the rest of the window stands apart.
+    int k = r0;
+    float4 c[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) t4[u] = tile[min(k + u, r1 - 1)];  // same address in every lane: broadcast
+    for (int u = 0; u < 4; ++u) c[u] = tile[min(k + u, kVoteTile - 1)];  // same address in every lane: broadcast; past r1: read, never voted on
+    for (; k + 8 <= r1; k += 4) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            if (k + u >= r1) break;   // wave-uniform
-            const float4 t = t4[u];
-            const float vx = xi.x - t.x, vy = xi.y - t.y, vz = xi.z - t.z;
-            // min <= v < max  <=>  the median of (v, min, pred(max)) is v: one v_med3 + one compare per axis
-            // instead of two compares and a scalar AND (NaN fails both forms)
-#ifdef ICPFLOW_VOTE_STATS
-            {
-                const bool in = __builtin_amdgcn_fmed3f(vx, box.min_x, hx) == vx && __builtin_amdgcn_fmed3f(vy, box.min_y, hy) == vy &&
-                                __builtin_amdgcn_fmed3f(vz, box.min_z, hz) == vz;
-                const unsigned long long m = __ballot(in);
-                if ((threadIdx.x & 63) == __builtin_ctzll(__ballot(true))) atomicAdd(&g_vote_stats[1], (unsigned long long)__popcll(m));
-            }
-#endif
-            if (__builtin_amdgcn_fmed3f(vx, box.min_x, hx) == vx && __builtin_amdgcn_fmed3f(vy, box.min_y, hy) == vy &&
-                __builtin_amdgcn_fmed3f(vz, box.min_z, hz) == vz) {
-                // (P2: the x and y extents of the box are powers of two -- the quotient is one exact product, see axis_quot_make)
-                // ... and with it the quotient's product with float(len): (a 2^-k) len rounds once, like a (2^-k len) -- 2^-k len is exact
-                // for any length the 24-bit fast path admits
-                const int px = P2 ? (int)((vx - box.min_x) * p2x) : (int)(axis_quot<FAST>(vx - box.min_x, dqx) * flx);   // >= 0: truncation == floor
-                const int py = P2 ? (int)((vy - box.min_y) * p2y) : (int)(axis_quot<FAST>(vy - box.min_y, dqy) * fly);
-                const int pz = (int)(axis_quot<FAST>(vz - box.min_z, dqz) * flz);
-                // FAST also promises len_x * len_y and len_z below 2^23: 24-bit multiplies (full rate) are exact
-                int bin;
-                if (FAST) {   // v_mad_i32_i24 is full rate (the compiler picks the quarter-rate v_mad_u64_u32 here)
-                    int row;
-                    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(row) : "v"(px), "s"(box.len_y), "v"(py));
-                    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(bin) : "v"(row), "s"(box.len_z), "v"(pz));
-                } else {
-                    bin = (px * box.len_y + py) * box.len_z + pz;
-                }
-                if (!LDS_HIST && bin >= limit) continue;   // last pair: past the allocation
-                atomicAdd(&counters[bin], 1u);
-            }
+            const float vx = xi.x - c[u].x, vy = xi.y - c[u].y, vz = xi.z - c[u].z;
+            __builtin_amdgcn_sched_barrier(0);   // (the registers of target k are free: its successor is read into them)
+            c[u] = tile[k + 4 + u];
+            vote(vx, vy, vz);
+            __builtin_amdgcn_sched_barrier(0);   // (one target after the other: interleaved, the four reads sink behind the votes)
         }
     }
+    // What is left: fewer than eight targets, the first four of them in the ring.  The others are read at once into registers of
+    // their own.  A row at or past r1 may be read (clamped to the tile: it is another window's, or a former tile's stale row) but is
+    // never voted on: every vote below stands behind its own k + u < r1.
+    float4 d[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) d[u] = tile[min(k + 4 + u, kVoteTile - 1)];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (k + u >= r1) break;   // wave-uniform
+        vote(xi.x - c[u].x, xi.y - c[u].y, xi.z - c[u].z);
+    }
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+        if (k + 4 + u >= r1) break;
+        vote(xi.x - d[u].x, xi.y - d[u].y, xi.z - d[u].z);
+    }
+    // the votes are outstanding LDS operations the compiler does not know of: the barrier behind the tile must find them done
+    if (LDS_HIST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
 // bins_u32: [B, L] zero-initialised.  swap (optional, per pair): vote with X and Y
@@ -508,7 +561,8 @@ __device__ __forceinline__ void hist_vote_sorted_body(
     const int limit = lastPair ? L : 0x7fffffff;
     const int lane = threadIdx.x & (kWave - 1);
     const int wv = (int)(threadIdx.x >> 6);
-    const int share = SPLIT > 1 ? wv / kRowWaves : 0;           // which part of the window this wave takes
+    // which part of the window this wave takes (wave-uniform: as a scalar it leaves vote_range's bounds, counter and addresses scalar)
+    const int share = SPLIT > 1 ? __builtin_amdgcn_readfirstlane(wv / kRowWaves) : 0;
     const int i = ((SPLIT > 1 ? wv % kRowWaves : wv) * rowBlocks + rb) * kWave + lane;
     const bool xvalid = i < nx;
     float4 xi = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -721,7 +775,7 @@ struct FrontRoleArgs {
 };
 constexpr int kFrontBlock = 512;
 
-__global__ __launch_bounds__(kFrontBlock) void front_roles_kernel(
+__global__ __launch_bounds__(kFrontBlock, 8) void front_roles_kernel(   // (8 waves per SIMD: the four workgroups per CU the LDS admits)
     const float4 *__restrict__ Xs, const float4 *__restrict__ Ys, const int32_t *__restrict__ nXv,
     const int32_t *__restrict__ nYv, int N, int len_x, int len_y, int len_z,
     const float *__restrict__ ex, const float *__restrict__ ey, const float *__restrict__ ez,
