@@ -108,6 +108,11 @@ SIGNATURES = {
     "icpflow_nn_residual": (_i, [_p, _p, _i, _p, _i, _d, _p, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_nn_residual_segments_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "icpflow_nn_residual_segments": (_i, [_p, _p, _p, _p, _i, _p, _i, _d, _p, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_sight_default_params": (_i, [_p]),
+    "icpflow_sight_build": (_i, [_p, _i, _p, _p, _p, _p, _p]),
+    "icpflow_sight_query": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "icpflow_sight_segments_workspace_bytes": (_sz, [_i, _i]),
+    "icpflow_sight_segments": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _d, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -146,6 +151,8 @@ CLASS_MAX_ROWS, CLASS_MAX_BUCKETS, CLASS_MAX_WORDS = 64, 8, 1024   # icpflow_seq
 BUCKET_MAX_ROWS, BUCKET_MAX_BUCKETS = 64, 64     # icpflow_seq_bucket_table: G and S (a workgroup's table of G * S * 3 words in LDS)
 NNR_MAX_GROUPS, NNR_MAX_EDGES = 64, 4            # icpflow_nn_residual: G and E
 NNRS_COLS, NNRS_MAX_SEGMENTS = 18, 4096           # icpflow_nn_residual_segments: columns of a row; Lmax at most
+SIGHT_COLS, SIGHT_MAX_SEGMENTS = 24, 4096         # icpflow_sight_segments: columns of a row; Lmax at most
+SIGHT_BAD_ROW, SIGHT_OUTSIDE, SIGHT_NO_RETURN, SIGHT_SEEN_THROUGH, SIGHT_AT_FIRST_RETURN, SIGHT_BEHIND = -2, 0, 1, 2, 3, 4
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical
@@ -293,6 +300,25 @@ class GroundParams(ctypes.Structure):
         p = GroundParams()
         call("icpflow_ground_default_params", ctypes.byref(p))
         return p
+
+
+class SightParams(ctypes.Structure):
+    """icpflow_sight_params_t: the depth image of a destination sweep and the margins of the ray test."""
+    _fields_ = [("struct_size", _sz), ("W", _i), ("H", _i), ("tan_lo", _d), ("tan_hi", _d), ("min_range", _d), ("max_range", _d),
+                ("margin_abs", _d), ("margin_rel", _d)]
+
+    @staticmethod
+    def defaults(**over):
+        p = SightParams()
+        call("icpflow_sight_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if k == "struct_size" or k not in dict(SightParams._fields_):
+                raise TypeError(f"SightParams: no parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
 class Profile:

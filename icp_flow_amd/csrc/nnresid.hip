@@ -93,12 +93,7 @@ constexpr int kWaves = kThreads / kWave;
 constexpr int kTile = 1024;                         // buckets per scan tile: four per thread
 constexpr int kPerThread = kTile / kThreads;
 constexpr int kMaxGroups = ICPFLOW_NNR_MAX_GROUPS;  // (the limits both entry points share: nnresid.hpp)
-constexpr float kFar = 1e6f;                        // a coordinate beyond it is a bad row
-
-__device__ __forceinline__ bool good_coord(float x, float y, float z)   // (a NaN fails every comparison)
-{
-    return fabsf(x) <= kFar && fabsf(y) <= kFar && fabsf(z) <= kFar;
-}
+using icpflow::nnr::good_coord;                     // (nnresid.hpp: a coordinate beyond 1e6 m is a bad row)
 
 __device__ __forceinline__ int cell_of(float v, double h) { return (int)floor((double)v / h); }
 

@@ -1,6 +1,6 @@
 // nnresid.hpp -- what nnresid.hip shares with segresid.hip: the hashed grid over one cloud, its carve, its build and the launch
 // of the binned query.  Declarations only: the kernels and every definition stay in nnresid.hip, so both entry points run the
-// same device code.
+// same device code.  The one inline function is the bad-row rule, which sight.hip applies word for word.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,14 @@ namespace nnr {
 constexpr int kMaxEdges = ICPFLOW_NNR_MAX_EDGES;
 constexpr int kMaxRows = 1 << 29;                   // of either cloud: 2^k >= 2 rows buckets stay an int
 constexpr double kMinRadius = 1e-3, kMaxRadius = 1e3;
+
+constexpr float kFar = 1e6f;                        // a coordinate beyond it is a bad row
+
+// the bad-row rule of every entry point that judges rows of a cloud (sight.hip's too)
+__device__ __forceinline__ bool good_coord(float x, float y, float z)   // (a NaN fails every comparison)
+{
+    return fabsf(x) <= kFar && fabsf(y) <= kFar && fabsf(z) <= kFar;
+}
 
 struct Edges {
     int E;

@@ -36,6 +36,10 @@ against the destination, truncated at R metres (2.0 when given bare), before and
 
     python -m icp_flow_amd.frame_pairs DIR --residual [R] [--in-flight 4]
 
+`--residual-segments [FILE]` lists the segments (clusters) that still fit badly under the flow, and `--residual-sight [X Y Z]`
+says of each whether the destination sweep contradicts it ("seen through") or merely lost it ("lost from view":
+`frame_segment_sight`, icpflow_sight_*); the summary gains `residual_sight` and `ms_sight_per_frame_pair`.
+
 `run_sequences` (`--protocol reference`) evaluates whole sequence files by the reference's metric protocol instead
 (utils_eval.py:185-368, main.py:173-181, 285-296): the frame pairs of a file as above, their flows assembled on the device
 into the sequence's flow (zeros for frame 0, main.py:217-260), one pass of icpflow_seq_metrics over it and ONE small
@@ -1226,6 +1230,26 @@ def frame_segment_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_ED
     return utils_eval.segment_residual(ps, raw, out["flow"].to(device).float(), _source_labels(fp, out, device), pd, radius, edges)
 
 
+def frame_segment_sight(fp, out, device, radius, origin=(0.0, 0.0, 0.0), edges=utils_eval.RESIDUAL_EDGES, **params):
+    """`frame_segment_residual` with the line-of-sight check beside it (utils_eval.segment_sight): the same residual call with
+    its per-row distances kept, one depth image over the destination as seen from `origin`, and the codes per segment among
+    the rows further than RESIDUAL_EDGES[1] metres from every destination point.  -> (SegmentResidual, sight), `sight` a
+    function without arguments that enqueues the image and the table and reads the table back -> SegmentSight (run_stream
+    times the two parts apart)."""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    flow, labels = out["flow"].to(device).float(), _source_labels(fp, out, device)
+    table, num, info, d2b, d2a = utils_eval.segment_residual_device(ps, raw, flow, labels, pd, radius, edges, per_row=True)
+    report = utils_eval.segment_residual_read(table, num, info, radius, edges)
+
+    def sight():
+        image = utils_eval.sight_image(pd, origin, **params)
+        return utils_eval.segment_sight(image, ps, raw, flow, labels, d2b, d2a, far=utils_eval.RESIDUAL_EDGES[1])
+
+    return report, sight
+
+
 RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
 
 
@@ -1295,7 +1319,14 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     flow exceeds utils_eval.RESIDUAL_EDGES[1] metres are collected, worst first.  The summary gains `residual_segments` (above,
     segments_judged, segments_listed, worst: at most RESIDUAL_SEGMENTS_SHOWN entries, each with its frame pair's number and
     path), `ms_segment_residual_per_frame_pair` (device-synchronised around the call and its read-back) and, with a file name,
-    `residual_segments_file`: the whole list written there as JSON."""
+    `residual_segments_file`: the whole list written there as JSON.
+    args.residual_sight = True or (x, y, z) (`--residual-sight [X Y Z]`; needs args.residual_segments; one process only): the
+    line-of-sight check beside the segments' residual -- `frame_segment_sight`: per frame pair one depth image over the
+    destination as seen from the origin (True: (0, 0, 0)), the codes per segment among the rows further than
+    utils_eval.RESIDUAL_EDGES[1] metres from every destination point, one more read-back.  The SegmentResidual is the one the run
+    without the attribute gets; every listed segment gains `seen_through`, `excused`, `far_rows` and a `verdict`
+    (utils_eval.SegmentSight.annotate), and the summary gains `residual_sight` (params, origin, far, verdicts: listed segments
+    per verdict) and `ms_sight_per_frame_pair` (device-synchronised around the image, the table and its read-back only)."""
     import torch.distributed as dist
     device = torch.device(device)
     pipelined = int(in_flight) > 1 and register_fn is None
@@ -1317,6 +1348,13 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     if per_segment and world > 1:
         raise ValueError("args.residual_segments under more than one rank: merging the lists is not built")
     segment_lists, segment_ms, segments_judged = {}, [], 0     # frame pair -> its listed segments
+    sight = getattr(args, "residual_sight", None)
+    if sight is not None and sight is not False and not per_segment:
+        raise ValueError("args.residual_sight needs args.residual_segments: it judges the segments that one lists")
+    sight_origin = (0.0, 0.0, 0.0) if sight is True or not sight else tuple(float(v) for v in sight)
+    if len(sight_origin) != 3:
+        raise ValueError(f"args.residual_sight: True or an origin (x, y, z), got {sight!r}")
+    sight_ms = []
 
     def account(fp, out, index=None):
         nonlocal matched, segments_judged
@@ -1330,11 +1368,20 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             k = len(segment_lists) if index is None else index
             sync()
             t0 = time.perf_counter()
-            report = frame_segment_residual(fp, out, device, float(radius))
+            if sight:
+                report, look = frame_segment_sight(fp, out, device, float(radius), sight_origin)
+            else:
+                report = frame_segment_residual(fp, out, device, float(radius))
             sync()
             segment_ms.append((time.perf_counter() - t0) * 1e3)
             segments_judged += sum(1 for v in report.labels.tolist() if v not in utils_eval.RESIDUAL_SKIP_LABELS)
             segment_lists[k] = [dict(frame_pair=k, path=fp.name, **e) for e in report.worst(pairs=out["pairs"])]
+            if sight:
+                t0 = time.perf_counter()
+                seen = look()
+                sync()
+                sight_ms.append((time.perf_counter() - t0) * 1e3)
+                seen.annotate(segment_lists[k])
         pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
         matched += int(out["pairs"].shape[0])
         if fp.gt_flow is not None:
@@ -1399,6 +1446,12 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             with open(per_segment, "w") as f:
                 json.dump(listed, f, indent=1)
             out["residual_segments_file"] = per_segment
+    if per_segment and sight:
+        from . import _lib
+        verdicts = {v: sum(1 for e in listed if e["verdict"] == v) for v in utils_eval.SIGHT_VERDICTS}
+        out["residual_sight"] = dict(params=_lib.SightParams.defaults().as_dict(), origin=list(sight_origin), far=utils_eval.RESIDUAL_EDGES[1],
+                                     verdicts=verdicts)
+        out["ms_sight_per_frame_pair"] = sum(sight_ms) / max(len(sight_ms), 1)
     return out
 
 
@@ -1461,6 +1514,11 @@ def argument_parser():
                     help="with --residual: the residual per segment (cluster) of every frame pair's source, before and after the "
                          "flow; lists the segments whose mean distance under the flow exceeds 0.1 m, worst first (FILE: the "
                          "whole list as JSON); one process only")
+    ap.add_argument("--residual-sight", type=float, nargs="*", default=None, metavar="X",
+                    help="with --residual-segments: the line-of-sight check of every listed segment against a depth image of the "
+                         "destination sweep -- 'seen through' (the flow put it where the sweep saw free space), 'lost from view' "
+                         "(occluded, no return, out of range) or 'undecided'; X Y Z: the sensor's position in the frame of the "
+                         "points (bare: 0 0 0)")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
                     help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
     return ap
@@ -1476,6 +1534,10 @@ def main(argv=None):
         raise SystemExit("--residual is not built into --protocol reference (COVERAGE.md row 13): run the frame pairs without --protocol")
     if ns.residual_segments is not None and ns.residual is None:
         raise SystemExit("--residual-segments goes with --residual (the two share the radius)")
+    if ns.residual_sight is not None and ns.residual_segments is None:
+        raise SystemExit("--residual-sight goes with --residual-segments (it judges the segments that one lists)")
+    if ns.residual_sight is not None and len(ns.residual_sight) not in (0, 3):
+        raise SystemExit("--residual-sight takes no number or the origin's three: X Y Z")
     if (ns.save_flows or ns.save_metrics) and ns.protocol != "reference":
         raise SystemExit("--save-flows and --save-metrics go with --protocol reference")
     if ns.dataset == "argo":
@@ -1548,12 +1610,15 @@ def main(argv=None):
         if world > 1:
             raise SystemExit("--residual-segments under more than one rank: merging the lists is not built")
         args.residual_segments = ns.residual_segments
+    if ns.residual_sight is not None:
+        args.residual_sight = tuple(ns.residual_sight) if ns.residual_sight else True
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         if ns.residual is not None:
             print(utils_eval.format_residual(*residual_tables(summary["residual"])))
         if ns.residual_segments is not None:
-            print("\n".join(utils_eval.format_segment_residual(summary["residual_segments"]["worst"])))
+            lines = utils_eval.format_segment_sight if ns.residual_sight is not None else utils_eval.format_segment_residual
+            print("\n".join(lines(summary["residual_segments"]["worst"])))
         print(json.dumps(summary))
     if world > 1:
         dist.destroy_process_group()

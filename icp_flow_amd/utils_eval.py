@@ -19,7 +19,9 @@ Without ground truth: `nn_residual` (icpflow_nn_residual, csrc/nnresid.hip) is t
 warped cloud against the next one -- a hashed grid over the whole frame and an exact radius-bounded search on the GPU;
 `ResidualTable` adds and prints it, `chamfer` is the two directions.  A label-free proxy, not a metric of the reference
 (COVERAGE.md, named deviations).  `segment_residual` (icpflow_nn_residual_segments, csrc/segresid.hip) is the same residual per
-segment of the source, before and after the flow, against one grid: `SegmentResidual.worst` names the clusters that fit badly."""
+segment of the source, before and after the flow, against one grid: `SegmentResidual.worst` names the clusters that fit badly;
+`sight_image` / `line_of_sight` / `segment_sight` (icpflow_sight_*, csrc/sight.hip) ask the destination sweep whether such a
+cluster was put where the sweep saw free space or merely went out of view: `SegmentSight.annotate` adds the verdict."""
 import numpy as np
 
 METRIC_NAMES = ("epe", "accs", "accr", "outlier", "Routlier")
@@ -899,12 +901,17 @@ def segment_residual(before, after, flow, labels, target, radius=2.0, edges=RESI
     (`before` as it is) and AFTER (`after` + `flow`): one grid over the target, two queries, one table.  Tensors on the GPU;
     there is no CPU path.  -> SegmentResidual; one read-back (the table, the number of segments and the info in one tensor).
     More distinct labels than Lmax is a ValueError."""
-    import torch
     table, num, info, _, _ = segment_residual_device(before, after, flow, labels, target, radius, edges, Lmax)
+    return segment_residual_read(table, num, info, radius, edges)
+
+
+def segment_residual_read(table, num, info, radius=2.0, edges=RESIDUAL_EDGES):
+    """segment_residual_device's table, number of segments and info read back in one tensor.  -> SegmentResidual"""
+    import torch
     host = torch.cat([num.to(torch.float64), info.to(torch.float64), table.reshape(-1)]).cpu().numpy()     # the one read-back
     L = int(host[0])
     if L < 0:
-        raise ValueError(f"segment_residual: {-L} distinct labels, Lmax = {int(Lmax)}")
+        raise ValueError(f"segment_residual: {-L} distinct labels, Lmax = {int(table.shape[0])}")
     facts = {name: int(host[1 + k]) for k, name in enumerate(SEGMENT_INFO_NAMES)}
     return SegmentResidual.from_table(host[7: 7 + L * 18], tuple(float(e) for e in edges), radius, facts)
 
@@ -919,4 +926,191 @@ def format_segment_residual(report):
         ij = f"i: {int(pair[0]):3d}, j: {int(pair[1]):3d}" if pair else "unmatched"
         lines.append(f"residual segment: {where}{e['label']:3g}, after: {e['after_mean']:.4f}, before: {e['before_mean']:.4f}, "
                      f"gain: {e['gain']:.4f}, {ij}; len_i: {e['rows']:6d}, hit rate: {e['hit_rate_after']:.4f}")
+    return lines
+
+
+# ---- line of sight: a missing neighbour told apart (icpflow_sight_*, csrc/sight.hip) -------------------------------------------
+SIGHT_VERDICTS = ("seen through", "lost from view", "undecided")
+SIGHT_EXCUSED = (0, 1, 4)              # outside the field of view, on a ray without a return, behind the first return
+
+
+class SightImage:
+    """The depth image of one destination sweep on the device (icpflow_sight_build): image uint32 [2, H, W] -- plane 0 the bits
+    of the nearest range per pixel, plane 1 its minimum over the 3 x 3 pixels around --, the parameters it was built with
+    (_lib.SightParams), the sensor origin (float64 [3]) and info, int64 [3] on the device: bad targets, targets outside the
+    field of view, occupied pixels."""
+
+    def __init__(self, image, params, origin, info):
+        self.image, self.params, self.info = image, params, info
+        self.origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+
+    @property
+    def device(self):
+        return self.image.device
+
+    def _args(self):
+        import ctypes
+        from . import _lib
+        return _lib.ptr(self.image), ctypes.byref(self.params), self.origin.ctypes.data_as(ctypes.c_void_p)
+
+
+def sight_image(points_dst, origin=(0.0, 0.0, 0.0), **params):
+    """The depth image of the destination sweep `points_dst` ([m, 3] on the GPU; there is no CPU path) as seen from `origin`
+    -- the sensor's position in the frame of the points --, enqueued on the current stream.  params: fields of
+    icpflow_sight_params_t (W, H, tan_lo, tan_hi, min_range, max_range, margin_abs, margin_rel) that replace the library's
+    defaults.  -> SightImage"""
+    import ctypes
+    import torch
+    from . import _lib
+    t = _cloud3(points_dst, "points_dst")
+    p = _lib.SightParams.defaults(**params)
+    o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+    image = torch.empty((2, max(int(p.H), 0), max(int(p.W), 0)), dtype=torch.int32, device=t.device)   # (the bits of a uint32 image)
+    info = torch.empty(3, dtype=torch.int64, device=t.device)
+    with torch.cuda.device(t.device):
+        _lib.call("icpflow_sight_build", _lib.ptr(t), t.shape[0], o.ctypes.data_as(ctypes.c_void_p), ctypes.byref(p), _lib.ptr(image),
+                  _lib.ptr(info), _lib.stream(t.device))
+    return SightImage(image, p, o, info)
+
+
+def line_of_sight(image, points, flow=None, near=False):
+    """The ray test of every row of `points` (+ `flow`) against a SightImage, enqueued on the current stream: -> codes int32 [n]
+    on the device (-2 a bad row, 0 outside the field of view, 1 no return on the ray, 2 seen through, 3 at the first return,
+    4 behind it); with near=True -> (codes, near float32 [n]: the nearest range of the 3 x 3 pixels, +inf without a pixel).
+    The six counts stay on the device as `image.last_counts` (int64 [6]: bad rows, then codes 0 .. 4)."""
+    import torch
+    from . import _lib
+    q = _cloud3(points, "points")
+    f = None if flow is None else _cloud3(flow, "flow")
+    n = q.shape[0]
+    if f is not None and f.shape[0] != n:
+        raise ValueError(f"flow: {tuple(f.shape)} for {n} rows")
+    if q.device != image.device or (f is not None and f.device != image.device):
+        raise ValueError("line_of_sight: every tensor on the image's device")
+    codes = torch.empty(n, dtype=torch.int32, device=q.device)
+    nearest = torch.empty(n, dtype=torch.float32, device=q.device) if near else None
+    counts = torch.empty(6, dtype=torch.int64, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.call("icpflow_sight_query", *image._args(), _lib.ptr(q), _lib.ptr(f), n, _lib.ptr(codes), _lib.ptr(nearest), _lib.ptr(counts),
+                  _lib.stream(q.device))
+    image.last_counts = counts
+    return (codes, nearest) if near else codes
+
+
+class SightCounts:
+    """one side of icpflow_sight_segments' table: good int64 [L], codes int64 [L, 5] (the rows of codes 0 .. 4), far int64
+    [L, 5] (the FAR rows among them)"""
+
+    def __init__(self, good, codes, far):
+        self.good = np.array(good, dtype=np.int64).reshape(-1)
+        self.codes, self.far = np.array(codes, dtype=np.int64).reshape(-1, 5), np.array(far, dtype=np.int64).reshape(-1, 5)
+
+
+class SegmentSight:
+    """icpflow_sight_segments' table on the host: labels float64 [L] ascending, rows int64 [L], `before` and `after`
+    SightCounts; info: the twelve counts of the call (bad rows and codes 0 .. 4 of either side)."""
+
+    def __init__(self, labels, rows, before, after, info=None):
+        self.labels, self.rows = np.array(labels, dtype=np.float64).reshape(-1), np.array(rows, dtype=np.int64).reshape(-1)
+        self.before, self.after = before, after
+        self.info = dict(info or {})
+        assert len(self.rows) == len(self.labels) == len(before.good) == len(after.good)
+
+    @classmethod
+    def from_table(cls, table, info=None):
+        """the kernel's float64 [L][24] -> SegmentSight"""
+        t = np.rint(np.asarray(table, dtype=np.float64).reshape(-1, 24))
+        side = lambda at: SightCounts(t[:, at], t[:, at + 1: at + 11: 2], t[:, at + 2: at + 12: 2])   # noqa: E731
+        return cls(np.asarray(table, dtype=np.float64).reshape(-1, 24)[:, 0], t[:, 1], side(2), side(13), info)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def far_rows(self, k):
+        """the good rows of segment k under the flow that are FAR from every destination point"""
+        return int(self.after.far[k].sum())
+
+    def seen_through_share(self, k):
+        """among the FAR rows of segment k under the flow, the share the destination sweep saw through (NaN without a far row)"""
+        n = self.far_rows(k)
+        return float(self.after.far[k, 2]) / n if n else float("nan")
+
+    def excused_share(self, k):
+        """... the share that is merely unobserved: outside the field of view, no return on the ray, or behind the first return"""
+        n = self.far_rows(k)
+        return float(sum(int(self.after.far[k, c]) for c in SIGHT_EXCUSED)) / n if n else float("nan")
+
+    def annotate(self, entries, share=0.5):
+        """SegmentResidual.worst's entries (dicts with a `label`) with `seen_through`, `excused` and `far_rows` (rows) and a
+        `verdict` added to each: "seen through" when more than `share` of the far rows have code 2, "lost from view" when more
+        than `share` have codes 0, 1 or 4, else "undecided" (a tie, a majority at the first return, or no far row).  -> entries"""
+        at = {float(v): k for k, v in enumerate(self.labels.tolist())}
+        for e in entries:
+            k = at.get(float(e["label"]))
+            if k is None:
+                raise ValueError(f"annotate: no segment with label {e['label']!r}")
+            far = self.far_rows(k)
+            seen, excused = int(self.after.far[k, 2]), int(sum(int(self.after.far[k, c]) for c in SIGHT_EXCUSED))
+            verdict = "seen through" if seen > share * far else "lost from view" if excused > share * far else "undecided"
+            e.update(seen_through=seen, excused=excused, far_rows=far, verdict=verdict)
+        return entries
+
+
+def segment_sight_device(image, before, after, flow, labels, d2_before=None, d2_after=None, far=RESIDUAL_EDGES[1], Lmax=4096, per_row=False):
+    """icpflow_sight_segments enqueued on the current stream, nothing read back.  image: a SightImage; before, after [n, 3], flow
+    [n, 3] or None, labels [n]; d2_before, d2_after: float32 [n] as segment_residual_device(per_row=True) returns them, or None
+    (then no row is FAR).  -> (table float64 [Lmax, 24], num int32 [1], info int64 [12], code_before, code_after): device
+    tensors; the last two int32 [n] with per_row, else None."""
+    import ctypes
+    import torch
+    from . import _lib
+    b = _cloud3(before, "before")
+    a = b if after is before else _cloud3(after, "after")
+    device = b.device
+    n, Lmax = b.shape[0], int(Lmax)
+    f = None if flow is None else _cloud3(flow, "flow")
+    _lib.require_gpu(labels, d2_before, d2_after)
+    lab = labels.to(torch.float32).contiguous()
+    d2 = [None if d is None else d.to(torch.float32).contiguous() for d in (d2_before, d2_after)]
+    if a.shape[0] != n or (f is not None and f.shape[0] != n) or lab.shape != (n,) or any(d is not None and d.shape != (n,) for d in d2):
+        raise ValueError(f"segment_sight: after {tuple(a.shape)}, flow {None if f is None else tuple(f.shape)}, labels {tuple(lab.shape)} for {n} rows")
+    if any(x is not None and x.device != device for x in (a, f, lab, image.image, *d2)):
+        raise ValueError("segment_sight: every tensor on the same device")
+    table = torch.empty((max(Lmax, 0), _lib.SIGHT_COLS), dtype=torch.float64, device=device)
+    num = torch.empty(1, dtype=torch.int32, device=device)
+    info = torch.empty(12, dtype=torch.int64, device=device)
+    codes = [torch.empty(n, dtype=torch.int32, device=device) if per_row else None for _ in range(2)]
+    with torch.cuda.device(device):
+        need = int(_lib._L.icpflow_sight_segments_workspace_bytes(n, Lmax))
+        ws = _lib.workspace(device, need)
+        _lib.call("icpflow_sight_segments", *image._args(), _lib.ptr(b), _lib.ptr(a), _lib.ptr(f), _lib.ptr(lab), n, _lib.ptr(d2[0]), _lib.ptr(d2[1]),
+                  float(far), _lib.ptr(table), Lmax, _lib.ptr(num), _lib.ptr(codes[0]), _lib.ptr(codes[1]), _lib.ptr(info), _lib.ptr(ws),
+                  ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    return table, num, info, codes[0], codes[1]
+
+
+SIGHT_INFO_NAMES = tuple(f"{side}_{name}" for side in ("before", "after")
+                         for name in ("bad_rows", "outside", "no_return", "seen_through", "at_first_return", "behind"))
+
+
+def segment_sight(image, before, after, flow, labels, d2_before=None, d2_after=None, far=RESIDUAL_EDGES[1], Lmax=4096):
+    """The line-of-sight codes of every segment (distinct label) of a source cloud against the SightImage of the destination,
+    BEFORE (`before` as it is) and AFTER (`after` + `flow`), and among them the rows whose nearest destination point is more
+    than `far` metres away.  Tensors on the GPU; there is no CPU path.  -> SegmentSight; one read-back.  More distinct labels
+    than Lmax is a ValueError."""
+    import torch
+    table, num, info, _, _ = segment_sight_device(image, before, after, flow, labels, d2_before, d2_after, far, Lmax)
+    host = torch.cat([num.to(torch.float64), info.to(torch.float64), table.reshape(-1)]).cpu().numpy()     # the one read-back
+    L = int(host[0])
+    if L < 0:
+        raise ValueError(f"segment_sight: {-L} distinct labels, Lmax = {int(Lmax)}")
+    facts = {name: int(host[1 + k]) for k, name in enumerate(SIGHT_INFO_NAMES)}
+    return SegmentSight.from_table(host[13: 13 + L * 24], facts)
+
+
+def format_segment_sight(report):
+    """One line per listed segment that SegmentSight.annotate has been through, behind format_segment_residual's line."""
+    lines = []
+    for line, e in zip(format_segment_residual(report), report):
+        lines.append(f"{line}; far rows: {e['far_rows']:6d}, seen through: {e['seen_through']:6d}, excused: {e['excused']:6d}, {e['verdict']}")
     return lines

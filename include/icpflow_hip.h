@@ -1106,6 +1106,108 @@ int icpflow_nn_residual_segments(const float *d_before, const float *d_after, co
                                  size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(h)  line of sight: a missing neighbour told apart -- contradicted by the destination sweep, or merely unobserved.  No
+ * counterpart in the reference: the free-space / visibility test of label-free scene-flow work (COVERAGE.md, named deviations).
+ * A LiDAR return certifies the ray in front of it as empty: a warped source point in FRONT of the nearest return along its ray
+ * sits in space the destination sweep saw through (evidence against the flow); one behind it, on a ray without a return or
+ * outside the field of view is unobserved (it excuses a missing neighbour).
+ *
+ * The pixel map.  No transcendental function; every operation below is ONE fp32 operation rounded by itself (the library is
+ * built with -ffp-contract=off, IEEE division and correctly rounded sqrtf).  The parameters and the origin o (HOST double[3],
+ * finite, within 1e6 m) are narrowed to float once, on the host; rs = (float)H / (tan_hi - tan_lo) in fp32, once.  For a point v:
+ *     u = v - o per coordinate;  h2 = ux ux + uy uy;  d2 = h2 + uz uz;  rho = sqrtf(d2)
+ *     column, by the diamond angle (monotone around the circle, one division):  s = |ux| + |uy|,  g = uy / s,
+ *         p = g where ux >= 0 and uy >= 0;  p = 4 + g where ux >= 0 and uy < 0;  p = 2 - g where ux < 0  (-0.0 counts as >= 0)
+ *         col = (int)floorf(p * (float)(W / 4));  col == W (p rounded to 4) wraps to 0
+ *     row, by the tangent of the elevation:  t = uz / sqrtf(h2),  row = (int)floorf((t - tan_lo) * rs);  row == H (rounding)
+ *         becomes H - 1
+ *     OUTSIDE (no pixel): s == 0, or !(t >= tan_lo && t < tan_hi) (an infinite or NaN t too), or rho < min_range, or
+ *         rho > max_range
+ *   A BAD row is icpflow_nn_residual's, word for word (the same device function): a non-finite coordinate or one beyond
+ *   +-1e6 m; it is never a target and never classified.
+ *
+ * icpflow_sight_params_t: W a multiple of 4 in [4, 8192], H in [1, 2048], W * H <= 2^22; tan_lo < tan_hi, finite (compared as
+ *   floats); 0 <= min_range < max_range <= 1e6 (as floats); margin_abs >= 0, 0 <= margin_rel < 1.  Anything else, or a
+ *   struct_size that is not sizeof(icpflow_sight_params_t), is ICPFLOW_E_ARG.  icpflow_sight_default_params fills the defaults
+ *   (COVERAGE.md row 15 says where they come from).
+ *
+ * icpflow_sight_build -- the depth image of one destination sweep, d_target float32 [m,3].  d_image is the caller's, uint32
+ *   [2][H][W], all of it written.  Plane 0: per pixel the BITS of the smallest rho of the targets in it, the bits of +inf
+ *   (0x7f800000) in an empty pixel -- non-negative floats order like their bits, so this is an integer atomicMin, which does not
+ *   depend on the order of arrival; no floating-point atomic.  Plane 1: per pixel the minimum of plane 0 over the 3 x 3 pixels
+ *   around it, columns modulo W, rows clipped to [0, H) -- a point correctly placed on an object's silhouette falls into a
+ *   pixel that may hold background only.  d_info int64 [3], required: bad targets, targets OUTSIDE, occupied pixels of plane 0.
+ *   Three launches (fill, scatter, 3 x 3), no workspace.  m = 0 succeeds and leaves an empty image; m < 0 and null pointers are
+ *   ICPFLOW_E_ARG, m > 2^29 is ICPFLOW_E_LIMIT, before any launch.
+ *
+ * icpflow_sight_query -- the ray test of n rows against an image built with the SAME params and origin.  q = d_query + d_flow,
+ *   one fp32 addition per coordinate (d_flow NULL: q = d_query); rho and the pixel of q by the map above; n9 = plane 1 at the
+ *   pixel; thr = margin_abs + margin_rel * rho (two fp32 operations).  d_code_out int32 [n]:
+ *       -2  a bad row                             ICPFLOW_SIGHT_OUTSIDE 0          no pixel
+ *       ICPFLOW_SIGHT_NO_RETURN 1      n9 == +inf           ICPFLOW_SIGHT_SEEN_THROUGH 2     rho + thr < n9
+ *       ICPFLOW_SIGHT_AT_FIRST_RETURN 3  not 2, and rho - thr <= n9               ICPFLOW_SIGHT_BEHIND 4   otherwise
+ *   d_near_out float32 [n] or NULL: n9 (+inf for a row without a pixel).  d_counts int64 [6], required: the bad rows, then the
+ *   rows of codes 0 .. 4, by ballot and popcount (integer atomics only).  n = 0 succeeds with six zeros.  Refusals as for the
+ *   build (n for m), before any launch.
+ *
+ * icpflow_sight_segments -- the codes counted per segment of a labelled source cloud, BEFORE (q = d_before) and AFTER
+ *   (q = d_after + d_flow; d_flow may be NULL, d_after may be d_before).  Segments are exactly icpflow_nn_residual_segments':
+ *   the distinct values of d_labels float32 [n] ascending, -0.0 and +0.0 one label, a NaN label one segment per bit pattern;
+ *   Lmax <= 4096; *d_num is the number of segments, or the NEGATIVE count when there are more (then no row of the table, no
+ *   per-row code and nothing of d_info beyond zeros is written).
+ *   d_d2_before, d_d2_after float32 [n] or NULL: what icpflow_nn_residual_segments writes per row.  A row is FAR iff its
+ *   d2 > (float)far * (float)far (one fp32 product on the host); a miss holds r2, so it is far for any far <= r; 0 <= far <= 1e3.
+ *   d_table double [Lmax][ICPFLOW_SIGHT_COLS], row c = the c-th label (rows from *d_num on are not written):
+ *       0        label                                1        rows of the segment
+ *       2        BEFORE: good rows                    3 - 12   BEFORE: for code k = 0 .. 4 column 3 + 2 k its rows, column
+ *                                                              4 + 2 k the FAR rows among them (0 where d_d2_before is NULL)
+ *       13       AFTER: good rows                     14 - 23  AFTER: the same ten
+ *   d_code_before, d_code_after int32 [n] or NULL: the per-row codes, equal to what icpflow_sight_query writes.
+ *   d_info int64 [12], required: icpflow_sight_query's d_counts of the BEFORE side, then of the AFTER side (the segments' counts
+ *   add up to them exactly).
+ *   By icpflow_nn_residual_segments' scheme with integer columns: chunks of 1024 rows of the stable order, a workgroup of 256
+ *   threads per chunk, counts by ballot and popcount, the chunks added in ascending order by a final kernel (csrc/sight.hip).
+ *   Refusals, all before any launch: a null required pointer, a negative size, Lmax < 1, far or the parameters outside their
+ *   ranges, a struct_size mismatch are ICPFLOW_E_ARG; n > 2^29 or Lmax > 4096 are ICPFLOW_E_LIMIT; fewer workspace bytes than
+ *   the query says are ICPFLOW_E_WORKSPACE before anything is written; a workspace that is not 16-byte aligned is ICPFLOW_E_ARG.
+ *   n = 0 succeeds with *d_num = 0.  The workspace is the caller's: icpflow_sight_segments_workspace_bytes(n, Lmax) =
+ *       a(8 n) + a(72 Lmax) + a(4 (Lmax + 1)) + a(88 chunks) + a(T)
+ *   bytes, a(x) = x rounded up to a multiple of 256: the stable order, the segments' (label, count, start) rows, the first chunk
+ *   of every segment, chunks = floor(n / 1024) + min(n, Lmax) + 1 partials of 2 x 11 ints, and
+ *   T = icpflow_cluster_table_workspace_bytes(max(n, 1), Lmax); 0 for arguments the call refuses.  Nothing in it is read before
+ *   it is written.  All three calls are asynchronous on `stream`, with no host synchronisation and no allocation.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_SIGHT_COLS 24
+#define ICPFLOW_SIGHT_OUTSIDE 0
+#define ICPFLOW_SIGHT_NO_RETURN 1
+#define ICPFLOW_SIGHT_SEEN_THROUGH 2
+#define ICPFLOW_SIGHT_AT_FIRST_RETURN 3
+#define ICPFLOW_SIGHT_BEHIND 4
+typedef struct icpflow_sight_params {
+    size_t struct_size; /* sizeof(icpflow_sight_params_t) */
+    int W;              /* columns of the image */
+    int H;              /* rows of the image */
+    double tan_lo;      /* tangent of the lowest elevation in view */
+    double tan_hi;      /* tangent of the highest (exclusive) */
+    double min_range;   /* metres */
+    double max_range;   /* metres */
+    double margin_abs;  /* metres */
+    double margin_rel;  /* share of the range */
+} icpflow_sight_params_t;
+int icpflow_sight_default_params(icpflow_sight_params_t *params);
+int icpflow_sight_build(const float *d_target, int m, const double *h_origin, const icpflow_sight_params_t *params,
+                        uint32_t *d_image, int64_t *d_info, icpflow_stream_t stream);
+int icpflow_sight_query(const uint32_t *d_image, const icpflow_sight_params_t *params, const double *h_origin,
+                        const float *d_query, const float *d_flow, int n, int32_t *d_code_out, float *d_near_out,
+                        int64_t *d_counts, icpflow_stream_t stream);
+size_t icpflow_sight_segments_workspace_bytes(int n, int Lmax);
+int icpflow_sight_segments(const uint32_t *d_image, const icpflow_sight_params_t *params, const double *h_origin,
+                           const float *d_before, const float *d_after, const float *d_flow, const float *d_labels, int n,
+                           const float *d_d2_before, const float *d_d2_after, double far, double *d_table, int Lmax,
+                           int32_t *d_num, int32_t *d_code_before, int32_t *d_code_after, int64_t *d_info, void *d_ws,
+                           size_t ws_bytes, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
