@@ -404,12 +404,38 @@ struct JoinGuard {
     void joined() { join = nullptr; }
 };
 
+// what a first half (register_stage_begin) can split off: ONE speculative launch whose history the consumers read themselves
+static bool icp_splittable(const Workspace &w, const GridScratch *search, const Opts &o, int stopMode, int maxIter)
+{
+    const bool sweepCheck = search != nullptr && search->mode == 3 && o.on(ICPFLOW_OPT_NO_CHECK_SWEEP);
+    return sweepCheck && o.arith == ICPFLOW_ARITH_FP64 && stopMode == ICPFLOW_STOP_REFERENCE && w.history != nullptr &&
+           o.on(ICPFLOW_OPT_NO_SPECULATIVE) && maxIter > 1 && maxIter <= kHistIters;
+}
+
+// hist_icp, decided before run_init_pose: the ICP launch picks the initial poses itself and no score_pick_kernel runs (IcpPick,
+// kernels.hpp).  Only where THIS call enqueues the ICP launch straight behind the scoring sweeps (sweepScore: they leave both
+// clouds sorted without a pre-pose) -- phase 0, or a first half that splits its launch off -- and the launch is one that can
+// take the pick (icp_pick_in_icp, icp.hip).  Every other call keeps the kernel.
+static bool pick_in_icp(Workspace &w, const Opts &o, int B, int N, int maxIter, int stopMode, int phase, bool sweepScore)
+{
+    if (!sweepScore || phase == 2) return false;
+    const GridScratch *search = search_scratch(w, N, o);
+    const IcpOpts io = o.icp(w.grid.sortX);
+    if (phase == 1 && (!icp_splittable(w, search, o, stopMode, maxIter) ||
+                       icp_teams_wanted(&w.team, io, search, B, N, maxIter, stopMode, w.history)))
+        return false;   // (the first half returns without an ICP launch: run_icp_and_select, part 1)
+    return icp_pick_in_icp(&w.team, io, search, true, B, N, maxIter, stopMode, w.history);
+}
+
 // shared tail of apply_icp / hist_icp: ICP from Tinit, compose, check, select
 int run_icp_and_select(const float *src, const float *dst, Workspace &w, const uint8_t *swap,
                        const float *init, int B, int N, double thres, int maxIter, double relThr,
                        int stopMode, int invertSwapped, float *Tout, int32_t *iters, const Opts &o, hipStream_t s,
-                       bool teamPlanned = false, int part = 0, int32_t *pending = nullptr, bool initSumValid = false)
+                       bool teamPlanned = false, int part = 0, int32_t *pending = nullptr, bool initSumValid = false,
+                       bool pickInIcp = false)
 {
+    // pickInIcp (hist_icp): run_init_pose has left the pick of the initial poses to the ICP launch of THIS call, which writes
+    // `init` (w.Tinit) and w.scoreAccum[0 .. B) itself (pick_in_icp below: the one decision both go by)
     // part 0: everything.  part 1: the ICP launch only, with the whole batch iterating (no pair mask); *pending = 1 when the launch
     // left every pair's trajectory in the history (the single speculative launch with the fused finish), 0 when it could not be
     // split off (then part 2 runs everything).  part 2 with *pending: the batch rule over o.pairActive from that history
@@ -424,8 +450,7 @@ int run_icp_and_select(const float *src, const float *dst, Workspace &w, const u
     io.splitScratch = w.icpSplit;
     io.teamPlanned = teamPlanned;
     if (sweepCheck && o.arith == ICPFLOW_ARITH_FP64) io.historyPending = &historyPending;
-    const bool splittable = sweepCheck && o.arith == ICPFLOW_ARITH_FP64 && stopMode == ICPFLOW_STOP_REFERENCE && w.history != nullptr &&
-                            o.on(ICPFLOW_OPT_NO_SPECULATIVE) && maxIter > 1 && maxIter <= kHistIters;
+    const bool splittable = icp_splittable(w, search, o, stopMode, maxIter);
     if (part == 1) {
         *pending = 0;
         if (!splittable) return 0;
@@ -439,6 +464,10 @@ int run_icp_and_select(const float *src, const float *dst, Workspace &w, const u
         historyPending = true;
         if (o.pairActive != nullptr) ICPFLOW_TRY(launch_icp_retally(w.ctrl, w.history, o.pairActive, B, maxIter, relThr, s));
     } else {
+        if (pickInIcp) {   // (what run_init_pose would have handed to launch_score_pick)
+            io.pick.partial = w.partial; io.pick.qblocks = sweep_qblocks(N); io.pick.cand = w.cand;
+            io.pick.initSum = w.scoreAccum; io.pick.Tinit = w.Tinit;
+        }
         ICPFLOW_TRY(launch_icp(src, dst, w.lenA, w.lenC, swap, init, B, N, thres, maxIter, relThr, stopMode,
                                w.state, w.ctrl, search, w.history, &w.team, io, s));
         if (part == 1) {
@@ -472,8 +501,11 @@ int run_icp_and_select(const float *src, const float *dst, Workspace &w, const u
 int run_init_pose(const float *src, const float *dst, Workspace &w, const uint8_t *swap, int B,
                   int N, const float *ex, int lx, const float *ey, int ly, const float *ez, int lz,
                   float shift, float *Tout, const Opts &o, hipStream_t s, hipEvent_t joinBefore = nullptr,
-                  const PairCountFuse *countFuse = nullptr, bool sideBusy = false, const FrontRoles *roles = nullptr)
+                  const PairCountFuse *countFuse = nullptr, bool sideBusy = false, const FrontRoles *roles = nullptr,
+                  bool pickInIcp = false)
 {
+    // pickInIcp (hist_icp, pick_in_icp above): the scoring sweeps are the last launches here -- the ICP launch that follows picks
+    // among their sums itself and writes Tout
     const int lens[3] = {lx, ly, lz};
     // vote with X = dst role, Y = src role (utils_hist.py:69); z-sorted sweep while the sort fits LDS
     // (N <= 16384), all-pairs otherwise -- identical bins either way
@@ -515,8 +547,11 @@ int run_init_pose(const float *src, const float *dst, Workspace &w, const uint8_
             ICPFLOW_TRY(launch_sweep_score_pruned(&w.grid, w.lenA, w.lenC, swap, B, N, w.cand, w.partial, w.scoreAccum, s));
         else
             ICPFLOW_TRY(launch_sweep_score(&w.grid, w.lenA, w.lenC, swap, B, N, w.cand, w.partial, s));
-        ICPFLOW_TRY(launch_score_pick(w.partial, sweep_qblocks(N), w.lenA, w.lenC, swap, w.cand, B, Tout, s, w.scoreAccum));
+        if (!pickInIcp)
+            ICPFLOW_TRY(launch_score_pick(w.partial, sweep_qblocks(N), w.lenA, w.lenC, swap, w.cand, B, Tout, s, w.scoreAccum));
         w.initSumValid = true;   // (scoreAccum is free once the scans are over; the next call clears it)
+    } else if (pickInIcp) {
+        return report_errorf(ICPFLOW_E_ARG, "hist_icp: the pick was left to the ICP launch, but the scoring did not run as sweeps");
     } else if (o.on(ICPFLOW_OPT_NO_SCORE_PRUNE)) {
         ICPFLOW_TRY(launch_scan_score_pruned(src, dst, w.lenA, w.lenC, swap, B, N, w.cand, w.partial, w.scoreAccum, s, true));
         ICPFLOW_TRY(launch_score_pick(w.partial, score_qblocks(N), w.lenA, w.lenC, swap, w.cand, B, Tout, s));
@@ -1173,9 +1208,11 @@ static int hist_icp_core(const float *d_src, const float *d_dst, int B, int N, c
     w.grid.shareCountClean = 1;   // (cleared with scoreAccum either way; the sweep launches of this call skip their memsets)
     w.grid.sweepTicket = w.ticketScratch;   // (cleared with it as well: the pruned scoring's count of listed scans)
     const bool sweepScore = score_by_sweep(N, join != nullptr || frontRoles, o);
+    // (the ICP launch below picks the initial poses itself where it can: one launch fewer between the scoring and the ICP)
+    const bool pickInIcp = pick_in_icp(w, o, B, N, max_iterations, stop_mode, phase, sweepScore);
     if (int r = run_init_pose(d_src, d_dst, w, w.swap, B, N, d_edges_x, len_x, d_edges_y, len_y, d_edges_z,
                               len_z, decode_shift, w.Tinit, o, s, sweepScore ? join : nullptr,
-                              countInSort ? &fuse : nullptr, join != nullptr, frontRoles ? &roles : nullptr))
+                              countInSort ? &fuse : nullptr, join != nullptr, frontRoles ? &roles : nullptr, pickInIcp))
         return r;
     if (join != nullptr && !sweepScore) ICPFLOW_TRY(hipStreamWaitEvent(s, join, 0));
     guard.joined();
@@ -1186,10 +1223,11 @@ static int hist_icp_core(const float *d_src, const float *d_dst, int B, int N, c
         // ... and, where ONE speculative launch runs the batch rule, the ICP of the whole batch as well (carry[2] = 1): the second
         // half then only has to find where the rule over ITS pairs stops
         return run_icp_and_select(d_src, d_dst, w, w.swap, w.Tinit, B, N, thres_dist, max_iterations, relative_rmse_thr,
-                                  stop_mode, 1, d_T_out, d_iters, o, s, teamPlanned, 1, &carry[2]);
+                                  stop_mode, 1, d_T_out, d_iters, o, s, teamPlanned, 1, &carry[2], false, pickInIcp);
     }
     return run_icp_and_select(d_src, d_dst, w, w.swap, w.Tinit, B, N, thres_dist, max_iterations,
-                              relative_rmse_thr, stop_mode, 1, d_T_out, d_iters, o, s, teamPlanned, 0, nullptr, w.initSumValid);
+                              relative_rmse_thr, stop_mode, 1, d_T_out, d_iters, o, s, teamPlanned, 0, nullptr, w.initSumValid,
+                              pickInIcp);
 }
 
 int icpflow_hist_icp(const float *d_src, const float *d_dst, int B, int N, const float *d_edges_x,

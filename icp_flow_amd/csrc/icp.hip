@@ -29,6 +29,7 @@
 #include "gridhash.hpp"
 #include "icp_instr.hip"   // ICPFLOW_STAMP, and the instruments of the debug variants (a part of this unit, not a source of its own)
 #include "kabsch.hpp"      // after ICPFLOW_STAMP: the solver carries the phase stamps of debug builds
+#include "scorepick.hpp"
 
 namespace icpflow {
 
@@ -96,6 +97,7 @@ struct IcpParams {
     const int32_t *pairMeta;
     int twoLaunch;               // host side only: two launches wanted where they apply (launch_icp_variant)
     int32_t *splitScratch;       // host side only: [B + 64] ints (the list, then count and floor)
+    IcpPick pick;                // partial != NULL: wave 0 of a pair's workgroup picks the pair's pre-pose itself (see icp_pair's prologue)
 };
 
 
@@ -319,6 +321,20 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
     const int ts = wave % TS;                // target share of this wave
     const int qg = wave / TS;                // query group of this wave
     IcpCtrl *ctrl = p.ctrl;
+    // The pick of the pair's initial pose (p.pick, hist_icp: no score_pick_kernel has run in front of this launch).  Everything
+    // it reads was complete before the launch, and this workgroup is the only one of the launch that reads the pair's pre-pose:
+    // wave 0 picks, writes Tinit[b] and initSum[b] for the kernels behind the launch and keeps the pose's words (lane l < 16:
+    // word l); the other waves meanwhile stage the sorted fixed cloud into LDS (below), which does not depend on the pose, and
+    // the barrier that ends the staging publishes the pose to them (preL, bcast[16..18]).  In front of the pair mask: a pair
+    // that is not in the batch gets its Tinit and initSum as the kernel wrote them.
+    // (one workgroup per pair, LDS image, no helpers: the instantiations launch_icp may hand a pick to -- icp_pick_in_icp)
+    constexpr bool PICK = kPickInIcp && GRID == 4 && !TEAM && !HELP;
+    [[maybe_unused]] float pickW = 0.f;
+    if constexpr (PICK) {
+        if (p.pick.partial != nullptr && wave == 0)
+            pickW = score_pick_wave(p.pick.partial, p.pick.qblocks, p.lenX, p.lenY, p.swap, p.pick.cand, b, lane, p.pick.Tinit,
+                                    p.pick.initSum);
+    }
     if (p.pairActive != nullptr && p.history != nullptr && p.pairActive[b] == 0) {
         // Not in the batch (options.d_pair_active; the caller handed the pair over as two empty clouds): the batch rule is
         // taken over the other pairs -- this one reports "arrived, converged" for every iteration of the launch, like a pair
@@ -351,7 +367,17 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
     yc.base = (sw ? p.X : p.Y) + (size_t)b * p.N * 4; yc.stride = 4; yc.n = (sw ? p.lenX : p.lenY)[b];
     PointXf pre;
     pre.kind = p.prePose ? XF_AFFINE : XF_NONE;
-    pre.a = p.prePose ? affine_from_pose(p.prePose + (size_t)b * 16) : affine_identity();
+    bool picked = false;   // the pre-pose is the one wave 0 has just picked: Tinit[b] is not read (workgroup-uniform)
+    if constexpr (PICK) picked = p.pick.partial != nullptr;
+    if (picked) {
+        // [I | t]: the words score_pick_wave wrote.  Meaningful in wave 0 only, whose thread 0 is the one that uses it below
+        // (sorted sweep with the LDS image: every other use of the pre-pose goes through preL).
+        pre.a = affine_identity();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pre.a.t[k] = __shfl(pickW, 4 * k + 3, kWave);
+    } else {
+        pre.a = p.prePose ? affine_from_pose(p.prePose + (size_t)b * 16) : affine_identity();
+    }
     PointXf none;
     none.kind = XF_NONE;
     none.a = affine_identity();
@@ -427,6 +453,22 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
         for (int k = 0; k < 9; ++k) preL[k] = pre.a.m[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) preL[9 + k] = pre.a.t[k];
+    }
+    if constexpr (PICK) {
+        // The sorted fixed cloud is staged into LDS HERE (these instantiations start at their first iteration with the image in
+        // place; the others stage it in the loop, behind a barrier of its own): with a pick by the waves that do not pick, and
+        // the barrier that follows publishes both.
+        if (!picked || wave != 0) {
+            const int NP16 = (p.N + kChunk - 1) / kChunk * kChunk;
+            const int np16 = (yc.n + kChunk - 1) / kChunk * kChunk;
+            const float *gx = p.sortYsoa + (size_t)b * 3 * NP16;
+            const float *gy = gx + NP16;
+            const float *gz = gy + NP16;
+            float *lx = reinterpret_cast<float *>(dynLds + (size_t)p.redPasses * (NWAVE * kMoments * sizeof(double)));
+            float *ly = lx + NP16, *lz = ly + NP16;
+            const int skip = picked ? kWave : 0;
+            for (int k = tid - skip; k < np16; k += BLOCK - skip) { lx[k] = gx[k]; ly[k] = gy[k]; lz[k] = gz[k]; }
+        }
     }
     __syncthreads();
 
@@ -649,7 +691,7 @@ __device__ __forceinline__ void icp_pair(const P &p, const int b, const int rank
             // (and the query's own point, pre-pose applied, when there is room: read from L2 once, not once per iteration)
             float *x0c = reinterpret_cast<float *>(dyn + (size_t)NP16 * 12 + (size_t)p.recCap * 20);
             const bool x0On = recOn && p.x0Cache != 0;
-            if (GRID == 4 && it == itFirst) {
+            if (GRID == 4 && !PICK && it == itFirst) {   // (PICK: staged in the prologue)
                 for (int k = tid; k < np16; k += BLOCK) { lx[k] = gx[k]; ly[k] = gy[k]; lz[k] = gz[k]; }
                 __syncthreads();
             }
@@ -2353,12 +2395,53 @@ bool icp_teams_wanted(const IcpTeam *team, const IcpOpts &opts, const GridScratc
     // 104, 110, 120 CUs -- the plan has fewer slots than CUs / 2, and a pair without a slot would never be served)
 }
 
+#ifndef ICPFLOW_HALF_CU_MIN_N
+#define ICPFLOW_HALF_CU_MIN_N 768
+#endif
+// Sorted sweep, one workgroup per pair: whether the launch takes 512-thread workgroups, two per CU (launch_icp: why and when).
+// A function of the batch's shape alone.
+static bool icp_half_cu(int B, int N)
+{
+    const int cus = device_cus();
+    const size_t img = (size_t)((N + kChunk - 1) / kChunk * kChunk) * 12;
+    const size_t recCap = N <= kRecMaxN ? (size_t)N : 0;
+    const size_t half = 76 * 1024;   // (+ 2.2 KiB of static LDS each)
+    const double fillHalf = (double)B / ((double)((B + 2 * cus - 1) / (2 * cus)) * 2 * cus);
+    const double fillFull = (double)B / ((double)((B + cus - 1) / cus) * cus);
+    const size_t redHalf = N <= kRecMaxN ? (size_t)((N + 511) / 512) * 8 * kMoments * sizeof(double) : 0;   // (512 threads: 8 waves)
+    return B >= 2 * cus && N > ICPFLOW_HALF_CU_MIN_N && redHalf + img + recCap * 20 <= half && 1.1 * fillHalf > fillFull;
+}
+
+bool icp_pick_in_icp(const IcpTeam *team, const IcpOpts &opts, const GridScratch *grid, bool presorted, int B, int N, int maxIter,
+                     int stopMode, const float *history)
+{
+    if (!kPickInIcp || opts.arith == ICPFLOW_ARITH_FP32_REFERENCE) return false;
+    // one launch for all iterations (beyond kHistIters, and with the speculative launch off: one launch per iteration)
+    const bool speculative = stopMode == ICPFLOW_STOP_REFERENCE_ && history != nullptr && opts.speculative &&
+                             maxIter > 1 && maxIter <= kHistIters;
+    if (!speculative) return false;
+    // the scoring's sort, which knows no pre-pose (a sort of the launch's own would read Tinit), and the LDS image
+    if (grid == nullptr || grid->mode != 3 || !presorted || N > 12288) return false;
+    if (icp_teams_wanted(team, opts, grid, B, N, maxIter, stopMode, history)) return false;
+    // persistent grids with helpers (launch_icp_variant: `eligible`): pairs of three passes or more in a batch larger than the
+    // GPU holds workgroups of that kernel -- at least one per CU, so a batch of up to one pair per CU never gets there
+    const int block = N <= 256 ? 256 : (N <= 512 ? 512 : (N <= 768 ? 768 : (icp_half_cu(B, N) ? 512 : 1024)));
+    const int passes = (N + block - 1) / block;
+    if (opts.persistent && N <= kRecMaxN && passes >= 3 && B > device_cus()) return false;
+    return true;
+}
+
 hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
                       const uint8_t *swap, const float *prePose, int B, int N, double thres,
                       int maxIter, double relThr, int stopMode, IcpState *state, IcpCtrl *ctrl,
                       const GridScratch *grid, float *history, const IcpTeam *team, const IcpOpts &opts,
                       hipStream_t s)
 {
+    // (a pick is handed over only where the launch can take it, and writes the very pre-poses the launch is given)
+    if (opts.pick.partial != nullptr &&
+        (opts.pick.Tinit != prePose || opts.pick.cand == nullptr ||
+         !icp_pick_in_icp(team, opts, grid, grid != nullptr && grid->presorted, B, N, maxIter, stopMode, history)))
+        return hipErrorInvalidValue;
     if (opts.arith == ICPFLOW_ARITH_FP32_REFERENCE) {   // study mode (icp_fp32.hip); api.hip validated the arguments
         if (history == nullptr || opts.fp32Scratch == nullptr || maxIter > kHistIters ||
             stopMode != ICPFLOW_STOP_REFERENCE_)
@@ -2409,7 +2492,6 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
         p.gridPts = (const float4 *)grid->pts; p.gridStart = grid->start; p.gridOrigin = grid->origin;
         p.gridH = grid->H; p.gridInvH = invh;
     }
-    const int cus = device_cus();
     const bool speculative = stopMode == ICPFLOW_STOP_REFERENCE_ && history != nullptr && opts.speculative &&
                              maxIter > 1 && maxIter <= kHistIters;
     if (icp_teams_wanted(team, opts, grid, B, N, maxIter, stopMode, history)) {
@@ -2438,16 +2520,11 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
         // workgroups run alone on their CUs or the last, partial round runs on a mostly empty GPU: hence two pairs per
         // CU at least, and the two ways of filling the GPU weighed.  (Decided on the shape alone, not on whether the
         // records are switched on: the moment sums follow the workgroup's shape.)
+        // (the test itself: icp_half_cu above, which icp_pick_in_icp asks too)
         const size_t half = 76 * 1024;   // (+ 2.2 KiB of static LDS each)
-#ifndef ICPFLOW_HALF_CU_MIN_N
-#define ICPFLOW_HALF_CU_MIN_N 768
-#endif
-        const double fillHalf = (double)B / ((double)((B + 2 * cus - 1) / (2 * cus)) * 2 * cus);
-        const double fillFull = (double)B / ((double)((B + cus - 1) / cus) * cus);
         const size_t redHalf = N <= kRecMaxN ? (size_t)((N + 511) / 512) * 8 * kMoments * sizeof(double) : 0;   // (512 threads: 8 waves)
         const size_t redFull = N <= kRecMaxN ? (size_t)((N + 1023) / 1024) * 16 * kMoments * sizeof(double) : 0;
-        if (p.team.wgPair == nullptr && B >= 2 * cus && N > ICPFLOW_HALF_CU_MIN_N && redHalf + img + (size_t)recCap * 20 <= half &&
-            1.1 * fillHalf > fillFull) {
+        if (p.team.wgPair == nullptr && icp_half_cu(B, N)) {
             p.halfCu = 1;
             x0Cache = redHalf + img + (size_t)recCap * 32 <= half;
         } else if (p.team.wgPair == nullptr) {
@@ -2471,6 +2548,7 @@ hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const
             p.splitScratch = opts.splitScratch;
             p.help = opts.help;
             p.helpOn = (opts.helpers && maxIter <= kHelpMaxEpoch - 2) ? 1 : 0;   // (always: maxIter <= kHistIters here)
+            p.pick = opts.pick;   // (checked on entry: this launch is one icp_pick_in_icp allows)
             launch_icp_iters(p, dirKeys, B, 0, maxIter, opts.profile, s);
             if (opts.historyPending != nullptr) {
                 *opts.historyPending = true;   // the consumers read the history themselves (posefuse.hpp)

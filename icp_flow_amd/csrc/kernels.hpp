@@ -252,6 +252,22 @@ struct GridScratch {   // scratch of the exact gated NN searches of the ICP loop
     int presorted;     // sortX / pts / sortYsoa / axis already hold both clouds sorted WITHOUT the pre-pose
                        // (scoring sweep ran on this batch): the ICP applies the pre-pose when it loads
 };
+// hist_icp's pick of the initial poses inside the ICP launch (scorepick.hpp): what score_pick_kernel reads and writes.  Where
+// `partial` is set, wave 0 of the workgroup that serves pair b picks the pair's pose itself -- it writes Tinit[b] and initSum[b]
+// as the kernel did and starts from that pose -- and no score_pick_kernel runs in front of the launch (icp_pick_in_icp below:
+// when).  NULL: the launch reads its pre-pose from memory, as ever.
+#ifdef ICPFLOW_NO_PICK_IN_ICP   // (build define for A/B runs: the kernel everywhere)
+constexpr bool kPickInIcp = false;
+#else
+constexpr bool kPickInIcp = true;
+#endif
+struct IcpPick {
+    const double *partial = nullptr;   // the scoring's block records [B * 12, qblocks, kPartial]
+    int qblocks = 0;
+    const float *cand = nullptr;       // [B, kCand, 3]
+    double *initSum = nullptr;         // out [B], or NULL
+    float *Tinit = nullptr;            // out [B, 4, 4]: the launch's prePose
+};
 // per-call switches of the ICP launch (icpflow_options_t, include/icpflow_hip.h); nothing process-global
 struct LaunchProfile;   // device.hip: HIP-event recorder behind icpflow_profile_t
 struct IcpOpts {
@@ -278,6 +294,7 @@ struct IcpOpts {
     bool sharedScans = true;       // teams: the waves of a member share their long window scans (ICPFLOW_OPT_NO_SHARED_SCANS)
     bool twoLaunch = false;        // persistent grids with helpers: drained for a second launch of whole-CU workgroups (ICPFLOW_OPT_TWO_LAUNCH)
     int32_t *splitScratch = nullptr;   // [B + 64] ints: the second launch's pair list, its count and the floor of its rule search (NULL: one launch)
+    IcpPick pick{};                // the launch picks its own pre-poses (only where icp_pick_in_icp() says so: launch_icp refuses it elsewhere)
 };
 
 // device.hip: per-device caches (a process may drive several GPUs) -- CU count, and the opt-in of a kernel to more
@@ -310,6 +327,13 @@ void launch_icp_team_plan(const IcpTeam *team, const int32_t *lenX, const int32_
 // icp.hip: the loop and its launch policy
 bool icp_teams_wanted(const IcpTeam *team, const IcpOpts &opts, const GridScratch *grid, int B, int N, int maxIter,
                       int stopMode, const float *history);
+// Whether launch_icp with these arguments may pick the initial poses itself (IcpOpts::pick): the launch gives every pair exactly
+// one workgroup that starts from the pre-pose and stages the sorted fixed cloud into LDS -- one speculative launch of the plain or
+// the persistent kernel over clouds the scoring has left sorted (`presorted`: what grid->presorted will be at the launch).  Teams,
+// persistent grids with helpers, one launch per iteration, the fp32 study mode and the scans that stream their targets keep
+// score_pick_kernel.  Decided on the shape of the batch and the options alone.
+bool icp_pick_in_icp(const IcpTeam *team, const IcpOpts &opts, const GridScratch *grid, bool presorted, int B, int N, int maxIter,
+                     int stopMode, const float *history);
 hipError_t launch_icp(const float *X, const float *Y, const int32_t *lenX, const int32_t *lenY,
                       const uint8_t *swap, const float *prePose, int B, int N, double thres,
                       int maxIter, double relThr, int stopMode, IcpState *state, IcpCtrl *ctrl,
