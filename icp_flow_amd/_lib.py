@@ -113,6 +113,8 @@ SIGNATURES = {
     "icpflow_sight_query": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
     "icpflow_sight_segments_workspace_bytes": (_sz, [_i, _i]),
     "icpflow_sight_segments": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _d, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_flow_trust_default_params": (_i, [_p]),
+    "icpflow_flow_trust": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -153,6 +155,7 @@ NNR_MAX_GROUPS, NNR_MAX_EDGES = 64, 4            # icpflow_nn_residual: G and E
 NNRS_COLS, NNRS_MAX_SEGMENTS = 18, 4096           # icpflow_nn_residual_segments: columns of a row; Lmax at most
 SIGHT_COLS, SIGHT_MAX_SEGMENTS = 24, 4096         # icpflow_sight_segments: columns of a row; Lmax at most
 SIGHT_BAD_ROW, SIGHT_OUTSIDE, SIGHT_NO_RETURN, SIGHT_SEEN_THROUGH, SIGHT_AT_FIRST_RETURN, SIGHT_BEHIND = -2, 0, 1, 2, 3, 4
+TRUST_COUNTS, TRUST_MAX_SEGMENTS = 16, 4096        # icpflow_flow_trust: words of d_counts; Lmax at most
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical
@@ -319,6 +322,27 @@ class SightParams(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+class TrustParams(ctypes.Structure):
+    """icpflow_trust_params_t: the thresholds of the trust byte (icpflow_flow_trust)."""
+    _fields_ = [("struct_size", _sz), ("above", _d), ("far", _d), ("share", _d), ("skip", _f * 2)]
+
+    @staticmethod
+    def defaults(**over):
+        p = TrustParams()
+        call("icpflow_flow_trust_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if k == "struct_size" or k not in dict(TrustParams._fields_):
+                raise TypeError(f"TrustParams: no parameter {k!r}")
+            if k == "skip":
+                p.skip[0], p.skip[1] = (float(x) for x in v)
+            else:
+                setattr(p, k, v)
+        return p
+
+    def as_dict(self):
+        return dict(above=self.above, far=self.far, share=self.share, skip=[float(self.skip[0]), float(self.skip[1])])
 
 
 class Profile:

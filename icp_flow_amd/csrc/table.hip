@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "host.hpp"
+#include "labelkey.hpp"
 
 namespace icpflow {
 namespace {
@@ -21,14 +22,7 @@ namespace {
 constexpr int kRowsBlock = 1024;
 constexpr int kTableCols = 9;   // label, count, start, mean (3), sorted bbox extents (3)
 
-// float -> uint32 whose unsigned order is the float order.  As bit patterns -0.0 < +0.0, where torch.argsort and
-// torch.unique -- and every `==` on labels downstream -- see one label: label_key below maps -0.0 to +0.0 first, so
-// the two are ONE cluster, reported as 0.0, its rows in original order.
-__device__ __forceinline__ uint32_t sortable(float f)
-{
-    const uint32_t u = (uint32_t)__float_as_int(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// (sortable and label_key, the order of the labels: labelkey.hpp, shared with trust.hip's search)
 __device__ __forceinline__ float unsortable(uint32_t k)
 {
     const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
@@ -66,15 +60,6 @@ struct TableSides {
 
 constexpr int kChunkRows = 512;
 constexpr int kDictSlots = 8192, kDictMax = 4096;
-constexpr uint32_t kEmpty = 0xffffffffu;
-
-__device__ __forceinline__ uint32_t label_key(float f)
-{
-    // both zeros are one label (a select, not sort_pack's f + 0.0f: an add would quiet a signalling NaN, and NaN labels are
-    // kept apart by their bits)
-    const uint32_t k = sortable(f == 0.0f ? 0.0f : f);
-    return k == kEmpty ? kEmpty - 1u : k;    // (one NaN payload shares the empty mark's pattern)
-}
 
 __global__ __launch_bounds__(1024) void table_dict_kernel(TableSides t, int Lmax)
 {

@@ -406,7 +406,8 @@ def register_frame_pair_steps(args, fp, device, gap=None, asynchronous=False):
     else:
         flow = utils_flow.flow_estimation_torch(a, flow_src, pd, ls, ld, pairs, T, pose)
     out = dict(pairs=pairs, transformations=T, flow=flow, translation_frame=a.translation_frame, association=a.association_path or "host")
-    if getattr(args, "if_verbose", False) or getattr(args, "residual", None):   # what the per-segment report (run_sequences) and the residual (run_stream) read besides the flow
+    # what the per-segment report (run_sequences), the residual (run_stream) and the trust bytes (run_sequences) read besides the flow
+    if getattr(args, "if_verbose", False) or getattr(args, "residual", None) or getattr(args, "save_trust", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -667,7 +668,8 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
     out = dict(pairs=rows[:P], transformations=T[:P], translation_frame=a.translation_frame, association="device")
     if flow is not None:
         out["flow"] = flow
-    if getattr(a, "if_verbose", False) or getattr(a, "residual", None):   # what the per-segment report (run_sequences) and the residual (run_stream) read besides the flow
+    # what the per-segment report (run_sequences), the residual (run_stream) and the trust bytes (run_sequences) read besides the flow
+    if getattr(a, "if_verbose", False) or getattr(a, "residual", None) or getattr(a, "save_trust", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -985,20 +987,28 @@ def flow_file(path, estimated_poses=False):
     raise ValueError(f"{path}: no split directory (train / val / test, or one of them plus '_...') to put the saved flow next to")
 
 
-def save_sequence_flow(path, flow_seq, fps, F):
+def save_sequence_flow(path, flow_seq, fps, F, trust=None, trust_params=None):
     """np.savez_compressed to flow_file(path), the reference's keys (main.py:281-284): scene_flow float64 [m,3] (the float32
     flows widened; zeros for frame 0; the rows of the sample as loaded), ego_motion float64 [F,4,4] (the poses the frame pairs
-    were registered with; identity for frame 0).  -> the file written"""
+    were registered with; identity for frame 0).  trust (uint8 [m], one byte per row of scene_flow: utils_eval.flow_trust's;
+    zeros for frame 0) adds two keys that the reference does not write: `trust`, and `trust_params`, a JSON string of
+    trust_params (a dict: what the bytes were made with).  -> the file written"""
     poses = np.stack([np.eye(4)] * F)
     for fp in fps:
         poses[fp.gap] = fp.pose_exact
     estimated = any(fp.pose_source in ("pose_file", "ego_motion", "estimate") for fp in fps)
     out = flow_file(path, estimated)
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    np.savez_compressed(out, scene_flow=flow_seq.to(torch.float64).cpu().numpy(), ego_motion=poses)
+    arrays = dict(scene_flow=flow_seq.to(torch.float64).cpu().numpy(), ego_motion=poses)
+    if trust is not None:
+        if trust.dtype != torch.uint8 or tuple(trust.shape) != (flow_seq.shape[0],):
+            raise ValueError(f"save_sequence_flow: trust {tuple(trust.shape)} {trust.dtype} for {flow_seq.shape[0]} rows of uint8")
+        arrays.update(trust=trust.cpu().numpy(), trust_params=np.array(json.dumps(dict(trust_params or {}), sort_keys=True)))
+    np.savez_compressed(out, **arrays)
     return out
 
 
+TRUST_RADIUS = 2.0  # metres: the residual's radius behind run_sequences' trust bytes (--residual's own default)
 RECORD_HEAD = 6     # file index, kept0, frame pairs, wall time, evaluation time, save time (the three in microseconds)
 
 
@@ -1087,7 +1097,12 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
     rank / world / group: the files are dealt round-robin (`shard_round_robin`), every rank keeps one record per file and
     `merge_sequence_records` gathers them once at the end and replays them in file order: `metrics`, `class_table`, the
     counts and the times are those of the whole run on every rank, bit for bit the single process's; ground and pose_sources
-    are this rank's, every rank saves its own files, and if_verbose is refused (merging the reports is not built)."""
+    are this rank's, every rank saves its own files, and if_verbose is refused (merging the reports is not built).
+    args.save_trust = True or (x, y, z) (absent = off; needs args.save_flows): one trust byte per point beside the saved flow --
+    `frame_trust` per frame pair at TRUST_RADIUS metres (True: the residual alone; an origin: the line of sight from there as
+    well), the bytes put into a uint8 [m] by the rows of their frame (zeros for frame 0) and written as the file's `trust` and
+    `trust_params` keys.  After the evaluation and outside its times: -> `trust` (the counts over this rank's files, kept_share,
+    params) and `ms_trust_per_sequence`; without the attribute the result and the files are what they were."""
     device = torch.device(device)
     F = int(args.num_frames)
     if dataset not in ("pca", "argo"):
@@ -1104,6 +1119,19 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
     verbose = bool(getattr(args, "if_verbose", False))
     if world > 1 and verbose:
         raise ValueError("if_verbose under more than one rank: merging the reports is not built")
+    trusting = getattr(args, "save_trust", None)
+    trusting = None if trusting is None or trusting is False else trusting
+    if trusting is not None and not saving:
+        raise ValueError("args.save_trust needs args.save_flows: the bytes go into the saved flow's file")
+    trust_origin = None if trusting is None or trusting is True else tuple(float(v) for v in trusting)
+    if trust_origin is not None and len(trust_origin) != 3:
+        raise ValueError(f"args.save_trust: True or an origin (x, y, z), got {trusting!r}")
+    trust_counts, trust_times, trust_params = utils_eval.TrustCounts(), [], None
+    if trusting is not None:
+        from . import _lib
+        trust_params = dict(radius=TRUST_RADIUS, origin=None if trust_origin is None else list(trust_origin), **_lib.TrustParams.defaults().as_dict())
+        if trust_origin is not None:
+            trust_params["sight"] = _lib.SightParams.defaults().as_dict()
     paths = list(paths)
     mine = shard_round_robin(list(enumerate(paths)), rank, world)        # (file index, path)
     class_shape = (utils_eval.ARGO_CLASS_ROWS, len(utils_eval.ARGO_SPEED_EDGES) + 1, len(utils_eval.ARGO_ERROR_EDGES) + 1) if with_classes else None
@@ -1129,7 +1157,7 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
         for _, fp, out in done:
             flow_seq.index_copy_(0, rows[fp.gap], out["flow"].to(torch.float32))
             pairs_here += 1
-            if verbose:
+            if verbose or trusting is not None:
                 kept.append((fp, out))
         n_pairs += pairs_here
         torch.cuda.synchronize(device)
@@ -1150,9 +1178,20 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
         if verbose:
             segments.extend(_sequence_reports(args, path, data, rows, kept))
             report_times.append((time.perf_counter() - t2) * 1e3)
+        trust_seq = None
+        if trusting is not None:                  # (outside the two times above: the registrations' results are resident)
+            torch.cuda.synchronize(device)
+            t4 = time.perf_counter()
+            trust_seq = torch.zeros(flow_seq.shape[0], dtype=torch.uint8, device=device)      # frame 0: zeros
+            for fp, out in kept:
+                bytes_, counted = frame_trust(fp, out, device, TRUST_RADIUS, trust_origin)
+                trust_seq.index_copy_(0, rows[fp.gap], bytes_)
+                trust_counts.add(counted)
+            torch.cuda.synchronize(device)
+            trust_times.append((time.perf_counter() - t4) * 1e3)
         if saving:
             t3 = time.perf_counter()
-            save_sequence_flow(path, flow_seq, fps, F)
+            save_sequence_flow(path, flow_seq, fps, F, trust=trust_seq, trust_params=trust_params)
             save_times.append((time.perf_counter() - t3) * 1e3)
         if world > 1:
             records.append(sequence_record(index, F, table, kept0, pairs_here,
@@ -1171,6 +1210,8 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
         res.update(segments=segments, ms_report_per_sequence=sum(report_times) / max(len(report_times), 1))
     if saving:
         res.update(ms_save_per_sequence=sum(save_times) / max(len(save_times), 1))
+    if trusting is not None:                      # (this rank's files, like ground and pose_sources)
+        res.update(trust=dict(trust_counts.summary(), params=trust_params), ms_trust_per_sequence=sum(trust_times) / max(len(trust_times), 1))
     if with_classes:
         res.update(class_table=classes, threeway=classes.threeway(utils_eval.ARGO_META_GROUPS["BACKGROUND"]))
     if with_buckets:
@@ -1250,6 +1291,27 @@ def frame_segment_sight(fp, out, device, radius, origin=(0.0, 0.0, 0.0), edges=u
     return report, sight
 
 
+def frame_trust(fp, out, device, radius, origin=None, params=None):
+    """One trust byte per source point of a registered frame pair (utils_eval.flow_trust_device), everything on the device: the
+    segments' residual with its per-row distances kept (`frame_segment_residual`'s call), with an `origin` the depth image over
+    the destination and the segments' line-of-sight table with its per-row codes (`frame_segment_sight`'s calls), then the one
+    call that turns the tables and the per-row arrays into bytes.  The far rows and the listing share utils_eval.RESIDUAL_EDGES[1]
+    (params: a _lib.TrustParams that says otherwise).  -> (trust uint8 [Ns] on the device, TrustCounts); one read-back, the
+    sixteen counts."""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    flow, labels = out["flow"].to(device).float(), _source_labels(fp, out, device)
+    far = utils_eval.RESIDUAL_EDGES[1] if params is None else float(params.far)
+    table, num, _, d2b, d2a = utils_eval.segment_residual_device(ps, raw, flow, labels, pd, radius, per_row=True)
+    seen = code = None
+    if origin is not None:
+        image = utils_eval.sight_image(pd, origin)
+        seen, _, _, _, code = utils_eval.segment_sight_device(image, ps, raw, flow, labels, d2b, d2a, far=far, per_row=True)
+    trust, _, counts = utils_eval.flow_trust_device(raw, flow, labels, table, num, d2a, out["pairs"].to(device), seen, code, params)
+    return trust, utils_eval.TrustCounts(counts.cpu().numpy())     # the one read-back
+
+
 RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
 
 
@@ -1326,7 +1388,13 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     utils_eval.RESIDUAL_EDGES[1] metres from every destination point, one more read-back.  The SegmentResidual is the one the run
     without the attribute gets; every listed segment gains `seen_through`, `excused`, `far_rows` and a `verdict`
     (utils_eval.SegmentSight.annotate), and the summary gains `residual_sight` (params, origin, far, verdicts: listed segments
-    per verdict) and `ms_sight_per_frame_pair` (device-synchronised around the image, the table and its read-back only)."""
+    per verdict) and `ms_sight_per_frame_pair` (device-synchronised around the image, the table and its read-back only).
+    args.residual_trust = True (`--residual-trust`; needs args.residual_segments): one trust byte per source point of every frame
+    pair -- `frame_trust` at the shared radius, with the line of sight from residual_sight's origin iff that attribute is set --
+    and the summary gains `residual_trust`: the counts added over the frame pairs (utils_eval.TrustCounts.summary, `kept_share`
+    among them), `ms_trust_per_frame_pair` (timed on its own, device-synchronised around the chain and its read-back of sixteen
+    words) and, where a frame pair carries gt_flow, `epe_kept`, `epe_dropped` and `rows_evaluated`: the mean end-point error of
+    the masked rows with and without KEEP, host numpy."""
     import torch.distributed as dist
     device = torch.device(device)
     pipelined = int(in_flight) > 1 and register_fn is None
@@ -1355,6 +1423,10 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     if len(sight_origin) != 3:
         raise ValueError(f"args.residual_sight: True or an origin (x, y, z), got {sight!r}")
     sight_ms = []
+    trust_on = bool(getattr(args, "residual_trust", False))
+    if trust_on and not per_segment:
+        raise ValueError("args.residual_trust needs args.residual and args.residual_segments: it spreads their verdicts over the rows")
+    trust_counts, trust_ms, trust_epe = utils_eval.TrustCounts(), [], [0.0, 0, 0.0, 0]    # sum and rows of e: kept, dropped
 
     def account(fp, out, index=None):
         nonlocal matched, segments_judged
@@ -1382,6 +1454,20 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
                 sync()
                 sight_ms.append((time.perf_counter() - t0) * 1e3)
                 seen.annotate(segment_lists[k])
+        if trust_on:
+            sync()
+            t0 = time.perf_counter()
+            bytes_, counted = frame_trust(fp, out, device, float(radius), sight_origin if sight else None)
+            sync()
+            trust_ms.append((time.perf_counter() - t0) * 1e3)
+            trust_counts.add(counted)
+            if fp.gt_flow is not None:             # (host numpy over the masked rows, like the meter below)
+                keep = utils_eval.trust_keep(bytes_).cpu().numpy()
+                e = np.linalg.norm(np.asarray(fp.gt_flow, np.float64) - out["flow"].cpu().numpy()[:, 0:3].astype(np.float64), axis=-1)
+                judged = np.asarray(fp.mask) > 0 if fp.mask is not None else np.ones(len(e), dtype=bool)
+                for at, rows_ in ((0, judged & keep), (2, judged & ~keep)):
+                    trust_epe[at] += float(e[rows_].sum())
+                    trust_epe[at + 1] += int(rows_.sum())
         pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
         matched += int(out["pairs"].shape[0])
         if fp.gt_flow is not None:
@@ -1452,6 +1538,15 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
         out["residual_sight"] = dict(params=_lib.SightParams.defaults().as_dict(), origin=list(sight_origin), far=utils_eval.RESIDUAL_EDGES[1],
                                      verdicts=verdicts)
         out["ms_sight_per_frame_pair"] = sum(sight_ms) / max(len(sight_ms), 1)
+    if trust_on:
+        from . import _lib
+        block = dict(trust_counts.summary(), params=_lib.TrustParams.defaults().as_dict(), line_of_sight=bool(sight),
+                     ms_trust_per_frame_pair=sum(trust_ms) / max(len(trust_ms), 1))
+        if trust_epe[1] + trust_epe[3]:
+            mean = lambda total, n: total / n if n else float("nan")   # noqa: E731
+            block.update(epe_kept=mean(trust_epe[0], trust_epe[1]), epe_dropped=mean(trust_epe[2], trust_epe[3]),
+                         rows_evaluated=trust_epe[1] + trust_epe[3])
+        out["residual_trust"] = block
     return out
 
 
@@ -1519,6 +1614,14 @@ def argument_parser():
                          "destination sweep -- 'seen through' (the flow put it where the sweep saw free space), 'lost from view' "
                          "(occluded, no return, out of range) or 'undecided'; X Y Z: the sensor's position in the frame of the "
                          "points (bare: 0 0 0)")
+    ap.add_argument("--residual-trust", action="store_true",
+                    help="with --residual-segments: one trust byte per source point (near / far and how the sweep saw it, its "
+                         "segment's verdict, KEEP), counted over the run; uses the line of sight iff --residual-sight is given; "
+                         "with gt_flow in the files, the EPE of the kept and of the dropped rows")
+    ap.add_argument("--save-trust", type=float, nargs="*", default=None, metavar="X",
+                    help="with --save-flows: write one trust byte per point into the saved flow's file (keys trust, trust_params), "
+                         "from the residual at 2 m; X Y Z: the sensor's position in the frame of the points, to use the line of "
+                         "sight as well (bare: the residual alone)")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
                     help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
     return ap
@@ -1538,6 +1641,12 @@ def main(argv=None):
         raise SystemExit("--residual-sight goes with --residual-segments (it judges the segments that one lists)")
     if ns.residual_sight is not None and len(ns.residual_sight) not in (0, 3):
         raise SystemExit("--residual-sight takes no number or the origin's three: X Y Z")
+    if ns.residual_trust and ns.residual_segments is None:
+        raise SystemExit("--residual-trust goes with --residual --residual-segments (it spreads their verdicts over the rows)")
+    if ns.save_trust is not None and not ns.save_flows:
+        raise SystemExit("--save-trust goes with --save-flows (the bytes go into the saved flow's file)")
+    if ns.save_trust is not None and len(ns.save_trust) not in (0, 3):
+        raise SystemExit("--save-trust takes no number or the origin's three: X Y Z")
     if (ns.save_flows or ns.save_metrics) and ns.protocol != "reference":
         raise SystemExit("--save-flows and --save-metrics go with --protocol reference")
     if ns.dataset == "argo":
@@ -1577,6 +1686,8 @@ def main(argv=None):
             args.bucket_table = True
         if ns.save_flows:
             args.save_flows = True
+        if ns.save_trust is not None:
+            args.save_trust = tuple(ns.save_trust) if ns.save_trust else True
         shard = dict(rank=rank, world=world) if world > 1 else {}
         if ns.dataset == "argo":
             res = run_sequences(args, [p for p in list_frame_pairs(ns.directory) if is_argo(p)], device, in_flight=ns.in_flight, dataset="argo", **shard)
@@ -1612,6 +1723,8 @@ def main(argv=None):
         args.residual_segments = ns.residual_segments
     if ns.residual_sight is not None:
         args.residual_sight = tuple(ns.residual_sight) if ns.residual_sight else True
+    if ns.residual_trust:
+        args.residual_trust = True
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         if ns.residual is not None:

@@ -21,7 +21,9 @@ warped cloud against the next one -- a hashed grid over the whole frame and an e
 (COVERAGE.md, named deviations).  `segment_residual` (icpflow_nn_residual_segments, csrc/segresid.hip) is the same residual per
 segment of the source, before and after the flow, against one grid: `SegmentResidual.worst` names the clusters that fit badly;
 `sight_image` / `line_of_sight` / `segment_sight` (icpflow_sight_*, csrc/sight.hip) ask the destination sweep whether such a
-cluster was put where the sweep saw free space or merely went out of view: `SegmentSight.annotate` adds the verdict."""
+cluster was put where the sweep saw free space or merely went out of view: `SegmentSight.annotate` adds the verdict.
+`flow_trust` (icpflow_flow_trust, csrc/trust.hip) spreads both verdicts over the rows: one byte per source point from the two
+tables and the per-row arrays, `trust_keep` its KEEP bit -- a stated policy for flows saved as pseudo labels, not a metric."""
 import numpy as np
 
 METRIC_NAMES = ("epe", "accs", "accr", "outlier", "Routlier")
@@ -1114,3 +1116,108 @@ def format_segment_sight(report):
     for line, e in zip(format_segment_residual(report), report):
         lines.append(f"{line}; far rows: {e['far_rows']:6d}, seen through: {e['seen_through']:6d}, excused: {e['excused']:6d}, {e['verdict']}")
     return lines
+
+
+# ---- the trust byte: the two verdicts per source point (icpflow_flow_trust, csrc/trust.hip) ------------------------------------
+TRUST_ROW_MASK, TRUST_FIT_SHIFT, TRUST_FIT_MASK = 0x07, 3, 0x03
+TRUST_MATCHED, TRUST_SKIPPED, TRUST_KEEP = 0x20, 0x40, 0x80
+TRUST_ROW_NAMES = ("not_judged", "near", "seen_through", "at_first_return", "behind", "no_return", "outside", "far_no_code")
+TRUST_FIT_NAMES = ("fits", "seen_through", "lost_from_view", "undecided")
+
+
+class TrustCounts:
+    """icpflow_flow_trust's d_counts on the host: rows int64 [8] (the rows with a segment per ROW class, TRUST_ROW_NAMES), fit
+    int64 [4] (the judged rows of segments that are not skipped per FIT class, TRUST_FIT_NAMES), matched, skipped, kept (the
+    rows with bit 5, 6, 7) and no_segment (the rows whose label has no segment: byte 0)."""
+
+    def __init__(self, words=None):
+        w = np.zeros(16, np.int64) if words is None else np.array(words, dtype=np.int64).reshape(16)
+        self.rows, self.fit = w[0:8].copy(), w[8:12].copy()
+        self.matched, self.skipped, self.kept, self.no_segment = int(w[12]), int(w[13]), int(w[14]), int(w[15])
+
+    def words(self):
+        """-> int64 [16], the kernel's layout"""
+        return np.concatenate([self.rows, self.fit, [self.matched, self.skipped, self.kept, self.no_segment]]).astype(np.int64)
+
+    def add(self, other):
+        """Accumulate another call's counts (integers: exact in any order).  -> self"""
+        self.rows, self.fit = self.rows + other.rows, self.fit + other.fit
+        self.matched, self.skipped = self.matched + other.matched, self.skipped + other.skipped
+        self.kept, self.no_segment = self.kept + other.kept, self.no_segment + other.no_segment
+        return self
+
+    def n(self):
+        """every row the calls saw"""
+        return int(self.rows.sum()) + self.no_segment
+
+    def kept_share(self):
+        """the share of all rows with KEEP set (NaN without a row)"""
+        n = self.n()
+        return self.kept / n if n else float("nan")
+
+    def summary(self):
+        """-> JSON-ready"""
+        return dict(n=self.n(), rows=dict(zip(TRUST_ROW_NAMES, self.rows.tolist())), fit=dict(zip(TRUST_FIT_NAMES, self.fit.tolist())),
+                    matched=self.matched, skipped=self.skipped, kept=self.kept, no_segment=self.no_segment, kept_share=self.kept_share())
+
+
+def flow_trust_device(after, flow, labels, resid_table, num, d2_after, pairs=None, sight_table=None, code_after=None, params=None):
+    """icpflow_flow_trust enqueued on the current stream, nothing read back.  after [n, 3], flow [n, 3] or None, labels [n]: what
+    segment_residual_device took; resid_table, num, d2_after: what it returned (per_row=True); sight_table, code_after: what
+    segment_sight_device returned for the same cloud (per_row=True), or both None; pairs [P, >= 1] (column 0 the source label
+    of a matched pair, as the registration leaves them) or None; params: a _lib.TrustParams (None: the library's defaults).
+    Device tensors; there is no CPU path.  -> (trust uint8 [n], segment uint8 [Lmax], counts int64 [16]) on the device; bytes of
+    `segment` from num on are not written."""
+    import ctypes
+    import torch
+    from . import _lib
+    a = _cloud3(after, "after")
+    device = a.device
+    n = a.shape[0]
+    f = None if flow is None else _cloud3(flow, "flow")
+    _lib.require_gpu(labels, resid_table, num, d2_after, pairs, sight_table, code_after)
+    lab, d2 = labels.to(torch.float32).contiguous(), d2_after.to(torch.float32).contiguous()
+    if resid_table.dtype != torch.float64 or resid_table.dim() != 2 or resid_table.shape[1] != _lib.NNRS_COLS or not resid_table.is_contiguous():
+        raise ValueError(f"flow_trust: resid_table {tuple(resid_table.shape)} {resid_table.dtype}, expected contiguous float64 [Lmax, {_lib.NNRS_COLS}]")
+    Lmax = int(resid_table.shape[0])
+    if sight_table is not None and (sight_table.dtype != torch.float64 or tuple(sight_table.shape) != (Lmax, _lib.SIGHT_COLS) or not sight_table.is_contiguous()):
+        raise ValueError(f"flow_trust: sight_table {tuple(sight_table.shape)} {sight_table.dtype}, expected contiguous float64 [{Lmax}, {_lib.SIGHT_COLS}]")
+    if (sight_table is None) != (code_after is None):
+        raise ValueError("flow_trust: the sight table and the per-row codes come together or not at all")
+    code = None if code_after is None else code_after.to(torch.int32).contiguous()
+    if num.dtype != torch.int32 or num.numel() != 1:
+        raise ValueError(f"flow_trust: num {tuple(num.shape)} {num.dtype}, expected int32 [1]")
+    if (f is not None and f.shape[0] != n) or lab.shape != (n,) or d2.shape != (n,) or (code is not None and code.shape != (n,)):
+        raise ValueError(f"flow_trust: flow {None if f is None else tuple(f.shape)}, labels {tuple(lab.shape)}, d2_after {tuple(d2.shape)}, "
+                         f"code_after {None if code is None else tuple(code.shape)} for {n} rows")
+    rows, P, stride = None, 0, 1
+    if pairs is not None and pairs.shape[0] > 0:
+        if pairs.dim() != 2 or pairs.shape[1] < 1:
+            raise ValueError(f"flow_trust: pairs {tuple(pairs.shape)}, expected [P, >= 1]")
+        rows = pairs.to(torch.float32).contiguous()
+        P, stride = int(rows.shape[0]), int(rows.shape[1])
+    if any(x is not None and x.device != device for x in (f, lab, d2, code, resid_table, sight_table, num, rows)):
+        raise ValueError("flow_trust: every tensor on the same device")
+    p = params if params is not None else _lib.TrustParams.defaults()
+    trust = torch.empty(n, dtype=torch.uint8, device=device)
+    segment = torch.empty(Lmax, dtype=torch.uint8, device=device)
+    counts = torch.empty(_lib.TRUST_COUNTS, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        _lib.call("icpflow_flow_trust", _lib.ptr(a), _lib.ptr(f), _lib.ptr(lab), n, _lib.ptr(resid_table), _lib.ptr(sight_table), _lib.ptr(num), Lmax,
+                  _lib.ptr(d2), _lib.ptr(code), _lib.ptr(rows), P, stride, ctypes.byref(p), _lib.ptr(trust), _lib.ptr(segment), _lib.ptr(counts),
+                  _lib.stream(device))
+    return trust, segment, counts
+
+
+def flow_trust(after, flow, labels, resid_table, num, d2_after, pairs=None, sight_table=None, code_after=None, params=None):
+    """One trust byte per row of a source cloud from the tables and per-row arrays of segment_residual_device and (optionally)
+    segment_sight_device: bits 0-2 the row's class (TRUST_ROW_NAMES), bits 3-4 its segment's fit (TRUST_FIT_NAMES), TRUST_MATCHED,
+    TRUST_SKIPPED, TRUST_KEEP (include/icpflow_hip.h, 8(i)).  Tensors on the GPU; there is no CPU path.  -> (trust uint8 [n] on
+    the device, TrustCounts); one read-back of sixteen words."""
+    trust, _, counts = flow_trust_device(after, flow, labels, resid_table, num, d2_after, pairs, sight_table, code_after, params)
+    return trust, TrustCounts(counts.cpu().numpy())
+
+
+def trust_keep(trust):
+    """the rows to keep as pseudo labels: bit 7 of the trust byte (a torch tensor or a numpy array of uint8) -> bool, same kind"""
+    return (trust & TRUST_KEEP) != 0

@@ -1208,6 +1208,71 @@ int icpflow_sight_segments(const uint32_t *d_image, const icpflow_sight_params_t
                            size_t ws_bytes, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(i)  trust byte: the verdicts of 8(g) and 8(h) per source point, for flows saved as pseudo labels.  No counterpart in the
+ * reference; KEEP below is a stated policy, not a metric of the reference (COVERAGE.md, named deviations).
+ *
+ * icpflow_flow_trust -- a pure function of tables and arrays that earlier calls left on the device:
+ *   d_after float32 [n,3], d_flow float32 [n,3] or NULL, d_labels float32 [n]: icpflow_nn_residual_segments' arguments of
+ *   the same names; d_resid_table double [Lmax][ICPFLOW_NNRS_COLS] and d_num: what that call wrote; d_d2_after float32 [n]: its
+ *   per-row output; d_sight_table double [Lmax][ICPFLOW_SIGHT_COLS] and d_code_after int32 [n]: what icpflow_sight_segments
+ *   wrote for the same cloud, or both NULL (n > 0: one without the other is ICPFLOW_E_ARG; codes without a table always);
+ *   d_pair_rows float32 [P][pair_stride], column 0 the source label of a matched pair -- the layout icpflow_flow_rigid_rows
+ *   reads (P = 0: may be NULL).
+ *   Segment c < *d_num is row c of the tables, both in ascending label order.  Its bits:
+ *     MATCHED   its label (column 0, a double) equals, by IEEE == on the widened value, column 0 of some pair row: -0.0
+ *               matches +0.0, a NaN matches nothing; a label listed twice counts once.
+ *     SKIPPED   its label equals (IEEE ==) (double)skip[0] or (double)skip[1].  FIT is then 0.
+ *     LISTED    not SKIPPED, column 10 (AFTER good rows) is not zero and column 16 / column 10 > above, one fp64 division: a
+ *               mean EQUAL to `above` is not listed, a segment without a good row is not listed (SegmentResidual.worst).
+ *     FIT       0 when not listed.  Listed, with a sight table: far = the sum of columns 15, 17, 19, 21, 23 (the AFTER far rows
+ *               of codes 0 .. 4, in that order, in fp64), seen = column 19, excused = columns 15 + 17 + 23 (codes 0, 1, 4);
+ *               1 "seen through" iff seen > share * far; else 2 "lost from view" iff excused > share * far; else 3 "undecided"
+ *               (one fp64 product; SegmentSight.annotate).  Listed, without a sight table: 3.
+ *   Row i finds its segment by binary search on table.hip's key of its label (csrc/labelkey.hpp) among the keys of column 0
+ *   narrowed to float: -0.0 and +0.0 are one label, a NaN label finds the segment with its bit pattern.  A SIGNALLING NaN is
+ *   quieted first (bit 22 set), on both sides: the table's float64 column has quieted it already -- widening a float does --,
+ *   so a signalling-NaN label finds the segment of its quiet form if there is one.
+ *   A row is BAD by icpflow_nn_residual's rule, the same device function, applied to d_after + d_flow (one fp32 addition per
+ *   coordinate; d_flow NULL: to d_after); NEAR iff d2_after <= far2, far2 = (float)far * (float)far, one fp32 product on the
+ *   host (a NaN d2 is not near); every other good row is FAR.
+ *   d_trust uint8 [n]:
+ *       bits 0-2  ROW   0 not judged (a bad row); 1 NEAR; far rows by d_code_after: 2 seen through (code 2), 3 at the first
+ *                       return (code 3), 4 behind (code 4), 5 no return (code 1), 6 outside (code 0); 7 far with no code
+ *                       given (d_code_after NULL, or a value that is none of the five)
+ *       bits 3-4  FIT of the row's segment             bit 5  MATCHED            bit 6  SKIPPED
+ *       bit 7     KEEP: ROW is neither 0 nor 2, and FIT is 0 or 2
+ *   A row whose label has no segment gets the whole byte 0; with *d_num <= 0 (overflow is reported as the negative count)
+ *   every row does.  *d_num above Lmax is read as Lmax.
+ *   d_segment uint8 [Lmax]: bits 3-6 of segment c, the other bits 0; bytes from *d_num on are not written.
+ *   d_counts int64 [ICPFLOW_TRUST_COUNTS], by ballot and popcount (integer atomics only): [0..7] the rows WITH a segment per
+ *   ROW class; [8..11] the judged (ROW != 0) rows of segments that are not SKIPPED, per FIT class; [12] the rows with bit 5,
+ *   [13] with bit 6, [14] with bit 7; [15] the rows without a segment.  [0..7] and [15] add up to n.
+ *   Two launches (csrc/trust.hip): one thread per segment, the pair labels through LDS in tiles of 1024; then a workgroup of
+ *   256 threads per 1024 rows with the segments' keys and bytes in LDS.  Exactly d_trust[0, n), d_segment[0, *d_num) and the
+ *   sixteen counts are written.  No workspace, no host synchronisation, no allocation; asynchronous on `stream`.
+ *   icpflow_trust_params_t: above in [0, 1e3] (default 0.1, RESIDUAL_EDGES[1]), far in [0, 1e3] (default 0.1), share in [0, 1)
+ *   (default 0.5), skip (defaults -1e8f, -1.0f: the ground and the unclustered rows, which no registration moved).
+ *   Refusals, all before any launch: a null required pointer, a negative size, Lmax < 1, pair_stride < 1, P > 0 with no pair
+ *   rows, a sight table without codes or codes without a sight table, a struct_size mismatch, above or far outside [0, 1e3]
+ *   (a NaN too), share outside [0, 1) are ICPFLOW_E_ARG; n > 2^29 or Lmax > 4096 are ICPFLOW_E_LIMIT.  n = 0 succeeds with
+ *   sixteen zeros.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_TRUST_COUNTS 16
+typedef struct icpflow_trust_params {
+    size_t struct_size; /* sizeof(icpflow_trust_params_t) */
+    double above;       /* a segment is LISTED when its AFTER mean distance exceeds this; default 0.1 */
+    double far;         /* a row is FAR when d2_after > (float)far * (float)far; default 0.1 */
+    double share;       /* majority share of the verdict; default 0.5 */
+    float skip[2];      /* labels no registration moved; default -1e8f, -1.0f */
+} icpflow_trust_params_t;
+int icpflow_flow_trust_default_params(icpflow_trust_params_t *params);
+int icpflow_flow_trust(const float *d_after, const float *d_flow, const float *d_labels, int n, const double *d_resid_table,
+                       const double *d_sight_table, const int32_t *d_num, int Lmax, const float *d_d2_after,
+                       const int32_t *d_code_after, const float *d_pair_rows, int P, int pair_stride,
+                       const icpflow_trust_params_t *params, uint8_t *d_trust, uint8_t *d_segment, int64_t *d_counts,
+                       icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
