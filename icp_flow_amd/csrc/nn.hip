@@ -988,7 +988,9 @@ __device__ __forceinline__ void sweep_job(const SweepParams &p, const int lin, c
     double v[kPartial];
 #pragma unroll
     for (int k = 0; k < kPartial; ++k) v[k] = 0.0;
-    if (live && nt > 0 && (!sharedWindow || wave == 0)) {
+    // (match_eval against an EMPTY cloud: nothing was scanned, best is still +inf -- the row adds sqrtf(inf) to the sum and no
+    // inlier, as the all-pairs scan's row does; a sum of 0 there was a mean error of 0, which passes every `error < thres`)
+    if (live && (nt > 0 || MODE == SWEEP_EVAL) && (!sharedWindow || wave == 0)) {
         const float d = sqrtf(best);
         v[0] = (double)d;
         if (MODE == SWEEP_EVAL) {
