@@ -115,6 +115,10 @@ SIGNATURES = {
     "icpflow_sight_segments": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _d, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_flow_trust_default_params": (_i, [_p]),
     "icpflow_flow_trust": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "icpflow_segment_boxes_workspace_bytes": (_sz, [_i, _i, _i]),
+    "icpflow_segment_boxes": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _d, _p, _p, _sz, _p]),
+    "icpflow_pair_objects_default_params": (_i, [_p]),
+    "icpflow_pair_objects": (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -156,6 +160,8 @@ NNRS_COLS, NNRS_MAX_SEGMENTS = 18, 4096           # icpflow_nn_residual_segments
 SIGHT_COLS, SIGHT_MAX_SEGMENTS = 24, 4096         # icpflow_sight_segments: columns of a row; Lmax at most
 SIGHT_BAD_ROW, SIGHT_OUTSIDE, SIGHT_NO_RETURN, SIGHT_SEEN_THROUGH, SIGHT_AT_FIRST_RETURN, SIGHT_BEHIND = -2, 0, 1, 2, 3, 4
 TRUST_COUNTS, TRUST_MAX_SEGMENTS = 16, 4096        # icpflow_flow_trust: words of d_counts; Lmax at most
+BOX_COLS, BOX_MAX_DIRECTIONS, BOX_MAX_SEGMENTS = 16, 360, 4096   # icpflow_segment_boxes: columns of a row; A and Lmax at most
+OBJECT_COLS, OBJECT_COUNTS = 24, 4                # icpflow_pair_objects: columns of a row; words of d_counts
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical
@@ -343,6 +349,24 @@ class TrustParams(ctypes.Structure):
 
     def as_dict(self):
         return dict(above=self.above, far=self.far, share=self.share, skip=[float(self.skip[0]), float(self.skip[1])])
+
+
+class ObjectParams(ctypes.Structure):
+    """icpflow_object_params_t: the time between the sweeps and the speed that tells movers apart (icpflow_pair_objects)."""
+    _fields_ = [("struct_size", _sz), ("seconds", _d), ("min_speed", _d)]
+
+    @staticmethod
+    def defaults(**over):
+        p = ObjectParams()
+        call("icpflow_pair_objects_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if k == "struct_size" or k not in dict(ObjectParams._fields_):
+                raise TypeError(f"ObjectParams: no parameter {k!r}")
+            setattr(p, k, float(v))
+        return p
+
+    def as_dict(self):
+        return dict(seconds=self.seconds, min_speed=self.min_speed)
 
 
 class Profile:

@@ -86,7 +86,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import utils_eval, utils_flow, utils_track
+from . import utils_eval, utils_flow, utils_objects, utils_track
 
 # demo.sh:9-13 / main.sh flags of the registration stage
 DEFAULT_ARGS = dict(max_points=10000, min_cluster_size=20, translation_frame=2.0, thres_dist=0.1, thres_box=0.1,
@@ -406,8 +406,8 @@ def register_frame_pair_steps(args, fp, device, gap=None, asynchronous=False):
     else:
         flow = utils_flow.flow_estimation_torch(a, flow_src, pd, ls, ld, pairs, T, pose)
     out = dict(pairs=pairs, transformations=T, flow=flow, translation_frame=a.translation_frame, association=a.association_path or "host")
-    # what the per-segment report (run_sequences), the residual (run_stream) and the trust bytes (run_sequences) read besides the flow
-    if getattr(args, "if_verbose", False) or getattr(args, "residual", None) or getattr(args, "save_trust", None):
+    # what the per-segment report (run_sequences), the residual and the objects (run_stream) and the trust bytes (run_sequences) read besides the flow
+    if getattr(args, "if_verbose", False) or getattr(args, "residual", None) or getattr(args, "save_trust", None) or getattr(args, "objects", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -668,8 +668,8 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
     out = dict(pairs=rows[:P], transformations=T[:P], translation_frame=a.translation_frame, association="device")
     if flow is not None:
         out["flow"] = flow
-    # what the per-segment report (run_sequences), the residual (run_stream) and the trust bytes (run_sequences) read besides the flow
-    if getattr(a, "if_verbose", False) or getattr(a, "residual", None) or getattr(a, "save_trust", None):
+    # what the per-segment report (run_sequences), the residual and the objects (run_stream) and the trust bytes (run_sequences) read besides the flow
+    if getattr(a, "if_verbose", False) or getattr(a, "residual", None) or getattr(a, "save_trust", None) or getattr(a, "objects", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -1312,6 +1312,28 @@ def frame_trust(fp, out, device, radius, origin=None, params=None):
     return trust, utils_eval.TrustCounts(counts.cpu().numpy())     # the one read-back
 
 
+def frame_objects(fp, out, device, seconds=None, min_speed=utils_objects.MIN_SPEED, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS):
+    """One object row per matched pair of a registered frame pair (utils_objects), everything on the device: the boxes of the
+    ego-compensated source's clusters and of the destination's (the cloud the pairs' transforms register, and the one they
+    register it to), then a box, a displacement, a velocity and a heading per pair from `out`'s pair rows and transforms.
+    seconds: the time between the two sweeps (None: fp.gap sweeps of utils_objects.SWEEP_SECONDS).  -> utils_objects.Objects;
+    one read-back, the pairs' table with its four counts."""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    ls = _source_labels(fp, out, device)
+    ld = out.get("labels_dst")
+    if ld is None and fp.labels_dst is not None:
+        ld = _input(fp, "labels_dst", device)
+    if ld is None:
+        raise ValueError("the objects need the destination's cluster labels: the registration must leave labels_dst in its result")
+    seconds = float(fp.gap) * utils_objects.SWEEP_SECONDS if seconds is None else float(seconds)
+    boxes_src, num_src = utils_objects.segment_boxes_device(ps, ls, delta, A)
+    boxes_dst, num_dst = utils_objects.segment_boxes_device(pd, ld.to(device).float(), delta, A)
+    rows, counts = utils_objects.pair_objects_device(boxes_src, num_src, out["pairs"].to(device), out["transformations"].to(device),
+                                                     boxes_dst, num_dst, seconds, min_speed)
+    return utils_objects.Objects.read(rows, counts, seconds, min_speed)     # the one read-back
+
+
 RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
 
 
@@ -1394,7 +1416,14 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     and the summary gains `residual_trust`: the counts added over the frame pairs (utils_eval.TrustCounts.summary, `kept_share`
     among them), `ms_trust_per_frame_pair` (timed on its own, device-synchronised around the chain and its read-back of sixteen
     words) and, where a frame pair carries gt_flow, `epe_kept`, `epe_dropped` and `rows_evaluated`: the mean end-point error of
-    the masked rows with and without KEEP, host numpy."""
+    the masked rows with and without KEEP, host numpy.
+    args.objects = True or a file name (`--objects [FILE]`; one process only; independent of args.residual): one object row per
+    matched pair of every frame pair -- `frame_objects`, outside the timed region of one pair at a time, with
+    seconds = fp.gap * args.sweep_seconds (default 0.1) and args.objects_min_speed (default 0.5 m/s).  The summary gains `objects`
+    (objects, movers, the pairs without a segment or a box, largest_centre_gap in metres, the parameters) and
+    `ms_objects_per_frame_pair` (device-synchronised around the three calls and their one read-back); with a file name, one JSON
+    line per frame pair is written there (counts, and per object its labels, centre, size, yaw, velocity, speed, moving,
+    centre_gap, point counts) and the summary names it as `objects_file`."""
     import torch.distributed as dist
     device = torch.device(device)
     pipelined = int(in_flight) > 1 and register_fn is None
@@ -1427,9 +1456,15 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     if trust_on and not per_segment:
         raise ValueError("args.residual_trust needs args.residual and args.residual_segments: it spreads their verdicts over the rows")
     trust_counts, trust_ms, trust_epe = utils_eval.TrustCounts(), [], [0.0, 0, 0.0, 0]    # sum and rows of e: kept, dropped
+    objects_on = getattr(args, "objects", None)
+    if objects_on and world > 1:
+        raise ValueError("args.objects under more than one rank: merging the files is not built")
+    sweep_seconds = float(getattr(args, "sweep_seconds", utils_objects.SWEEP_SECONDS))
+    objects_min_speed = float(getattr(args, "objects_min_speed", utils_objects.MIN_SPEED))
+    object_lines, objects_ms, object_counts, object_gap = {}, [], np.zeros(5, np.int64), None    # frame pair -> its line of the file
 
     def account(fp, out, index=None):
-        nonlocal matched, segments_judged
+        nonlocal matched, segments_judged, object_counts, object_gap
         if radius:
             sync()
             t0 = time.perf_counter()
@@ -1468,6 +1503,19 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
                 for at, rows_ in ((0, judged & keep), (2, judged & ~keep)):
                     trust_epe[at] += float(e[rows_].sum())
                     trust_epe[at + 1] += int(rows_.sum())
+        if objects_on:
+            k = len(object_lines) if index is None else index
+            sync()
+            t0 = time.perf_counter()
+            seen_objects = frame_objects(fp, out, device, float(fp.gap) * sweep_seconds, objects_min_speed)
+            sync()
+            objects_ms.append((time.perf_counter() - t0) * 1e3)
+            s = seen_objects.summary()
+            object_counts += [s[name] for name in utils_objects.COUNT_NAMES] + [s["pairs"]]
+            gap_ = seen_objects.largest_centre_gap()
+            if gap_ is not None and (object_gap is None or gap_ > object_gap):
+                object_gap = gap_
+            object_lines[k] = dict(frame_pair=k, path=fp.name, seconds=seen_objects.seconds, counts=s, objects=seen_objects.as_list())
         pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
         matched += int(out["pairs"].shape[0])
         if fp.gt_flow is not None:
@@ -1547,6 +1595,17 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             block.update(epe_kept=mean(trust_epe[0], trust_epe[1]), epe_dropped=mean(trust_epe[2], trust_epe[3]),
                          rows_evaluated=trust_epe[1] + trust_epe[3])
         out["residual_trust"] = block
+    if objects_on:
+        names = utils_objects.COUNT_NAMES + ("pairs",)
+        out["objects"] = dict({name: int(v) for name, v in zip(names, object_counts)}, pairs_without_box=int(object_counts[4] - object_counts[0]),
+                              largest_centre_gap=object_gap, sweep_seconds=sweep_seconds, min_speed=objects_min_speed,
+                              delta=utils_objects.BOX_DELTA, directions=utils_objects.BOX_DIRECTIONS)
+        out["ms_objects_per_frame_pair"] = sum(objects_ms) / max(len(objects_ms), 1)
+        if isinstance(objects_on, str):
+            with open(objects_on, "w") as f:
+                for k in sorted(object_lines):       # one JSON line per frame pair, in their order
+                    f.write(json.dumps(object_lines[k]) + "\n")
+            out["objects_file"] = objects_on
     return out
 
 
@@ -1622,6 +1681,14 @@ def argument_parser():
                     help="with --save-flows: write one trust byte per point into the saved flow's file (keys trust, trust_params), "
                          "from the residual at 2 m; X Y Z: the sensor's position in the frame of the points, to use the line of "
                          "sight as well (bare: the residual alone)")
+    ap.add_argument("--objects", nargs="?", const=True, default=None, metavar="FILE",
+                    help="object pseudo labels: per matched cluster pair an oriented box, a velocity, a heading and the distance "
+                         "of the moved box's centre from the matched destination cluster's (FILE: one JSON line per frame pair); "
+                         "one process only; not with --protocol reference")
+    ap.add_argument("--sweep-seconds", type=float, default=utils_objects.SWEEP_SECONDS, metavar="S",
+                    help="with --objects: the time between two sweeps; a frame pair `gap` sweeps apart spans gap * S seconds")
+    ap.add_argument("--objects-min-speed", type=float, default=utils_objects.MIN_SPEED, metavar="V",
+                    help="with --objects: an object moves when its xy speed reaches V m/s")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
                     help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
     return ap
@@ -1643,6 +1710,10 @@ def main(argv=None):
         raise SystemExit("--residual-sight takes no number or the origin's three: X Y Z")
     if ns.residual_trust and ns.residual_segments is None:
         raise SystemExit("--residual-trust goes with --residual --residual-segments (it spreads their verdicts over the rows)")
+    if ns.objects is not None and ns.protocol == "reference":
+        raise SystemExit("--objects is not built into --protocol reference (COVERAGE.md row 17): run the frame pairs without --protocol")
+    if ns.objects is not None and not (ns.sweep_seconds > 0 and ns.objects_min_speed >= 0):
+        raise SystemExit("--sweep-seconds must be positive and --objects-min-speed must not be negative")
     if ns.save_trust is not None and not ns.save_flows:
         raise SystemExit("--save-trust goes with --save-flows (the bytes go into the saved flow's file)")
     if ns.save_trust is not None and len(ns.save_trust) not in (0, 3):
@@ -1725,6 +1796,10 @@ def main(argv=None):
         args.residual_sight = tuple(ns.residual_sight) if ns.residual_sight else True
     if ns.residual_trust:
         args.residual_trust = True
+    if ns.objects is not None:
+        if world > 1:
+            raise SystemExit("--objects under more than one rank: merging the files is not built")
+        args.objects, args.sweep_seconds, args.objects_min_speed = ns.objects, ns.sweep_seconds, ns.objects_min_speed
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         if ns.residual is not None:

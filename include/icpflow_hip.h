@@ -1273,6 +1273,89 @@ int icpflow_flow_trust(const float *d_after, const float *d_flow, const float *d
                        icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(j)  object boxes: an oriented box per segment and a box, a velocity and a heading per matched pair, for object pseudo
+ * labels.  No counterpart in the reference; the fitting rule and the 0.5 m/s that tells movers from standing objects are
+ * stated policies (COVERAGE.md, named deviations).
+ *
+ * icpflow_segment_boxes -- one box per segment of ONE labelled cloud:
+ *   d_points float32 [n,3]; d_order int64 [n], d_table double [Lmax][9] and d_num: exactly what icpflow_cluster_table /
+ *   icpflow_cluster_table_pair wrote for that cloud (its dictionary, stable order, counts and starts are reused, not rebuilt);
+ *   h_dirs (HOST) float32 [A][2]: unit vectors (c_k, s_k), 1 <= A <= ICPFLOW_BOX_MAX_DIRECTIONS, copied before the call
+ *   returns (they travel in the kernel arguments) -- the directions are the caller's, so no libm enters the contract;
+ *   delta (metres) in [0, 1e3]; d_boxes double [Lmax][ICPFLOW_BOX_COLS].
+ *   Arithmetic, float32, every fused operation an explicit fmaf: r = (float) of the table's centroid (columns 3, 4);
+ *   x' = x - r_x, y' = y - r_y (one subtraction each: a cluster kilometres from the origin keeps its precision);
+ *   u = fmaf(y', s_k, x' * c_k); v = fmaf(y', c_k, -(x' * s_k)).  A row is GOOD iff its three coordinates are finite; the
+ *   other rows enter nothing (the centroid is the table's, though: a segment that holds such rows has a centroid that is not
+ *   finite, and its box is then NaN, with its good rows counted).  Per direction k over the good rows: umin, umax, vmin, vmax; area = (umax - umin) * (vmax - vmin)
+ *   in float32; near = the rows with min(min(umax - u, u - umin), min(vmax - v, v - vmin)) <= (float)delta, float32
+ *   subtractions of the same u and v the extrema were taken from.  The best k maximises near, then minimises area, then k.
+ *   Row c < *d_num of d_boxes:
+ *       0  label            1  rows (the table's count)    2  good rows        3  k           4  near at k
+ *       5  area at k, widened                              6-8  the centre, in fp64 in this order and without fma:
+ *            um = ((double)umin + (double)umax) * 0.5, vm likewise; X = (double)r_x + ((double)c_k * um - (double)s_k * vm);
+ *            Y = (double)r_y + ((double)s_k * um + (double)c_k * vm); Z = ((double)zmin + (double)zmax) * 0.5
+ *       9  du = (double)umax - (double)umin    10  dv    11  height = (double)zmax - (double)zmin
+ *       12-13  c_k, s_k widened                14-15  zmin, zmax
+ *   A segment with a negative label (ground -1e8, noise -1: the cluster table computes no statistics for them either) and a
+ *   segment without a good row get columns 0 and 1, column 3 = -1 and zeros elsewhere.  Rows from *d_num on are not written;
+ *   with *d_num <= 0 (overflow is reported as the negative count) nothing is; *d_num above Lmax is read as Lmax.
+ *   What the table claims is clipped to the cloud and never dereferenced beyond it: a start outside [0, n] leaves its segment
+ *   no row, a count is cut at n - start, an entry of d_order outside [0, n) is skipped.
+ *   Workspace, the caller's, 16-byte aligned: icpflow_segment_boxes_workspace_bytes(n, Lmax, A) =
+ *       a256(4 (Lmax + 1)) + a256(16 C A) + a256(8 C) + a256(4 C) + a256(16 Lmax A) + a256(8 Lmax) + a256(4 Lmax) + a256(4 Lmax A),
+ *   C = n / 1024 + min(n, Lmax) + 1 chunks of 1024 rows, a256 = rounded up to a multiple of 256; non-decreasing in n, Lmax and
+ *   A; 0 for arguments the call refuses.  Nothing in it is read before it is written.
+ *   Five launches (csrc/boxes.hip), asynchronous on `stream`, no host synchronisation, no allocation, no floating-point atomic:
+ *   every number is a function of the arguments alone.
+ *   Refusals, all before any launch: a null required pointer, n < 0, Lmax < 1, A outside [1, 360], delta outside [0, 1e3] (a NaN
+ *   too), a direction that is not finite or has |c * c + s * s - 1| > 1e-3 (in fp64), a workspace not 16-byte aligned are
+ *   ICPFLOW_E_ARG; n > 2^29 or Lmax > 4096 are ICPFLOW_E_LIMIT; a missing or short workspace is ICPFLOW_E_WORKSPACE.  n = 0
+ *   succeeds (every segment of the table is then without a row).
+ *
+ * icpflow_pair_objects -- one row per matched pair, from the two box tables and what the registration left on the device:
+ *   d_boxes_src, d_num_src: icpflow_segment_boxes' table of the source cloud; d_boxes_dst, d_num_dst: of the destination, or
+ *   both NULL; d_pair_rows float32 [P][pair_stride], pair_stride >= 2: column 0 the source label, column 1 the destination
+ *   label of a pair; d_T float32 [P][16], row-major 4 x 4; d_objects double [P][ICPFLOW_OBJECT_COLS]; d_counts int64
+ *   [ICPFLOW_OBJECT_COUNTS].  A label finds its segment as icpflow_flow_trust's rows do: by binary search on the key
+ *   (csrc/labelkey.hpp) of the quieted label among column 0 narrowed to float.  A segment HAS A BOX iff its column 3 >= 0.
+ *   Row p, everything in fp64 in the order written, no fma:
+ *       0-1    the two labels                      2-3    their segments' indices, or -1
+ *       4-6    c = the source box's centre         7-9    d = T c - c: d_x = (((m00 cx + m01 cy) + m02 cz) + m03) - cx, ...
+ *       10-12  d / seconds                         13     vx vx + vy vy (the square root is the caller's)
+ *       14     moving: 1 iff column 13 >= min_speed * min_speed (one product on the host)
+ *       15     the heading's quadrant m among e0 = (c_k, s_k), e1 = (-s_k, c_k), e2 = -e0, e3 = -e1 -- moving: the m with the
+ *              largest e_m . d_xy (ex dx + ey dy), ties to the lowest m; standing: 0 if du >= dv, else 1
+ *       16-18  length (the extent along e_m), width, height                    19-20  e_m
+ *       21     the squared xy distance of c + d from the destination box's centre; -1 without a destination box
+ *       22-23  the good rows of the source and of the destination box (0 without one)
+ *   A pair whose source segment is missing or has no box gets columns 0-3 and zeros elsewhere.
+ *   d_counts: [0] pairs with a source box, [1] of them moving, [2] pairs whose source label finds no segment, [3] pairs whose
+ *   destination label finds none (every pair when there is no destination table); by ballot and popcount, integer atomics only.
+ *   One launch, one thread per pair, no workspace; asynchronous on `stream`.  Refusals, before any launch: a null required
+ *   pointer, P < 0, Lmax < 1, pair_stride < 2, one of the destination's two arguments without the other, P > 0 with no pair
+ *   rows or no transforms, a struct_size mismatch, seconds not positive and finite, min_speed negative or not finite are
+ *   ICPFLOW_E_ARG; Lmax > 4096 is ICPFLOW_E_LIMIT.  P = 0 succeeds with four zeros.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_BOX_COLS 16
+#define ICPFLOW_BOX_MAX_DIRECTIONS 360
+#define ICPFLOW_OBJECT_COLS 24
+#define ICPFLOW_OBJECT_COUNTS 4
+typedef struct icpflow_object_params {
+    size_t struct_size; /* sizeof(icpflow_object_params_t) */
+    double seconds;     /* the time between the two sweeps; default 0.1 */
+    double min_speed;   /* an object moves when its xy speed reaches this, m/s; default 0.5 */
+} icpflow_object_params_t;
+size_t icpflow_segment_boxes_workspace_bytes(int n, int Lmax, int A);
+int icpflow_segment_boxes(const float *d_points, int n, const int64_t *d_order, const double *d_table, const int32_t *d_num,
+                          int Lmax, const float *h_dirs, int A, double delta, double *d_boxes, void *d_ws, size_t ws_bytes,
+                          icpflow_stream_t stream);
+int icpflow_pair_objects_default_params(icpflow_object_params_t *params);
+int icpflow_pair_objects(const double *d_boxes_src, const int32_t *d_num_src, const double *d_boxes_dst,
+                         const int32_t *d_num_dst, int Lmax, const float *d_pair_rows, int P, int pair_stride, const float *d_T,
+                         const icpflow_object_params_t *params, double *d_objects, int64_t *d_counts, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
