@@ -119,6 +119,12 @@ SIGNATURES = {
     "icpflow_segment_boxes": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _d, _p, _p, _sz, _p]),
     "icpflow_pair_objects_default_params": (_i, [_p]),
     "icpflow_pair_objects": (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "icpflow_label_overlap_workspace_bytes": (_sz, [_i, _i]),
+    "icpflow_label_overlap": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_object_tracks_default_params": (_i, [_p]),
+    "icpflow_object_tracks_extend_workspace_bytes": (_sz, [_i, _i]),
+    "icpflow_object_tracks_extend": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _d, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_object_tracks_fit": (_i, [_p, _i, _i, _p, _p, _p, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -162,6 +168,9 @@ SIGHT_BAD_ROW, SIGHT_OUTSIDE, SIGHT_NO_RETURN, SIGHT_SEEN_THROUGH, SIGHT_AT_FIRS
 TRUST_COUNTS, TRUST_MAX_SEGMENTS = 16, 4096        # icpflow_flow_trust: words of d_counts; Lmax at most
 BOX_COLS, BOX_MAX_DIRECTIONS, BOX_MAX_SEGMENTS = 16, 360, 4096   # icpflow_segment_boxes: columns of a row; A and Lmax at most
 OBJECT_COLS, OBJECT_COUNTS = 24, 4                # icpflow_pair_objects: columns of a row; words of d_counts
+OVERLAP_COLS, OVERLAP_COUNTS, OVERLAP_MAX_SEGMENTS = 10, 4, 4096   # icpflow_label_overlap: columns of a row; words of d_counts; Lmax at most
+TRACK_SEGMENT_COLS, TRACK_OBS_COLS, TRACK_COLS = 6, 13, 16        # icpflow_object_tracks_extend / _fit: columns of their rows
+TRACK_EXTEND_COUNTS, TRACK_FIT_COUNTS = 6, 5                      # ... words of their d_counts
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical
@@ -349,6 +358,25 @@ class TrustParams(ctypes.Structure):
 
     def as_dict(self):
         return dict(above=self.above, far=self.far, share=self.share, skip=[float(self.skip[0]), float(self.skip[1])])
+
+
+class TrackParams(ctypes.Structure):
+    """icpflow_track_params_t: the IoU at which a cluster inherits a track, the residual a consistent track stays within and the
+    speed that tells movers apart (icpflow_object_tracks_extend, icpflow_object_tracks_fit)."""
+    _fields_ = [("struct_size", _sz), ("min_iou", _d), ("max_residual", _d), ("min_speed", _d)]
+
+    @staticmethod
+    def defaults(**over):
+        p = TrackParams()
+        call("icpflow_object_tracks_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if k == "struct_size" or k not in dict(TrackParams._fields_):
+                raise TypeError(f"TrackParams: no parameter {k!r}")
+            setattr(p, k, float(v))
+        return p
+
+    def as_dict(self):
+        return dict(min_iou=self.min_iou, max_residual=self.max_residual, min_speed=self.min_speed)
 
 
 class ObjectParams(ctypes.Structure):

@@ -1,0 +1,365 @@
+// tracks.hip -- the clusters of a sample's shared sweep linked across its gaps, and a constant velocity per track
+// (include/icpflow_hip.h, "8(k) object tracks": icpflow_object_tracks_extend, icpflow_object_tracks_fit).
+//
+// icpflow_object_tracks_extend, one gap:
+//   1. trk_labels_kernel    "track id per row" as a float32 labelling (an id is its own label, no track is -1)
+//   2. overlap.hip's chain  this gap's labels (side A) against it (side B): partner, mutual and IoU per segment of A
+//   3. trk_assign_kernel    ONE workgroup of 1024, thread t segments 4 t .. 4 t + 3: inherit or fresh, the fresh ids by an
+//                           exclusive scan in ascending label order; the rows of d_segments, the counts, overflow, *d_next_id
+//   4. trk_relabel_kernel   a thread per row: the rows of linkable segments take their segment's id
+//   5. trk_obs_kernel       a thread per object row: the id of its destination label's segment (binary search on label_key)
+// The state is written by kernels 3 (its last statement) and 4 only, behind everything that reads it, and not at all on
+// overflow.  icpflow_object_tracks_fit: one thread per track walks all observations in row order -- T * M is a few thousand
+// tracks times a few thousand rows at most (a sample has at most 15 gaps of at most 4096 pairs), far below what a segmented
+// reduction would pay for; the order of the sums is then the order of the rows, and the numbers a function of the arguments.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "boxes.hpp"
+#include "common.hpp"
+#include "host.hpp"
+#include "overlap.hpp"
+
+using icpflow::kWave;
+using icpflow::pointer_error;
+using icpflow::report_error;
+using icpflow::report_errorf;
+using icpflow::workspace_error;
+using icpflow::overlap::kLmax;
+using icpflow::overlap::kMaxRows;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kAssignThreads = 1024;
+constexpr int kAssignEach = kLmax / kAssignThreads;
+constexpr int kOvCols = ICPFLOW_OVERLAP_COLS, kSegCols = ICPFLOW_TRACK_SEGMENT_COLS, kObsCols = ICPFLOW_TRACK_OBS_COLS;
+constexpr int kTrackCols = ICPFLOW_TRACK_COLS, kObjectCols = ICPFLOW_OBJECT_COLS;
+constexpr int kFitCounts = ICPFLOW_TRACK_FIT_COUNTS;
+static_assert(ICPFLOW_TRACK_EXTEND_COUNTS == 6, "segments, inherited, fresh, observations with and without an id, overflow");
+constexpr int kMaxId = 1 << 24;                        // ids travel as float32 labels: exact up to here
+constexpr int kMaxFitRows = 1 << 24;
+
+// what an extension carves out of its workspace, in this order (the size query runs it on a null base)
+struct Carve {
+    icpflow::overlap::Carve ov;
+    float *trackLabel;       // [n]
+    double *table[2];        // [Lmax][kOvCols] each: the overlap's tables, A = this gap's labels, B = the tracks
+    int32_t *num;            // [2]
+    int64_t *ovCounts;       // [4]
+    int32_t *segId;          // [Lmax] the id of every segment of A, -1 when it is not linkable
+    int32_t *state;          // [2] 1 iff the extension went through; the segments of A
+    size_t total;
+};
+
+bool carve(void *base, int n, int Lmax, Carve *c)
+{
+    icpflow::Carver ws(base);
+    if (!icpflow::overlap::carve(ws, n, Lmax, &c->ov)) return false;
+    c->trackLabel = ws.take<float>((size_t)n * sizeof(float));
+    for (int k = 0; k < 2; ++k) c->table[k] = ws.take<double>((size_t)Lmax * kOvCols * sizeof(double));
+    c->num = ws.take<int32_t>(2 * sizeof(int32_t));
+    c->ovCounts = ws.take<int64_t>(ICPFLOW_OVERLAP_COUNTS * sizeof(int64_t));
+    c->segId = ws.take<int32_t>((size_t)Lmax * sizeof(int32_t));
+    c->state = ws.take<int32_t>(2 * sizeof(int32_t));
+    c->total = ws.total();
+    return true;
+}
+
+__global__ __launch_bounds__(kThreads) void trk_labels_kernel(const int32_t *__restrict__ trackOfRow, int n, float *__restrict__ label)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int t = trackOfRow[i];
+    label[i] = t < 0 ? -1.0f : (float)t;               // (an id beyond 2^24 never enters the state: overflow below)
+}
+
+__global__ __launch_bounds__(kAssignThreads) void trk_assign_kernel(const int32_t *__restrict__ num, const double *__restrict__ tableA, int Lmax,
+                                                                    double minIou, int32_t *__restrict__ nextId, int32_t *__restrict__ segId,
+                                                                    int32_t *__restrict__ state, double *__restrict__ segments,
+                                                                    int32_t *__restrict__ dNum, unsigned long long *__restrict__ counts)
+{
+    __shared__ int part[3][kAssignThreads / kWave];
+    const int La = num[0], Lb = num[1], tid = threadIdx.x, wave = tid >> 6, lane = tid & (kWave - 1);
+    const bool tooMany = La < 0 || Lb < 0;
+    const int L = tooMany ? 0 : min(La, Lmax);
+    const int next = *nextId;
+    bool link[kAssignEach], inherit[kAssignEach];
+    int fresh = 0, linked = 0, kept = 0;
+#pragma unroll
+    for (int e = 0; e < kAssignEach; ++e) {
+        const int c = tid * kAssignEach + e;
+        link[e] = inherit[e] = false;
+        if (c < L) {
+            const double *row = tableA + (size_t)c * kOvCols;
+            link[e] = icpflow::overlap::linkable(row[0]);
+            inherit[e] = link[e] && row[3] >= 0.0 && row[8] != 0.0 && row[9] >= minIou;
+        }
+        linked += link[e] ? 1 : 0, kept += inherit[e] ? 1 : 0, fresh += (link[e] && !inherit[e]) ? 1 : 0;
+    }
+    int incl = fresh;                                  // the fresh segments before this thread's, in ascending label order
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const int up = __shfl_up(incl, o, kWave);
+        if (lane >= o) incl += up;
+    }
+    const int linkedW = icpflow::wave_sum(linked), keptW = icpflow::wave_sum(kept);
+    if (lane == kWave - 1) part[0][wave] = incl;
+    if (lane == 0) part[1][wave] = linkedW, part[2][wave] = keptW;
+    __syncthreads();
+    int before = incl - fresh, allFresh = 0, allLinked = 0, allKept = 0;
+    for (int w = 0; w < kAssignThreads / kWave; ++w) {
+        if (w < wave) before += part[0][w];
+        allFresh += part[0][w], allLinked += part[1][w], allKept += part[2][w];
+    }
+    const bool overflow = tooMany || next < 0 || next > kMaxId - allFresh;
+    if (tid == 0) {
+        state[0] = overflow ? 0 : 1, state[1] = L;
+        *dNum = La < 0 ? La : Lb < 0 ? Lb : overflow ? -max(La, 1) : La;
+        counts[0] = overflow ? 0ull : (unsigned long long)allLinked;
+        counts[1] = overflow ? 0ull : (unsigned long long)allKept;
+        counts[2] = overflow ? 0ull : (unsigned long long)allFresh;
+        counts[3] = 0ull, counts[4] = 0ull, counts[5] = overflow ? 1ull : 0ull;
+    }
+    if (overflow) return;                              // (workgroup-uniform) the state keeps every bit
+#pragma unroll
+    for (int e = 0; e < kAssignEach; ++e) {
+        const int c = tid * kAssignEach + e;
+        if (c >= L) continue;
+        const double *row = tableA + (size_t)c * kOvCols;
+        const int id = !link[e] ? -1 : inherit[e] ? (int)row[4] : next + before;
+        if (link[e] && !inherit[e]) ++before;
+        segId[c] = id;
+        double *out = segments + (size_t)c * kSegCols;
+        out[0] = row[0], out[1] = row[1], out[2] = (double)id, out[3] = inherit[e] ? 1.0 : 0.0, out[4] = row[5], out[5] = row[9];
+    }
+    if (tid == 0) *nextId = next + allFresh;           // (read into `next` by every thread before the barrier above)
+}
+
+__global__ __launch_bounds__(kThreads) void trk_relabel_kernel(const int32_t *__restrict__ state, const int32_t *__restrict__ segOf,
+                                                               const int32_t *__restrict__ segId, int n, int32_t *__restrict__ trackOfRow)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n || state[0] == 0) return;
+    const int s = segOf[i];
+    if (s >= 0 && s < state[1]) {
+        const int id = segId[s];
+        if (id >= 0) trackOfRow[i] = id;
+    }
+}
+
+// the segment of a label in the overlap's table of side A (column 0, ascending by label_key), or -1
+__device__ __forceinline__ int find_segment(const double *__restrict__ table, int L, float label)
+{
+    const uint32_t want = icpflow::label_key(icpflow::boxes::quieted(label));
+    int lo = 0, hi = L;                                // the first segment whose key is not below `want`
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (icpflow::label_key(icpflow::boxes::quieted((float)table[(size_t)mid * kOvCols])) < want) lo = mid + 1; else hi = mid;
+    }
+    return lo < L && icpflow::label_key(icpflow::boxes::quieted((float)table[(size_t)lo * kOvCols])) == want ? lo : -1;
+}
+
+__global__ __launch_bounds__(kThreads) void trk_obs_kernel(const int32_t *__restrict__ state, const double *__restrict__ tableA,
+                                                           const int32_t *__restrict__ segId, const double *__restrict__ objects, int P,
+                                                           double gap, double seconds, double *__restrict__ obs,
+                                                           unsigned long long *__restrict__ counts)
+{
+    __shared__ int sh[kWaves][2];
+    const int p = blockIdx.x * kThreads + (int)threadIdx.x;
+    const bool live = p < P;
+    bool with = false;
+    if (live) {
+        const double *o = objects + (size_t)p * kObjectCols;
+        int id = -1;
+        if (state[0] != 0 && o[22] > 0.0) {
+            const int c = find_segment(tableA, state[1], (float)o[1]);
+            if (c >= 0) id = segId[c];
+        }
+        with = id >= 0;
+        const double len = o[16], wid = o[17];
+        double *row = obs + (size_t)p * kObsCols;
+        row[0] = (double)id, row[1] = gap, row[2] = seconds;
+        row[3] = o[7], row[4] = o[8], row[5] = o[9];
+        row[6] = len >= wid ? len : wid, row[7] = len >= wid ? wid : len, row[8] = o[18];
+        row[9] = o[22], row[10] = o[4], row[11] = o[5], row[12] = o[6];
+    }
+    const bool flag[2] = {with, live && !with};
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {                      // (every lane takes every round: the ballots see whole waves)
+        const int t = __popcll(__ballot(flag[k]));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh[wave][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        int t = 0;
+        for (int w = 0; w < kWaves; ++w) t += sh[w][threadIdx.x];
+        if (t != 0) atomicAdd(&counts[3 + threadIdx.x], (unsigned long long)t);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void trk_fit_kernel(const double *__restrict__ obs, int M, int T, double maxResidual, double minSpeed,
+                                                           double *__restrict__ tracks, unsigned long long *__restrict__ counts)
+{
+    __shared__ int sh[kWaves][kFitCounts];
+    const int t = blockIdx.x * kThreads + (int)threadIdx.x;
+    const bool live = t < T;
+    bool observed = false, judged = false, consistent = false, moving = false;
+    if (live) {
+        const double id = (double)t;
+        int seen = 0;
+        unsigned long long mask = 0ull;
+        double num[3] = {0.0, 0.0, 0.0}, den = 0.0, longest = 0.0, shortest = 0.0, height = 0.0, points = 0.0;
+        for (int k = 0; k < M; ++k) {
+            const double *o = obs + (size_t)k * kObsCols;
+            if (o[0] != id) continue;
+            const double s = o[2];
+            num[0] += s * o[3], num[1] += s * o[4], num[2] += s * o[5];
+            den += s * s;
+            ++seen;
+            if (o[1] >= 0.0 && o[1] < 64.0) mask |= 1ull << (int)o[1];
+            longest = o[6] > longest ? o[6] : longest, shortest = o[7] > shortest ? o[7] : shortest;
+            height = o[8] > height ? o[8] : height, points = o[9] > points ? o[9] : points;
+        }
+        double v[3] = {0.0, 0.0, 0.0}, worst = 0.0, sum = 0.0;
+        if (seen > 0) {
+            v[0] = num[0] / den, v[1] = num[1] / den, v[2] = num[2] / den;
+            for (int k = 0; k < M; ++k) {
+                const double *o = obs + (size_t)k * kObsCols;
+                if (o[0] != id) continue;
+                const double rx = o[3] - o[2] * v[0], ry = o[4] - o[2] * v[1];
+                const double r2 = rx * rx + ry * ry;
+                worst = r2 > worst ? r2 : worst;
+                sum += r2;
+            }
+        }
+        const double speed = sqrt(v[0] * v[0] + v[1] * v[1]);
+        const double largest = sqrt(worst), rms = seen > 0 ? sqrt(sum / (double)seen) : 0.0;
+        observed = seen > 0;
+        moving = observed && speed >= minSpeed;
+        judged = __popcll(mask) >= 2;
+        consistent = judged && largest <= maxResidual;
+        double *row = tracks + (size_t)t * kTrackCols;
+        row[0] = id, row[1] = (double)seen, row[2] = (double)mask;
+        row[3] = v[0], row[4] = v[1], row[5] = v[2], row[6] = speed, row[7] = largest, row[8] = rms;
+        row[9] = moving ? 1.0 : 0.0, row[10] = judged ? 1.0 : 0.0, row[11] = consistent ? 1.0 : 0.0;
+        row[12] = longest, row[13] = shortest, row[14] = height, row[15] = points;
+    }
+    const bool flag[kFitCounts] = {live, observed, judged, consistent, moving};
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kFitCounts; ++k) {             // (every lane takes every round: the ballots see whole waves)
+        const int c = __popcll(__ballot(flag[k]));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh[wave][k] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x < kFitCounts) {
+        int c = 0;
+        for (int w = 0; w < kWaves; ++w) c += sh[w][threadIdx.x];
+        if (c != 0) atomicAdd(&counts[threadIdx.x], (unsigned long long)c);
+    }
+}
+
+bool sizes_ok(int n, int Lmax) { return n >= 0 && n <= kMaxRows && Lmax >= 1 && Lmax <= kLmax; }
+
+// -> 0, or the status of a refused parameter block
+int check_params(const char *fn, const icpflow_track_params_t *p)
+{
+    if (p->struct_size != sizeof(icpflow_track_params_t))
+        return report_errorf(ICPFLOW_E_ARG, "%s: params->struct_size = %zu, this library's icpflow_track_params_t has %zu bytes", fn, p->struct_size,
+                             sizeof(icpflow_track_params_t));
+    if (!(p->min_iou > 0.0 && p->min_iou <= 1.0)) return report_errorf(ICPFLOW_E_ARG, "%s: min_iou = %g: min_iou must lie in (0, 1]", fn, p->min_iou);
+    if (!(p->max_residual >= 0.0) || !std::isfinite(p->max_residual))
+        return report_errorf(ICPFLOW_E_ARG, "%s: max_residual = %g: max_residual must be finite and not negative", fn, p->max_residual);
+    if (!(p->min_speed >= 0.0) || !std::isfinite(p->min_speed))
+        return report_errorf(ICPFLOW_E_ARG, "%s: min_speed = %g: min_speed must be finite and not negative", fn, p->min_speed);
+    return ICPFLOW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int icpflow_object_tracks_default_params(icpflow_track_params_t *params)
+{
+    if (!params) return pointer_error("icpflow_object_tracks_default_params");
+    params->struct_size = sizeof(icpflow_track_params_t);
+    params->min_iou = 0.5, params->max_residual = 0.2, params->min_speed = 0.5;
+    return ICPFLOW_OK;
+}
+
+size_t icpflow_object_tracks_extend_workspace_bytes(int n, int Lmax)
+{
+    if (!sizes_ok(n, Lmax)) return 0;
+    Carve c{};
+    return carve(nullptr, n, Lmax, &c) ? c.total : 0;
+}
+
+int icpflow_object_tracks_extend(const float *d_labels, int n, int Lmax, int32_t *d_track_of_row, int32_t *d_next_id, const double *d_objects,
+                                 int P, int gap, double seconds, const icpflow_track_params_t *params, double *d_segments, int32_t *d_num,
+                                 double *d_obs, int64_t *d_counts, void *d_ws, size_t ws_bytes, icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_object_tracks_extend";
+    if (n < 0 || P < 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: n = %d, P = %d: a negative size", n, P);
+    if (n > kMaxRows) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_extend: n = %d: at most %d rows", n, kMaxRows);
+    if (Lmax < 1) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: Lmax = %d: Lmax must be at least 1", Lmax);
+    if (Lmax > kLmax) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_extend: Lmax = %d: at most %d segments", Lmax, kLmax);
+    if (gap < 0 || gap > 63) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: gap = %d: gap must lie in [0, 63]", gap);
+    if (!(seconds > 0.0) || !std::isfinite(seconds))
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: seconds = %g: seconds must be positive and finite", seconds);
+    if (!d_next_id || !params || !d_segments || !d_num || !d_counts || (n > 0 && (!d_labels || !d_track_of_row)) || (P > 0 && (!d_objects || !d_obs)))
+        return pointer_error(fn);
+    if (const int rc = check_params(fn, params)) return rc;
+    Carve c{};
+    if (!carve(d_ws, n, Lmax, &c)) return report_error(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: no workspace layout for these sizes");
+    if (!d_ws || ws_bytes < c.total) return workspace_error(fn, "icpflow_object_tracks_extend_workspace_bytes", d_ws, ws_bytes, c.total);
+    if (((uintptr_t)d_ws & 15) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: d_ws must be 16-byte aligned");
+
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        ICPFLOW_TRY(hipMemsetAsync(c.num, 0, 2 * sizeof(int32_t), st));
+    } else {
+        trk_labels_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_track_of_row, n, c.trackLabel);
+        ICPFLOW_TRY(hipGetLastError());
+        ICPFLOW_TRY(icpflow::overlap::launch_links(d_labels, c.trackLabel, n, Lmax, c.num, c.num + 1, c.ov, st));
+        ICPFLOW_TRY(icpflow::overlap::launch_tables(c.ov, c.num, c.num + 1, Lmax, c.table[0], c.table[1], c.ovCounts, st));
+    }
+    trk_assign_kernel<<<1, kAssignThreads, 0, st>>>(c.num, c.table[0], Lmax, params->min_iou, d_next_id, c.segId, c.state, d_segments, d_num,
+                                                    (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    if (n > 0) {
+        trk_relabel_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(c.state, c.ov.side[0].segOf, c.segId, n, d_track_of_row);
+        ICPFLOW_TRY(hipGetLastError());
+    }
+    if (P > 0) {
+        trk_obs_kernel<<<(P + kThreads - 1) / kThreads, kThreads, 0, st>>>(c.state, c.table[0], c.segId, d_objects, P, (double)gap, seconds, d_obs,
+                                                                           (unsigned long long *)d_counts);
+        ICPFLOW_TRY(hipGetLastError());
+    }
+    return ICPFLOW_OK;
+}
+
+int icpflow_object_tracks_fit(const double *d_obs, int M, int T, const icpflow_track_params_t *params, double *d_tracks, int64_t *d_counts,
+                              icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_object_tracks_fit";
+    if (M < 0 || T < 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_fit: M = %d, T = %d: a negative size", M, T);
+    if (M > kMaxFitRows || T > kMaxFitRows)
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_fit: M = %d, T = %d: at most %d observations and tracks", M, T, kMaxFitRows);
+    if (!params || !d_counts || (M > 0 && !d_obs) || (T > 0 && !d_tracks)) return pointer_error(fn);
+    if (const int rc = check_params(fn, params)) return rc;
+
+    hipStream_t st = (hipStream_t)stream;
+    ICPFLOW_TRY(hipMemsetAsync(d_counts, 0, kFitCounts * sizeof(int64_t), st));
+    if (T == 0) return ICPFLOW_OK;
+    trk_fit_kernel<<<(T + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_obs, M, T, params->max_residual, params->min_speed, d_tracks,
+                                                                       (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    return ICPFLOW_OK;
+}
+
+}  // extern "C"

@@ -86,7 +86,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import utils_eval, utils_flow, utils_objects, utils_track
+from . import utils_eval, utils_flow, utils_objects, utils_track, utils_tracks
 
 # demo.sh:9-13 / main.sh flags of the registration stage
 DEFAULT_ARGS = dict(max_points=10000, min_cluster_size=20, translation_frame=2.0, thres_dist=0.1, thres_box=0.1,
@@ -108,7 +108,7 @@ def default_args(**over):
 
 class FramePair:
     def __init__(self, points_src, points_dst, labels_src=None, labels_dst=None, pose=None, gt_flow=None, mask=None,
-                 name="", nonground_src=None, nonground_dst=None, gap=1, points_src_raw=None, pose_source="given"):
+                 name="", nonground_src=None, nonground_dst=None, gap=1, points_src_raw=None, pose_source="given", sequence=None):
         self.points_src = np.ascontiguousarray(points_src, dtype=np.float32)[:, 0:3]
         self.points_dst = np.ascontiguousarray(points_dst, dtype=np.float32)[:, 0:3]
         if (labels_src is None) != (labels_dst is None):
@@ -137,6 +137,9 @@ class FramePair:
         # multi-gap samples (Waymo / nuScenes): frame `gap` against frame 0; the flow is reported on the source
         # points BEFORE ego-motion compensation (main.py:230-234), registration runs on the compensated ones
         self.gap = int(gap)
+        # the sample this frame pair is one gap of (load_sequence: the file's path), or None: the frame pairs of one sample share
+        # points_dst row for row, which is what run_stream's object tracks link (utils_tracks)
+        self.sequence = sequence
         self.points_src_raw = None if points_src_raw is None else np.ascontiguousarray(points_src_raw, dtype=np.float32)[:, 0:3]
         if self.points_src_raw is not None and self.points_src_raw.shape != self.points_src.shape:
             raise ValueError(f"frame pair {name!r}: points_src_raw must match points_src")
@@ -291,7 +294,7 @@ def load_sequence(path, args=None, pose_source=None):
                              name=f"{os.path.basename(path)}#gap{j}",
                              nonground_src=None if nonground is None else nonground[m],
                              nonground_dst=None if nonground is None else nonground[t == 0],
-                             gap=j, points_src_raw=src_raw, pose_source=used))
+                             gap=j, points_src_raw=src_raw, pose_source=used, sequence=path))
     return out
 
 
@@ -407,7 +410,7 @@ def register_frame_pair_steps(args, fp, device, gap=None, asynchronous=False):
         flow = utils_flow.flow_estimation_torch(a, flow_src, pd, ls, ld, pairs, T, pose)
     out = dict(pairs=pairs, transformations=T, flow=flow, translation_frame=a.translation_frame, association=a.association_path or "host")
     # what the per-segment report (run_sequences), the residual and the objects (run_stream) and the trust bytes (run_sequences) read besides the flow
-    if getattr(args, "if_verbose", False) or getattr(args, "residual", None) or getattr(args, "save_trust", None) or getattr(args, "objects", None):
+    if getattr(args, "if_verbose", False) or getattr(args, "residual", None) or getattr(args, "save_trust", None) or getattr(args, "objects", None) or getattr(args, "tracks", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -669,7 +672,7 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
     if flow is not None:
         out["flow"] = flow
     # what the per-segment report (run_sequences), the residual and the objects (run_stream) and the trust bytes (run_sequences) read besides the flow
-    if getattr(a, "if_verbose", False) or getattr(a, "residual", None) or getattr(a, "save_trust", None) or getattr(a, "objects", None):
+    if getattr(a, "if_verbose", False) or getattr(a, "residual", None) or getattr(a, "save_trust", None) or getattr(a, "objects", None) or getattr(a, "tracks", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -1318,6 +1321,13 @@ def frame_objects(fp, out, device, seconds=None, min_speed=utils_objects.MIN_SPE
     register it to), then a box, a displacement, a velocity and a heading per pair from `out`'s pair rows and transforms.
     seconds: the time between the two sweeps (None: fp.gap sweeps of utils_objects.SWEEP_SECONDS).  -> utils_objects.Objects;
     one read-back, the pairs' table with its four counts."""
+    seconds = float(fp.gap) * utils_objects.SWEEP_SECONDS if seconds is None else float(seconds)
+    rows, counts, _ = _frame_objects_device(fp, out, device, seconds, min_speed, delta, A)
+    return utils_objects.Objects.read(rows, counts, seconds, min_speed)     # the one read-back
+
+
+def _frame_objects_device(fp, out, device, seconds, min_speed, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS):
+    """frame_objects' three calls, nothing read back -> (rows float64 [P, 24], counts int64 [4], the destination's labels)"""
     device = torch.device(device)
     ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
     ls = _source_labels(fp, out, device)
@@ -1326,12 +1336,32 @@ def frame_objects(fp, out, device, seconds=None, min_speed=utils_objects.MIN_SPE
         ld = _input(fp, "labels_dst", device)
     if ld is None:
         raise ValueError("the objects need the destination's cluster labels: the registration must leave labels_dst in its result")
-    seconds = float(fp.gap) * utils_objects.SWEEP_SECONDS if seconds is None else float(seconds)
+    ld = ld.to(device).float()
     boxes_src, num_src = utils_objects.segment_boxes_device(ps, ls, delta, A)
-    boxes_dst, num_dst = utils_objects.segment_boxes_device(pd, ld.to(device).float(), delta, A)
+    boxes_dst, num_dst = utils_objects.segment_boxes_device(pd, ld, delta, A)
     rows, counts = utils_objects.pair_objects_device(boxes_src, num_src, out["pairs"].to(device), out["transformations"].to(device),
                                                      boxes_dst, num_dst, seconds, min_speed)
-    return utils_objects.Objects.read(rows, counts, seconds, min_speed)     # the one read-back
+    return rows, counts, ld
+
+
+def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, min_speed=utils_tracks.MIN_SPEED, min_iou=utils_tracks.MIN_IOU,
+                 max_residual=utils_tracks.MAX_RESIDUAL, Lmax=4096):
+    """The object tracks of ONE sample (utils_tracks), everything on the device: `fps` the sample's frame pairs in gap order --
+    they share the destination sweep, row for row -- and `outs` their registrations.  Per gap the object rows of frame_objects
+    (not read back), then the shared sweep's clusters linked to the tracks so far (icpflow_object_tracks_extend); at the end one
+    fit over all gaps and ONE read-back.  A gap of `gap` sweeps spans gap * sweep_seconds.  -> utils_tracks.Tracks"""
+    device = torch.device(device)
+    n = len(fps[0].points_dst)
+    if any(len(fp.points_dst) != n for fp in fps):
+        raise ValueError(f"object tracks: the frame pairs of {fps[0].sequence or fps[0].name!r} disagree on the rows of the shared sweep "
+                         f"({sorted({len(fp.points_dst) for fp in fps})}): they are not the gaps of one sample")
+    state = utils_tracks.TrackState(n, device, Lmax, min_iou, max_residual, min_speed)
+    for fp, out in zip(fps, outs):
+        seconds = float(fp.gap) * float(sweep_seconds)
+        rows, _, ld = _frame_objects_device(fp, out, device, seconds, min_speed)
+        state.extend(ld, rows, fp.gap, seconds)
+    state.fit()
+    return state.read()
 
 
 RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
@@ -1383,6 +1413,39 @@ def residual_tables(block):
             dict(forward=table("after_forward", G), backward=table("after_backward", 1)))
 
 
+def _by_sample(items, args, sample_of, samples):
+    """run_stream's frame pairs, in their order, with the samples they are gaps of written down as they go by: sample_of[number
+    of the frame pair] = its sample, samples[sample] = dict(sample, size, outs).  The frame pairs of one sequence file are one
+    sample (load_sequence tags them with the file's path), and so are consecutive FramePair objects that carry the same tag; a
+    frame-pair file or an untagged FramePair is a sample of its own.  Frame pairs of one sample that disagree on the rows of the
+    shared sweep are a ValueError before any of them is registered."""
+    number, k, begun = 0, 0, 0
+    while k < len(items):
+        item = items[k]
+        if isinstance(item, FramePair):
+            j = k + 1
+            while item.sequence is not None and j < len(items) and isinstance(items[j], FramePair) and items[j].sequence == item.sequence:
+                j += 1
+            groups, k = [list(items[k:j])], j
+        else:
+            fps, k = load_any(item, args), k + 1
+            tagged = bool(fps) and fps[0].sequence is not None and all(fp.sequence == fps[0].sequence for fp in fps)
+            groups = [fps] if tagged else [[fp] for fp in fps]
+        for fps in groups:
+            if not fps:
+                continue
+            rows = sorted({len(fp.points_dst) for fp in fps})
+            if len(rows) > 1:
+                raise ValueError(f"object tracks: the frame pairs of {fps[0].sequence!r} disagree on the rows of the shared sweep ({rows}): "
+                                 "they are not the gaps of one sample")
+            s, begun = begun, begun + 1                       # (samples are numbered in the order they begin)
+            samples[s] = dict(sample=s, size=len(fps), outs={})
+            for fp in fps:
+                sample_of[number] = s
+                number += 1
+                yield fp
+
+
 def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, register_fn=None, in_flight=1):
     """Register this rank's share of `paths`; -> summary dict (identical on every rank).
     ms / frame pair is the mean wall time per pair, host -> device upload of the clouds included
@@ -1423,7 +1486,17 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     (objects, movers, the pairs without a segment or a box, largest_centre_gap in metres, the parameters) and
     `ms_objects_per_frame_pair` (device-synchronised around the three calls and their one read-back); with a file name, one JSON
     line per frame pair is written there (counts, and per object its labels, centre, size, yaw, velocity, speed, moving,
-    centre_gap, point counts) and the summary names it as `objects_file`."""
+    centre_gap, point counts) and the summary names it as `objects_file`.
+    args.tracks = True or a file name (`--tracks [FILE]`; one process only; independent of args.objects): the objects of a
+    multi-frame sample linked across its gaps -- `frame_tracks` over the frame pairs of one sequence file (they share the
+    destination sweep; a frame-pair file is a sample of its own), once the sample's LAST gap has been accounted and in gap order,
+    so the tracks do not depend on the order in which frame pairs complete.  It uses args.sweep_seconds and
+    args.objects_min_speed and adds args.tracks_min_iou (default 0.5) and args.tracks_max_residual (default 0.2 m).  The summary
+    gains `tracks` (samples, tracks, observed, judged, consistent, inconsistent, moving, overflow, the parameters) and
+    `ms_tracks_per_sample` (device-synchronised around the chain and its one read-back); with a file name, one JSON line per
+    sample is written there (counts, per observed track its velocity, residuals, verdicts and size, and per gap the track of
+    every object row) and the summary names it as `tracks_file`.  With args.objects and a file too, every object entry gains
+    `track`."""
     import torch.distributed as dist
     device = torch.device(device)
     pipelined = int(in_flight) > 1 and register_fn is None
@@ -1462,9 +1535,37 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     sweep_seconds = float(getattr(args, "sweep_seconds", utils_objects.SWEEP_SECONDS))
     objects_min_speed = float(getattr(args, "objects_min_speed", utils_objects.MIN_SPEED))
     object_lines, objects_ms, object_counts, object_gap = {}, [], np.zeros(5, np.int64), None    # frame pair -> its line of the file
+    tracks_on = getattr(args, "tracks", None)
+    if tracks_on and world > 1:
+        raise ValueError("args.tracks under more than one rank: a sample's gaps would have to meet on one rank, which is not built")
+    tracks_min_iou = float(getattr(args, "tracks_min_iou", utils_tracks.MIN_IOU))
+    tracks_max_residual = float(getattr(args, "tracks_max_residual", utils_tracks.MAX_RESIDUAL))
+    sample_of, samples, track_lines, tracks_ms = {}, {}, {}, []     # frame pair -> its sample; sample -> its frame pairs; -> its line
+    track_totals = dict(tracks=0, observed=0, judged=0, consistent=0, inconsistent=0, moving=0, overflow=0)
+    accounted = 0
+
+    def close_sample(s):
+        """the chain of sample s, once every gap of it has been accounted: in gap order, whatever order they completed in"""
+        sample = samples.pop(s)
+        ks = sorted(sample["outs"])
+        fps = [sample["outs"][k][0] for k in ks]
+        sync()
+        t0 = time.perf_counter()
+        seen = frame_tracks(fps, [sample["outs"][k][1] for k in ks], device, sweep_seconds, objects_min_speed, tracks_min_iou, tracks_max_residual)
+        sync()
+        tracks_ms.append((time.perf_counter() - t0) * 1e3)
+        summary = seen.summary()
+        for name in track_totals:
+            track_totals[name] += summary[name]
+        track_lines[s] = dict(sample=s, path=fps[0].sequence or fps[0].name, frame_pairs=ks, gaps=[fp.gap for fp in fps], counts=summary,
+                              tracks=seen.as_list(), observations=[ids.tolist() for ids in seen.observation_ids])
+        for k, ids in zip(ks, seen.observation_ids):
+            for e in object_lines.get(k, {}).get("objects", []):
+                e["track"] = int(ids[e["pair"]])
 
     def account(fp, out, index=None):
-        nonlocal matched, segments_judged, object_counts, object_gap
+        nonlocal matched, segments_judged, object_counts, object_gap, accounted
+        number, accounted = (accounted if index is None else index), accounted + 1
         if radius:
             sync()
             t0 = time.perf_counter()
@@ -1516,6 +1617,11 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             if gap_ is not None and (object_gap is None or gap_ > object_gap):
                 object_gap = gap_
             object_lines[k] = dict(frame_pair=k, path=fp.name, seconds=seen_objects.seconds, counts=s, objects=seen_objects.as_list())
+        if tracks_on:
+            sample = samples[sample_of.pop(number)]
+            sample["outs"][number] = (fp, out)
+            if len(sample["outs"]) == sample["size"]:
+                close_sample(sample["sample"])
         pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
         matched += int(out["pairs"].shape[0])
         if fp.gt_flow is not None:
@@ -1524,6 +1630,8 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             meter.update(*m, n)
 
     every = (fp for path in mine for fp in ([path] if isinstance(path, FramePair) else load_any(path, args)))   # a sequence file yields one pair per gap
+    if tracks_on:
+        every = _by_sample(mine, args, sample_of, samples)
     if pipelined:
         sync()
         t0 = time.perf_counter()
@@ -1606,6 +1714,15 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
                 for k in sorted(object_lines):       # one JSON line per frame pair, in their order
                     f.write(json.dumps(object_lines[k]) + "\n")
             out["objects_file"] = objects_on
+    if tracks_on:
+        out["tracks"] = dict(track_totals, samples=len(track_lines), min_iou=tracks_min_iou, max_residual=tracks_max_residual,
+                             min_speed=objects_min_speed, sweep_seconds=sweep_seconds)
+        out["ms_tracks_per_sample"] = sum(tracks_ms) / max(len(tracks_ms), 1)
+        if isinstance(tracks_on, str):
+            with open(tracks_on, "w") as f:
+                for s in sorted(track_lines):        # one JSON line per sample, in their order
+                    f.write(json.dumps(track_lines[s]) + "\n")
+            out["tracks_file"] = tracks_on
     return out
 
 
@@ -1689,6 +1806,15 @@ def argument_parser():
                     help="with --objects: the time between two sweeps; a frame pair `gap` sweeps apart spans gap * S seconds")
     ap.add_argument("--objects-min-speed", type=float, default=utils_objects.MIN_SPEED, metavar="V",
                     help="with --objects: an object moves when its xy speed reaches V m/s")
+    ap.add_argument("--tracks", nargs="?", const=True, default=None, metavar="FILE",
+                    help="object tracks: the objects of a multi-frame sample linked across its gaps (they share the sweep of frame 0), "
+                         "per track a velocity fitted over all gaps, the residuals from it, a size over all views and whether the "
+                         "gaps agree on one constant velocity (FILE: one JSON line per sample); uses --sweep-seconds and "
+                         "--objects-min-speed; one process only; not with --protocol reference")
+    ap.add_argument("--tracks-min-iou", type=float, default=utils_tracks.MIN_IOU, metavar="I",
+                    help="with --tracks: a cluster inherits a track when the two are each other's largest overlap at IoU >= I")
+    ap.add_argument("--tracks-max-residual", type=float, default=utils_tracks.MAX_RESIDUAL, metavar="M",
+                    help="with --tracks: a track is consistent when no gap's displacement lies more than M metres off the fitted velocity")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
                     help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
     return ap
@@ -1714,6 +1840,11 @@ def main(argv=None):
         raise SystemExit("--objects is not built into --protocol reference (COVERAGE.md row 17): run the frame pairs without --protocol")
     if ns.objects is not None and not (ns.sweep_seconds > 0 and ns.objects_min_speed >= 0):
         raise SystemExit("--sweep-seconds must be positive and --objects-min-speed must not be negative")
+    if ns.tracks is not None and ns.protocol == "reference":
+        raise SystemExit("--tracks is not built into --protocol reference (COVERAGE.md row 18): run the frame pairs without --protocol")
+    if ns.tracks is not None and not (ns.sweep_seconds > 0 and ns.objects_min_speed >= 0 and 0 < ns.tracks_min_iou <= 1 and ns.tracks_max_residual >= 0):
+        raise SystemExit("--sweep-seconds must be positive, --objects-min-speed and --tracks-max-residual must not be negative, "
+                         "--tracks-min-iou must lie in (0, 1]")
     if ns.save_trust is not None and not ns.save_flows:
         raise SystemExit("--save-trust goes with --save-flows (the bytes go into the saved flow's file)")
     if ns.save_trust is not None and len(ns.save_trust) not in (0, 3):
@@ -1800,6 +1931,11 @@ def main(argv=None):
         if world > 1:
             raise SystemExit("--objects under more than one rank: merging the files is not built")
         args.objects, args.sweep_seconds, args.objects_min_speed = ns.objects, ns.sweep_seconds, ns.objects_min_speed
+    if ns.tracks is not None:
+        if world > 1:
+            raise SystemExit("--tracks under more than one rank: a sample's gaps would have to meet on one rank, which is not built")
+        args.tracks, args.sweep_seconds, args.objects_min_speed = ns.tracks, ns.sweep_seconds, ns.objects_min_speed
+        args.tracks_min_iou, args.tracks_max_residual = ns.tracks_min_iou, ns.tracks_max_residual
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         if ns.residual is not None:

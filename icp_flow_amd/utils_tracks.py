@@ -1,0 +1,164 @@
+"""Object tracks: the clusters of a sample's shared destination sweep linked across its gaps, and one constant velocity per
+track (include/icpflow_hip.h, "8(k) object tracks"; csrc/overlap.hip, csrc/tracks.hip).  No counterpart in the reference.
+
+Every frame pair of a multi-frame sample ends at frame 0, and every gap clusters that sweep anew.  Two labellings of the same
+rows say which clusters are the same object (`label_overlap_device`); `TrackState.extend` carries one id per object from gap
+to gap and turns the gap's object rows (utils_objects) into observations; `TrackState.fit` fits d = s v per track over all
+gaps.  min_iou, max_residual and min_speed are stated policies, like KEEP of the trust byte.
+
+Everything stays on the device until `TrackState.read` reads it back, once.  There is no CPU path."""
+import ctypes
+
+import numpy as np
+
+MIN_IOU = 0.5
+MAX_RESIDUAL = 0.2            # metres
+MIN_SPEED = 0.5               # m/s (utils_objects.MIN_SPEED)
+MAX_ID = 1 << 24
+
+
+def label_overlap_device(labels_a, labels_b, Lmax=4096):
+    """icpflow_label_overlap enqueued on the current stream, nothing read back.  labels_a, labels_b [n]: two labellings of the
+    same rows, device tensors.  -> (table_a float64 [Lmax, 10], num_a int32 [1], table_b, num_b, counts int64 [4]) on the device;
+    rows of a table from its number on are not written, and neither table is when a number is negative."""
+    import torch
+    from . import _lib
+    _lib.require_gpu(labels_a, labels_b)
+    a, b = labels_a.to(torch.float32).contiguous(), labels_b.to(torch.float32).contiguous()
+    n, device, Lmax = int(a.shape[0]), a.device, int(Lmax)
+    if a.dim() != 1 or b.shape != a.shape or b.device != device:
+        raise ValueError(f"label_overlap: labels {tuple(a.shape)} on {a.device} and {tuple(b.shape)} on {b.device}, expected two of [n] on one device")
+    tables = [torch.empty((Lmax, _lib.OVERLAP_COLS), dtype=torch.float64, device=device) for _ in range(2)]
+    nums = [torch.empty(1, dtype=torch.int32, device=device) for _ in range(2)]
+    counts = torch.empty(_lib.OVERLAP_COUNTS, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        ws = _lib.workspace(device, int(_lib._L.icpflow_label_overlap_workspace_bytes(n, Lmax)))
+        _lib.call("icpflow_label_overlap", _lib.ptr(a), _lib.ptr(b), n, Lmax, _lib.ptr(tables[0]), _lib.ptr(nums[0]), _lib.ptr(tables[1]),
+                  _lib.ptr(nums[1]), _lib.ptr(counts), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    return tables[0], nums[0], tables[1], nums[1], counts
+
+
+class TrackState:
+    """The tracks of ONE shared sweep of n rows, on the device: a track id per row and the next free id, carried from gap to gap
+    by `extend`; `fit` and `read` close the sample."""
+
+    def __init__(self, n, device, Lmax=4096, min_iou=MIN_IOU, max_residual=MAX_RESIDUAL, min_speed=MIN_SPEED):
+        import torch
+        from . import _lib
+        self.n, self.device, self.Lmax = int(n), torch.device(device), int(Lmax)
+        if self.device.type != "cuda":
+            raise RuntimeError("icp_flow_amd: the tracks live on a GPU (HIP) device -- there is no CPU path")
+        self.params = _lib.TrackParams.defaults(min_iou=min_iou, max_residual=max_residual, min_speed=min_speed)
+        self.track_of_row = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+        self.next_id = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.obs, self.gaps, self.segments, self.counts = [], [], [], []
+        self.bound = 0                       # no track id reaches this: every gap founds at most min(n, Lmax) tracks
+        self.tracks = self.fit_counts = None
+
+    def extend(self, labels, objects_rows, gap, seconds):
+        """One gap: labels [n] of the shared sweep under this gap's clustering, objects_rows float64 [P, 24] (or None) the gap's
+        table of utils_objects.pair_objects_device.  Enqueued on the current stream.  -> (segments float64 [Lmax, 6], num int32
+        [1], obs float64 [P, 13], counts int64 [6]) on the device, kept for `read` as well."""
+        import torch
+        from . import _lib
+        _lib.require_gpu(labels, objects_rows)
+        lab = labels.to(torch.float32).contiguous()
+        if lab.shape != (self.n,) or lab.device != self.device:
+            raise ValueError(f"TrackState.extend: labels {tuple(lab.shape)} on {lab.device} for a sweep of {self.n} rows on {self.device}")
+        rows = None
+        P = 0 if objects_rows is None else int(objects_rows.shape[0])
+        if P > 0:
+            rows = objects_rows.contiguous()
+            if rows.dtype != torch.float64 or tuple(rows.shape) != (P, _lib.OBJECT_COLS) or rows.device != self.device:
+                raise ValueError(f"TrackState.extend: object rows {tuple(rows.shape)} {rows.dtype}, expected float64 [P, {_lib.OBJECT_COLS}]")
+        segments = torch.empty((self.Lmax, _lib.TRACK_SEGMENT_COLS), dtype=torch.float64, device=self.device)
+        num = torch.empty(1, dtype=torch.int32, device=self.device)
+        obs = torch.empty((P, _lib.TRACK_OBS_COLS), dtype=torch.float64, device=self.device)
+        counts = torch.empty(_lib.TRACK_EXTEND_COUNTS, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            ws = _lib.workspace(self.device, int(_lib._L.icpflow_object_tracks_extend_workspace_bytes(self.n, self.Lmax)))
+            _lib.call("icpflow_object_tracks_extend", _lib.ptr(lab) if self.n else None, self.n, self.Lmax,
+                      _lib.ptr(self.track_of_row) if self.n else None, _lib.ptr(self.next_id), _lib.ptr(rows), P, int(gap), float(seconds),
+                      ctypes.byref(self.params), _lib.ptr(segments), _lib.ptr(num), _lib.ptr(obs) if P else None, _lib.ptr(counts), _lib.ptr(ws),
+                      ctypes.c_size_t(ws.numel()), _lib.stream(self.device))
+        self.obs.append(obs), self.gaps.append(int(gap)), self.segments.append((segments, num)), self.counts.append(counts)
+        self.bound = min(self.bound + min(self.n, self.Lmax), MAX_ID)
+        self.tracks = None
+        return segments, num, obs, counts
+
+    def fit(self):
+        """icpflow_object_tracks_fit over the observations of every gap so far, enqueued on the current stream.  The number of
+        tracks is on the device; the call takes the bound the gaps imply (a track beyond *next_id has its id and zeros).
+        -> (tracks float64 [bound, 16], counts int64 [5]) on the device."""
+        import torch
+        from . import _lib
+        every = torch.cat(self.obs) if self.obs else torch.empty((0, _lib.TRACK_OBS_COLS), dtype=torch.float64, device=self.device)
+        M, T = int(every.shape[0]), self.bound
+        self.tracks = torch.empty((T, _lib.TRACK_COLS), dtype=torch.float64, device=self.device)
+        self.fit_counts = torch.empty(_lib.TRACK_FIT_COUNTS, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.call("icpflow_object_tracks_fit", _lib.ptr(every) if M else None, M, T, ctypes.byref(self.params), _lib.ptr(self.tracks) if T else None,
+                      _lib.ptr(self.fit_counts), _lib.stream(self.device))
+        return self.tracks, self.fit_counts
+
+    def read(self):
+        """-> Tracks: the fitted table, the counts of every call and the observations' ids in ONE transfer (ids and counts are
+        exact in a float64)"""
+        import torch
+        if self.tracks is None:
+            self.fit()
+        f64 = lambda t: t.to(torch.float64).reshape(-1)     # noqa: E731
+        parts = [f64(self.next_id), f64(self.fit_counts)] + [f64(c) for c in self.counts] + [o[:, 0].reshape(-1) for o in self.obs] + [self.tracks.reshape(-1)]
+        host = torch.cat(parts).cpu().numpy()
+        at = 0
+
+        def take(k):
+            nonlocal at
+            at += k
+            return host[at - k: at]
+
+        next_id = int(take(1)[0])
+        fit_counts = np.rint(take(5)).astype(np.int64)
+        extend_counts = [np.rint(take(6)).astype(np.int64) for _ in self.counts]
+        ids = [np.rint(take(int(o.shape[0]))).astype(np.int64) for o in self.obs]
+        rows = take(self.bound * 16).reshape(self.bound, 16)[:next_id]
+        return Tracks(rows, fit_counts, next_id, list(self.gaps), ids, extend_counts, self.params.as_dict())
+
+
+class Tracks:
+    """The tracks of one sample on the host (icpflow_object_tracks_fit's table, read back once)."""
+
+    def __init__(self, rows, fit_counts, next_id, gaps, observation_ids, extend_counts, params):
+        self.rows = np.asarray(rows, np.float64).reshape(-1, 16)
+        self.fit_counts = np.asarray(fit_counts, np.int64).reshape(5)
+        self.next_id, self.gaps, self.params = int(next_id), list(gaps), dict(params)
+        self.observation_ids = [np.asarray(i, np.int64) for i in observation_ids]      # per gap, one per object row (-1: none)
+        self.extend_counts = [np.asarray(c, np.int64).reshape(6) for c in extend_counts]
+
+    def summary(self):
+        _, observed, judged, consistent, moving = (int(v) for v in self.fit_counts)
+        return dict(tracks=self.next_id, observed=observed, judged=judged, consistent=consistent, inconsistent=judged - consistent, moving=moving,
+                    gaps=len(self.gaps), overflow=int(sum(int(c[5]) for c in self.extend_counts)))
+
+    def as_list(self):
+        """one dict per track with an observation, in the order of the ids"""
+        out = []
+        for r in self.rows:
+            if r[1] <= 0:
+                continue
+            mask = int(r[2])
+            out.append(dict(track=int(r[0]), observations=int(r[1]), gaps=[g for g in range(64) if mask >> g & 1], velocity=[float(v) for v in r[3:6]],
+                            speed=float(r[6]), residual_max=float(r[7]), residual_rms=float(r[8]), moving=bool(r[9]), judged=bool(r[10]),
+                            consistent=bool(r[11]), size=[float(v) for v in r[12:15]], points=int(r[15])))
+        return out
+
+
+def format_tracks(tracks):
+    """`Tracks.as_list()` as lines of text"""
+    lines = ["  track  views       vx       vy       vz    speed  residual  moving  judged  consistent   length    width   height  points"]
+    yes = lambda b: "yes" if b else "no"    # noqa: E731
+    for e in tracks:
+        lines.append(f"{e['track']:7d}{e['observations']:7d}{e['velocity'][0]:9.2f}{e['velocity'][1]:9.2f}{e['velocity'][2]:9.2f}{e['speed']:9.2f}"
+                     f"{e['residual_max']:10.3f}{yes(e['moving']):>8}{yes(e['judged']):>8}{yes(e['consistent']):>12}"
+                     f"{e['size'][0]:9.2f}{e['size'][1]:9.2f}{e['size'][2]:9.2f}{e['points']:8d}")
+    return lines

@@ -1356,6 +1356,109 @@ int icpflow_pair_objects(const double *d_boxes_src, const int32_t *d_num_src, co
                          const icpflow_object_params_t *params, double *d_objects, int64_t *d_counts, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(k)  object tracks: the clusters of ONE sweep under several labellings linked into tracks, and a constant velocity fitted
+ * per track over all the gaps of a multi-frame sample (every frame pair of a sample ends at frame 0: the destination sweep
+ * is shared, row for row, and every gap re-clusters it).  No counterpart in the reference; the linking rule, min_iou 0.5,
+ * max_residual 0.2 m and min_speed 0.5 m/s are stated policies (COVERAGE.md, named deviations).
+ *
+ * icpflow_label_overlap -- which segments of two labellings of the same n rows are the same set of rows:
+ *   d_labels_a, d_labels_b float32 [n]; d_table_a, d_table_b double [Lmax][ICPFLOW_OVERLAP_COLS]; d_num_a, d_num_b int32 [1];
+ *   d_counts int64 [ICPFLOW_OVERLAP_COUNTS].  Segments are the distinct labels in ascending order, as icpflow_cluster_table
+ *   reports them (+0.0 and -0.0 one label, reported as 0.0; NaNs kept apart by their bits, behind +inf or, with the sign bit, before -inf).  A label < 0 (ground
+ *   -1e8, noise -1, -inf) is NO SEGMENT TO LINK: its rows enter no intersection and its segment gets no partner; every other
+ *   label, a NaN too, is.  inter(c, e) = the rows in segment c of one side and segment e of the other, both linkable.
+ *   The PARTNER of c is the e with the largest inter(c, e) > 0, ties to the lower e (the ascending label order).
+ *   Row c < *d_num_a of d_table_a (d_table_b likewise, the roles exchanged):
+ *       0  label                      1  rows of the segment         2  of them, rows whose other label is linkable
+ *       3  partner e, or -1           4  its label (0 without one)   5  inter(c, partner)
+ *       6  the second-largest inter(c, .), the partner's left out (0 without one; equal to column 5 on a tie)
+ *       7  the partner's rows         8  mutual: 1 iff the partner's own partner is c
+ *       9  IoU = col 5 / (col 1 + col 7 - col 5): ONE fp64 division of exact integers; 0 without a partner
+ *   d_counts: [0] rows linkable on both sides, [1] mutual pairs (each has IoU > 0), [2] segments of A with a partner, [3] of B.
+ *   *d_num_a, *d_num_b: the segments of each side, or the negative count when a side holds more than Lmax labels (as
+ *   icpflow_cluster_table); if either is negative NEITHER table is written and d_counts is four zeros.  Rows from *d_num on are
+ *   not written.  n = 0 succeeds with both numbers 0 and four zeros.
+ *   Every number is an exact integer count or one fp64 division of such counts; integer atomics in LDS only, no
+ *   floating-point atomic: the output is a function of the arguments alone, whatever the stream and the scheduling.
+ *   Workspace, the caller's, 16-byte aligned: icpflow_label_overlap_workspace_bytes(n, Lmax), a multiple of 256, non-decreasing
+ *   in n and Lmax, 0 for arguments the call refuses; nothing in it is read before it is written.  Asynchronous on `stream`, no
+ *   host synchronisation, no allocation (csrc/overlap.hip: segments cut into chunks of 1024 rows, a workgroup per chunk, the
+ *   other side's segment indices counted in an LDS histogram of Lmax integers; a workgroup per segment folds its chunks).
+ *   Refusals, all before any launch: a null required pointer, n < 0, Lmax < 1, a workspace not 16-byte aligned are
+ *   ICPFLOW_E_ARG; n > 2^29 or Lmax > 4096 are ICPFLOW_E_LIMIT; a missing or short workspace is ICPFLOW_E_WORKSPACE.
+ *
+ * icpflow_object_tracks_extend -- one gap of a sample: the track ids of the shared sweep's rows carried on.
+ *   State, the caller's, on the device: d_track_of_row int32 [n] (-1 = no track; all -1 before the first gap) and d_next_id
+ *   int32 [1] (0 before the first gap).  d_labels float32 [n]: this gap's labels of the shared sweep.  They are overlapped
+ *   (icpflow_label_overlap's kernels) with the labelling "track id per row" -- an id is its own label, -1 is negative.
+ *   A linkable segment INHERITS the id of its partner iff mutual and IoU >= min_iou (so linking is one to one); every other
+ *   linkable segment is FRESH and takes *d_next_id + its rank among the fresh segments in ascending label order.  The rows of
+ *   every linkable segment are set to its id, the other rows keep theirs; *d_next_id advances by the fresh segments.
+ *   d_segments double [Lmax][ICPFLOW_TRACK_SEGMENT_COLS], row c < *d_num:
+ *       0  label    1  rows    2  track id (-1: not linkable)    3  inherited    4  inter with its partner    5  IoU
+ *   (columns 4 and 5 are the overlap's whether or not the link was taken; 0 without a partner).
+ *   d_objects double [P][ICPFLOW_OBJECT_COLS]: this gap's table of icpflow_pair_objects, or NULL with P = 0; d_obs double
+ *   [P][ICPFLOW_TRACK_OBS_COLS], row p:
+ *       0  the track id of the pair's destination label (column 1 of the object row; its segment found by binary search on the
+ *          key of the quieted label, as icpflow_pair_objects does), or -1 when the pair has no box (its column 22 is not
+ *          positive) or the label finds no linkable segment
+ *       1  gap    2  seconds    3-5  the displacement (columns 7-9)    6  max(length, width)    7  min(length, width)
+ *       8  height    9  source points (column 22)    10-12  the centre (columns 4-6)
+ *   d_counts int64 [ICPFLOW_TRACK_EXTEND_COUNTS]: segments (linkable), inherited, fresh, observations with an id, observations
+ *   without, overflow.  OVERFLOW: more than Lmax distinct labels, more than Lmax distinct values in d_track_of_row (the live
+ *   ids and -1), or an id beyond 2^24 (ids travel as float32 labels): overflow = 1, *d_num is negative, d_track_of_row and *d_next_id keep every bit, d_segments is
+ *   not written, every row of d_obs has id -1.
+ *   gap in [0, 63]; seconds positive and finite: the time this gap spans.  params: icpflow_track_params_t from
+ *   icpflow_object_tracks_default_params (min_iou 0.5 in (0, 1], max_residual 0.2 m, min_speed 0.5 m/s; for min_iou > 0.5
+ *   mutuality is implied).  Workspace: icpflow_object_tracks_extend_workspace_bytes(n, Lmax), as above.  Asynchronous on
+ *   `stream`; fresh ids come from a scan, never from the order in which workgroups finish.
+ *   Refusals, before any launch: a null required pointer (d_objects with P > 0, d_obs with P > 0), n < 0, P < 0, Lmax < 1, gap
+ *   outside [0, 63], seconds not positive and finite, a struct_size mismatch, min_iou outside (0, 1], a negative or
+ *   non-finite max_residual or min_speed, a misaligned workspace are ICPFLOW_E_ARG; n > 2^29 or Lmax > 4096 are
+ *   ICPFLOW_E_LIMIT; a short workspace is ICPFLOW_E_WORKSPACE.
+ *
+ * icpflow_object_tracks_fit -- one row per track from the observations of all gaps:
+ *   d_obs double [M][ICPFLOW_TRACK_OBS_COLS], the gaps concatenated in gap order; T: the tracks (ids 0 .. T - 1, T = *d_next_id
+ *   read by the caller or an upper bound); d_tracks double [T][ICPFLOW_TRACK_COLS]; d_counts int64 [ICPFLOW_TRACK_FIT_COUNTS].
+ *   One thread per track walks the M rows in ascending order, fp64, every operation written out, no fma; with s = seconds and
+ *   d the displacement of an observation of the track:
+ *       0  id    1  observations    2  the bit mask of the gaps seen, as a double    3-5  v = (sum s d) / (sum s s) per axis
+ *       6  sqrt(vx vx + vy vy)     7  sqrt of the largest r2 = (dx - s vx)^2 + (dy - s vy)^2     8  sqrt((sum r2) / observations)
+ *       9  moving: observed and col 6 >= min_speed    10  judged: seen in at least two distinct gaps (gaps outside [0, 63] set no bit)
+ *       11  consistent: judged and col 7 <= max_residual
+ *       12-14  the largest long side, short side and height over the views    15  the most source points in one view
+ *   A track without an observation has its id and zeros.  All pairs of a sample end at frame 0: constant velocity means
+ *   d_j = s_j v, least squares through the origin.  d_counts: tracks, observed (>= 1 observation), judged, consistent, moving
+ *   (observed and col 9).  Refusals: a null required pointer, M < 0, T < 0, a struct_size mismatch, parameters as above are
+ *   ICPFLOW_E_ARG; M or T > 2^24 is ICPFLOW_E_LIMIT.  T = 0 succeeds with five zeros.  No workspace.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_OVERLAP_COLS 10
+#define ICPFLOW_OVERLAP_COUNTS 4
+#define ICPFLOW_TRACK_SEGMENT_COLS 6
+#define ICPFLOW_TRACK_OBS_COLS 13
+#define ICPFLOW_TRACK_COLS 16
+#define ICPFLOW_TRACK_EXTEND_COUNTS 6
+#define ICPFLOW_TRACK_FIT_COUNTS 5
+typedef struct icpflow_track_params {
+    size_t struct_size;  /* sizeof(icpflow_track_params_t) */
+    double min_iou;      /* a segment inherits a track at this IoU or more; default 0.5 */
+    double max_residual; /* metres: a track is consistent when no observation lies farther from the fitted line; default 0.2 */
+    double min_speed;    /* a track moves when its fitted xy speed reaches this, m/s; default 0.5 */
+} icpflow_track_params_t;
+size_t icpflow_label_overlap_workspace_bytes(int n, int Lmax);
+int icpflow_label_overlap(const float *d_labels_a, const float *d_labels_b, int n, int Lmax, double *d_table_a, int32_t *d_num_a,
+                          double *d_table_b, int32_t *d_num_b, int64_t *d_counts, void *d_ws, size_t ws_bytes,
+                          icpflow_stream_t stream);
+int icpflow_object_tracks_default_params(icpflow_track_params_t *params);
+size_t icpflow_object_tracks_extend_workspace_bytes(int n, int Lmax);
+int icpflow_object_tracks_extend(const float *d_labels, int n, int Lmax, int32_t *d_track_of_row, int32_t *d_next_id,
+                                 const double *d_objects, int P, int gap, double seconds, const icpflow_track_params_t *params,
+                                 double *d_segments, int32_t *d_num, double *d_obs, int64_t *d_counts, void *d_ws, size_t ws_bytes,
+                                 icpflow_stream_t stream);
+int icpflow_object_tracks_fit(const double *d_obs, int M, int T, const icpflow_track_params_t *params, double *d_tracks,
+                              int64_t *d_counts, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
