@@ -32,13 +32,18 @@ independent, main.py:184), and reports ms / frame pair and the reference's accur
 
 `--residual [R]` judges every frame pair WITHOUT ground truth as well: the nearest-neighbour residual of the warped source
 against the destination, truncated at R metres (2.0 when given bare), before and after the registration, both directions
-(`frame_residual`, icpflow_nn_residual); the summary gains a `residual` block and `ms_residual_per_frame_pair`.
+(`pair_judges.frame_residual`, icpflow_nn_residual); the summary gains a `residual` block and `ms_residual_per_frame_pair`.
 
     python -m icp_flow_amd.frame_pairs DIR --residual [R] [--in-flight 4]
 
 `--residual-segments [FILE]` lists the segments (clusters) that still fit badly under the flow, and `--residual-sight [X Y Z]`
 says of each whether the destination sweep contradicts it ("seen through") or merely lost it ("lost from view":
-`frame_segment_sight`, icpflow_sight_*); the summary gains `residual_sight` and `ms_sight_per_frame_pair`.
+`pair_judges.frame_segment_sight`, icpflow_sight_*); the summary gains `residual_sight` and `ms_sight_per_frame_pair`.
+
+This module holds the loaders of sequences and samples, the registration paths, the two in-flight schedulers, both drivers
+(`run_stream`, `run_sequences`) and the command line.  The `FramePair` class, its file and its device copies are pair_data.py's,
+the judges of a registered frame pair (the `frame_*` device functions, the `residual_*` helpers and the six classes run_stream
+calls) pair_judges.py's; their names are imported here, so `frame_pairs.FramePair`, `frame_pairs.frame_trust` & co. stay.
 
 `run_sequences` (`--protocol reference`) evaluates whole sequence files by the reference's metric protocol instead
 (utils_eval.py:185-368, main.py:173-181, 285-296): the frame pairs of a file as above, their flows assembled on the device
@@ -87,6 +92,12 @@ import numpy as np
 import torch
 
 from . import utils_eval, utils_flow, utils_objects, utils_track, utils_tracks
+# the frame pair itself and the judges of a registered one live in modules of their own; their names stay reachable here
+from .pair_data import FramePair, _input, _upload, load_frame_pair, make_resident, save_frame_pair  # noqa: F401
+from .pair_judges import (RESIDUAL_SEGMENTS_SHOWN, ObjectJudge, ResidualJudge, SegmentJudge, SightJudge, TrackJudge, TrustJudge,  # noqa: F401
+                          _frame_objects_device, _residual_flat, _residual_unflat, _residual_zero, _source_labels, frame_objects,
+                          frame_residual, frame_segment_residual, frame_segment_sight, frame_tracks, frame_trust, residual_block,
+                          residual_groups, residual_tables)
 
 # demo.sh:9-13 / main.sh flags of the registration stage
 DEFAULT_ARGS = dict(max_points=10000, min_cluster_size=20, translation_frame=2.0, thres_dist=0.1, thres_box=0.1,
@@ -104,80 +115,6 @@ def default_args(**over):
     d = dict(DEFAULT_ARGS)
     d.update(over)
     return SimpleNamespace(**d)
-
-
-class FramePair:
-    def __init__(self, points_src, points_dst, labels_src=None, labels_dst=None, pose=None, gt_flow=None, mask=None,
-                 name="", nonground_src=None, nonground_dst=None, gap=1, points_src_raw=None, pose_source="given", sequence=None):
-        self.points_src = np.ascontiguousarray(points_src, dtype=np.float32)[:, 0:3]
-        self.points_dst = np.ascontiguousarray(points_dst, dtype=np.float32)[:, 0:3]
-        if (labels_src is None) != (labels_dst is None):
-            raise ValueError(f"frame pair {name!r}: labels of both clouds or of neither")
-        self.labels_src = None if labels_src is None else np.ascontiguousarray(labels_src, dtype=np.float32)
-        self.labels_dst = None if labels_dst is None else np.ascontiguousarray(labels_dst, dtype=np.float32)
-        self.nonground_src = None if nonground_src is None else np.asarray(nonground_src).astype(bool)
-        self.nonground_dst = None if nonground_dst is None else np.asarray(nonground_dst).astype(bool)
-        for m, pts in ((self.nonground_src, self.points_src), (self.nonground_dst, self.points_dst)):
-            if m is not None and m.shape != (len(pts),):
-                raise ValueError(f"frame pair {name!r}: one non-ground flag per point required")
-        if self.labels_src is not None and (
-                len(self.labels_src) != len(self.points_src) or len(self.labels_dst) != len(self.points_dst)):
-            raise ValueError(f"frame pair {name!r}: one label per point required "
-                             f"({len(self.labels_src)}/{len(self.points_src)} src, "
-                             f"{len(self.labels_dst)}/{len(self.points_dst)} dst)")
-        self.pose = np.eye(4, dtype=np.float32) if pose is None else np.asarray(pose, dtype=np.float32).reshape(4, 4)
-        # the pose as given (the reference's ego poses are float64 and main.py:200 takes their norm as such)
-        self.pose_exact = np.eye(4) if pose is None else np.asarray(pose, dtype=np.float64).reshape(4, 4)
-        self.gt_flow = None if gt_flow is None else np.asarray(gt_flow, dtype=np.float32)
-        if self.gt_flow is not None and self.gt_flow.shape != self.points_src.shape:
-            raise ValueError(f"frame pair {name!r}: gt_flow must be [Ns,3]")
-        self.mask = None if mask is None else np.asarray(mask)
-        self.name = name
-        self.pose_source = pose_source        # where the ego pose came from (load_sequence), reported by run_stream
-        # multi-gap samples (Waymo / nuScenes): frame `gap` against frame 0; the flow is reported on the source
-        # points BEFORE ego-motion compensation (main.py:230-234), registration runs on the compensated ones
-        self.gap = int(gap)
-        # the sample this frame pair is one gap of (load_sequence: the file's path), or None: the frame pairs of one sample share
-        # points_dst row for row, which is what run_stream's object tracks link (utils_tracks)
-        self.sequence = sequence
-        self.points_src_raw = None if points_src_raw is None else np.ascontiguousarray(points_src_raw, dtype=np.float32)[:, 0:3]
-        if self.points_src_raw is not None and self.points_src_raw.shape != self.points_src.shape:
-            raise ValueError(f"frame pair {name!r}: points_src_raw must match points_src")
-
-
-def save_frame_pair(path, fp):
-    arrays = dict(points_src=fp.points_src, points_dst=fp.points_dst, pose=fp.pose)
-    for k in ("labels_src", "labels_dst", "nonground_src", "nonground_dst"):
-        if getattr(fp, k) is not None:
-            arrays[k] = getattr(fp, k)
-    if fp.gt_flow is not None:
-        arrays["gt_flow"] = fp.gt_flow
-    if fp.mask is not None:
-        arrays["mask"] = fp.mask
-    np.savez_compressed(path, **arrays)
-
-
-def load_frame_pair(path):
-    with np.load(path) as z:
-        keys = set(z.files)
-
-        def first(*names):
-            for n in names:
-                if n in keys:
-                    return z[n]
-            return None
-
-        labels_src, labels_dst = first("labels_src", "label_src"), first("labels_dst", "label_dst")
-        ng = dict(nonground_src=first("nonground_src"), nonground_dst=first("nonground_dst"))
-        if "points_src" in keys:
-            return FramePair(z["points_src"], z["points_dst"], labels_src, labels_dst, first("pose"),
-                             first("gt_flow"), first("mask"), name=os.path.basename(path), **ng)
-        if "pc1" in keys:                                   # dataset_argo.py:34-53, demo.py:37-51
-            v0, v1 = z["pc1_flows_valid_idx"], z["pc2_flows_valid_idx"]
-            gt = z["gt_flow_0_1"][v0] if "gt_flow_0_1" in keys else None
-            return FramePair(z["pc1"][v0], z["pc2"][v1], labels_src, labels_dst, first("pose"), gt, first("mask"),
-                             name=os.path.basename(path), **ng)
-        raise ValueError(f"{path}: neither points_src/points_dst nor pc1/pc2 present")
 
 
 def is_sequence(path):
@@ -345,33 +282,6 @@ def cluster_frame_pair(args, ps, pd, nonground_src=None, nonground_dst=None):
 
 
 _stream_pool = {}
-
-
-def make_resident(fp, device):
-    """Upload the frame pair's arrays once and keep the device tensors with it (`register_frame_pair_native` then takes those:
-    inputs resident in HBM, what bench.py's stream workload times).  -> fp"""
-    device = torch.device(device)
-    keep = {}
-    for name in ("points_src", "points_dst", "labels_src", "labels_dst", "points_src_raw"):
-        arr = getattr(fp, name)
-        if arr is not None:
-            keep[name] = torch.from_numpy(arr).to(device)
-    fp._resident = (device, keep)
-    return fp
-
-
-def _input(fp, name, device):
-    res = getattr(fp, "_resident", None)
-    if res is not None and res[0] == torch.device(device) and name in res[1]:
-        return res[1][name]
-    return _upload(getattr(fp, name), device)
-
-
-def _upload(arr, device):
-    """Host array -> device tensor, from pageable memory.  (Measured on this stack: 41 us for a 63 k-point cloud; the
-    same upload through a pinned staging buffer with a non-blocking copy made a stream of frame pairs ten times SLOWER --
-    the copies serialise against the kernels of the other streams.)"""
-    return torch.from_numpy(arr).to(device)
 
 
 def register_frame_pair_steps(args, fp, device, gap=None, asynchronous=False):
@@ -1222,197 +1132,6 @@ def run_sequences(args, paths, device, in_flight=1, dataset="pca", rank=0, world
     return res
 
 
-def residual_groups(labels_src, pairs):
-    """The group of every source row for the residual's table (utils_eval.RESIDUAL_GROUPS): 0 ground (label -1e8), 1 unclustered
-    (-1), 2 clustered but unmatched, 3 matched -- its label is the source label of a row of `pairs` ([P,10], column 0).  Device
-    tensors in, int32 [Ns] on the device out."""
-    matched = torch.isin(labels_src, pairs[:, 0].to(labels_src.dtype)) if pairs.shape[0] else torch.zeros_like(labels_src, dtype=torch.bool)
-    g = torch.where(matched, 3, 2).to(torch.int32)
-    g = torch.where(labels_src == -1.0, torch.ones_like(g), g)
-    return torch.where(labels_src == -1e8, torch.zeros_like(g), g).contiguous()
-
-
-def frame_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
-    """The four residual calls of one registered frame pair and their one read-back: AFTER (the flow's source points -- raw when
-    the pair carries them -- plus the predicted flow against the destination, and the destination against that warped cloud) and
-    BEFORE (the ego-compensated source against the destination with no flow, and back).  The source's rows are grouped by
-    `residual_groups`, the destination's form one group.  -> [after forward, after backward, before forward, before backward],
-    ResidualTables."""
-    device = torch.device(device)
-    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
-    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
-    groups = residual_groups(_source_labels(fp, out, device), out["pairs"].to(device))
-    flow = out["flow"].to(device).float()
-    G = len(utils_eval.RESIDUAL_GROUPS)
-    calls = ((raw, pd, flow, groups, G), (pd, raw[:, 0:3] + flow[:, 0:3], None, None, 1), (ps, pd, None, groups, G), (pd, ps, None, None, 1))
-    words = [utils_eval.nn_residual_device(q, t, f, radius, g, n, edges, per_row=False)[2] for q, t, f, g, n in calls]
-    host = torch.cat(words).cpu().numpy()             # the one read-back
-    tables, at = [], 0
-    for _, _, _, _, n in calls:
-        size = n * (len(edges) + 4)
-        tables.append(utils_eval.ResidualTable.from_words(host[at: at + size], n, tuple(edges), radius, bad=int(host[at + size])))
-        at += size + 4
-    return tables
-
-
-def _source_labels(fp, out, device):
-    ls = out.get("labels_src")
-    if ls is None and fp.labels_src is not None:
-        ls = _input(fp, "labels_src", device)
-    if ls is None:
-        raise ValueError("the residual groups the source rows by their cluster labels: the registration must leave labels_src in its result")
-    return ls.to(device).float()
-
-
-def frame_segment_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
-    """The residual of one registered frame pair PER SEGMENT of the source (utils_eval.segment_residual: one call, one
-    read-back): BEFORE the ego-compensated source, AFTER the flow's source points -- raw when the pair carries them -- plus the
-    predicted flow, both against the destination; the source labels as `frame_residual` finds them.  -> SegmentResidual"""
-    device = torch.device(device)
-    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
-    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
-    return utils_eval.segment_residual(ps, raw, out["flow"].to(device).float(), _source_labels(fp, out, device), pd, radius, edges)
-
-
-def frame_segment_sight(fp, out, device, radius, origin=(0.0, 0.0, 0.0), edges=utils_eval.RESIDUAL_EDGES, **params):
-    """`frame_segment_residual` with the line-of-sight check beside it (utils_eval.segment_sight): the same residual call with
-    its per-row distances kept, one depth image over the destination as seen from `origin`, and the codes per segment among
-    the rows further than RESIDUAL_EDGES[1] metres from every destination point.  -> (SegmentResidual, sight), `sight` a
-    function without arguments that enqueues the image and the table and reads the table back -> SegmentSight (run_stream
-    times the two parts apart)."""
-    device = torch.device(device)
-    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
-    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
-    flow, labels = out["flow"].to(device).float(), _source_labels(fp, out, device)
-    table, num, info, d2b, d2a = utils_eval.segment_residual_device(ps, raw, flow, labels, pd, radius, edges, per_row=True)
-    report = utils_eval.segment_residual_read(table, num, info, radius, edges)
-
-    def sight():
-        image = utils_eval.sight_image(pd, origin, **params)
-        return utils_eval.segment_sight(image, ps, raw, flow, labels, d2b, d2a, far=utils_eval.RESIDUAL_EDGES[1])
-
-    return report, sight
-
-
-def frame_trust(fp, out, device, radius, origin=None, params=None):
-    """One trust byte per source point of a registered frame pair (utils_eval.flow_trust_device), everything on the device: the
-    segments' residual with its per-row distances kept (`frame_segment_residual`'s call), with an `origin` the depth image over
-    the destination and the segments' line-of-sight table with its per-row codes (`frame_segment_sight`'s calls), then the one
-    call that turns the tables and the per-row arrays into bytes.  The far rows and the listing share utils_eval.RESIDUAL_EDGES[1]
-    (params: a _lib.TrustParams that says otherwise).  -> (trust uint8 [Ns] on the device, TrustCounts); one read-back, the
-    sixteen counts."""
-    device = torch.device(device)
-    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
-    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
-    flow, labels = out["flow"].to(device).float(), _source_labels(fp, out, device)
-    far = utils_eval.RESIDUAL_EDGES[1] if params is None else float(params.far)
-    table, num, _, d2b, d2a = utils_eval.segment_residual_device(ps, raw, flow, labels, pd, radius, per_row=True)
-    seen = code = None
-    if origin is not None:
-        image = utils_eval.sight_image(pd, origin)
-        seen, _, _, _, code = utils_eval.segment_sight_device(image, ps, raw, flow, labels, d2b, d2a, far=far, per_row=True)
-    trust, _, counts = utils_eval.flow_trust_device(raw, flow, labels, table, num, d2a, out["pairs"].to(device), seen, code, params)
-    return trust, utils_eval.TrustCounts(counts.cpu().numpy())     # the one read-back
-
-
-def frame_objects(fp, out, device, seconds=None, min_speed=utils_objects.MIN_SPEED, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS):
-    """One object row per matched pair of a registered frame pair (utils_objects), everything on the device: the boxes of the
-    ego-compensated source's clusters and of the destination's (the cloud the pairs' transforms register, and the one they
-    register it to), then a box, a displacement, a velocity and a heading per pair from `out`'s pair rows and transforms.
-    seconds: the time between the two sweeps (None: fp.gap sweeps of utils_objects.SWEEP_SECONDS).  -> utils_objects.Objects;
-    one read-back, the pairs' table with its four counts."""
-    seconds = float(fp.gap) * utils_objects.SWEEP_SECONDS if seconds is None else float(seconds)
-    rows, counts, _ = _frame_objects_device(fp, out, device, seconds, min_speed, delta, A)
-    return utils_objects.Objects.read(rows, counts, seconds, min_speed)     # the one read-back
-
-
-def _frame_objects_device(fp, out, device, seconds, min_speed, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS):
-    """frame_objects' three calls, nothing read back -> (rows float64 [P, 24], counts int64 [4], the destination's labels)"""
-    device = torch.device(device)
-    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
-    ls = _source_labels(fp, out, device)
-    ld = out.get("labels_dst")
-    if ld is None and fp.labels_dst is not None:
-        ld = _input(fp, "labels_dst", device)
-    if ld is None:
-        raise ValueError("the objects need the destination's cluster labels: the registration must leave labels_dst in its result")
-    ld = ld.to(device).float()
-    boxes_src, num_src = utils_objects.segment_boxes_device(ps, ls, delta, A)
-    boxes_dst, num_dst = utils_objects.segment_boxes_device(pd, ld, delta, A)
-    rows, counts = utils_objects.pair_objects_device(boxes_src, num_src, out["pairs"].to(device), out["transformations"].to(device),
-                                                     boxes_dst, num_dst, seconds, min_speed)
-    return rows, counts, ld
-
-
-def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, min_speed=utils_tracks.MIN_SPEED, min_iou=utils_tracks.MIN_IOU,
-                 max_residual=utils_tracks.MAX_RESIDUAL, Lmax=4096):
-    """The object tracks of ONE sample (utils_tracks), everything on the device: `fps` the sample's frame pairs in gap order --
-    they share the destination sweep, row for row -- and `outs` their registrations.  Per gap the object rows of frame_objects
-    (not read back), then the shared sweep's clusters linked to the tracks so far (icpflow_object_tracks_extend); at the end one
-    fit over all gaps and ONE read-back.  A gap of `gap` sweeps spans gap * sweep_seconds.  -> utils_tracks.Tracks"""
-    device = torch.device(device)
-    n = len(fps[0].points_dst)
-    if any(len(fp.points_dst) != n for fp in fps):
-        raise ValueError(f"object tracks: the frame pairs of {fps[0].sequence or fps[0].name!r} disagree on the rows of the shared sweep "
-                         f"({sorted({len(fp.points_dst) for fp in fps})}): they are not the gaps of one sample")
-    state = utils_tracks.TrackState(n, device, Lmax, min_iou, max_residual, min_speed)
-    for fp, out in zip(fps, outs):
-        seconds = float(fp.gap) * float(sweep_seconds)
-        rows, _, ld = _frame_objects_device(fp, out, device, seconds, min_speed)
-        state.extend(ld, rows, fp.gap, seconds)
-    state.fit()
-    return state.read()
-
-
-RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
-
-
-def _residual_flat(tables):
-    """the four tables as one list of numbers for the closing all_reduce (counts are exact in a float64), and back"""
-    flat = []
-    for t in tables:
-        flat += t.rows.tolist() + t.hits.tolist() + t.under.reshape(-1).tolist() + t.dsum.tolist() + t.ddsum.tolist() + [t.bad]
-    return [float(v) for v in flat]
-
-
-def _residual_unflat(flat, like):
-    tables, at = [], 0
-    for t in like:
-        G, E = len(t.rows), len(t.edges)
-        take = lambda k: [flat[at + j] for j in range(k)]   # noqa: E731
-        rows = take(G); at += G
-        hits = take(G); at += G
-        under = take(G * E); at += G * E
-        dsum = take(G); at += G
-        ddsum = take(G); at += G
-        tables.append(utils_eval.ResidualTable(np.rint(rows), np.rint(hits), np.rint(under), dsum, ddsum, t.edges, t.radius, bad=int(round(flat[at]))))
-        at += 1
-    return tables
-
-
-def _residual_zero(radius, edges=utils_eval.RESIDUAL_EDGES):
-    G = len(utils_eval.RESIDUAL_GROUPS)
-    return [utils_eval.ResidualTable.zeros(n, tuple(edges), radius) for n in (G, 1, G, 1)]
-
-
-def residual_block(tables):
-    """[after forward, after backward, before forward, before backward] -> the summary's `residual` block"""
-    af, ab, bf, bb = tables
-    side = lambda f, b: dict(forward=f.summary(utils_eval.RESIDUAL_GROUPS), backward=b.summary(("all",)), chamfer=f.mean() + b.mean())   # noqa: E731
-    words = dict(after_forward=af.words().tolist(), after_backward=ab.words().tolist(), before_forward=bf.words().tolist(),
-                 before_backward=bb.words().tolist())      # the tables themselves (ResidualTable.from_words): runs can be added
-    return dict(radius=af.radius, edges=list(af.edges), groups=list(utils_eval.RESIDUAL_GROUPS), before=side(bf, bb), after=side(af, ab),
-                words=words)
-
-
-def residual_tables(block):
-    """the summary's `residual` block -> (before, after), each dict(forward, backward: ResidualTable), what format_residual takes"""
-    edges, r, G = tuple(block["edges"]), block["radius"], len(block["groups"])
-    table = lambda key, n: utils_eval.ResidualTable.from_words(block["words"][key], n, edges, r)   # noqa: E731
-    return (dict(forward=table("before_forward", G), backward=table("before_backward", 1)),
-            dict(forward=table("after_forward", G), backward=table("after_backward", 1)))
-
-
 def _by_sample(items, args, sample_of, samples):
     """run_stream's frame pairs, in their order, with the samples they are gaps of written down as they go by: sample_of[number
     of the frame pair] = its sample, samples[sample] = dict(sample, size, outs).  The frame pairs of one sequence file are one
@@ -1455,48 +1174,13 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     in_flight > 1 (HIP path only): that many frame pairs at once (`register_in_flight`: one stream and one host thread each, a
     blocking call into the library per frame pair; or the one-thread scheduler with asynchronous hand-overs); ms / frame pair is then the wall time of the whole share over its frame pairs --
     throughput of the stream, not the latency of one pair.
-    args.residual = r (metres; `--residual [R]`): every frame pair is also judged WITHOUT ground truth -- `frame_residual`, after
-    the pair is registered (and, in flight, delivered) and outside the timed region of one pair at a time; the tables are added
-    in the order of the frame pairs whatever order they complete in, ride the closing all_reduce, and the summary gains a
-    `residual` block and `ms_residual_per_frame_pair` (device-synchronised around the four calls and their read-back).  In flight,
-    ms / frame pair is the wall time of the share and then includes this work.
-    args.residual_segments = True or a file name (`--residual-segments [FILE]`; needs args.residual, whose radius it shares; one
-    process only): every frame pair is judged PER SEGMENT of its source as well -- `frame_segment_residual`, next to
-    `frame_residual` and like it outside the timed region of one pair at a time -- and the segments whose mean distance under the
-    flow exceeds utils_eval.RESIDUAL_EDGES[1] metres are collected, worst first.  The summary gains `residual_segments` (above,
-    segments_judged, segments_listed, worst: at most RESIDUAL_SEGMENTS_SHOWN entries, each with its frame pair's number and
-    path), `ms_segment_residual_per_frame_pair` (device-synchronised around the call and its read-back) and, with a file name,
-    `residual_segments_file`: the whole list written there as JSON.
-    args.residual_sight = True or (x, y, z) (`--residual-sight [X Y Z]`; needs args.residual_segments; one process only): the
-    line-of-sight check beside the segments' residual -- `frame_segment_sight`: per frame pair one depth image over the
-    destination as seen from the origin (True: (0, 0, 0)), the codes per segment among the rows further than
-    utils_eval.RESIDUAL_EDGES[1] metres from every destination point, one more read-back.  The SegmentResidual is the one the run
-    without the attribute gets; every listed segment gains `seen_through`, `excused`, `far_rows` and a `verdict`
-    (utils_eval.SegmentSight.annotate), and the summary gains `residual_sight` (params, origin, far, verdicts: listed segments
-    per verdict) and `ms_sight_per_frame_pair` (device-synchronised around the image, the table and its read-back only).
-    args.residual_trust = True (`--residual-trust`; needs args.residual_segments): one trust byte per source point of every frame
-    pair -- `frame_trust` at the shared radius, with the line of sight from residual_sight's origin iff that attribute is set --
-    and the summary gains `residual_trust`: the counts added over the frame pairs (utils_eval.TrustCounts.summary, `kept_share`
-    among them), `ms_trust_per_frame_pair` (timed on its own, device-synchronised around the chain and its read-back of sixteen
-    words) and, where a frame pair carries gt_flow, `epe_kept`, `epe_dropped` and `rows_evaluated`: the mean end-point error of
-    the masked rows with and without KEEP, host numpy.
-    args.objects = True or a file name (`--objects [FILE]`; one process only; independent of args.residual): one object row per
-    matched pair of every frame pair -- `frame_objects`, outside the timed region of one pair at a time, with
-    seconds = fp.gap * args.sweep_seconds (default 0.1) and args.objects_min_speed (default 0.5 m/s).  The summary gains `objects`
-    (objects, movers, the pairs without a segment or a box, largest_centre_gap in metres, the parameters) and
-    `ms_objects_per_frame_pair` (device-synchronised around the three calls and their one read-back); with a file name, one JSON
-    line per frame pair is written there (counts, and per object its labels, centre, size, yaw, velocity, speed, moving,
-    centre_gap, point counts) and the summary names it as `objects_file`.
-    args.tracks = True or a file name (`--tracks [FILE]`; one process only; independent of args.objects): the objects of a
-    multi-frame sample linked across its gaps -- `frame_tracks` over the frame pairs of one sequence file (they share the
-    destination sweep; a frame-pair file is a sample of its own), once the sample's LAST gap has been accounted and in gap order,
-    so the tracks do not depend on the order in which frame pairs complete.  It uses args.sweep_seconds and
-    args.objects_min_speed and adds args.tracks_min_iou (default 0.5) and args.tracks_max_residual (default 0.2 m).  The summary
-    gains `tracks` (samples, tracks, observed, judged, consistent, inconsistent, moving, overflow, the parameters) and
-    `ms_tracks_per_sample` (device-synchronised around the chain and its one read-back); with a file name, one JSON line per
-    sample is written there (counts, per observed track its velocity, residuals, verdicts and size, and per gap the track of
-    every object row) and the summary names it as `tracks_file`.  With args.objects and a file too, every object entry gains
-    `track`."""
+    Every registered frame pair -- in flight: once delivered -- then goes to the judges that `args` switches on, outside the
+    timed region of one pair at a time (in flight, ms / frame pair is the wall time of the share and includes their work).
+    There are six, each described at its class in pair_judges.py: args.residual (ResidualJudge), args.residual_segments
+    (SegmentJudge), args.residual_sight (SightJudge), args.residual_trust (TrustJudge), args.objects (ObjectJudge) and args.tracks
+    (TrackJudge).  A judge is handed the frame pair's number in this rank's share (in flight: `register_in_flight`'s index) and
+    keeps what it finds under it, so no result depends on the order in which frame pairs complete; after the one all_reduce
+    each adds its keys to the summary, in the order above, and writes its file."""
     import torch.distributed as dist
     device = torch.device(device)
     pipelined = int(in_flight) > 1 and register_fn is None
@@ -1508,130 +1192,33 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
 
     mine = shard_round_robin(paths, rank, world)
     meter = utils_eval.AverageMeter()
-    times, matched = [], 0
-    pose_sources = {}
-    radius = getattr(args, "residual", None)
-    residuals, residual_ms = {}, []              # frame pair (its number in this rank's share) -> its four tables
-    per_segment = getattr(args, "residual_segments", None)
-    if per_segment and not radius:
-        raise ValueError("args.residual_segments needs args.residual: the two share the radius")
-    if per_segment and world > 1:
-        raise ValueError("args.residual_segments under more than one rank: merging the lists is not built")
-    segment_lists, segment_ms, segments_judged = {}, [], 0     # frame pair -> its listed segments
-    sight = getattr(args, "residual_sight", None)
-    if sight is not None and sight is not False and not per_segment:
-        raise ValueError("args.residual_sight needs args.residual_segments: it judges the segments that one lists")
-    sight_origin = (0.0, 0.0, 0.0) if sight is True or not sight else tuple(float(v) for v in sight)
-    if len(sight_origin) != 3:
-        raise ValueError(f"args.residual_sight: True or an origin (x, y, z), got {sight!r}")
-    sight_ms = []
-    trust_on = bool(getattr(args, "residual_trust", False))
-    if trust_on and not per_segment:
-        raise ValueError("args.residual_trust needs args.residual and args.residual_segments: it spreads their verdicts over the rows")
-    trust_counts, trust_ms, trust_epe = utils_eval.TrustCounts(), [], [0.0, 0, 0.0, 0]    # sum and rows of e: kept, dropped
-    objects_on = getattr(args, "objects", None)
-    if objects_on and world > 1:
-        raise ValueError("args.objects under more than one rank: merging the files is not built")
-    sweep_seconds = float(getattr(args, "sweep_seconds", utils_objects.SWEEP_SECONDS))
-    objects_min_speed = float(getattr(args, "objects_min_speed", utils_objects.MIN_SPEED))
-    object_lines, objects_ms, object_counts, object_gap = {}, [], np.zeros(5, np.int64), None    # frame pair -> its line of the file
-    tracks_on = getattr(args, "tracks", None)
-    if tracks_on and world > 1:
-        raise ValueError("args.tracks under more than one rank: a sample's gaps would have to meet on one rank, which is not built")
-    tracks_min_iou = float(getattr(args, "tracks_min_iou", utils_tracks.MIN_IOU))
-    tracks_max_residual = float(getattr(args, "tracks_max_residual", utils_tracks.MAX_RESIDUAL))
-    sample_of, samples, track_lines, tracks_ms = {}, {}, {}, []     # frame pair -> its sample; sample -> its frame pairs; -> its line
-    track_totals = dict(tracks=0, observed=0, judged=0, consistent=0, inconsistent=0, moving=0, overflow=0)
-    accounted = 0
-
-    def close_sample(s):
-        """the chain of sample s, once every gap of it has been accounted: in gap order, whatever order they completed in"""
-        sample = samples.pop(s)
-        ks = sorted(sample["outs"])
-        fps = [sample["outs"][k][0] for k in ks]
-        sync()
-        t0 = time.perf_counter()
-        seen = frame_tracks(fps, [sample["outs"][k][1] for k in ks], device, sweep_seconds, objects_min_speed, tracks_min_iou, tracks_max_residual)
-        sync()
-        tracks_ms.append((time.perf_counter() - t0) * 1e3)
-        summary = seen.summary()
-        for name in track_totals:
-            track_totals[name] += summary[name]
-        track_lines[s] = dict(sample=s, path=fps[0].sequence or fps[0].name, frame_pairs=ks, gaps=[fp.gap for fp in fps], counts=summary,
-                              tracks=seen.as_list(), observations=[ids.tolist() for ids in seen.observation_ids])
-        for k, ids in zip(ks, seen.observation_ids):
-            for e in object_lines.get(k, {}).get("objects", []):
-                e["track"] = int(ids[e["pair"]])
+    times, matched, accounted = [], 0, 0
+    pose_sources, scores = {}, {}        # scores: frame pair -> its five metrics and its rows
+    every = (fp for path in mine for fp in ([path] if isinstance(path, FramePair) else load_any(path, args)))   # a sequence file yields one pair per gap
+    # the judges: every constructor checks its attributes of `args`, so the order here decides which error wins
+    residual = ResidualJudge(args, world, device)
+    segments = SegmentJudge(args, world, device, residual)
+    sight = SightJudge(args, world, device, segments)
+    trust = TrustJudge(args, world, device, segments, sight)
+    objects = ObjectJudge(args, world, device)
+    sample_of, samples = {}, {}      # frame pair -> its sample; sample -> its frame pairs: _by_sample fills them, the tracks empty them
+    tracks = TrackJudge(args, world, device, objects, sample_of, samples)
+    if tracks.on:
+        every = _by_sample(mine, args, sample_of, samples)
+    judges = [j for j in (residual, segments, sight, trust, objects, tracks) if j.on]
 
     def account(fp, out, index=None):
-        nonlocal matched, segments_judged, object_counts, object_gap, accounted
+        nonlocal matched, accounted
         number, accounted = (accounted if index is None else index), accounted + 1
-        if radius:
-            sync()
-            t0 = time.perf_counter()
-            residuals[len(residuals) if index is None else index] = frame_residual(fp, out, device, float(radius))
-            sync()
-            residual_ms.append((time.perf_counter() - t0) * 1e3)
-        if per_segment:
-            k = len(segment_lists) if index is None else index
-            sync()
-            t0 = time.perf_counter()
-            if sight:
-                report, look = frame_segment_sight(fp, out, device, float(radius), sight_origin)
-            else:
-                report = frame_segment_residual(fp, out, device, float(radius))
-            sync()
-            segment_ms.append((time.perf_counter() - t0) * 1e3)
-            segments_judged += sum(1 for v in report.labels.tolist() if v not in utils_eval.RESIDUAL_SKIP_LABELS)
-            segment_lists[k] = [dict(frame_pair=k, path=fp.name, **e) for e in report.worst(pairs=out["pairs"])]
-            if sight:
-                t0 = time.perf_counter()
-                seen = look()
-                sync()
-                sight_ms.append((time.perf_counter() - t0) * 1e3)
-                seen.annotate(segment_lists[k])
-        if trust_on:
-            sync()
-            t0 = time.perf_counter()
-            bytes_, counted = frame_trust(fp, out, device, float(radius), sight_origin if sight else None)
-            sync()
-            trust_ms.append((time.perf_counter() - t0) * 1e3)
-            trust_counts.add(counted)
-            if fp.gt_flow is not None:             # (host numpy over the masked rows, like the meter below)
-                keep = utils_eval.trust_keep(bytes_).cpu().numpy()
-                e = np.linalg.norm(np.asarray(fp.gt_flow, np.float64) - out["flow"].cpu().numpy()[:, 0:3].astype(np.float64), axis=-1)
-                judged = np.asarray(fp.mask) > 0 if fp.mask is not None else np.ones(len(e), dtype=bool)
-                for at, rows_ in ((0, judged & keep), (2, judged & ~keep)):
-                    trust_epe[at] += float(e[rows_].sum())
-                    trust_epe[at + 1] += int(rows_.sum())
-        if objects_on:
-            k = len(object_lines) if index is None else index
-            sync()
-            t0 = time.perf_counter()
-            seen_objects = frame_objects(fp, out, device, float(fp.gap) * sweep_seconds, objects_min_speed)
-            sync()
-            objects_ms.append((time.perf_counter() - t0) * 1e3)
-            s = seen_objects.summary()
-            object_counts += [s[name] for name in utils_objects.COUNT_NAMES] + [s["pairs"]]
-            gap_ = seen_objects.largest_centre_gap()
-            if gap_ is not None and (object_gap is None or gap_ > object_gap):
-                object_gap = gap_
-            object_lines[k] = dict(frame_pair=k, path=fp.name, seconds=seen_objects.seconds, counts=s, objects=seen_objects.as_list())
-        if tracks_on:
-            sample = samples[sample_of.pop(number)]
-            sample["outs"][number] = (fp, out)
-            if len(sample["outs"]) == sample["size"]:
-                close_sample(sample["sample"])
+        for j in judges:
+            j.account(number, fp, out)
         pose_sources[fp.pose_source] = pose_sources.get(fp.pose_source, 0) + 1
         matched += int(out["pairs"].shape[0])
         if fp.gt_flow is not None:
             m = utils_eval.compute_epe_test(out["flow"].cpu().numpy(), fp.gt_flow, fp.mask)
             n = int((np.asarray(fp.mask) > 0).sum()) if fp.mask is not None else len(fp.gt_flow)
-            meter.update(*m, n)
+            scores[number] = (*m, n)
 
-    every = (fp for path in mine for fp in ([path] if isinstance(path, FramePair) else load_any(path, args)))   # a sequence file yields one pair per gap
-    if tracks_on:
-        every = _by_sample(mine, args, sample_of, samples)
     if pipelined:
         sync()
         t0 = time.perf_counter()
@@ -1652,14 +1239,12 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             sync()
             times.append((time.perf_counter() - t0) / repeat * 1e3)
             account(fp, out)
-    # five weighted sums + point count + time + frame pairs + matches: one small all_reduce
+    for number in sorted(scores):       # (the meter's sums in the order of the frame pairs, whatever order they completed in)
+        meter.update(*scores[number])
+    # five weighted sums + point count + time + frame pairs + matches (+ what a judge adds): one small all_reduce
     local = [getattr(meter, m + "_sum") for m in utils_eval.METRIC_NAMES] + [meter.num, sum(times), len(times), matched]
-    if radius:
-        total = _residual_zero(float(radius))
-        for index in sorted(residuals):
-            for acc, t in zip(total, residuals[index]):
-                acc.add(t)
-        local = local + [sum(residual_ms)] + _residual_flat(total)
+    riding = [(j, j.reduce_words()) for j in judges if hasattr(j, "reduce_words")]
+    local += [w for _, words in riding for w in words]
     on_gpu = world > 1 and dist.get_backend(group) == "nccl"
     tot = torch.tensor(local, dtype=torch.float64, device=device if on_gpu else "cpu")
     tmax = torch.tensor([sum(times)], dtype=torch.float64, device=tot.device)
@@ -1667,7 +1252,10 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
         dist.all_reduce(tot, group=group)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=group)
     tot = tot.tolist()
-    n_pts, n_fp = tot[5], int(tot[7])
+    n_pts, n_fp, at = tot[5], int(tot[7]), 9
+    for j, words in riding:
+        j.take_words(tot[at: at + len(words)])
+        at += len(words)
     out = {"frame_pairs": n_fp, "matched_cluster_pairs": int(tot[8]), "n_gpus": world,
            "ms_per_frame_pair": tot[6] / max(n_fp, 1),
            "frame_pairs_per_s": n_fp / (float(tmax.item()) * 1e-3) if n_fp else 0.0,
@@ -1675,54 +1263,8 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
            "pose_sources": pose_sources}     # (this rank's frame pairs: "ego_motion_gt" = ground-truth ego poses were used)
     if n_pts > 0:
         out.update({m: tot[k] / n_pts for k, m in enumerate(utils_eval.METRIC_NAMES)})
-    if radius:
-        out["ms_residual_per_frame_pair"] = tot[9] / max(n_fp, 1)
-        out["residual"] = residual_block(_residual_unflat(tot[10:], total) if world > 1 else total)
-    if per_segment:
-        listed = [e for k in sorted(segment_lists) for e in segment_lists[k]]
-        listed.sort(key=lambda e: (-e["after_mean"], e["frame_pair"], e["label"]))
-        out["residual_segments"] = dict(above=utils_eval.RESIDUAL_EDGES[1], segments_judged=segments_judged, segments_listed=len(listed),
-                                        worst=listed[:RESIDUAL_SEGMENTS_SHOWN])
-        out["ms_segment_residual_per_frame_pair"] = sum(segment_ms) / max(len(segment_ms), 1)
-        if isinstance(per_segment, str):
-            with open(per_segment, "w") as f:
-                json.dump(listed, f, indent=1)
-            out["residual_segments_file"] = per_segment
-    if per_segment and sight:
-        from . import _lib
-        verdicts = {v: sum(1 for e in listed if e["verdict"] == v) for v in utils_eval.SIGHT_VERDICTS}
-        out["residual_sight"] = dict(params=_lib.SightParams.defaults().as_dict(), origin=list(sight_origin), far=utils_eval.RESIDUAL_EDGES[1],
-                                     verdicts=verdicts)
-        out["ms_sight_per_frame_pair"] = sum(sight_ms) / max(len(sight_ms), 1)
-    if trust_on:
-        from . import _lib
-        block = dict(trust_counts.summary(), params=_lib.TrustParams.defaults().as_dict(), line_of_sight=bool(sight),
-                     ms_trust_per_frame_pair=sum(trust_ms) / max(len(trust_ms), 1))
-        if trust_epe[1] + trust_epe[3]:
-            mean = lambda total, n: total / n if n else float("nan")   # noqa: E731
-            block.update(epe_kept=mean(trust_epe[0], trust_epe[1]), epe_dropped=mean(trust_epe[2], trust_epe[3]),
-                         rows_evaluated=trust_epe[1] + trust_epe[3])
-        out["residual_trust"] = block
-    if objects_on:
-        names = utils_objects.COUNT_NAMES + ("pairs",)
-        out["objects"] = dict({name: int(v) for name, v in zip(names, object_counts)}, pairs_without_box=int(object_counts[4] - object_counts[0]),
-                              largest_centre_gap=object_gap, sweep_seconds=sweep_seconds, min_speed=objects_min_speed,
-                              delta=utils_objects.BOX_DELTA, directions=utils_objects.BOX_DIRECTIONS)
-        out["ms_objects_per_frame_pair"] = sum(objects_ms) / max(len(objects_ms), 1)
-        if isinstance(objects_on, str):
-            with open(objects_on, "w") as f:
-                for k in sorted(object_lines):       # one JSON line per frame pair, in their order
-                    f.write(json.dumps(object_lines[k]) + "\n")
-            out["objects_file"] = objects_on
-    if tracks_on:
-        out["tracks"] = dict(track_totals, samples=len(track_lines), min_iou=tracks_min_iou, max_residual=tracks_max_residual,
-                             min_speed=objects_min_speed, sweep_seconds=sweep_seconds)
-        out["ms_tracks_per_sample"] = sum(tracks_ms) / max(len(tracks_ms), 1)
-        if isinstance(tracks_on, str):
-            with open(tracks_on, "w") as f:
-                for s in sorted(track_lines):        # one JSON line per sample, in their order
-                    f.write(json.dumps(track_lines[s]) + "\n")
-            out["tracks_file"] = tracks_on
+    for j in judges:
+        j.summarise(out)
     return out
 
 

@@ -1,0 +1,468 @@
+"""Judges of a registered frame pair that need no ground truth, and the shape run_stream gives them.
+
+The device functions take a FramePair and what its registration returned (dict(pairs, transformations, flow, ...)):
+`frame_residual` (the nearest-neighbour residual, icpflow_nn_residual), `frame_segment_residual` (per segment of the source),
+`frame_segment_sight` (with the line of sight beside it, icpflow_sight_*), `frame_trust` (one trust byte per source point),
+`frame_objects` (a box and a velocity per matched pair) and `frame_tracks` (a sample's objects linked across its gaps); the
+`residual_*` helpers carry the residual's tables through the all_reduce and in and out of the summary's block.
+
+Below them one plain class per judge: its constructor reads its attributes of `args` and raises on a bad combination,
+`account(number, fp, out)` judges one registered frame pair (`timed` brackets the device work), `summarise(out)` adds its keys
+to the summary and writes its file; the residual alone has `reduce_words` / `take_words`, its ride on the closing all_reduce.
+frame_pairs.run_stream builds the six in one place and calls them in that order; what one judge needs of another is a
+constructor argument."""
+import contextlib
+import json
+import time
+
+import numpy as np
+import torch
+
+from . import utils_eval, utils_objects, utils_tracks
+from .pair_data import _input
+
+
+def residual_groups(labels_src, pairs):
+    """The group of every source row for the residual's table (utils_eval.RESIDUAL_GROUPS): 0 ground (label -1e8), 1 unclustered
+    (-1), 2 clustered but unmatched, 3 matched -- its label is the source label of a row of `pairs` ([P,10], column 0).  Device
+    tensors in, int32 [Ns] on the device out."""
+    matched = torch.isin(labels_src, pairs[:, 0].to(labels_src.dtype)) if pairs.shape[0] else torch.zeros_like(labels_src, dtype=torch.bool)
+    g = torch.where(matched, 3, 2).to(torch.int32)
+    g = torch.where(labels_src == -1.0, torch.ones_like(g), g)
+    return torch.where(labels_src == -1e8, torch.zeros_like(g), g).contiguous()
+
+
+def frame_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
+    """The four residual calls of one registered frame pair and their one read-back: AFTER (the flow's source points -- raw when
+    the pair carries them -- plus the predicted flow against the destination, and the destination against that warped cloud) and
+    BEFORE (the ego-compensated source against the destination with no flow, and back).  The source's rows are grouped by
+    `residual_groups`, the destination's form one group.  -> [after forward, after backward, before forward, before backward],
+    ResidualTables."""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    groups = residual_groups(_source_labels(fp, out, device), out["pairs"].to(device))
+    flow = out["flow"].to(device).float()
+    G = len(utils_eval.RESIDUAL_GROUPS)
+    calls = ((raw, pd, flow, groups, G), (pd, raw[:, 0:3] + flow[:, 0:3], None, None, 1), (ps, pd, None, groups, G), (pd, ps, None, None, 1))
+    words = [utils_eval.nn_residual_device(q, t, f, radius, g, n, edges, per_row=False)[2] for q, t, f, g, n in calls]
+    host = torch.cat(words).cpu().numpy()             # the one read-back
+    tables, at = [], 0
+    for _, _, _, _, n in calls:
+        size = n * (len(edges) + 4)
+        tables.append(utils_eval.ResidualTable.from_words(host[at: at + size], n, tuple(edges), radius, bad=int(host[at + size])))
+        at += size + 4
+    return tables
+
+
+def _source_labels(fp, out, device):
+    ls = out.get("labels_src")
+    if ls is None and fp.labels_src is not None:
+        ls = _input(fp, "labels_src", device)
+    if ls is None:
+        raise ValueError("the residual groups the source rows by their cluster labels: the registration must leave labels_src in its result")
+    return ls.to(device).float()
+
+
+def frame_segment_residual(fp, out, device, radius, edges=utils_eval.RESIDUAL_EDGES):
+    """The residual of one registered frame pair PER SEGMENT of the source (utils_eval.segment_residual: one call, one
+    read-back): BEFORE the ego-compensated source, AFTER the flow's source points -- raw when the pair carries them -- plus the
+    predicted flow, both against the destination; the source labels as `frame_residual` finds them.  -> SegmentResidual"""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    return utils_eval.segment_residual(ps, raw, out["flow"].to(device).float(), _source_labels(fp, out, device), pd, radius, edges)
+
+
+def frame_segment_sight(fp, out, device, radius, origin=(0.0, 0.0, 0.0), edges=utils_eval.RESIDUAL_EDGES, **params):
+    """`frame_segment_residual` with the line-of-sight check beside it (utils_eval.segment_sight): the same residual call with
+    its per-row distances kept, one depth image over the destination as seen from `origin`, and the codes per segment among
+    the rows further than RESIDUAL_EDGES[1] metres from every destination point.  -> (SegmentResidual, sight), `sight` a
+    function without arguments that enqueues the image and the table and reads the table back -> SegmentSight (run_stream
+    times the two parts apart)."""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    flow, labels = out["flow"].to(device).float(), _source_labels(fp, out, device)
+    table, num, info, d2b, d2a = utils_eval.segment_residual_device(ps, raw, flow, labels, pd, radius, edges, per_row=True)
+    report = utils_eval.segment_residual_read(table, num, info, radius, edges)
+
+    def sight():
+        image = utils_eval.sight_image(pd, origin, **params)
+        return utils_eval.segment_sight(image, ps, raw, flow, labels, d2b, d2a, far=utils_eval.RESIDUAL_EDGES[1])
+
+    return report, sight
+
+
+def frame_trust(fp, out, device, radius, origin=None, params=None):
+    """One trust byte per source point of a registered frame pair (utils_eval.flow_trust_device), everything on the device: the
+    segments' residual with its per-row distances kept (`frame_segment_residual`'s call), with an `origin` the depth image over
+    the destination and the segments' line-of-sight table with its per-row codes (`frame_segment_sight`'s calls), then the one
+    call that turns the tables and the per-row arrays into bytes.  The far rows and the listing share utils_eval.RESIDUAL_EDGES[1]
+    (params: a _lib.TrustParams that says otherwise).  -> (trust uint8 [Ns] on the device, TrustCounts); one read-back, the
+    sixteen counts."""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    raw = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+    flow, labels = out["flow"].to(device).float(), _source_labels(fp, out, device)
+    far = utils_eval.RESIDUAL_EDGES[1] if params is None else float(params.far)
+    table, num, _, d2b, d2a = utils_eval.segment_residual_device(ps, raw, flow, labels, pd, radius, per_row=True)
+    seen = code = None
+    if origin is not None:
+        image = utils_eval.sight_image(pd, origin)
+        seen, _, _, _, code = utils_eval.segment_sight_device(image, ps, raw, flow, labels, d2b, d2a, far=far, per_row=True)
+    trust, _, counts = utils_eval.flow_trust_device(raw, flow, labels, table, num, d2a, out["pairs"].to(device), seen, code, params)
+    return trust, utils_eval.TrustCounts(counts.cpu().numpy())     # the one read-back
+
+
+def frame_objects(fp, out, device, seconds=None, min_speed=utils_objects.MIN_SPEED, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS):
+    """One object row per matched pair of a registered frame pair (utils_objects), everything on the device: the boxes of the
+    ego-compensated source's clusters and of the destination's (the cloud the pairs' transforms register, and the one they
+    register it to), then a box, a displacement, a velocity and a heading per pair from `out`'s pair rows and transforms.
+    seconds: the time between the two sweeps (None: fp.gap sweeps of utils_objects.SWEEP_SECONDS).  -> utils_objects.Objects;
+    one read-back, the pairs' table with its four counts."""
+    seconds = float(fp.gap) * utils_objects.SWEEP_SECONDS if seconds is None else float(seconds)
+    rows, counts, _ = _frame_objects_device(fp, out, device, seconds, min_speed, delta, A)
+    return utils_objects.Objects.read(rows, counts, seconds, min_speed)     # the one read-back
+
+
+def _frame_objects_device(fp, out, device, seconds, min_speed, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS):
+    """frame_objects' three calls, nothing read back -> (rows float64 [P, 24], counts int64 [4], the destination's labels)"""
+    device = torch.device(device)
+    ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+    ls = _source_labels(fp, out, device)
+    ld = out.get("labels_dst")
+    if ld is None and fp.labels_dst is not None:
+        ld = _input(fp, "labels_dst", device)
+    if ld is None:
+        raise ValueError("the objects need the destination's cluster labels: the registration must leave labels_dst in its result")
+    ld = ld.to(device).float()
+    boxes_src, num_src = utils_objects.segment_boxes_device(ps, ls, delta, A)
+    boxes_dst, num_dst = utils_objects.segment_boxes_device(pd, ld, delta, A)
+    rows, counts = utils_objects.pair_objects_device(boxes_src, num_src, out["pairs"].to(device), out["transformations"].to(device),
+                                                     boxes_dst, num_dst, seconds, min_speed)
+    return rows, counts, ld
+
+
+def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, min_speed=utils_tracks.MIN_SPEED, min_iou=utils_tracks.MIN_IOU,
+                 max_residual=utils_tracks.MAX_RESIDUAL, Lmax=4096):
+    """The object tracks of ONE sample (utils_tracks), everything on the device: `fps` the sample's frame pairs in gap order --
+    they share the destination sweep, row for row -- and `outs` their registrations.  Per gap the object rows of frame_objects
+    (not read back), then the shared sweep's clusters linked to the tracks so far (icpflow_object_tracks_extend); at the end one
+    fit over all gaps and ONE read-back.  A gap of `gap` sweeps spans gap * sweep_seconds.  -> utils_tracks.Tracks"""
+    device = torch.device(device)
+    n = len(fps[0].points_dst)
+    if any(len(fp.points_dst) != n for fp in fps):
+        raise ValueError(f"object tracks: the frame pairs of {fps[0].sequence or fps[0].name!r} disagree on the rows of the shared sweep "
+                         f"({sorted({len(fp.points_dst) for fp in fps})}): they are not the gaps of one sample")
+    state = utils_tracks.TrackState(n, device, Lmax, min_iou, max_residual, min_speed)
+    for fp, out in zip(fps, outs):
+        seconds = float(fp.gap) * float(sweep_seconds)
+        rows, _, ld = _frame_objects_device(fp, out, device, seconds, min_speed)
+        state.extend(ld, rows, fp.gap, seconds)
+    state.fit()
+    return state.read()
+
+
+RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
+
+
+def _residual_flat(tables):
+    """the four tables as one list of numbers for the closing all_reduce (counts are exact in a float64), and back"""
+    flat = []
+    for t in tables:
+        flat += t.rows.tolist() + t.hits.tolist() + t.under.reshape(-1).tolist() + t.dsum.tolist() + t.ddsum.tolist() + [t.bad]
+    return [float(v) for v in flat]
+
+
+def _residual_unflat(flat, like):
+    tables, at = [], 0
+    for t in like:
+        G, E = len(t.rows), len(t.edges)
+        take = lambda k: [flat[at + j] for j in range(k)]   # noqa: E731
+        rows = take(G); at += G
+        hits = take(G); at += G
+        under = take(G * E); at += G * E
+        dsum = take(G); at += G
+        ddsum = take(G); at += G
+        tables.append(utils_eval.ResidualTable(np.rint(rows), np.rint(hits), np.rint(under), dsum, ddsum, t.edges, t.radius, bad=int(round(flat[at]))))
+        at += 1
+    return tables
+
+
+def _residual_zero(radius, edges=utils_eval.RESIDUAL_EDGES):
+    G = len(utils_eval.RESIDUAL_GROUPS)
+    return [utils_eval.ResidualTable.zeros(n, tuple(edges), radius) for n in (G, 1, G, 1)]
+
+
+def residual_block(tables):
+    """[after forward, after backward, before forward, before backward] -> the summary's `residual` block"""
+    af, ab, bf, bb = tables
+    side = lambda f, b: dict(forward=f.summary(utils_eval.RESIDUAL_GROUPS), backward=b.summary(("all",)), chamfer=f.mean() + b.mean())   # noqa: E731
+    words = dict(after_forward=af.words().tolist(), after_backward=ab.words().tolist(), before_forward=bf.words().tolist(),
+                 before_backward=bb.words().tolist())      # the tables themselves (ResidualTable.from_words): runs can be added
+    return dict(radius=af.radius, edges=list(af.edges), groups=list(utils_eval.RESIDUAL_GROUPS), before=side(bf, bb), after=side(af, ab),
+                words=words)
+
+
+def residual_tables(block):
+    """the summary's `residual` block -> (before, after), each dict(forward, backward: ResidualTable), what format_residual takes"""
+    edges, r, G = tuple(block["edges"]), block["radius"], len(block["groups"])
+    table = lambda key, n: utils_eval.ResidualTable.from_words(block["words"][key], n, edges, r)   # noqa: E731
+    return (dict(forward=table("before_forward", G), backward=table("before_backward", 1)),
+            dict(forward=table("after_forward", G), backward=table("after_backward", 1)))
+
+
+@contextlib.contextmanager
+def timed(device, sink, settled=False):
+    """Synchronise `device`, start the clock, run the body, synchronise, append the milliseconds to `sink`.  settled: the body
+    follows a synchronise with nothing enqueued since, and the clock starts without another one."""
+    if device.type == "cuda" and not settled:
+        torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    yield
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    sink.append((time.perf_counter() - t0) * 1e3)
+
+
+class ResidualJudge:
+    """args.residual = r (metres; `--residual [R]`): every frame pair is also judged WITHOUT ground truth -- `frame_residual`, after
+    the pair is registered (and, in flight, delivered) and outside the timed region of one pair at a time; the tables are added
+    in the order of the frame pairs whatever order they complete in, ride the closing all_reduce, and the summary gains a
+    `residual` block and `ms_residual_per_frame_pair` (device-synchronised around the four calls and their read-back).  In flight,
+    ms / frame pair is the wall time of the share and then includes this work."""
+
+    def __init__(self, args, world, device):
+        self.radius, self.world, self.device = getattr(args, "residual", None), world, device
+        self.on = bool(self.radius)
+        self.tables, self.ms = {}, []              # frame pair (its number in this rank's share) -> its four tables
+
+    def account(self, number, fp, out):
+        with timed(self.device, self.ms):
+            self.tables[number] = frame_residual(fp, out, self.device, float(self.radius))
+
+    def reduce_words(self):
+        self.total = _residual_zero(float(self.radius))
+        for number in sorted(self.tables):
+            for acc, t in zip(self.total, self.tables[number]):
+                acc.add(t)
+        return [sum(self.ms)] + _residual_flat(self.total)
+
+    def take_words(self, words):
+        self.ms_sum = words[0]
+        if self.world > 1:
+            self.total = _residual_unflat(words[1:], self.total)
+
+    def summarise(self, out):
+        out["ms_residual_per_frame_pair"] = self.ms_sum / max(out["frame_pairs"], 1)
+        out["residual"] = residual_block(self.total)
+
+
+class SegmentJudge:
+    """args.residual_segments = True or a file name (`--residual-segments [FILE]`; needs args.residual, whose radius it shares; one
+    process only): every frame pair is judged PER SEGMENT of its source as well -- `frame_segment_residual`, next to
+    `frame_residual` and like it outside the timed region of one pair at a time -- and the segments whose mean distance under the
+    flow exceeds utils_eval.RESIDUAL_EDGES[1] metres are collected, worst first.  The summary gains `residual_segments` (above,
+    segments_judged, segments_listed, worst: at most RESIDUAL_SEGMENTS_SHOWN entries, each with its frame pair's number and
+    path), `ms_segment_residual_per_frame_pair` (device-synchronised around the call and its read-back) and, with a file name,
+    `residual_segments_file`: the whole list written there as JSON.  A SightJudge that is on leaves its `origin` here: the call is
+    then `frame_segment_sight`, and `look`, the sight half of the frame pair just accounted, waits for that judge."""
+
+    def __init__(self, args, world, device, residual):
+        self.file = getattr(args, "residual_segments", None)
+        self.on = bool(self.file)
+        if self.file and not residual.radius:
+            raise ValueError("args.residual_segments needs args.residual: the two share the radius")
+        if self.file and world > 1:
+            raise ValueError("args.residual_segments under more than one rank: merging the lists is not built")
+        self.radius, self.device, self.origin, self.look = residual.radius, device, None, None
+        self.lists, self.ms, self.judged = {}, [], 0     # frame pair -> its listed segments
+
+    def account(self, number, fp, out):
+        with timed(self.device, self.ms):
+            if self.origin is not None:
+                report, self.look = frame_segment_sight(fp, out, self.device, float(self.radius), self.origin)
+            else:
+                report = frame_segment_residual(fp, out, self.device, float(self.radius))
+        self.judged += sum(1 for v in report.labels.tolist() if v not in utils_eval.RESIDUAL_SKIP_LABELS)
+        self.lists[number] = [dict(frame_pair=number, path=fp.name, **e) for e in report.worst(pairs=out["pairs"])]
+
+    def summarise(self, out):
+        self.listed = [e for k in sorted(self.lists) for e in self.lists[k]]
+        self.listed.sort(key=lambda e: (-e["after_mean"], e["frame_pair"], e["label"]))
+        out["residual_segments"] = dict(above=utils_eval.RESIDUAL_EDGES[1], segments_judged=self.judged, segments_listed=len(self.listed),
+                                        worst=self.listed[:RESIDUAL_SEGMENTS_SHOWN])
+        out["ms_segment_residual_per_frame_pair"] = sum(self.ms) / max(len(self.ms), 1)
+        if isinstance(self.file, str):
+            with open(self.file, "w") as f:
+                json.dump(self.listed, f, indent=1)
+            out["residual_segments_file"] = self.file
+
+
+class SightJudge:
+    """args.residual_sight = True or (x, y, z) (`--residual-sight [X Y Z]`; needs args.residual_segments; one process only): the
+    line-of-sight check beside the segments' residual -- `frame_segment_sight`, the SegmentJudge's call: per frame pair one depth
+    image over the destination as seen from the origin (True: (0, 0, 0)), the codes per segment among the rows further than
+    utils_eval.RESIDUAL_EDGES[1] metres from every destination point, one more read-back.  The SegmentResidual is the one the run
+    without the attribute gets; every listed segment gains `seen_through`, `excused`, `far_rows` and a `verdict`
+    (utils_eval.SegmentSight.annotate), and the summary gains `residual_sight` (params, origin, far, verdicts: listed segments
+    per verdict) and `ms_sight_per_frame_pair` (device-synchronised around the image, the table and its read-back only)."""
+
+    def __init__(self, args, world, device, segments):
+        sight = getattr(args, "residual_sight", None)
+        if sight is not None and sight is not False and not segments.on:
+            raise ValueError("args.residual_sight needs args.residual_segments: it judges the segments that one lists")
+        self.origin = (0.0, 0.0, 0.0) if sight is True or not sight else tuple(float(v) for v in sight)
+        if len(self.origin) != 3:
+            raise ValueError(f"args.residual_sight: True or an origin (x, y, z), got {sight!r}")
+        self.on = bool(segments.on and sight)
+        self.segments, self.device, self.ms = segments, device, []
+        if self.on:
+            segments.origin = self.origin
+
+    def account(self, number, fp, out):
+        with timed(self.device, self.ms, settled=True):
+            seen = self.segments.look()
+        seen.annotate(self.segments.lists[number])
+
+    def summarise(self, out):
+        from . import _lib
+        verdicts = {v: sum(1 for e in self.segments.listed if e["verdict"] == v) for v in utils_eval.SIGHT_VERDICTS}
+        out["residual_sight"] = dict(params=_lib.SightParams.defaults().as_dict(), origin=list(self.origin), far=utils_eval.RESIDUAL_EDGES[1],
+                                     verdicts=verdicts)
+        out["ms_sight_per_frame_pair"] = sum(self.ms) / max(len(self.ms), 1)
+
+
+class TrustJudge:
+    """args.residual_trust = True (`--residual-trust`; needs args.residual_segments): one trust byte per source point of every frame
+    pair -- `frame_trust` at the shared radius, with the line of sight from the SightJudge's origin iff that judge is on --
+    and the summary gains `residual_trust`: the counts added over the frame pairs (utils_eval.TrustCounts.summary, `kept_share`
+    among them), `ms_trust_per_frame_pair` (timed on its own, device-synchronised around the chain and its read-back of sixteen
+    words) and, where a frame pair carries gt_flow, `epe_kept`, `epe_dropped` and `rows_evaluated`: the mean end-point error of
+    the masked rows with and without KEEP, host numpy, their sums added in the order of the frame pairs like every other sum."""
+
+    def __init__(self, args, world, device, segments, sight):
+        self.on = bool(getattr(args, "residual_trust", False))
+        if self.on and not segments.on:
+            raise ValueError("args.residual_trust needs args.residual and args.residual_segments: it spreads their verdicts over the rows")
+        self.radius, self.device, self.origin = segments.radius, device, sight.origin if sight.on else None
+        self.counts, self.ms, self.epe = utils_eval.TrustCounts(), [], {}    # frame pair -> sum and rows of e: kept, dropped
+
+    def account(self, number, fp, out):
+        with timed(self.device, self.ms):
+            bytes_, counted = frame_trust(fp, out, self.device, float(self.radius), self.origin)
+        self.counts.add(counted)
+        if fp.gt_flow is not None:             # (host numpy over the masked rows, like run_stream's meter)
+            keep = utils_eval.trust_keep(bytes_).cpu().numpy()
+            e = np.linalg.norm(np.asarray(fp.gt_flow, np.float64) - out["flow"].cpu().numpy()[:, 0:3].astype(np.float64), axis=-1)
+            judged = np.asarray(fp.mask) > 0 if fp.mask is not None else np.ones(len(e), dtype=bool)
+            self.epe[number] = [v for rows_ in (judged & keep, judged & ~keep) for v in (float(e[rows_].sum()), int(rows_.sum()))]
+
+    def summarise(self, out):
+        from . import _lib
+        block = dict(self.counts.summary(), params=_lib.TrustParams.defaults().as_dict(), line_of_sight=self.origin is not None,
+                     ms_trust_per_frame_pair=sum(self.ms) / max(len(self.ms), 1))
+        epe = [sum(self.epe[k][at] for k in sorted(self.epe)) for at in range(4)]    # added in the order of the frame pairs
+        if epe[1] + epe[3]:
+            mean = lambda total, n: total / n if n else float("nan")   # noqa: E731
+            block.update(epe_kept=mean(epe[0], epe[1]), epe_dropped=mean(epe[2], epe[3]), rows_evaluated=epe[1] + epe[3])
+        out["residual_trust"] = block
+
+
+class ObjectJudge:
+    """args.objects = True or a file name (`--objects [FILE]`; one process only; independent of args.residual): one object row per
+    matched pair of every frame pair -- `frame_objects`, outside the timed region of one pair at a time, with
+    seconds = fp.gap * args.sweep_seconds (default 0.1) and args.objects_min_speed (default 0.5 m/s).  The summary gains `objects`
+    (objects, movers, the pairs without a segment or a box, largest_centre_gap in metres, the parameters) and
+    `ms_objects_per_frame_pair` (device-synchronised around the three calls and their one read-back); with a file name, one JSON
+    line per frame pair is written there (counts, and per object its labels, centre, size, yaw, velocity, speed, moving,
+    centre_gap, point counts) and the summary names it as `objects_file`."""
+
+    def __init__(self, args, world, device):
+        self.file = getattr(args, "objects", None)
+        self.on = bool(self.file)
+        if self.file and world > 1:
+            raise ValueError("args.objects under more than one rank: merging the files is not built")
+        self.sweep_seconds = float(getattr(args, "sweep_seconds", utils_objects.SWEEP_SECONDS))
+        self.min_speed = float(getattr(args, "objects_min_speed", utils_objects.MIN_SPEED))
+        self.device = device
+        self.lines, self.ms, self.counts, self.gap = {}, [], np.zeros(5, np.int64), None    # frame pair -> its line of the file
+
+    def account(self, number, fp, out):
+        with timed(self.device, self.ms):
+            seen = frame_objects(fp, out, self.device, float(fp.gap) * self.sweep_seconds, self.min_speed)
+        s = seen.summary()
+        self.counts += [s[name] for name in utils_objects.COUNT_NAMES] + [s["pairs"]]
+        gap = seen.largest_centre_gap()
+        if gap is not None and (self.gap is None or gap > self.gap):
+            self.gap = gap
+        self.lines[number] = dict(frame_pair=number, path=fp.name, seconds=seen.seconds, counts=s, objects=seen.as_list())
+
+    def summarise(self, out):
+        names = utils_objects.COUNT_NAMES + ("pairs",)
+        out["objects"] = dict({name: int(v) for name, v in zip(names, self.counts)}, pairs_without_box=int(self.counts[4] - self.counts[0]),
+                              largest_centre_gap=self.gap, sweep_seconds=self.sweep_seconds, min_speed=self.min_speed,
+                              delta=utils_objects.BOX_DELTA, directions=utils_objects.BOX_DIRECTIONS)
+        out["ms_objects_per_frame_pair"] = sum(self.ms) / max(len(self.ms), 1)
+        if isinstance(self.file, str):
+            with open(self.file, "w") as f:
+                for k in sorted(self.lines):       # one JSON line per frame pair, in their order
+                    f.write(json.dumps(self.lines[k]) + "\n")
+            out["objects_file"] = self.file
+
+
+class TrackJudge:
+    """args.tracks = True or a file name (`--tracks [FILE]`; one process only; independent of args.objects): the objects of a
+    multi-frame sample linked across its gaps -- `frame_tracks` over the frame pairs of one sequence file (they share the
+    destination sweep; a frame-pair file is a sample of its own), once the sample's LAST gap has been accounted and in gap order,
+    so the tracks do not depend on the order in which frame pairs complete.  It uses the ObjectJudge's args.sweep_seconds and
+    args.objects_min_speed and adds args.tracks_min_iou (default 0.5) and args.tracks_max_residual (default 0.2 m).  The summary
+    gains `tracks` (samples, tracks, observed, judged, consistent, inconsistent, moving, overflow, the parameters) and
+    `ms_tracks_per_sample` (device-synchronised around the chain and its one read-back); with a file name, one JSON line per
+    sample is written there (counts, per observed track its velocity, residuals, verdicts and size, and per gap the track of
+    every object row) and the summary names it as `tracks_file`.  Where the ObjectJudge keeps lines, every object entry gains
+    `track`.  sample_of, samples: the maps that frame_pairs._by_sample fills as the frame pairs go by."""
+
+    def __init__(self, args, world, device, objects, sample_of, samples):
+        self.file = getattr(args, "tracks", None)
+        self.on = bool(self.file)
+        if self.file and world > 1:
+            raise ValueError("args.tracks under more than one rank: a sample's gaps would have to meet on one rank, which is not built")
+        self.min_iou = float(getattr(args, "tracks_min_iou", utils_tracks.MIN_IOU))
+        self.max_residual = float(getattr(args, "tracks_max_residual", utils_tracks.MAX_RESIDUAL))
+        self.device, self.objects, self.sample_of, self.samples = device, objects, sample_of, samples
+        self.lines, self.ms = {}, []               # sample -> its line of the file
+        self.totals = dict(tracks=0, observed=0, judged=0, consistent=0, inconsistent=0, moving=0, overflow=0)
+
+    def account(self, number, fp, out):
+        sample = self.samples[self.sample_of.pop(number)]
+        sample["outs"][number] = (fp, out)
+        if len(sample["outs"]) < sample["size"]:
+            return
+        # the chain of the sample, once every gap of it has been accounted: in gap order, whatever order they completed in
+        s = sample["sample"]
+        del self.samples[s]
+        ks = sorted(sample["outs"])
+        fps = [sample["outs"][k][0] for k in ks]
+        with timed(self.device, self.ms):
+            seen = frame_tracks(fps, [sample["outs"][k][1] for k in ks], self.device, self.objects.sweep_seconds, self.objects.min_speed,
+                                self.min_iou, self.max_residual)
+        summary = seen.summary()
+        for name in self.totals:
+            self.totals[name] += summary[name]
+        self.lines[s] = dict(sample=s, path=fps[0].sequence or fps[0].name, frame_pairs=ks, gaps=[fp.gap for fp in fps], counts=summary,
+                             tracks=seen.as_list(), observations=[ids.tolist() for ids in seen.observation_ids])
+        for k, ids in zip(ks, seen.observation_ids):
+            for e in self.objects.lines.get(k, {}).get("objects", []):
+                e["track"] = int(ids[e["pair"]])
+
+    def summarise(self, out):
+        out["tracks"] = dict(self.totals, samples=len(self.lines), min_iou=self.min_iou, max_residual=self.max_residual,
+                             min_speed=self.objects.min_speed, sweep_seconds=self.objects.sweep_seconds)
+        out["ms_tracks_per_sample"] = sum(self.ms) / max(len(self.ms), 1)
+        if isinstance(self.file, str):
+            with open(self.file, "w") as f:
+                for s in sorted(self.lines):        # one JSON line per sample, in their order
+                    f.write(json.dumps(self.lines[s]) + "\n")
+            out["tracks_file"] = self.file

@@ -157,6 +157,33 @@ def test_stream_eight_ranks_uneven_equals_single_process(tmp_path):
     assert np.allclose(eight[3:], want[3:], rtol=1e-6, atol=0)       # (weighted means: the sums are added in another order)
 
 
+def test_frame_pairs_delivered_out_of_order_give_the_summary_of_the_order(monkeypatch):
+    """In flight, frame pairs complete in any order; the meter's weighted sums are added in the order of the frame pairs all the
+    same, so the summary is the one-at-a-time run's to the last bit.  The in-flight driver is replaced by one that delivers the
+    same made-up registrations backwards, in a rotated and in the stream's own order (no GPU)."""
+    fps = []
+    for k in range(7):
+        d = synthetic.make_frame_pair(seed=k, n_objects=3, n_max=40 + 13 * k, n_background=30 + 7 * k)
+        fps.append(frame_pairs.FramePair(d["points_src"], d["points_dst"], d["labels_src"], d["labels_dst"], d["pose"], d["gt_flow"], name=str(k)))
+
+    def register(args, fp, device):      # (a flow that misses the truth by a different amount in every row and frame pair;
+        # with this seed the sums added backwards, and rotated, differ from the ones added in order in their last bits)
+        off = np.random.default_rng(len(fp.points_src) + 1).normal(0.0, 0.2, fp.gt_flow.shape).astype(np.float32)
+        return dict(pairs=torch.zeros((2, 10)), transformations=torch.eye(4).repeat(2, 1, 1), flow=torch.from_numpy(fp.gt_flow + off))
+
+    args, keep = frame_pairs.default_args(), ("frame_pairs", "matched_cluster_pairs", "evaluated_points", "pose_sources") + utils_eval.METRIC_NAMES
+    one = frame_pairs.run_stream(args, fps, "cpu", register_fn=register)
+    assert one["frame_pairs"] == 7 and 0.1 < one["epe"] < 1.0
+    for order in ([6, 5, 4, 3, 2, 1, 0], [3, 4, 5, 6, 0, 1, 2], [0, 1, 2, 3, 4, 5, 6]):
+        def deliver(args_, every, device, in_flight, order=order):
+            every = list(every)
+            for k in order:
+                yield k, every[k], register(args_, every[k], device)
+        monkeypatch.setattr(frame_pairs, "register_in_flight", deliver)
+        got = frame_pairs.run_stream(args, fps, "cpu", in_flight=4)
+        assert [got[k] for k in keep] == [one[k] for k in keep], order
+
+
 def test_sequence_files_in_the_reference_waymo_format(tmp_path):
     """dataset_pca.py:41-45 keys -> num_frames - 1 frame pairs (frame j -> frame 0): ego compensation
     (utils_helper.py:89-93), range crop (dataset_pca.py:61-64), per-gap translation frame (main.py:200), the estimated

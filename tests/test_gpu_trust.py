@@ -253,7 +253,7 @@ def sequence(tmp_path_factory):
 
 def _spied(monkeypatch):
     """frame_trust as the drivers call it, its results kept: [(gap, bytes uint8 [Ns], counts int64 [16], origin)]"""
-    from icp_flow_amd import frame_pairs
+    from icp_flow_amd import frame_pairs, pair_judges
     real, calls = frame_pairs.frame_trust, []
 
     def spy(fp, out, device, radius, origin=None, params=None):
@@ -261,7 +261,8 @@ def _spied(monkeypatch):
         calls.append((fp.gap, trust.cpu().numpy().copy(), counts.words(), origin, radius))
         return trust, counts
 
-    monkeypatch.setattr(frame_pairs, "frame_trust", spy)
+    monkeypatch.setattr(frame_pairs, "frame_trust", spy)           # where run_sequences reads it
+    monkeypatch.setattr(pair_judges, "frame_trust", spy)           # where run_stream's TrustJudge reads it
     return calls
 
 

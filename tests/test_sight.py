@@ -387,6 +387,53 @@ def test_without_the_attribute_the_summary_has_todays_keys():
     assert callable(frame_pairs.frame_segment_sight)
 
 
+NEEDS_RESIDUAL = "args.residual_segments needs args.residual: the two share the radius"
+SEGMENTS_ONE_RANK = "args.residual_segments under more than one rank: merging the lists is not built"
+NEEDS_SEGMENTS = "args.residual_sight needs args.residual_segments: it judges the segments that one lists"
+AN_ORIGIN = "args.residual_sight: True or an origin (x, y, z), got (0.0, 1.0)"
+TRUST_NEEDS = "args.residual_trust needs args.residual and args.residual_segments: it spreads their verdicts over the rows"
+OBJECTS_ONE_RANK = "args.objects under more than one rank: merging the files is not built"
+TRACKS_ONE_RANK = "args.tracks under more than one rank: a sample's gaps would have to meet on one rank, which is not built"
+WITH_SEGMENTS = dict(residual=2.0, residual_segments=True)
+# (attributes, world, the message): run_stream checks in the order residual_segments (its residual, then the ranks), residual_sight
+# (its segments, then the origin), residual_trust, objects, tracks -- read off the run_stream that held all of this in one function --
+# and the first complaint wins
+WRONG = [
+    (dict(residual_segments=True), 1, NEEDS_RESIDUAL),
+    (dict(residual_sight=True), 1, NEEDS_SEGMENTS),
+    (dict(residual=2.0, residual_sight=(0.0, 0.0, 1.5)), 1, NEEDS_SEGMENTS),
+    (dict(residual_trust=True), 1, TRUST_NEEDS),
+    (dict(residual=2.0, residual_trust=True), 1, TRUST_NEEDS),
+    (dict(WITH_SEGMENTS, residual_sight=(0.0, 1.0)), 1, AN_ORIGIN),
+    (WITH_SEGMENTS, 2, SEGMENTS_ONE_RANK),
+    (dict(objects=True), 2, OBJECTS_ONE_RANK),
+    (dict(tracks="tracks.jsonl"), 2, TRACKS_ONE_RANK),
+    # two at once
+    (dict(residual_segments=True), 2, NEEDS_RESIDUAL),
+    (dict(residual_segments="worst.json", residual_sight=(0.0, 1.0), residual_trust=True, objects=True), 2, NEEDS_RESIDUAL),
+    (dict(residual_sight=(0.0, 1.0)), 1, NEEDS_SEGMENTS),
+    (dict(residual_sight=True, residual_trust=True), 1, NEEDS_SEGMENTS),
+    (dict(WITH_SEGMENTS, residual_sight=(0.0, 1.0)), 2, SEGMENTS_ONE_RANK),
+    (dict(WITH_SEGMENTS, objects=True, tracks=True), 2, SEGMENTS_ONE_RANK),
+    (dict(residual_sight=(0.0, 1.0), objects=True), 2, NEEDS_SEGMENTS),
+    (dict(residual_trust=True, objects=True, tracks=True), 2, TRUST_NEEDS),
+    (dict(objects=True, tracks=True), 2, OBJECTS_ONE_RANK),
+]
+
+
+@pytest.mark.parametrize("attributes, world, message", WRONG)
+def test_every_wrong_combination_keeps_its_message_and_its_turn(attributes, world, message):
+    from icp_flow_amd import frame_pairs, synthetic
+    d = synthetic.make_frame_pair(seed=1, n_objects=3, n_max=60, n_background=50)
+    fp = frame_pairs.FramePair(d["points_src"], d["points_dst"], d["labels_src"], d["labels_dst"], d["pose"], d["gt_flow"])
+    a = frame_pairs.default_args()
+    for name, value in attributes.items():
+        setattr(a, name, value)
+    with pytest.raises(ValueError) as refusal:          # (before any frame pair is registered, and before any collective)
+        frame_pairs.run_stream(a, [fp, fp], "cpu", world=world, register_fn=_stub_register)
+    assert str(refusal.value) == message
+
+
 # ---- the conditions of the GPU tests' scenes ----------------------------------------------------------------------------------
 def test_the_sweeps_cover_every_code_and_the_bad_rows():
     v = S.view(cases.ORIGIN)
