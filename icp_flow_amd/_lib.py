@@ -125,6 +125,13 @@ SIGNATURES = {
     "icpflow_object_tracks_extend_workspace_bytes": (_sz, [_i, _i]),
     "icpflow_object_tracks_extend": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _d, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_object_tracks_fit": (_i, [_p, _i, _i, _p, _p, _p, _p]),
+    "icpflow_rows_carry_workspace_bytes": (_sz, [_i, _i]),
+    "icpflow_rows_carry": (_i, [_p, _p, _i, _p, _p, _i, _d, _d, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_pair_row_ids_workspace_bytes": (_sz, [_i]),
+    "icpflow_pair_row_ids": (_i, [_p, _i, _p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _p]),
+    "icpflow_object_tracks_extend_side": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "icpflow_object_tracks_path_default_params": (_i, [_p]),
+    "icpflow_object_tracks_path": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -171,6 +178,8 @@ OBJECT_COLS, OBJECT_COUNTS = 24, 4                # icpflow_pair_objects: column
 OVERLAP_COLS, OVERLAP_COUNTS, OVERLAP_MAX_SEGMENTS = 10, 4, 4096   # icpflow_label_overlap: columns of a row; words of d_counts; Lmax at most
 TRACK_SEGMENT_COLS, TRACK_OBS_COLS, TRACK_COLS = 6, 13, 16        # icpflow_object_tracks_extend / _fit: columns of their rows
 TRACK_EXTEND_COUNTS, TRACK_FIT_COUNTS = 6, 5                      # ... words of their d_counts
+CARRY_COUNTS, PAIR_ROW_ID_COUNTS, PAIR_ROW_ID_MAX_PAIRS = 6, 3, 4096   # icpflow_rows_carry, icpflow_pair_row_ids: words of d_counts; P at most
+TRACK_PATH_COLS, TRACK_PATH_COUNTS = 24, 5                        # icpflow_object_tracks_path: columns of a row; words of d_counts
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical
@@ -377,6 +386,25 @@ class TrackParams(ctypes.Structure):
 
     def as_dict(self):
         return dict(min_iou=self.min_iou, max_residual=self.max_residual, min_speed=self.min_speed)
+
+
+class TrackPathParams(ctypes.Structure):
+    """icpflow_track_path_params_t: the velocity change between adjacent steps a smooth track stays within and the speed that
+    tells movers apart (icpflow_object_tracks_path)."""
+    _fields_ = [("struct_size", _sz), ("max_dv", _d), ("min_speed", _d)]
+
+    @staticmethod
+    def defaults(**over):
+        p = TrackPathParams()
+        call("icpflow_object_tracks_path_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if k == "struct_size" or k not in dict(TrackPathParams._fields_):
+                raise TypeError(f"TrackPathParams: no parameter {k!r}")
+            setattr(p, k, float(v))
+        return p
+
+    def as_dict(self):
+        return dict(max_dv=self.max_dv, min_speed=self.min_speed)
 
 
 class ObjectParams(ctypes.Structure):

@@ -95,7 +95,7 @@ constexpr int kPerThread = kTile / kThreads;
 constexpr int kMaxGroups = ICPFLOW_NNR_MAX_GROUPS;  // (the limits both entry points share: nnresid.hpp)
 using icpflow::nnr::good_coord;                     // (nnresid.hpp: a coordinate beyond 1e6 m is a bad row)
 
-__device__ __forceinline__ int cell_of(float v, double h) { return (int)floor((double)v / h); }
+using icpflow::nnr::cell_of;                        // (nnresid.hpp: floor((double)v / h), one fp64 division)
 
 // row j of the cloud -> its coordinates; false for a bad row
 __device__ __forceinline__ bool load_row(const Cloud &c, size_t j, float &x, float &y, float &z)
@@ -492,6 +492,13 @@ Grid carve_grid(Carver &ws, int rows)
     return g;
 }
 
+void scan_grid(const Grid &g, unsigned long long *d_info, hipStream_t st)
+{
+    nnr_tile_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_sum, g.tile_occupied, g.tile_longest);
+    nnr_offsets_kernel<<<1, kThreads, 0, st>>>(g.tile_sum, g.tile_occupied, g.tile_longest, g.tiles, g.tile_offset, g.rows, d_info);
+    nnr_starts_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_offset, g.start);
+}
+
 hipError_t bin_cloud(const Cloud &cloud, const Grid &g, double h, unsigned long long *bad_rows, unsigned long long *d_info, float r2,
                      float *d2, int32_t *idx, hipStream_t st)
 {
@@ -499,9 +506,7 @@ hipError_t bin_cloud(const Cloud &cloud, const Grid &g, double h, unsigned long 
     hipError_t e = hipMemsetAsync(g.cursor, 0, (size_t)g.H * sizeof(unsigned), st);
     if (e != hipSuccess) return e;
     if (cloud.rows > 0) nnr_count_kernel<<<blocks_for(cloud.rows), kThreads, 0, st>>>(cloud, h, mask, g.cursor, bad_rows);
-    nnr_tile_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_sum, g.tile_occupied, g.tile_longest);
-    nnr_offsets_kernel<<<1, kThreads, 0, st>>>(g.tile_sum, g.tile_occupied, g.tile_longest, g.tiles, g.tile_offset, g.rows, d_info);
-    nnr_starts_kernel<<<g.tiles, kThreads, 0, st>>>(g.cursor, g.H, g.tile_offset, g.start);
+    scan_grid(g, d_info, st);
     if (cloud.rows > 0) nnr_scatter_kernel<<<blocks_for(cloud.rows), kThreads, 0, st>>>(cloud, h, mask, g.cursor, g.records, r2, d2, idx);
     return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 // nnresid.hpp -- what nnresid.hip shares with segresid.hip: the hashed grid over one cloud, its carve, its build and the launch
 // of the binned query.  Declarations only: the kernels and every definition stay in nnresid.hip, so both entry points run the
-// same device code.  The one inline function is the bad-row rule, which sight.hip applies word for word.
+// same device code.  The inline functions are the bad-row rule, which sight.hip applies word for word, and the cell of a coordinate.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,9 @@ __device__ __forceinline__ bool good_coord(float x, float y, float z)   // (a Na
 {
     return fabsf(x) <= kFar && fabsf(y) <= kFar && fabsf(z) <= kFar;
 }
+
+// the cell of a coordinate on a grid of edge h: one IEEE fp64 division (nnresid.hip states why the index fits an int)
+__device__ __forceinline__ int cell_of(float v, double h) { return (int)floor((double)v / h); }
 
 struct Edges {
     int E;
@@ -51,6 +54,11 @@ Grid carve_grid(Carver &ws, int rows);
 // d2 / idx (the queries only): the outputs of the bad rows
 hipError_t bin_cloud(const Cloud &cloud, const Grid &g, double h, unsigned long long *bad_rows, unsigned long long *d_info, float r2,
                      float *d2, int32_t *idx, hipStream_t st);
+
+// the middle of bin_cloud on its own, for a caller that counts and scatters with kernels of its own (carry.hip moves its rows
+// first): g.cursor holds the count of every bucket (grid_hash of the rows' cells, mask H - 1); after it g.start has every
+// bucket's first slot, g.cursor the same as a running cursor, *g.rows the total; d_info as bin_cloud's
+void scan_grid(const Grid &g, unsigned long long *d_info, hipStream_t st);
 
 // the binned query: the n rows that bin_cloud left in `queries` against the grid `targets`; writes d2 and idx of every good
 // query row (the bad ones have theirs from bin_cloud).  n == 0: nothing is launched.

@@ -1,5 +1,7 @@
 // tracks.hip -- the clusters of a sample's shared sweep linked across its gaps, and a constant velocity per track
-// (include/icpflow_hip.h, "8(k) object tracks": icpflow_object_tracks_extend, icpflow_object_tracks_fit).
+// (include/icpflow_hip.h, "8(k) object tracks": icpflow_object_tracks_extend, icpflow_object_tracks_fit); the same extension
+// on the SOURCE side of a pair and one row per track over a log ("8(l)": icpflow_object_tracks_extend_side,
+// icpflow_object_tracks_path -- trk_path_kernel, a thread per track like the fit).
 //
 // icpflow_object_tracks_extend, one gap:
 //   1. trk_labels_kernel    "track id per row" as a float32 labelling (an id is its own label, no track is -1)
@@ -7,7 +9,8 @@
 //   3. trk_assign_kernel    ONE workgroup of 1024, thread t segments 4 t .. 4 t + 3: inherit or fresh, the fresh ids by an
 //                           exclusive scan in ascending label order; the rows of d_segments, the counts, overflow, *d_next_id
 //   4. trk_relabel_kernel   a thread per row: the rows of linkable segments take their segment's id
-//   5. trk_obs_kernel       a thread per object row: the id of its destination label's segment (binary search on label_key)
+//   5. trk_obs_kernel       a thread per object row: the id of its destination label's segment (binary search on label_key);
+//                           side 0: of its source label's
 // The state is written by kernels 3 (its last statement) and 4 only, behind everything that reads it, and not at all on
 // overflow.  icpflow_object_tracks_fit: one thread per track walks all observations in row order -- T * M is a few thousand
 // tracks times a few thousand rows at most (a sample has at most 15 gaps of at most 4096 pairs), far below what a segmented
@@ -165,7 +168,7 @@ __device__ __forceinline__ int find_segment(const double *__restrict__ table, in
 
 __global__ __launch_bounds__(kThreads) void trk_obs_kernel(const int32_t *__restrict__ state, const double *__restrict__ tableA,
                                                            const int32_t *__restrict__ segId, const double *__restrict__ objects, int P,
-                                                           double gap, double seconds, double *__restrict__ obs,
+                                                           int side, double gap, double seconds, double *__restrict__ obs,
                                                            unsigned long long *__restrict__ counts)
 {
     __shared__ int sh[kWaves][2];
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void trk_obs_kernel(const int32_t *__rest
         const double *o = objects + (size_t)p * kObjectCols;
         int id = -1;
         if (state[0] != 0 && o[22] > 0.0) {
-            const int c = find_segment(tableA, state[1], (float)o[1]);
+            const int c = find_segment(tableA, state[1], (float)o[side]);   // (side 1: the destination label, side 0: the source label)
             if (c >= 0) id = segId[c];
         }
         with = id >= 0;
@@ -264,6 +267,99 @@ __global__ __launch_bounds__(kThreads) void trk_fit_kernel(const double *__restr
     }
 }
 
+// One row per track over a log (8(l)): a thread per track walks the M observations in row order; of the observations of one
+// step the one with the most source points is COUNTED (the lower row on a tie) -- a step's rows are contiguous, the steps are
+// non-decreasing, so the walk keeps one candidate and counts it when the step changes.  fp64, every operation written out.
+struct PathWalk {
+    int seen = 0, first = 0, last = 0, pairs = 0;
+    double seconds = 0.0, length = 0.0, sum[3] = {0.0, 0.0, 0.0}, dv = 0.0, jump = 0.0;
+    double longest = 0.0, shortest = 0.0, height = 0.0, points = 0.0, start[3] = {0.0, 0.0, 0.0};
+    double pc[3], pd[3], pv[3];                        // the previous counted observation: centre, displacement, velocity
+};
+
+__device__ __forceinline__ void path_count(PathWalk &w, const double *__restrict__ o, const double *__restrict__ f, int step)
+{
+    const double cx = o[10], cy = o[11], cz = o[12], dx = o[3], dy = o[4], dz = o[5], s = o[2];
+    const double c[3] = {((f[0] * cx + f[1] * cy) + f[2] * cz) + f[9], ((f[3] * cx + f[4] * cy) + f[5] * cz) + f[10],
+                         ((f[6] * cx + f[7] * cy) + f[8] * cz) + f[11]};
+    const double d[3] = {(f[0] * dx + f[1] * dy) + f[2] * dz, (f[3] * dx + f[4] * dy) + f[5] * dz, (f[6] * dx + f[7] * dy) + f[8] * dz};
+    const double v[3] = {d[0] / s, d[1] / s, d[2] / s};
+    if (w.seen == 0) w.first = step, w.start[0] = c[0], w.start[1] = c[1], w.start[2] = c[2];
+    else if (step == w.last + 1) {                     // ADJACENT steps only
+        const double ax = v[0] - w.pv[0], ay = v[1] - w.pv[1];
+        const double dv = sqrt(ax * ax + ay * ay);
+        const double jx = (w.pc[0] + w.pd[0]) - c[0], jy = (w.pc[1] + w.pd[1]) - c[1];
+        const double jump = sqrt(jx * jx + jy * jy);
+        w.dv = dv > w.dv ? dv : w.dv, w.jump = jump > w.jump ? jump : w.jump;
+        ++w.pairs;
+    }
+    ++w.seen;
+    w.last = step;
+    w.seconds += s;
+    w.length += sqrt(d[0] * d[0] + d[1] * d[1]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) w.sum[a] += d[a], w.pc[a] = c[a], w.pd[a] = d[a], w.pv[a] = v[a];
+    w.longest = o[6] > w.longest ? o[6] : w.longest, w.shortest = o[7] > w.shortest ? o[7] : w.shortest;
+    w.height = o[8] > w.height ? o[8] : w.height, w.points = o[9] > w.points ? o[9] : w.points;
+}
+
+__global__ __launch_bounds__(kThreads) void trk_path_kernel(const double *__restrict__ obs, const int32_t *__restrict__ stepOf, int M,
+                                                            const double *__restrict__ frames, int F, int T, double maxDv, double minSpeed,
+                                                            double *__restrict__ paths, unsigned long long *__restrict__ counts)
+{
+    constexpr int kCols = ICPFLOW_TRACK_PATH_COLS, kCounts = ICPFLOW_TRACK_PATH_COUNTS;
+    __shared__ int sh[kWaves][kCounts];
+    const int t = blockIdx.x * kThreads + (int)threadIdx.x;
+    const bool live = t < T;
+    bool observed = false, judged = false, smooth = false, moving = false;
+    if (live) {
+        const double id = (double)t;
+        PathWalk w;
+        int cand = -1, candStep = 0;                    // the row that stands for candStep so far
+        for (int k = 0; k < M; ++k) {
+            const double *o = obs + (size_t)k * kObsCols;
+            if (o[0] != id) continue;
+            const int s = stepOf[k];
+            if (s < 0 || s >= F) continue;              // a step outside [0, F): not counted
+            if (cand >= 0 && s == candStep) {
+                if (o[9] > obs[(size_t)cand * kObsCols + 9]) cand = k;
+                continue;
+            }
+            if (cand >= 0) path_count(w, obs + (size_t)cand * kObsCols, frames + (size_t)candStep * 12, candStep);
+            cand = k, candStep = s;
+        }
+        if (cand >= 0) path_count(w, obs + (size_t)cand * kObsCols, frames + (size_t)candStep * 12, candStep);
+        double v[3] = {0.0, 0.0, 0.0};
+        if (w.seen > 0) v[0] = w.sum[0] / w.seconds, v[1] = w.sum[1] / w.seconds, v[2] = w.sum[2] / w.seconds;
+        const double speed = sqrt(v[0] * v[0] + v[1] * v[1]);
+        observed = w.seen > 0;
+        moving = observed && speed >= minSpeed;
+        judged = w.pairs >= 1;
+        smooth = judged && w.dv <= maxDv;
+        double *row = paths + (size_t)t * kCols;
+        row[0] = id, row[1] = (double)w.seen, row[2] = (double)w.first, row[3] = (double)w.last;
+        row[4] = observed ? (double)((w.last - w.first + 1) - w.seen) : 0.0;
+        row[5] = w.seconds, row[6] = w.length, row[7] = v[0], row[8] = v[1], row[9] = v[2], row[10] = speed;
+        row[11] = w.dv, row[12] = (double)w.pairs, row[13] = w.jump;
+        row[14] = moving ? 1.0 : 0.0, row[15] = judged ? 1.0 : 0.0, row[16] = smooth ? 1.0 : 0.0;
+        row[17] = w.longest, row[18] = w.shortest, row[19] = w.height, row[20] = w.points;
+        row[21] = w.start[0], row[22] = w.start[1], row[23] = w.start[2];
+    }
+    const bool flag[kCounts] = {live, observed, judged, smooth, moving};
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kCounts; ++k) {                // (every lane takes every round: the ballots see whole waves)
+        const int c = __popcll(__ballot(flag[k]));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh[wave][k] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCounts) {
+        int c = 0;
+        for (int w = 0; w < kWaves; ++w) c += sh[w][threadIdx.x];
+        if (c != 0) atomicAdd(&counts[threadIdx.x], (unsigned long long)c);
+    }
+}
+
 bool sizes_ok(int n, int Lmax) { return n >= 0 && n <= kMaxRows && Lmax >= 1 && Lmax <= kLmax; }
 
 // -> 0, or the status of a refused parameter block
@@ -277,6 +373,51 @@ int check_params(const char *fn, const icpflow_track_params_t *p)
         return report_errorf(ICPFLOW_E_ARG, "%s: max_residual = %g: max_residual must be finite and not negative", fn, p->max_residual);
     if (!(p->min_speed >= 0.0) || !std::isfinite(p->min_speed))
         return report_errorf(ICPFLOW_E_ARG, "%s: min_speed = %g: min_speed must be finite and not negative", fn, p->min_speed);
+    return ICPFLOW_OK;
+}
+
+// both entry points of the extension; `fn` names the one that was called in every message
+int extend(const char *fn, const float *d_labels, int n, int Lmax, int32_t *d_track_of_row, int32_t *d_next_id, const double *d_objects, int P,
+           int side, int gap, double seconds, const icpflow_track_params_t *params, double *d_segments, int32_t *d_num, double *d_obs,
+           int64_t *d_counts, void *d_ws, size_t ws_bytes, icpflow_stream_t stream)
+{
+    if (n < 0 || P < 0) return report_errorf(ICPFLOW_E_ARG, "%s: n = %d, P = %d: a negative size", fn, n, P);
+    if (n > kMaxRows) return report_errorf(ICPFLOW_E_LIMIT, "%s: n = %d: at most %d rows", fn, n, kMaxRows);
+    if (Lmax < 1) return report_errorf(ICPFLOW_E_ARG, "%s: Lmax = %d: Lmax must be at least 1", fn, Lmax);
+    if (Lmax > kLmax) return report_errorf(ICPFLOW_E_LIMIT, "%s: Lmax = %d: at most %d segments", fn, Lmax, kLmax);
+    if (side != 0 && side != 1) return report_errorf(ICPFLOW_E_ARG, "%s: side = %d: side is 0 (the source labels) or 1 (the destination labels)", fn, side);
+    if (gap < 0 || gap > 63) return report_errorf(ICPFLOW_E_ARG, "%s: gap = %d: gap must lie in [0, 63]", fn, gap);
+    if (!(seconds > 0.0) || !std::isfinite(seconds))
+        return report_errorf(ICPFLOW_E_ARG, "%s: seconds = %g: seconds must be positive and finite", fn, seconds);
+    if (!d_next_id || !params || !d_segments || !d_num || !d_counts || (n > 0 && (!d_labels || !d_track_of_row)) || (P > 0 && (!d_objects || !d_obs)))
+        return pointer_error(fn);
+    if (const int rc = check_params(fn, params)) return rc;
+    Carve c{};
+    if (!carve(d_ws, n, Lmax, &c)) return report_errorf(ICPFLOW_E_ARG, "%s: no workspace layout for these sizes", fn);
+    if (!d_ws || ws_bytes < c.total) return workspace_error(fn, "icpflow_object_tracks_extend_workspace_bytes", d_ws, ws_bytes, c.total);
+    if (((uintptr_t)d_ws & 15) != 0) return report_errorf(ICPFLOW_E_ARG, "%s: d_ws must be 16-byte aligned", fn);
+
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        ICPFLOW_TRY(hipMemsetAsync(c.num, 0, 2 * sizeof(int32_t), st));
+    } else {
+        trk_labels_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_track_of_row, n, c.trackLabel);
+        ICPFLOW_TRY(hipGetLastError());
+        ICPFLOW_TRY(icpflow::overlap::launch_links(d_labels, c.trackLabel, n, Lmax, c.num, c.num + 1, c.ov, st));
+        ICPFLOW_TRY(icpflow::overlap::launch_tables(c.ov, c.num, c.num + 1, Lmax, c.table[0], c.table[1], c.ovCounts, st));
+    }
+    trk_assign_kernel<<<1, kAssignThreads, 0, st>>>(c.num, c.table[0], Lmax, params->min_iou, d_next_id, c.segId, c.state, d_segments, d_num,
+                                                    (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    if (n > 0) {
+        trk_relabel_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(c.state, c.ov.side[0].segOf, c.segId, n, d_track_of_row);
+        ICPFLOW_TRY(hipGetLastError());
+    }
+    if (P > 0) {
+        trk_obs_kernel<<<(P + kThreads - 1) / kThreads, kThreads, 0, st>>>(c.state, c.table[0], c.segId, d_objects, P, side, (double)gap, seconds, d_obs,
+                                                                           (unsigned long long *)d_counts);
+        ICPFLOW_TRY(hipGetLastError());
+    }
     return ICPFLOW_OK;
 }
 
@@ -303,44 +444,17 @@ int icpflow_object_tracks_extend(const float *d_labels, int n, int Lmax, int32_t
                                  int P, int gap, double seconds, const icpflow_track_params_t *params, double *d_segments, int32_t *d_num,
                                  double *d_obs, int64_t *d_counts, void *d_ws, size_t ws_bytes, icpflow_stream_t stream)
 {
-    const char *fn = "icpflow_object_tracks_extend";
-    if (n < 0 || P < 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: n = %d, P = %d: a negative size", n, P);
-    if (n > kMaxRows) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_extend: n = %d: at most %d rows", n, kMaxRows);
-    if (Lmax < 1) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: Lmax = %d: Lmax must be at least 1", Lmax);
-    if (Lmax > kLmax) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_extend: Lmax = %d: at most %d segments", Lmax, kLmax);
-    if (gap < 0 || gap > 63) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: gap = %d: gap must lie in [0, 63]", gap);
-    if (!(seconds > 0.0) || !std::isfinite(seconds))
-        return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: seconds = %g: seconds must be positive and finite", seconds);
-    if (!d_next_id || !params || !d_segments || !d_num || !d_counts || (n > 0 && (!d_labels || !d_track_of_row)) || (P > 0 && (!d_objects || !d_obs)))
-        return pointer_error(fn);
-    if (const int rc = check_params(fn, params)) return rc;
-    Carve c{};
-    if (!carve(d_ws, n, Lmax, &c)) return report_error(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: no workspace layout for these sizes");
-    if (!d_ws || ws_bytes < c.total) return workspace_error(fn, "icpflow_object_tracks_extend_workspace_bytes", d_ws, ws_bytes, c.total);
-    if (((uintptr_t)d_ws & 15) != 0) return report_error(ICPFLOW_E_ARG, "icpflow_object_tracks_extend: d_ws must be 16-byte aligned");
+    return extend("icpflow_object_tracks_extend", d_labels, n, Lmax, d_track_of_row, d_next_id, d_objects, P, 1, gap, seconds, params, d_segments,
+                  d_num, d_obs, d_counts, d_ws, ws_bytes, stream);
+}
 
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) {
-        ICPFLOW_TRY(hipMemsetAsync(c.num, 0, 2 * sizeof(int32_t), st));
-    } else {
-        trk_labels_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_track_of_row, n, c.trackLabel);
-        ICPFLOW_TRY(hipGetLastError());
-        ICPFLOW_TRY(icpflow::overlap::launch_links(d_labels, c.trackLabel, n, Lmax, c.num, c.num + 1, c.ov, st));
-        ICPFLOW_TRY(icpflow::overlap::launch_tables(c.ov, c.num, c.num + 1, Lmax, c.table[0], c.table[1], c.ovCounts, st));
-    }
-    trk_assign_kernel<<<1, kAssignThreads, 0, st>>>(c.num, c.table[0], Lmax, params->min_iou, d_next_id, c.segId, c.state, d_segments, d_num,
-                                                    (unsigned long long *)d_counts);
-    ICPFLOW_TRY(hipGetLastError());
-    if (n > 0) {
-        trk_relabel_kernel<<<(n + kThreads - 1) / kThreads, kThreads, 0, st>>>(c.state, c.ov.side[0].segOf, c.segId, n, d_track_of_row);
-        ICPFLOW_TRY(hipGetLastError());
-    }
-    if (P > 0) {
-        trk_obs_kernel<<<(P + kThreads - 1) / kThreads, kThreads, 0, st>>>(c.state, c.table[0], c.segId, d_objects, P, (double)gap, seconds, d_obs,
-                                                                           (unsigned long long *)d_counts);
-        ICPFLOW_TRY(hipGetLastError());
-    }
-    return ICPFLOW_OK;
+int icpflow_object_tracks_extend_side(const float *d_labels, int n, int Lmax, int32_t *d_track_of_row, int32_t *d_next_id,
+                                      const double *d_objects, int P, int side, int gap, double seconds, const icpflow_track_params_t *params,
+                                      double *d_segments, int32_t *d_num, double *d_obs, int64_t *d_counts, void *d_ws, size_t ws_bytes,
+                                      icpflow_stream_t stream)
+{
+    return extend("icpflow_object_tracks_extend_side", d_labels, n, Lmax, d_track_of_row, d_next_id, d_objects, P, side, gap, seconds, params,
+                  d_segments, d_num, d_obs, d_counts, d_ws, ws_bytes, stream);
 }
 
 int icpflow_object_tracks_fit(const double *d_obs, int M, int T, const icpflow_track_params_t *params, double *d_tracks, int64_t *d_counts,
@@ -358,6 +472,41 @@ int icpflow_object_tracks_fit(const double *d_obs, int M, int T, const icpflow_t
     if (T == 0) return ICPFLOW_OK;
     trk_fit_kernel<<<(T + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_obs, M, T, params->max_residual, params->min_speed, d_tracks,
                                                                        (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    return ICPFLOW_OK;
+}
+
+int icpflow_object_tracks_path_default_params(icpflow_track_path_params_t *params)
+{
+    if (!params) return pointer_error("icpflow_object_tracks_path_default_params");
+    params->struct_size = sizeof(icpflow_track_path_params_t);
+    params->max_dv = 1.0, params->min_speed = 0.5;
+    return ICPFLOW_OK;
+}
+
+int icpflow_object_tracks_path(const double *d_obs, const int32_t *d_step, int M, const double *d_frames, int F, int T,
+                               const icpflow_track_path_params_t *params, double *d_paths, int64_t *d_counts, icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_object_tracks_path";
+    if (M < 0 || T < 0 || F < 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_path: M = %d, T = %d, F = %d: a negative size", M, T, F);
+    if (M > kMaxFitRows || T > kMaxFitRows || F > kMaxFitRows)
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_path: M = %d, T = %d, F = %d: at most %d observations, tracks and files", M, T, F,
+                             kMaxFitRows);
+    if (M > 0 && F < 1) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_path: M = %d observations and F = %d files", M, F);
+    if (!params || !d_counts || (M > 0 && (!d_obs || !d_step)) || (F > 0 && !d_frames) || (T > 0 && !d_paths)) return pointer_error(fn);
+    if (params->struct_size != sizeof(icpflow_track_path_params_t))
+        return report_errorf(ICPFLOW_E_ARG, "%s: params->struct_size = %zu, this library's icpflow_track_path_params_t has %zu bytes", fn, params->struct_size,
+                             sizeof(icpflow_track_path_params_t));
+    if (!(params->max_dv >= 0.0) || !std::isfinite(params->max_dv))
+        return report_errorf(ICPFLOW_E_ARG, "%s: max_dv = %g: max_dv must be finite and not negative", fn, params->max_dv);
+    if (!(params->min_speed >= 0.0) || !std::isfinite(params->min_speed))
+        return report_errorf(ICPFLOW_E_ARG, "%s: min_speed = %g: min_speed must be finite and not negative", fn, params->min_speed);
+
+    hipStream_t st = (hipStream_t)stream;
+    ICPFLOW_TRY(hipMemsetAsync(d_counts, 0, ICPFLOW_TRACK_PATH_COUNTS * sizeof(int64_t), st));
+    if (T == 0) return ICPFLOW_OK;
+    trk_path_kernel<<<(T + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_obs, d_step, M, d_frames, F, T, params->max_dv, params->min_speed, d_paths,
+                                                                        (unsigned long long *)d_counts);
     ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }

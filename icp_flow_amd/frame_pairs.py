@@ -94,7 +94,7 @@ import torch
 from . import utils_eval, utils_flow, utils_objects, utils_track, utils_tracks
 # the frame pair itself and the judges of a registered one live in modules of their own; their names stay reachable here
 from .pair_data import FramePair, _input, _upload, load_frame_pair, make_resident, save_frame_pair  # noqa: F401
-from .pair_judges import (RESIDUAL_SEGMENTS_SHOWN, ObjectJudge, ResidualJudge, SegmentJudge, SightJudge, TrackJudge, TrustJudge,  # noqa: F401
+from .pair_judges import (RESIDUAL_SEGMENTS_SHOWN, LogTrackJudge, ObjectJudge, ResidualJudge, SegmentJudge, SightJudge, TrackJudge, TrustJudge,  # noqa: F401
                           _frame_objects_device, _residual_flat, _residual_unflat, _residual_zero, _source_labels, frame_objects,
                           frame_residual, frame_segment_residual, frame_segment_sight, frame_tracks, frame_trust, residual_block,
                           residual_groups, residual_tables)
@@ -320,7 +320,7 @@ def register_frame_pair_steps(args, fp, device, gap=None, asynchronous=False):
         flow = utils_flow.flow_estimation_torch(a, flow_src, pd, ls, ld, pairs, T, pose)
     out = dict(pairs=pairs, transformations=T, flow=flow, translation_frame=a.translation_frame, association=a.association_path or "host")
     # what the per-segment report (run_sequences), the residual and the objects (run_stream) and the trust bytes (run_sequences) read besides the flow
-    if getattr(args, "if_verbose", False) or getattr(args, "residual", None) or getattr(args, "save_trust", None) or getattr(args, "objects", None) or getattr(args, "tracks", None):
+    if getattr(args, "if_verbose", False) or getattr(args, "residual", None) or getattr(args, "save_trust", None) or getattr(args, "objects", None) or getattr(args, "tracks", None) or getattr(args, "tracks_log", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -582,7 +582,7 @@ def track_frame_native(a, ps, pd, ls, ld, pose=None, flow_points=None, seed=0, g
     if flow is not None:
         out["flow"] = flow
     # what the per-segment report (run_sequences), the residual and the objects (run_stream) and the trust bytes (run_sequences) read besides the flow
-    if getattr(a, "if_verbose", False) or getattr(a, "residual", None) or getattr(a, "save_trust", None) or getattr(a, "objects", None) or getattr(a, "tracks", None):
+    if getattr(a, "if_verbose", False) or getattr(a, "residual", None) or getattr(a, "save_trust", None) or getattr(a, "objects", None) or getattr(a, "tracks", None) or getattr(a, "tracks_log", None):
         out.update(labels_src=ls, labels_dst=ld)
     return out
 
@@ -1176,9 +1176,9 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     throughput of the stream, not the latency of one pair.
     Every registered frame pair -- in flight: once delivered -- then goes to the judges that `args` switches on, outside the
     timed region of one pair at a time (in flight, ms / frame pair is the wall time of the share and includes their work).
-    There are six, each described at its class in pair_judges.py: args.residual (ResidualJudge), args.residual_segments
-    (SegmentJudge), args.residual_sight (SightJudge), args.residual_trust (TrustJudge), args.objects (ObjectJudge) and args.tracks
-    (TrackJudge).  A judge is handed the frame pair's number in this rank's share (in flight: `register_in_flight`'s index) and
+    There are seven, each described at its class in pair_judges.py: args.residual (ResidualJudge), args.residual_segments
+    (SegmentJudge), args.residual_sight (SightJudge), args.residual_trust (TrustJudge), args.objects (ObjectJudge), args.tracks
+    (TrackJudge) and args.tracks_log (LogTrackJudge, which also closes its log once the last frame pair is accounted).  A judge is handed the frame pair's number in this rank's share (in flight: `register_in_flight`'s index) and
     keeps what it finds under it, so no result depends on the order in which frame pairs complete; after the one all_reduce
     each adds its keys to the summary, in the order above, and writes its file."""
     import torch.distributed as dist
@@ -1205,7 +1205,8 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
     tracks = TrackJudge(args, world, device, objects, sample_of, samples)
     if tracks.on:
         every = _by_sample(mine, args, sample_of, samples)
-    judges = [j for j in (residual, segments, sight, trust, objects, tracks) if j.on]
+    log = LogTrackJudge(args, world, device, objects)
+    judges = [j for j in (residual, segments, sight, trust, objects, tracks, log) if j.on]
 
     def account(fp, out, index=None):
         nonlocal matched, accounted
@@ -1239,6 +1240,8 @@ def run_stream(args, paths, device, rank=0, world=1, repeat=1, group=None, regis
             sync()
             times.append((time.perf_counter() - t0) / repeat * 1e3)
             account(fp, out)
+    if log.on:
+        log.close()
     for number in sorted(scores):       # (the meter's sums in the order of the frame pairs, whatever order they completed in)
         meter.update(*scores[number])
     # five weighted sums + point count + time + frame pairs + matches (+ what a judge adds): one small all_reduce
@@ -1357,6 +1360,18 @@ def argument_parser():
                     help="with --tracks: a cluster inherits a track when the two are each other's largest overlap at IoU >= I")
     ap.add_argument("--tracks-max-residual", type=float, default=utils_tracks.MAX_RESIDUAL, metavar="M",
                     help="with --tracks: a track is consistent when no gap's displacement lies more than M metres off the fitted velocity")
+    ap.add_argument("--tracks-log", nargs="?", const=True, default=None, metavar="FILE",
+                    help="object tracks over a log: the directory's frame-pair files are consecutive (file k registers sweep k onto "
+                         "sweep k + 1; the source of a file is the destination of the one before, carried over by the file's pose); "
+                         "track ids are carried from file to file by nearest rows, per track a path, a mean velocity and whether "
+                         "its velocity changes smoothly (FILE: one JSON line per track); uses --sweep-seconds, --objects-min-speed "
+                         "and --tracks-min-iou; one process only; not with --protocol reference; not for sequence files")
+    ap.add_argument("--tracks-log-radius", type=float, default=utils_tracks.CARRY_RADIUS, metavar="R",
+                    help="with --tracks-log: a row takes the id of the nearest row of the other view within R metres")
+    ap.add_argument("--tracks-log-min-share", type=float, default=utils_tracks.CARRY_MIN_SHARE, metavar="Q",
+                    help="with --tracks-log: when fewer than Q of a file's source rows find a row of the file before, the ids start afresh")
+    ap.add_argument("--tracks-log-max-dv", type=float, default=utils_tracks.MAX_DV, metavar="V",
+                    help="with --tracks-log: a track is smooth when its velocity changes by at most V m/s between adjacent files")
     ap.add_argument("--save-metrics", metavar="FILE", default=None,
                     help="--protocol reference: write the meters' per-sequence values as the reference's closing file (main.py:298-312)")
     return ap
@@ -1387,6 +1402,17 @@ def main(argv=None):
     if ns.tracks is not None and not (ns.sweep_seconds > 0 and ns.objects_min_speed >= 0 and 0 < ns.tracks_min_iou <= 1 and ns.tracks_max_residual >= 0):
         raise SystemExit("--sweep-seconds must be positive, --objects-min-speed and --tracks-max-residual must not be negative, "
                          "--tracks-min-iou must lie in (0, 1]")
+    if ns.tracks_log is not None and ns.protocol == "reference":
+        raise SystemExit("--tracks-log is not built into --protocol reference (COVERAGE.md row 19): run the frame pairs without --protocol")
+    if ns.tracks_log is not None and not (ns.sweep_seconds > 0 and ns.objects_min_speed >= 0 and 0 < ns.tracks_min_iou <= 1 and
+                                          1e-3 <= ns.tracks_log_radius <= 1e3 and 0 <= ns.tracks_log_min_share <= 1 and ns.tracks_log_max_dv >= 0):
+        raise SystemExit("--sweep-seconds must be positive, --objects-min-speed and --tracks-log-max-dv must not be negative, --tracks-min-iou "
+                         "must lie in (0, 1], --tracks-log-radius in [1e-3, 1e3] metres, --tracks-log-min-share in [0, 1]")
+    if ns.tracks_log is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--tracks-log under more than one rank: a log's files would have to meet on one rank in their order, which is not built")
+    if ns.tracks_log is not None and any(is_sequence(p) for p in list_frame_pairs(ns.directory)):
+        raise SystemExit("--tracks-log takes frame-pair files: which sweep consecutive multi-frame samples share is not in a sequence file "
+                         "(utils_tracks.TrackState(track_of_row=...) composes that case)")
     if ns.save_trust is not None and not ns.save_flows:
         raise SystemExit("--save-trust goes with --save-flows (the bytes go into the saved flow's file)")
     if ns.save_trust is not None and len(ns.save_trust) not in (0, 3):
@@ -1478,6 +1504,9 @@ def main(argv=None):
             raise SystemExit("--tracks under more than one rank: a sample's gaps would have to meet on one rank, which is not built")
         args.tracks, args.sweep_seconds, args.objects_min_speed = ns.tracks, ns.sweep_seconds, ns.objects_min_speed
         args.tracks_min_iou, args.tracks_max_residual = ns.tracks_min_iou, ns.tracks_max_residual
+    if ns.tracks_log is not None:
+        args.tracks_log, args.sweep_seconds, args.objects_min_speed, args.tracks_min_iou = ns.tracks_log, ns.sweep_seconds, ns.objects_min_speed, ns.tracks_min_iou
+        args.tracks_log_radius, args.tracks_log_min_share, args.tracks_log_max_dv = ns.tracks_log_radius, ns.tracks_log_min_share, ns.tracks_log_max_dv
     summary = run_stream(args, list_frame_pairs(ns.directory), device, rank, world, ns.repeat, in_flight=ns.in_flight)
     if rank == 0:
         if ns.residual is not None:

@@ -3,14 +3,14 @@
 The device functions take a FramePair and what its registration returned (dict(pairs, transformations, flow, ...)):
 `frame_residual` (the nearest-neighbour residual, icpflow_nn_residual), `frame_segment_residual` (per segment of the source),
 `frame_segment_sight` (with the line of sight beside it, icpflow_sight_*), `frame_trust` (one trust byte per source point),
-`frame_objects` (a box and a velocity per matched pair) and `frame_tracks` (a sample's objects linked across its gaps); the
-`residual_*` helpers carry the residual's tables through the all_reduce and in and out of the summary's block.
+`frame_objects` (a box and a velocity per matched pair), `frame_tracks` (a sample's objects linked across its gaps) and
+`log_tracks` (a log's objects linked from file to file); the `residual_*` helpers carry the residual's tables through the all_reduce and in and out of the summary's block.
 
 Below them one plain class per judge: its constructor reads its attributes of `args` and raises on a bad combination,
 `account(number, fp, out)` judges one registered frame pair (`timed` brackets the device work), `summarise(out)` adds its keys
 to the summary and writes its file; the residual alone has `reduce_words` / `take_words`, its ride on the closing all_reduce.
-frame_pairs.run_stream builds the six in one place and calls them in that order; what one judge needs of another is a
-constructor argument."""
+The log's tracks alone have `close`, called once the stream's last frame pair is accounted.  frame_pairs.run_stream builds the
+seven in one place and calls them in that order; what one judge needs of another is a constructor argument."""
 import contextlib
 import json
 import time
@@ -162,6 +162,116 @@ def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, m
         state.extend(ld, rows, fp.gap, seconds)
     state.fit()
     return state.read()
+
+
+def log_frames(poses):
+    """The frames of a log's files for icpflow_object_tracks_path, on the host in float64: file k's destination frame into the
+    log's frame (file 0's destination frame).  poses: FramePair.pose_exact of every file, in order -- pose k carries sweep k's
+    frame into sweep k + 1's.  W_0 = I, W_{k+1} = W_k inverse(pose_{k+1}), the inverse of a rigid pose (R, t) being (R^T, -R^T t).
+    -> float64 [F, 12]: the rotation row-major, then the translation"""
+    W, out = np.eye(4), []
+    for k, pose in enumerate(poses):
+        if k > 0:
+            P = np.asarray(pose, np.float64).reshape(4, 4)
+            inv = np.eye(4)
+            inv[:3, :3] = P[:3, :3].T
+            inv[:3, 3] = -(P[:3, :3].T @ P[:3, 3])
+            W = W @ inv
+        out.append(np.concatenate([W[:3, :3].reshape(9), W[:3, 3]]))
+    return np.array(out, np.float64).reshape(len(out), 12)
+
+
+class LogChain:
+    """The object tracks of ONE log (utils_tracks, include/icpflow_hip.h 8(l)), everything on the device: `add` takes the log's
+    registered frame pairs in file order -- file k registers sweep k onto sweep k + 1, so the destination of one file is the
+    source of the next, in another frame and with other rows.  Per file: the ids of the previous file's destination rows are
+    carried onto this file's source rows by nearest rows under this file's pose (icpflow_rows_carry; all -1 for the first file
+    or after a break), the source clusters are linked to them (icpflow_object_tracks_extend_side, side 0, one running id
+    counter), and the destination rows take the ids of their pairs (icpflow_pair_row_ids), kept with the destination points
+    for the next file -- nothing older is kept.  `read` closes the log: one icpflow_object_tracks_path and ONE read-back."""
+
+    def __init__(self, device, sweep_seconds=utils_objects.SWEEP_SECONDS, min_speed=utils_tracks.MIN_SPEED, min_iou=utils_tracks.MIN_IOU,
+                 radius=utils_tracks.CARRY_RADIUS, min_share=utils_tracks.CARRY_MIN_SHARE, max_dv=utils_tracks.MAX_DV, Lmax=4096):
+        from . import _lib
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("icp_flow_amd: the tracks live on a GPU (HIP) device -- there is no CPU path")
+        self.sweep_seconds, self.min_speed, self.min_iou, self.Lmax = float(sweep_seconds), float(min_speed), float(min_iou), int(Lmax)
+        self.radius, self.min_share = float(radius), float(min_share)
+        self.params = _lib.TrackPathParams.defaults(max_dv=max_dv, min_speed=min_speed)
+        self.next_id = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.bound = 0                           # no track id reaches this
+        self.last = None                         # (points_dst, the ids of its rows) of the file before
+        self.obs, self.carry_counts, self.extend_counts, self.poses, self.names, self.source_rows = [], [], [], [], [], []
+
+    def add(self, fp, out):
+        """one file, enqueued on the current stream; nothing is read back"""
+        device = self.device
+        seconds = float(fp.gap) * self.sweep_seconds
+        rows, _, ld = _frame_objects_device(fp, out, device, seconds, self.min_speed)
+        ps, pd, ls = _input(fp, "points_src", device), _input(fp, "points_dst", device), _source_labels(fp, out, device)
+        n = int(ps.shape[0])
+        if self.last is None:
+            prior = torch.full((n,), -1, dtype=torch.int32, device=device)
+            carried = torch.zeros(6, dtype=torch.int64, device=device)
+        else:
+            prior, carried = utils_tracks.rows_carry_device(self.last[0], self.last[1], fp.pose_exact, ps, self.radius, self.min_share)
+        state = utils_tracks.TrackState(n, device, self.Lmax, self.min_iou, min_speed=self.min_speed, track_of_row=prior, next_id=self.next_id,
+                                        bound=self.bound)
+        _, _, obs, counts = state.extend(ls, rows, 0, seconds, side=0)
+        self.bound = state.bound
+        weight = rows[:, 22] if rows.shape[0] else None       # the pairs' source points: a strided view, taken as it is
+        ids, _ = utils_tracks.pair_row_ids_device(ld, out["pairs"].to(device), 1, obs[:, 0].to(torch.int32), weight)
+        self.last = (pd, ids)
+        self.obs.append(obs), self.carry_counts.append(carried), self.extend_counts.append(counts)
+        self.poses.append(np.asarray(fp.pose_exact, np.float64)), self.names.append(fp.name), self.source_rows.append(n)
+
+    def read(self):
+        """-> utils_tracks.LogTracks: the table over the whole log, every file's counts and observations in ONE transfer"""
+        from . import _lib
+        import ctypes
+        device, F = self.device, len(self.obs)
+        every = torch.cat(self.obs) if self.obs else torch.empty((0, _lib.TRACK_OBS_COLS), dtype=torch.float64, device=device)
+        M, T = int(every.shape[0]), self.bound
+        step_host = np.repeat(np.arange(F, dtype=np.int32), [int(o.shape[0]) for o in self.obs]) if F else np.zeros(0, np.int32)
+        frames_host = log_frames(self.poses)
+        step, frames = torch.from_numpy(step_host).to(device), torch.from_numpy(frames_host).to(device)
+        paths = torch.empty((T, _lib.TRACK_PATH_COLS), dtype=torch.float64, device=device)
+        counts = torch.empty(_lib.TRACK_PATH_COUNTS, dtype=torch.int64, device=device)
+        with torch.cuda.device(device):
+            _lib.call("icpflow_object_tracks_path", _lib.ptr(every) if M else None, _lib.ptr(step) if M else None, M, _lib.ptr(frames) if F else None, F, T,
+                      ctypes.byref(self.params), _lib.ptr(paths) if T else None, _lib.ptr(counts), _lib.stream(device))
+        f64 = lambda t: t.to(torch.float64).reshape(-1)     # noqa: E731  (ids and counts are exact in a float64)
+        parts = [f64(self.next_id), f64(counts)] + [f64(c) for c in self.carry_counts] + [f64(c) for c in self.extend_counts] + [every.reshape(-1), paths.reshape(-1)]
+        host = torch.cat(parts).cpu().numpy()             # the one read-back
+        at = 0
+
+        def take(k):
+            nonlocal at
+            at += k
+            return host[at - k: at]
+
+        next_id = int(take(1)[0])
+        path_counts = np.rint(take(5)).astype(np.int64)
+        carry = [np.rint(take(6)).astype(np.int64) for _ in range(F)]
+        extend = [np.rint(take(6)).astype(np.int64) for _ in range(F)]
+        table = take(M * 13).reshape(M, 13)
+        observations = np.split(table, np.cumsum([int(o.shape[0]) for o in self.obs])[:-1]) if F else []
+        rows = take(T * 24).reshape(T, 24)[:next_id]
+        path_counts[0] = next_id                        # (the call counted the bound's rows; the tracks are the ids handed out)
+        params = dict(self.params.as_dict(), radius=self.radius, min_share=self.min_share, min_iou=self.min_iou, sweep_seconds=self.sweep_seconds)
+        return utils_tracks.LogTracks(rows, path_counts, next_id, observations, carry, extend, frames_host, self.names, self.source_rows, params)
+
+
+def log_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, min_speed=utils_tracks.MIN_SPEED, min_iou=utils_tracks.MIN_IOU,
+               radius=utils_tracks.CARRY_RADIUS, min_share=utils_tracks.CARRY_MIN_SHARE, max_dv=utils_tracks.MAX_DV, Lmax=4096):
+    """The object tracks of one log: `fps` its frame pairs in file order (the destination sweep of one is the source sweep of the
+    next, carried over by the next one's pose) and `outs` their registrations -- `LogChain.add` for each, then its `read`.
+    -> utils_tracks.LogTracks"""
+    chain = LogChain(device, sweep_seconds, min_speed, min_iou, radius, min_share, max_dv, Lmax)
+    for fp, out in zip(fps, outs):
+        chain.add(fp, out)
+    return chain.read()
 
 
 RESIDUAL_SEGMENTS_SHOWN = 50     # entries of the summary's `residual_segments` block (the file takes all of them)
@@ -466,3 +576,63 @@ class TrackJudge:
                 for s in sorted(self.lines):        # one JSON line per sample, in their order
                     f.write(json.dumps(self.lines[s]) + "\n")
             out["tracks_file"] = self.file
+
+
+class LogTrackJudge:
+    """args.tracks_log = True or a file name (`--tracks-log [FILE]`; one process only; independent of args.tracks and
+    args.objects): the objects of a LOG linked from file to file -- the frame pairs of the stream are consecutive files, file k
+    registers sweep k onto sweep k + 1 -- by `LogChain`: the files are added in the stream's order whatever order they complete
+    in (a file that completes early waits for the ones before it), and `close`, once the stream is through, reads the whole log
+    back at once.  It uses the ObjectJudge's args.sweep_seconds and args.objects_min_speed and adds args.tracks_log_radius
+    (default 0.02 m), args.tracks_log_min_share (default 0.5) and args.tracks_log_max_dv (default 1.0 m/s).  The summary gains
+    `tracks_log` (files, tracks, observed, judged, smooth, rough, moving, breaks, carried_rows, rows, overflow, the parameters)
+    and `ms_tracks_log_per_file` (device-synchronised around every file's chain and around the closing call with its read-back);
+    with a file name, one JSON line per track is written there (its table row, and per object row of the track its step, file,
+    pair and velocity in the log's frame) and the summary names it as `tracks_log_file`.  Where the ObjectJudge keeps lines,
+    every object entry gains `log_track`.  A frame pair of a multi-frame sample is refused: which sweeps consecutive samples
+    share is not in their files."""
+
+    def __init__(self, args, world, device, objects):
+        self.file = getattr(args, "tracks_log", None)
+        self.on = bool(self.file)
+        if self.file and world > 1:
+            raise ValueError("args.tracks_log under more than one rank: a log's files would have to meet on one rank in their order, which is not built")
+        self.device, self.objects = device, objects
+        self.waiting, self.next, self.ms, self.numbers = {}, 0, [], []
+        self.chain = None
+        if self.on:
+            self.chain = LogChain(device, objects.sweep_seconds, objects.min_speed, float(getattr(args, "tracks_min_iou", utils_tracks.MIN_IOU)),
+                                  float(getattr(args, "tracks_log_radius", utils_tracks.CARRY_RADIUS)),
+                                  float(getattr(args, "tracks_log_min_share", utils_tracks.CARRY_MIN_SHARE)),
+                                  float(getattr(args, "tracks_log_max_dv", utils_tracks.MAX_DV)))
+
+    def account(self, number, fp, out):
+        if fp.sequence is not None:
+            raise ValueError(f"args.tracks_log: {fp.name!r} is a gap of a multi-frame sample; a log is a stream of frame-pair files "
+                             "(utils_tracks.TrackState(track_of_row=...) composes logs of samples)")
+        self.waiting[number] = (fp, out)
+        while self.next in self.waiting:          # in the stream's order, whatever order the frame pairs completed in
+            fp, out = self.waiting.pop(self.next)
+            with timed(self.device, self.ms):
+                self.chain.add(fp, out)
+            self.numbers.append(self.next)
+            self.next += 1
+
+    def close(self):
+        """after the stream's last frame pair: the table over the log, the one read-back, the ids into the ObjectJudge's lines"""
+        if self.waiting:
+            raise RuntimeError(f"args.tracks_log: frame pairs {sorted(self.waiting)} arrived, {self.next} never did")
+        with timed(self.device, self.ms):
+            self.seen = self.chain.read()
+        for k, ids in zip(self.numbers, self.seen.observation_ids):
+            for e in self.objects.lines.get(k, {}).get("objects", []):
+                e["log_track"] = int(ids[e["pair"]])
+
+    def summarise(self, out):
+        out["tracks_log"] = dict(self.seen.summary(), **self.seen.params)
+        out["ms_tracks_log_per_file"] = sum(self.ms) / max(len(self.numbers), 1)
+        if isinstance(self.file, str):
+            with open(self.file, "w") as f:
+                for e in self.seen.as_list():       # one JSON line per track, in the order of the ids
+                    f.write(json.dumps(e) + "\n")
+            out["tracks_log_file"] = self.file

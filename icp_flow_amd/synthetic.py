@@ -182,3 +182,120 @@ def make_sequence(seed=0, num_frames=3, n_objects=10, n_min=60, n_max=600, speed
     return dict(raw_points=np.concatenate(raw).astype(np.float32), time_indice=np.concatenate(tim).astype(np.int64),
                 ego_motion_gt=np.stack(poses).astype(np.float64), nonground=np.concatenate(ng),
                 scene_flow=np.concatenate(sf).astype(np.float32))
+
+
+# ---- a log: consecutive frame-pair files that share their sweeps ------------------------------------------------------------
+LOG_SWEEP_SECONDS = 0.1
+LOG_CLUSTER = dict(cluster="dbscan", epsilon=0.25, min_cluster_size=10, num_clusters=200)     # what make_log is made for
+# the objects of a log, in the world frame (the sensor frame of sweep 0): centre at sweep 0, metres per sweep, size (a width of
+# 0: a wall, one face).  Object LOG_BRAKING loses 3 m/s from file LOG_BRAKE_FILE on; object LOG_LATE is first seen in sweep
+# LOG_LATE_FILE (the source of that file); the wall stands.
+LOG_CENTRES = np.array([[12.0, 8.0, 0.0], [-10.0, 12.0, 0.0], [14.0, -12.0, 0.0], [-12.0, -10.0, 0.0], [0.0, 20.0, 0.0], [22.0, 0.0, 0.0]])
+LOG_STEPS = np.array([[0.4, 0.0, 0.0], [-0.2, 0.3, 0.0], [0.5, 0.0, 0.0], [0.0, -0.35, 0.0], [0.3, 0.1, 0.0], [0.0, 0.0, 0.0]])
+LOG_SIZES = np.array([[3.0, 1.6, 1.0], [3.0, 1.6, 1.0], [3.0, 1.6, 1.0], [2.4, 1.4, 1.0], [3.0, 1.6, 1.0], [6.0, 0.0, 1.0]])
+LOG_BRAKING, LOG_BRAKE_FILE, LOG_BRAKE_LOSS = 2, 3, np.array([0.3, 0.0, 0.0])       # 0.3 m per 0.1 s sweep: 3 m/s
+LOG_LATE, LOG_LATE_FILE, LOG_WALL = 4, 2, 5
+
+
+def _box_faces(rng, size, spacing=0.1, jitter=0.03):
+    """points on the four vertical faces of a box (a wall: one face), a jittered grid: every point has neighbours within
+    spacing + 2 jitter along its face"""
+    L, W, H = size
+    corners = [(-L / 2, -W / 2), (L / 2, -W / 2), (L / 2, W / 2), (-L / 2, W / 2)]
+    edges = [(corners[k], corners[(k + 1) % 4]) for k in range(4)] if W > 0 else [((-L / 2, 0.0), (L / 2, 0.0))]
+    pts = []
+    for (x0, y0), (x1, y1) in edges:
+        steps = int(round(np.hypot(x1 - x0, y1 - y0) / spacing))
+        for a in (np.arange(steps) + 0.5) / steps:
+            for z in np.arange(-H / 2 + spacing / 2, H / 2, spacing):
+                pts.append((x0 + a * (x1 - x0), y0 + a * (y1 - y0), z))
+    pts = np.array(pts)
+    return pts + rng.uniform(-jitter, jitter, pts.shape)
+
+
+def log_centre(k, sweep):
+    """the world position of object k's centre at `sweep`: its step per sweep, less what the braking object loses per sweep from
+    sweep LOG_BRAKE_FILE on"""
+    late = max(sweep - LOG_BRAKE_FILE, 0) if k == LOG_BRAKING else 0
+    return LOG_CENTRES[k] + sweep * LOG_STEPS[k] - late * LOG_BRAKE_LOSS
+
+
+def make_log(seed=0, files=6, ego_speed=8.0, ego_yaw_rate_deg=15.0, drop=0.1, noise=0.005, ground_spacing=1.0, extra=0):
+    """A log of `files` consecutive frame-pair files for unlabelled use with LOG_CLUSTER: file k registers sweep k onto sweep
+    k + 1.  An ego vehicle at `ego_speed` m/s with a yaw rate; boxes at constant velocity, one that loses 3 m/s between two
+    files, one that appears in file LOG_LATE_FILE, a static wall, and ground (flagged, as ground removal upstream leaves it).
+    Every sweep is sampled ONCE, in its own sensor frame; its two views -- the destination of file k - 1 and the source of file
+    k -- are made differently: each is shuffled by a permutation of its own, each drops `drop` of the rows independently, they
+    are cropped differently (the destination to a square of 30 m, the source to a circle of 33 m), and the source view is
+    stored as the float32 of the float64 product with the file's pose, which carries sweep k's frame into sweep k + 1's.
+    extra (the timing tool's; the tests leave it 0): that many more boxes at up to 1.5 m/s on the free cells of a 7.5 m grid;
+    ground_spacing sets the rows of a sweep.
+    -> (pairs, truth): pairs a list of dicts(points_src, points_dst, pose, nonground_src, nonground_dst), what
+    pair_data.FramePair takes; truth dict(ids_src, ids_dst: per file the object of every row, -1 for ground, -2 for a few isolated points; velocity float64
+    [objects, files, 3]: every object's true velocity over file k in the LOG's frame, the destination frame of file 0; seen
+    bool [objects, files])"""
+    rng = np.random.default_rng(77_000_003 + seed)
+    dt = LOG_SWEEP_SECONDS
+    shapes = [_box_faces(rng, s) for s in LOG_SIZES]
+    more = []                                              # (centre, step) of the extra boxes
+    if extra:
+        cells = [(x, y) for x in np.arange(-26.0, 27.0, 7.5) for y in np.arange(-26.0, 27.0, 7.5)
+                 if min(np.hypot(x - log_centre(j, k)[0], y - log_centre(j, k)[1]) for j in range(len(LOG_SIZES)) for k in (0, files)) > 7.0]
+        for x, y in [cells[i] for i in rng.permutation(len(cells))[:extra]]:
+            more.append((np.array([x, y, 0.0]), np.append(rng.uniform(-0.15, 0.15, 2), 0.0)))
+            shapes.append(_box_faces(rng, np.array([rng.uniform(2.0, 3.0), rng.uniform(1.2, 1.8), 1.0])))
+    span = 34.0
+    axis = np.arange(-span, span + 1e-9, ground_spacing)
+    gx, gy = np.meshgrid(axis, axis, indexing="ij")
+
+    def rz(a):
+        c, s_ = np.cos(a), np.sin(a)
+        return np.array([[c, -s_, 0.0], [s_, c, 0.0], [0.0, 0.0, 1.0]])
+
+    ego = []                                               # sensor frame of sweep k -> world
+    at, yaw = np.zeros(3), 0.0
+    for k in range(files + 1):
+        E = np.eye(4)
+        E[:3, :3], E[:3, 3] = rz(yaw), at
+        ego.append(E)
+        yaw += np.radians(ego_yaw_rate_deg) * dt
+        at = at + rz(yaw) @ np.array([ego_speed * dt, 0.0, 0.0])
+    sweeps = []
+    for k in range(files + 1):
+        pts, obj = [], []
+        for j, local in enumerate(shapes):
+            if j == LOG_LATE and k < LOG_LATE_FILE:
+                continue
+            centre = log_centre(j, k) if j < len(LOG_SIZES) else more[j - len(LOG_SIZES)][0] + k * more[j - len(LOG_SIZES)][1]
+            world = local + centre + np.array([0.0, 0.0, 0.8]) + rng.normal(0.0, noise, local.shape)
+            pts.append((world - ego[k][:3, 3]) @ ego[k][:3, :3])          # R^T (x - t), row vectors
+            obj.append(np.full(len(local), j))
+        ground = np.stack([gx.reshape(-1), gy.reshape(-1), np.zeros(gx.size)], axis=1) + rng.uniform(-0.3, 0.3, (gx.size, 3)) * np.array([1.0, 1.0, 0.05])
+        pts.append(ground), obj.append(np.full(len(ground), -1))
+        # a few isolated points as noise (the reference's keep_largest drops the first label unseen, which is the noise label only
+        # when there is noise)
+        lonely = np.stack([np.linspace(-12.0, 12.0, 6), np.full(6, 27.0), np.full(6, 0.5)], axis=1) + rng.uniform(-0.2, 0.2, (6, 3))
+        pts.append(lonely), obj.append(np.full(6, -2))
+        sweeps.append((np.concatenate(pts), np.concatenate(obj)))
+
+    def view(points, obj, keep):
+        rows = np.flatnonzero(keep)
+        rows = rows[rng.permutation(len(rows))]
+        rows = rows[: len(rows) - int(round(drop * len(rows)))]
+        return points[rows], obj[rows]
+
+    pairs, ids_src, ids_dst = [], [], []
+    for k in range(files):
+        pose = np.linalg.inv(ego[k + 1]) @ ego[k]
+        p, o = sweeps[k]
+        src, src_obj = view(p, o, np.hypot(p[:, 0], p[:, 1]) < 33.0)
+        src = (src @ pose[:3, :3].T + pose[:3, 3]).astype(np.float32)     # the float64 product, then narrowed
+        p, o = sweeps[k + 1]
+        dst, dst_obj = view(p, o, (np.abs(p[:, 0]) < 30.0) & (np.abs(p[:, 1]) < 30.0))
+        pairs.append(dict(points_src=src, points_dst=dst.astype(np.float32), pose=pose, nonground_src=src_obj != -1, nonground_dst=dst_obj != -1))
+        ids_src.append(src_obj), ids_dst.append(dst_obj)
+    to_log = ego[1][:3, :3].T                                # world -> the destination frame of file 0
+    velocity = np.array([[to_log @ ((log_centre(j, k + 1) - log_centre(j, k)) / dt) for k in range(files)] for j in range(len(LOG_SIZES))]
+                        + [[to_log @ (step / dt)] * files for _, step in more])
+    seen = np.array([[not (j == LOG_LATE and k < LOG_LATE_FILE) for k in range(files)] for j in range(len(shapes))])
+    return pairs, dict(ids_src=ids_src, ids_dst=ids_dst, velocity=velocity, seen=seen)

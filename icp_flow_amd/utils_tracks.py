@@ -6,7 +6,13 @@ rows say which clusters are the same object (`label_overlap_device`); `TrackStat
 to gap and turns the gap's object rows (utils_objects) into observations; `TrackState.fit` fits d = s v per track over all
 gaps.  min_iou, max_residual and min_speed are stated policies, like KEEP of the trust byte.
 
-Everything stays on the device until `TrackState.read` reads it back, once.  There is no CPU path."""
+Across the files of a LOG (8(l); csrc/carry.hip) the shared sweep is the destination of one file and the source of the next, in
+another frame and with other rows: `rows_carry_device` carries the ids by nearest rows under the file's pose, a `TrackState`
+seeded with them links the file's SOURCE clusters (`extend(side=0)`), `pair_row_ids_device` hands the ids to the destination
+rows for the next file, and `LogTracks` is the table over the log (pair_judges.LogChain runs the chain).  The radius, min_share
+and max_dv are stated policies too.
+
+Everything stays on the device until `TrackState.read` (`LogChain.read`) reads it back, once.  There is no CPU path."""
 import ctypes
 
 import numpy as np
@@ -15,6 +21,10 @@ MIN_IOU = 0.5
 MAX_RESIDUAL = 0.2            # metres
 MIN_SPEED = 0.5               # m/s (utils_objects.MIN_SPEED)
 MAX_ID = 1 << 24
+CARRY_RADIUS = 0.02           # metres: far above the float32 rounding of a pose product at 100 m (8e-6 m), below the spacing at
+                              # which a wrong neighbour would belong to another cluster -- a stated policy
+CARRY_MIN_SHARE = 0.5         # fewer rows of a view with a partner in the other: the chain of ids breaks and starts afresh
+MAX_DV = 1.0                  # m/s between adjacent steps: 10 cm per 0.1 s sweep
 
 
 def label_overlap_device(labels_a, labels_b, Lmax=4096):
@@ -38,26 +48,89 @@ def label_overlap_device(labels_a, labels_b, Lmax=4096):
     return tables[0], nums[0], tables[1], nums[1], counts
 
 
+def rows_carry_device(prev, prev_id, pose, nxt, radius=CARRY_RADIUS, min_share=CARRY_MIN_SHARE):
+    """icpflow_rows_carry enqueued on the current stream, nothing read back.  prev float32 [m, 3] and prev_id int32 [m]: one view
+    of a sweep and an id per row (device tensors); pose: a 4 x 4 on the HOST that maps prev's coordinates into nxt's; nxt
+    float32 [n, 3]: the other view.  -> (ids int32 [n], counts int64 [6]) on the device: the id of the nearest moved row within
+    `radius`, all -1 when fewer than min_share * n rows found one (counts[5])."""
+    import torch
+    from . import _lib
+    _lib.require_gpu(prev, prev_id, nxt)
+    a, b = prev.to(torch.float32).contiguous(), nxt.to(torch.float32).contiguous()
+    ids = prev_id.to(torch.int32).contiguous()
+    m, n, device = int(a.shape[0]), int(b.shape[0]), b.device
+    if tuple(a.shape) != (m, 3) or tuple(b.shape) != (n, 3) or tuple(ids.shape) != (m,) or a.device != device or ids.device != device:
+        raise ValueError(f"rows_carry: views {tuple(a.shape)} and {tuple(b.shape)}, ids {tuple(ids.shape)}: expected [m, 3], [n, 3] and [m] on one device")
+    h_pose = np.ascontiguousarray(np.asarray(pose, np.float64).reshape(16))
+    out = torch.empty(n, dtype=torch.int32, device=device)
+    counts = torch.empty(_lib.CARRY_COUNTS, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        ws = _lib.workspace(device, int(_lib._L.icpflow_rows_carry_workspace_bytes(n, m)))
+        _lib.call("icpflow_rows_carry", _lib.ptr(a) if m else None, _lib.ptr(ids) if m else None, m, h_pose.ctypes.data_as(ctypes.c_void_p),
+                  _lib.ptr(b) if n else None, n, float(radius), float(min_share), _lib.ptr(out) if n else None, None, None, _lib.ptr(counts),
+                  _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    return out, counts
+
+
+def pair_row_ids_device(labels, pair_rows, col, pair_id, weight=None):
+    """icpflow_pair_row_ids enqueued on the current stream.  labels [n] of one side of a frame pair, pair_rows float32 [P, >= 2]
+    (column 0 the source label, column 1 the destination label), col 0 or 1: that side; pair_id int32 [P]; weight: a float64
+    COLUMN of P values (a strided view such as objects_rows[:, 22] is taken as it is), or None.  -> (ids int32 [n], counts
+    int64 [3]) on the device."""
+    import torch
+    from . import _lib
+    _lib.require_gpu(labels, pair_rows, pair_id, weight)
+    lab = labels.to(torch.float32).contiguous()
+    n, device = int(lab.shape[0]), lab.device
+    P = 0 if pair_rows is None else int(pair_rows.shape[0])
+    rows = pid = None
+    stride, wstride = 2, 1
+    if P > 0:
+        rows, pid = pair_rows.to(torch.float32).contiguous(), pair_id.to(torch.int32).contiguous()
+        stride = int(rows.shape[1])
+        if rows.dim() != 2 or stride < 2 or tuple(pid.shape) != (P,) or rows.device != device or pid.device != device:
+            raise ValueError(f"pair_row_ids: pair rows {tuple(rows.shape)}, ids {tuple(pid.shape)}: expected [P, >= 2] and [P] on the labels' device")
+        if weight is not None:
+            if weight.dtype != torch.float64 or tuple(weight.shape) != (P,) or weight.device != device or (P > 1 and weight.stride(0) < 1):
+                raise ValueError(f"pair_row_ids: weights {tuple(weight.shape)} {weight.dtype}, expected float64 [P] on the labels' device")
+            wstride = int(weight.stride(0)) if P > 1 else 1
+    out = torch.empty(n, dtype=torch.int32, device=device)
+    counts = torch.empty(_lib.PAIR_ROW_ID_COUNTS, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        ws = _lib.workspace(device, int(_lib._L.icpflow_pair_row_ids_workspace_bytes(P)))
+        _lib.call("icpflow_pair_row_ids", _lib.ptr(lab) if n else None, n, _lib.ptr(rows), P, stride, int(col), _lib.ptr(pid),
+                  ctypes.c_void_p(weight.data_ptr()) if (P > 0 and weight is not None) else None, wstride, _lib.ptr(out) if n else None,
+                  _lib.ptr(counts), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream(device))
+    return out, counts
+
+
 class TrackState:
     """The tracks of ONE shared sweep of n rows, on the device: a track id per row and the next free id, carried from gap to gap
-    by `extend`; `fit` and `read` close the sample."""
+    by `extend`; `fit` and `read` close the sample.  track_of_row int32 [n] and next_id int32 [1] (device tensors, taken BY
+    REFERENCE and written by `extend`) seed the state with ids carried over from elsewhere (`rows_carry_device`) and a running
+    id counter, for tracks that outlive a sample; `bound`: an upper bound of that counter on entry."""
 
-    def __init__(self, n, device, Lmax=4096, min_iou=MIN_IOU, max_residual=MAX_RESIDUAL, min_speed=MIN_SPEED):
+    def __init__(self, n, device, Lmax=4096, min_iou=MIN_IOU, max_residual=MAX_RESIDUAL, min_speed=MIN_SPEED, track_of_row=None, next_id=None,
+                 bound=0):
         import torch
         from . import _lib
         self.n, self.device, self.Lmax = int(n), torch.device(device), int(Lmax)
         if self.device.type != "cuda":
             raise RuntimeError("icp_flow_amd: the tracks live on a GPU (HIP) device -- there is no CPU path")
         self.params = _lib.TrackParams.defaults(min_iou=min_iou, max_residual=max_residual, min_speed=min_speed)
-        self.track_of_row = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
-        self.next_id = torch.zeros(1, dtype=torch.int32, device=self.device)
+        for name, t, shape in (("track_of_row", track_of_row, (self.n,)), ("next_id", next_id, (1,))):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"TrackState: {name} {tuple(t.shape)} {t.dtype} on {t.device}, expected contiguous int32 {list(shape)} on {self.device}")
+        self.track_of_row = torch.full((self.n,), -1, dtype=torch.int32, device=self.device) if track_of_row is None else track_of_row
+        self.next_id = torch.zeros(1, dtype=torch.int32, device=self.device) if next_id is None else next_id
         self.obs, self.gaps, self.segments, self.counts = [], [], [], []
-        self.bound = 0                       # no track id reaches this: every gap founds at most min(n, Lmax) tracks
+        self.bound = int(bound)              # no track id reaches this: every gap founds at most min(n, Lmax) tracks
         self.tracks = self.fit_counts = None
 
-    def extend(self, labels, objects_rows, gap, seconds):
+    def extend(self, labels, objects_rows, gap, seconds, side=1):
         """One gap: labels [n] of the shared sweep under this gap's clustering, objects_rows float64 [P, 24] (or None) the gap's
-        table of utils_objects.pair_objects_device.  Enqueued on the current stream.  -> (segments float64 [Lmax, 6], num int32
+        table of utils_objects.pair_objects_device.  side 1: the sweep is the pairs' destination (a sample's gaps); side 0: it is
+        their source (the files of a log).  Enqueued on the current stream.  -> (segments float64 [Lmax, 6], num int32
         [1], obs float64 [P, 13], counts int64 [6]) on the device, kept for `read` as well."""
         import torch
         from . import _lib
@@ -77,8 +150,8 @@ class TrackState:
         counts = torch.empty(_lib.TRACK_EXTEND_COUNTS, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             ws = _lib.workspace(self.device, int(_lib._L.icpflow_object_tracks_extend_workspace_bytes(self.n, self.Lmax)))
-            _lib.call("icpflow_object_tracks_extend", _lib.ptr(lab) if self.n else None, self.n, self.Lmax,
-                      _lib.ptr(self.track_of_row) if self.n else None, _lib.ptr(self.next_id), _lib.ptr(rows), P, int(gap), float(seconds),
+            _lib.call("icpflow_object_tracks_extend_side", _lib.ptr(lab) if self.n else None, self.n, self.Lmax,
+                      _lib.ptr(self.track_of_row) if self.n else None, _lib.ptr(self.next_id), _lib.ptr(rows), P, int(side), int(gap), float(seconds),
                       ctypes.byref(self.params), _lib.ptr(segments), _lib.ptr(num), _lib.ptr(obs) if P else None, _lib.ptr(counts), _lib.ptr(ws),
                       ctypes.c_size_t(ws.numel()), _lib.stream(self.device))
         self.obs.append(obs), self.gaps.append(int(gap)), self.segments.append((segments, num)), self.counts.append(counts)
@@ -160,5 +233,64 @@ def format_tracks(tracks):
     for e in tracks:
         lines.append(f"{e['track']:7d}{e['observations']:7d}{e['velocity'][0]:9.2f}{e['velocity'][1]:9.2f}{e['velocity'][2]:9.2f}{e['speed']:9.2f}"
                      f"{e['residual_max']:10.3f}{yes(e['moving']):>8}{yes(e['judged']):>8}{yes(e['consistent']):>12}"
+                     f"{e['size'][0]:9.2f}{e['size'][1]:9.2f}{e['size'][2]:9.2f}{e['points']:8d}")
+    return lines
+
+
+class LogTracks:
+    """The tracks of one log on the host (icpflow_object_tracks_path's table, read back once): rows [tracks, 24], the table's
+    five counts, and per file its observations ([P, 13], column 0 the track of every object row), its six carry counts and its
+    six extend counts; frames [F, 12]: every file's destination frame in the log's frame; names: the files."""
+
+    def __init__(self, rows, path_counts, next_id, observations, carry_counts, extend_counts, frames, names, source_rows, params):
+        self.rows = np.asarray(rows, np.float64).reshape(-1, 24)
+        self.path_counts = np.asarray(path_counts, np.int64).reshape(5)
+        self.next_id, self.params, self.names = int(next_id), dict(params), list(names)
+        self.observations = [np.asarray(o, np.float64).reshape(-1, 13) for o in observations]
+        self.observation_ids = [np.rint(o[:, 0]).astype(np.int64) for o in self.observations]
+        self.carry_counts = [np.asarray(c, np.int64).reshape(6) for c in carry_counts]
+        self.extend_counts = [np.asarray(c, np.int64).reshape(6) for c in extend_counts]
+        self.frames = np.asarray(frames, np.float64).reshape(-1, 12)
+        self.source_rows = [int(n) for n in source_rows]
+
+    def breaks(self):
+        """the files at which the chain of ids started afresh (the carry found too few rows of the shared sweep)"""
+        return [k for k, c in enumerate(self.carry_counts) if c[5]]
+
+    def summary(self):
+        observed, judged, smooth, moving = (int(v) for v in self.path_counts[1:])
+        carried = sum(int(c[1]) for c in self.carry_counts if not c[5])
+        return dict(files=len(self.observations), tracks=self.next_id, observed=observed, judged=judged, smooth=smooth, rough=judged - smooth,
+                    moving=moving, breaks=len(self.breaks()), carried_rows=carried, rows=sum(self.source_rows[1:]),
+                    overflow=int(sum(int(c[5]) for c in self.extend_counts)))
+
+    def as_list(self):
+        """one dict per track with a counted observation, in the order of the ids; `observations`: every object row of the
+        track, file by file -- step, file, pair (its row in the file's tables), velocity in the log's frame (R d / seconds,
+        float64 on the host)"""
+        seen = {}
+        for step, obs in enumerate(self.observations):
+            R = self.frames[step, :9].reshape(3, 3)
+            for pair, o in enumerate(obs):
+                if o[0] >= 0:
+                    seen.setdefault(int(o[0]), []).append(dict(step=step, file=self.names[step], pair=pair, velocity=[float(v) for v in (R @ o[3:6]) / o[2]]))
+        out = []
+        for r in self.rows:
+            if r[1] <= 0:
+                continue
+            out.append(dict(track=int(r[0]), observations=seen.get(int(r[0]), []), counted=int(r[1]), first_step=int(r[2]), last_step=int(r[3]),
+                            missing=int(r[4]), seconds=float(r[5]), path_length=float(r[6]), velocity=[float(v) for v in r[7:10]], speed=float(r[10]),
+                            dv_max=float(r[11]), adjacent=int(r[12]), jump=float(r[13]), moving=bool(r[14]), judged=bool(r[15]), smooth=bool(r[16]),
+                            size=[float(v) for v in r[17:20]], points=int(r[20]), start=[float(v) for v in r[21:24]]))
+        return out
+
+
+def format_log_tracks(tracks):
+    """`LogTracks.as_list()` as lines of text"""
+    lines = ["  track  steps  first   last  missing       vx       vy    speed   dv_max     jump  moving  judged  smooth   length    width   height  points"]
+    yes = lambda b: "yes" if b else "no"    # noqa: E731
+    for e in tracks:
+        lines.append(f"{e['track']:7d}{e['counted']:7d}{e['first_step']:7d}{e['last_step']:7d}{e['missing']:9d}{e['velocity'][0]:9.2f}{e['velocity'][1]:9.2f}"
+                     f"{e['speed']:9.2f}{e['dv_max']:9.3f}{e['jump']:9.3f}{yes(e['moving']):>8}{yes(e['judged']):>8}{yes(e['smooth']):>8}"
                      f"{e['size'][0]:9.2f}{e['size'][1]:9.2f}{e['size'][2]:9.2f}{e['points']:8d}")
     return lines

@@ -1459,6 +1459,121 @@ int icpflow_object_tracks_fit(const double *d_obs, int M, int T, const icpflow_t
                               int64_t *d_counts, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(l)  object tracks across the files of a log: ids carried by nearest rows.  Consecutive frame-pair files of a log share a
+ * sweep -- the destination of file k is the source of file k + 1 -- but not its rows: the two views differ in order, crop and
+ * ground removal, and in the float32 rounding of the pose product.  Row identity (8(k)) is replaced by "the nearest row
+ * within a small radius after applying the pose".  No counterpart in the reference; the radius, min_share, max_dv and
+ * min_speed are stated policies (COVERAGE.md, named deviations).
+ *
+ * icpflow_rows_carry -- an id per row of one view from the ids of the other view's rows.
+ *   d_prev float32 [m,3] and d_prev_id int32 [m]: one view of a sweep and an id per row, a negative id means none; h_pose
+ *   double [16], row-major 4 x 4, HOST: it maps d_prev's coordinates into d_next's; d_next float32 [n,3]: the other view;
+ *   radius in [1e-3, 1e3] metres; min_share in [0, 1].
+ *   Arithmetic: the pose is narrowed to float on the host; a previous row is moved in fp32 by
+ *       x' = ((m00 x + m01 y) + m02 z) + m03,   y' and z' alike with rows 1 and 2,
+ *   every operation rounded by itself.  After that every word of icpflow_nn_residual's contract (8(g)) holds with the moved
+ *   previous rows as targets and d_next as queries without a flow: r2 = (float)r * (float)r, d2 = (dx dx + dy dy) + dz dz, a
+ *   hit iff d2 <= r2, the LOWEST previous row on equal d2, the same grid and the same exact search.  Bad rows: a query with a
+ *   non-finite coordinate or one beyond +-1e6 m; a previous row with such a coordinate BEFORE OR AFTER the move (a pad row
+ *   (1e8, 1e8, 1e8) stays bad under a rotation that happens to cancel it) -- it is never a neighbour.
+ *   d_id int32 [n]: the id of the hit's previous row; -1 without a hit, for a bad query, or where that row's id is negative.
+ *   d_d2 float32 [n] and d_idx int32 [n], each may be NULL: as icpflow_nn_residual defines d_d2_out and d_idx_out (no hit:
+ *   r2 and -1, a bad query: r2 and -2).
+ *   d_counts int64 [ICPFLOW_CARRY_COUNTS]: [0] queries with a hit, [1] of them those whose previous row has an id >= 0,
+ *   [2] misses, [3] bad queries, [4] bad previous rows, [5] BROKEN.  BROKEN is decided on the device by a closing launch:
+ *   1 iff (double)counts[0] < min_share * (double)n, one fp64 product.  Every d_id is then -1 -- the chain starts afresh and no
+ *   host sees a number in between --; d_d2, d_idx and counts [0] .. [4] are what they are without the break.  n = 0 is not
+ *   broken; m = 0 with n > 0 is broken unless min_share is 0.
+ *   Counts by ballot and popcount with integer atomics only; no floating-point atomic: every output is a function of the
+ *   arguments alone.  Workspace, the caller's, 16-byte aligned: icpflow_rows_carry_workspace_bytes(n, m) =
+ *   table(m) + table(n) + 2 a(4 n) with 8(g)'s table(k) and a(x): a multiple of 256, non-decreasing, 0 for sizes the call
+ *   refuses; nothing in it is read before it is written.  Asynchronous on `stream`, no host synchronisation, no allocation.
+ *   Refusals, all before any launch: a null required pointer (d_prev and d_prev_id with m > 0, d_next and d_id with n > 0,
+ *   h_pose, d_counts), n < 0, m < 0, a radius or min_share outside its range, a pose entry that is not finite (as a float
+ *   too), a misaligned workspace are ICPFLOW_E_ARG; n or m > 2^29 is ICPFLOW_E_LIMIT; a missing or short workspace is
+ *   ICPFLOW_E_WORKSPACE.
+ *
+ * icpflow_pair_row_ids -- an id per row of one side of a frame pair, from the ids of its pairs.
+ *   d_labels float32 [n]: the labels of that side's rows; d_pair_rows float32 [P][pair_stride] (pair_stride >= 2): column 0 the
+ *   source label of a pair, column 1 its destination label; col: 0 for the source side, 1 for the destination side;
+ *   d_pair_id int32 [P]; d_weight double, P values weight_stride doubles apart (column 22 of the object rows with stride
+ *   ICPFLOW_OBJECT_COLS), or NULL: every pair weighs the same.
+ *   A row takes the id of the pair whose label in column `col` equals its own: equality by the key of csrc/labelkey.hpp on
+ *   the quieted label, as icpflow_flow_trust finds MATCHED by keys (+0.0 and -0.0 one label, NaNs by their bits).  Among
+ *   several such pairs with an id >= 0 the largest weight wins (a NaN weighs least); on a tie, or without weights, the
+ *   lowest p.  A row gets -1 when its label is negative, has no such pair, or has only pairs with negative ids.
+ *   d_row_id int32 [n]; d_counts int64 [ICPFLOW_PAIR_ROW_ID_COUNTS]: [0] rows with an id, [1] rows without, [2] pairs whose
+ *   label (column col) an earlier pair has too.
+ *   Two launches: a thread per pair builds a table of (key, winner) sorted by key -- the pairs pass through LDS in tiles of
+ *   1024, a pair's slot is its rank --, then a workgroup of 256 threads per 1024 rows finds each row's key by binary search.
+ *   Workspace: icpflow_pair_row_ids_workspace_bytes(P) (a multiple of 256, constant in P, 0 for a P the call refuses),
+ *   16-byte aligned.  Refusals before any launch: a null required pointer, n < 0, P < 0, col outside {0, 1}, pair_stride < 2,
+ *   weight_stride < 1 with weights, a misaligned workspace are ICPFLOW_E_ARG; n > 2^29 or P > ICPFLOW_PAIR_ROW_ID_MAX_PAIRS are
+ *   ICPFLOW_E_LIMIT; a missing or short workspace is ICPFLOW_E_WORKSPACE.
+ *
+ * icpflow_object_tracks_extend_side -- icpflow_object_tracks_extend (8(k)) with one more argument, `side`.  With side 1 it IS
+ *   that call, bit for bit.  With side 0 d_labels are the SOURCE labels of the file, d_track_of_row has n = source rows, and
+ *   column 0 of an observation is found through the pair's SOURCE label (column 0 of the object row; "has a box" is still
+ *   column 22 > 0).  Everything else is word for word the same: overlap, inherit or fresh, ids by a scan in label order,
+ *   overflow.  side outside {0, 1} is ICPFLOW_E_ARG; the workspace is icpflow_object_tracks_extend_workspace_bytes(n, Lmax).
+ *
+ * icpflow_object_tracks_path -- one row per track over a log.
+ *   d_obs double [M][ICPFLOW_TRACK_OBS_COLS]: the files' observation tables concatenated in file order; d_step int32 [M]: the
+ *   file index of each observation, from 0, non-decreasing; d_frames double [F][12]: per file the rotation (9 values,
+ *   row-major) and the translation that map that file's destination frame into the log's frame (the host forms the chain in
+ *   fp64: W_0 = I, W_{k+1} = W_k inverse(pose_{k+1}), the inverse of a rigid pose (R, t) being (R^T, -R^T t)); T: the tracks
+ *   (ids 0 .. T - 1).  d_paths double [T][ICPFLOW_TRACK_PATH_COLS]; d_counts int64 [ICPFLOW_TRACK_PATH_COUNTS].
+ *   One thread per track walks the M rows in ascending order; fp64, every operation written out, no fma.  An observation with
+ *   a step outside [0, F) is left out.  Of the observations of one track in one step -- consecutive rows of the track with
+ *   the same step -- the one with the most source points (column 9) COUNTS, the lower row on a tie.  Per counted
+ *   observation with centre c, displacement d, seconds s and its step's (R, t):
+ *       c_w = R c + t: ((R00 cx + R01 cy) + R02 cz) + tx, ...;   d_w = R d: (R00 dx + R01 dy) + R02 dz, ...;   v = d_w / s
+ *   Row t:
+ *       0  id    1  counted observations    2  first step    3  last step    4  steps missing in between: (last - first + 1) - col 1
+ *       5  the sum of s    6  path length, the sum of sqrt(dwx dwx + dwy dwy)    7-9  mean velocity, (sum of d_w) / col 5
+ *       10  sqrt(vx vx + vy vy) of it
+ *       11  the largest sqrt((vx' - vx)^2 + (vy' - vy)^2) over counted observations at ADJACENT steps s, s + 1; 0 without one
+ *       12  the number of such pairs
+ *       13  jump: the largest xy distance of c_w + d_w at step s from c_w at step s + 1 over the same pairs; reported, no verdict
+ *           hangs on it
+ *       14  moving: col 1 > 0 and col 10 >= min_speed    15  judged: col 12 >= 1    16  smooth: judged and col 11 <= max_dv
+ *       17-19  the largest long side, short side and height over the counted views    20  the most source points in one view
+ *       21-23  c_w of the first counted observation
+ *   A track without a counted observation has its id and zeros.  d_counts: tracks, observed, judged, smooth, moving.
+ *   params: icpflow_track_path_params_t from icpflow_object_tracks_path_default_params (max_dv 1.0 m/s: a velocity change
+ *   of 10 cm per 0.1 s sweep -- a log-long track cannot be held to one constant velocity, cars brake; min_speed 0.5 m/s).
+ *   Refusals: a null required pointer (d_obs and d_step with M > 0, d_frames with F > 0, d_paths with T > 0, params,
+ *   d_counts), a negative size, F < 1 with M > 0, a struct_size mismatch, a negative or non-finite parameter are
+ *   ICPFLOW_E_ARG; M, T or F > 2^24 is ICPFLOW_E_LIMIT.  T = 0 succeeds with five zeros.  No workspace.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_CARRY_COUNTS 6
+#define ICPFLOW_PAIR_ROW_ID_COUNTS 3
+#define ICPFLOW_PAIR_ROW_ID_MAX_PAIRS 4096
+#define ICPFLOW_TRACK_PATH_COLS 24
+#define ICPFLOW_TRACK_PATH_COUNTS 5
+typedef struct icpflow_track_path_params {
+    size_t struct_size; /* sizeof(icpflow_track_path_params_t) */
+    double max_dv;      /* m/s: a track is smooth when its velocity changes by no more between adjacent steps; default 1.0 */
+    double min_speed;   /* a track moves when its mean xy speed reaches this, m/s; default 0.5 */
+} icpflow_track_path_params_t;
+size_t icpflow_rows_carry_workspace_bytes(int n, int m);
+int icpflow_rows_carry(const float *d_prev, const int32_t *d_prev_id, int m, const double *h_pose, const float *d_next, int n,
+                       double radius, double min_share, int32_t *d_id, float *d_d2, int32_t *d_idx, int64_t *d_counts, void *d_ws,
+                       size_t ws_bytes, icpflow_stream_t stream);
+size_t icpflow_pair_row_ids_workspace_bytes(int P);
+int icpflow_pair_row_ids(const float *d_labels, int n, const float *d_pair_rows, int P, int pair_stride, int col,
+                         const int32_t *d_pair_id, const double *d_weight, int weight_stride, int32_t *d_row_id, int64_t *d_counts,
+                         void *d_ws, size_t ws_bytes, icpflow_stream_t stream);
+int icpflow_object_tracks_extend_side(const float *d_labels, int n, int Lmax, int32_t *d_track_of_row, int32_t *d_next_id,
+                                      const double *d_objects, int P, int side, int gap, double seconds,
+                                      const icpflow_track_params_t *params, double *d_segments, int32_t *d_num, double *d_obs,
+                                      int64_t *d_counts, void *d_ws, size_t ws_bytes, icpflow_stream_t stream);
+int icpflow_object_tracks_path_default_params(icpflow_track_path_params_t *params);
+int icpflow_object_tracks_path(const double *d_obs, const int32_t *d_step, int M, const double *d_frames, int F, int T,
+                               const icpflow_track_path_params_t *params, double *d_paths, int64_t *d_counts,
+                               icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
