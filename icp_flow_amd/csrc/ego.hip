@@ -366,7 +366,7 @@ __global__ __launch_bounds__(kRegThreads) void ego_register_kernel(const float *
     }
 }
 
-// with an empty map (frame 0) the result is the guess
+// with a map that has received no frame since the state was created or reset (frame 0) the result is the guess
 __global__ void ego_guess_kernel(RegArgs a, double *__restrict__ result)
 {
     const int t = threadIdx.x;
@@ -635,7 +635,9 @@ int enqueue_register(icpflow_ego *e, const float *pts, const int32_t *rows, cons
                      double sigma, double *d_result, hipStream_t st)
 {
     const RegArgs a = reg_args(e, guess, sigma);
-    if (e->mapEmpty || m_max == 0)
+    // (a source of no points is no short cut: the loop runs once, finds fewer than 3 correspondences and stops -- the same
+    // result whether the count is known here (m_max) or only on the device (d_m); a null `pts` is never read then)
+    if (e->mapEmpty)
         ego_guess_kernel<<<1, 64, 0, st>>>(a, d_result);
     else
         ego_register_kernel<<<1, kRegThreads, 0, st>>>(pts, rows, d_m, m_max, e->table(e->cur), (unsigned)e->par.map_capacity - 1, a, d_result);

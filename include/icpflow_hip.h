@@ -737,7 +737,10 @@ int icpflow_track_frame_points(const float *d_points_src, const uint8_t *d_mask_
  *                    floor(x / v), kept if |x - q|^2 < (3 sigma)^2; weight w = (k / (k + |r|^2))^2, k = sigma / 3, r = x - q;
  *                    J = [I | -[x]_x]; (sum w J^T J) dx = -sum w J^T r in fp64, sums in a fixed order; T <- exp(dx) T;
  *                    stop when |dx| < convergence.  Fewer than 3 correspondences, or a dx that is not finite: the loop stops
- *                    without a step.  With an empty map the result is the guess, 0 iterations.
+ *                    without a step (that iteration counts: a source of no points, m = 0, or a map whose voxels were
+ *                    all pruned gives the guess, 1 iteration, 0 correspondences -- through register_frame and through
+ *                    register_step alike).  Only against a map that has received no frame since the state was created or
+ *                    reset is no loop run: the result is the guess, 0 iterations.
  *   6. bookkeeping   deviation D = inv(guess) new_pose adds (|t_D| + 2 max_range sin(theta_D / 2))^2 to sse when that error
  *                    exceeds min_motion_th; frame_ds moved by the new pose (fp64, ((R0 x + R1 y) + R2 z) + t, rounded to
  *                    float32) is added to the map -- voxel size v, at most max_points_per_voxel points per voxel, in input
@@ -774,7 +777,9 @@ typedef struct icpflow_ego_params {
     int max_points_per_voxel; /* 20, at most 20 (mapping.max_points_per_voxel) */
     int max_iterations;       /* 500    (registration.max_num_iterations) */
     int max_points;           /* capacity: points of one frame */
-    int map_capacity;         /* capacity: slots of each map table, a power of two >= 1024; at most half may be live */
+    int map_capacity;         /* capacity: slots of each map table, a power of two >= 1024; at most half may be live (a
+                               * fuller table, up to every slot, is still CORRECT -- every probe loop ends after
+                               * map_capacity steps -- but its chains grow long; one voxel more is ICPFLOW_E_LIMIT) */
 } icpflow_ego_params_t;
 int icpflow_ego_default_params(icpflow_ego_params_t *params);
 size_t icpflow_ego_state_bytes(const icpflow_ego_params_t *params);

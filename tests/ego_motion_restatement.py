@@ -106,14 +106,15 @@ class VoxelMap:
         return keys, counts, pts
 
 
-def correspondences(map_arrays, x, voxel):
+def correspondences(map_arrays, x, voxel, offsets=OFFSETS):
     """closest map point of every x [m,3] among the 27 voxels around it -> (q [m,3], d2 [m]); d2 = inf without any.
-    First minimum in the order voxel offset (dx, dy, dz ascending, dz fastest), then insertion order."""
+    First minimum in the order voxel offset (dx, dy, dz ascending, dz fastest), then insertion order.  (`offsets`: the
+    voxels searched, in the order searched -- other than OFFSETS only where a test states a WRONG rule on purpose.)"""
     keys, counts, pts = map_arrays
     m = len(x)
     if len(keys) == 0 or m == 0:
         return np.zeros((m, 3)), np.full(m, np.inf)
-    around = pack(voxel_coords(x, voxel)[:, None, :] + OFFSETS[None, :, :])            # [m,27]
+    around = pack(voxel_coords(x, voxel)[:, None, :] + np.asarray(offsets)[None, :, :])    # [m,27]
     at = np.clip(np.searchsorted(keys, around), 0, len(keys) - 1)
     found = keys[at] == around
     cand = pts[at]                                                                      # [m,27,P,3]
@@ -133,17 +134,21 @@ def twist_matrix(dx):
     return M
 
 
-def register(source, map_arrays, guess, sigma, voxel, max_iterations=500, convergence=1e-4, trace=None):
-    """step 5 -> (pose [4,4], iterations, final |dx|, correspondences of the last iteration)"""
+def register(source, map_arrays, guess, sigma, voxel, max_iterations=500, convergence=1e-4, trace=None,
+             find=correspondences, gate=np.less, fresh=True):
+    """step 5 -> (pose [4,4], iterations, final |dx|, correspondences of the last iteration).  `find` and `gate` are the
+    two decisions of an iteration (which map point, and whether it counts); a test replaces one to state a wrong rule.
+    `fresh`: an empty map is one that has received no frame yet (0 iterations); False: one whose voxels were all pruned,
+    against which the loop runs like against any other (1 iteration, no correspondence)."""
     T = np.array(guess, dtype=np.float64)
-    if len(map_arrays[0]) == 0:
+    if len(map_arrays[0]) == 0 and fresh:
         return T, 0, 0.0, 0
     gate2, kern = (3.0 * sigma) ** 2, sigma / 3.0
     iterations, last, ncorr = 0, 0.0, 0
     for it in range(max_iterations):
         x = move(T, source)
-        q, d2 = correspondences(map_arrays, x, voxel)
-        keep = d2 < gate2
+        q, d2 = find(map_arrays, x, voxel)
+        keep = gate(d2, gate2)
         ncorr = int(keep.sum())
         iterations = it + 1
         if trace is not None:
@@ -212,7 +217,7 @@ class Odometry:
         idx_ds, idx_source = downsample(points, c["min_range"], c["max_range"], self.voxel)
         sigma, guess = self.threshold(), self.guess()
         pose, iterations, last, ncorr = register(points[idx_source], self.map.arrays(), guess, sigma, self.voxel,
-                                                 c["max_iterations"], c["convergence"])
+                                                 c["max_iterations"], c["convergence"], fresh=not self.poses)
         err = model_error(rigid_inverse(guess) @ pose, c["max_range"])
         if err > c["min_motion_th"]:
             self.sse += err * err
