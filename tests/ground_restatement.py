@@ -10,7 +10,17 @@ threshold (every point-plane test of every round, the seed thresholds, 0.707, th
 the product 0.5, the count 1500 and th_dist^2); gap: the smallest (s1 - s2) / s0 of its plane estimates, which makes the normal
 well defined.  A decision taken on a NaN plane is IEEE-defined (false) and has no margin.  Also border float64 [n]
 (border_distance: the binning's own margin, kept apart from the patches') and rings: per ring that had revert candidates, the
-flatness list as it stood (`listed`), the values that ring itself pushed (`own`) and mu."""
+flatness list as it stood (`listed`), the values that ring itself pushed (`own`) and mu; seeds: per patch the seed thresholds
+in the order the method forms them (R-VPF's, then R-GPF's); covs: per patch (the covariance behind its last plane, the size of
+that set).
+
+Every function takes an optional `params=` (a Params; the defaults are the reference's constants, which the module-level names
+keep for the callers that know no other).  The zone layout {2, 4, 4, 4} x {16, 32, 54, 32} is no parameter: the library refuses
+any other.  Two hooks state a WRONG rule, so that a CPU test can show that a case notices it: seed_rule= ("z_only": the lowest
+DISTINCT heights, a tie counted once; an int: that many seeds in place of num_lpr) and final_plane= ("by", the rule: the last
+set is decided by the plane that was fitted before it; "pl": by the plane fitted to it)."""
+import dataclasses
+
 import numpy as np
 
 SENSOR_HEIGHT, MIN_RANGE, MAX_RANGE = 1.723, 1.0, 64.0
@@ -24,13 +34,53 @@ TOO_FEW, NOT_UPRIGHT, FAR, HEADING, ACCEPTED, CANDIDATE = range(6)
 TGR_NONE, TGR_REVERTED, TGR_REJECTED = range(3)
 MARGIN_BAR, GAP_BAR = 1e-9, 1e-3
 
+
+
+@dataclasses.dataclass(frozen=True)
+class Params:
+    """icpflow_ground_params_t without the layout; the defaults are the constants above"""
+    sensor_height: float = SENSOR_HEIGHT
+    min_range: float = MIN_RANGE
+    max_range: float = MAX_RANGE
+    num_iter: int = NUM_ITER
+    num_lpr: int = NUM_LPR
+    num_min_pts: int = NUM_MIN_PTS
+    th_seeds: float = TH_SEEDS
+    th_dist: float = TH_DIST
+    th_seeds_v: float = TH_SEEDS_V
+    th_dist_v: float = TH_DIST_V
+    uprightness_thr: float = UPRIGHT
+    adaptive_seed_selection_margin: float = SEED_MARGIN
+
+    @property
+    def lo(self):
+        a, b = self.min_range, self.max_range
+        return (a, (7 * a + b) / 8.0, (3 * a + b) / 4.0, (a + b) / 2.0)
+
+    @property
+    def ring_size(self):
+        lo = self.lo
+        return tuple(((lo[k + 1] if k < 3 else self.max_range) - lo[k]) / RINGS[k] for k in range(4))
+
+    @property
+    def skip_below(self):
+        return self.adaptive_seed_selection_margin * self.sensor_height
+
+    def replace(self, **kw):
+        return dataclasses.replace(self, **kw)
+
+
+DEFAULT = Params()
+
 LO = (MIN_RANGE, (7 * MIN_RANGE + MAX_RANGE) / 8.0, (3 * MIN_RANGE + MAX_RANGE) / 4.0, (MIN_RANGE + MAX_RANGE) / 2.0)
 RING_SIZE = tuple(((LO[k + 1] if k < 3 else MAX_RANGE) - LO[k]) / RINGS[k] for k in range(4))
 SECTOR_SIZE = tuple(2 * np.pi / SECTORS[k] for k in range(4))
 
 
-def patch_bounds(zone, ring, sector):
+def patch_bounds(zone, ring, sector, params=None):
     """(r_lo, r_hi, theta_lo, theta_hi) of a patch"""
+    par = params or DEFAULT
+    LO, RING_SIZE = par.lo, par.ring_size
     return (LO[zone] + ring * RING_SIZE[zone], LO[zone] + (ring + 1) * RING_SIZE[zone],
             sector * SECTOR_SIZE[zone], (sector + 1) * SECTOR_SIZE[zone])
 
@@ -44,8 +94,10 @@ def patch_zone_ring(p):
     return zone, RING_BASE[zone] + (p - PATCH_BASE[zone]) // SECTORS[zone]
 
 
-def patch_ids(points):
+def patch_ids(points, params=None):
     """pc2czm: float32 coordinates, r and theta in double; -1 = the row takes no part"""
+    par = params or DEFAULT
+    LO, RING_SIZE, MIN_RANGE, MAX_RANGE = par.lo, par.ring_size, par.min_range, par.max_range
     p = np.asarray(points)[:, 0:3].astype(np.float32)
     out = np.full(len(p), -1, dtype=np.int64)
     fin = np.flatnonzero(np.isfinite(p).all(axis=1))
@@ -63,7 +115,7 @@ def patch_ids(points):
     return out
 
 
-def border_distance(points):
+def border_distance(points, params=None):
     """float64 [n]: how far a row is from the nearest border of the binning, in bins -- |u - round(u)| of its ring coordinate
     u = (r - min_range_k) / ring_size_k (the zone boundaries, min_range and max_range are whole u) and of its sector coordinate
     theta / sector_size_k; for a row out of range its distance to min_range or max_range in rings of the nearest zone.  inf for
@@ -74,6 +126,8 @@ def border_distance(points):
     bin from a border -- seven orders over what a sqrt and an atan2 that is a few ulp off can move it -- except the rows that
     `edges` puts ON a border by construction.  Those are exact in IEEE arithmetic: r is a correctly rounded sqrt of exactly
     representable squares, and atan2 on an axis is the rounded multiple of pi / 2 in every libm."""
+    par = params or DEFAULT
+    LO, RING_SIZE, MIN_RANGE, MAX_RANGE = par.lo, par.ring_size, par.min_range, par.max_range
     p = np.asarray(points)[:, 0:3].astype(np.float32)
     out = np.full(len(p), np.inf)
     fin = np.flatnonzero(np.isfinite(p).all(axis=1))
@@ -92,7 +146,7 @@ def border_distance(points):
 
 class _Margin:
     def __init__(self):
-        self.margin, self.gap = np.inf, np.inf
+        self.margin, self.gap, self.seeds = np.inf, np.inf, []
 
     def rel(self, diff, scale):
         d = np.abs(np.asarray(diff, dtype=np.float64)) / scale
@@ -120,15 +174,20 @@ def estimate_plane(P, plane, mg):
     if normal[2] < 0:
         normal = -normal
     mg.gap = min(mg.gap, float((S[1] - S[2]) / S[0]) if S[0] > 0 else 0.0)
-    return dict(mean=mean, normal=normal, sv=S, d=-((normal[0] * mean[0] + normal[1] * mean[1]) + normal[2] * mean[2]))
+    return dict(mean=mean, normal=normal, sv=S, d=-((normal[0] * mean[0] + normal[1] * mean[1]) + normal[2] * mean[2]), cov=cov, size=m)
 
 
-def seed_threshold(z, zone, th):
-    """lpr + th: the double mean of the up to 20 lowest z, in zone 0 after the leading z < -1.2 * sensor_height"""
+def seed_threshold(z, zone, th, params=None, seed_rule=None):
+    """lpr + th: the double mean of the up to num_lpr (20) lowest z, in zone 0 after the leading z < margin (-1.2) * sensor_height"""
+    par = params or DEFAULT
     zs = np.sort(z)
     if zone == 0:
-        zs = zs[~(zs < SEED_MARGIN * SENSOR_HEIGHT)]
-    s, low = 0.0, zs[:NUM_LPR]
+        zs = zs[~(zs < par.skip_below)]
+    if seed_rule == "z_only":
+        zs = np.unique(zs)
+    elif seed_rule is not None:
+        par = par.replace(num_lpr=int(seed_rule))
+    s, low = 0.0, zs[:par.num_lpr]
     for v in low:
         s += float(v)
     return (s / len(low) if len(low) else 0.0) + th
@@ -140,13 +199,18 @@ def plane_dist(plane, P):
         return ((n[0] * P[:, 0] + n[1] * P[:, 1]) + n[2] * P[:, 2]) + plane["d"]
 
 
-def piecewise_ground(P, zone, mg):
+def piecewise_ground(P, zone, mg, params=None, seed_rule=None, final_plane="by"):
     """extract_piecewiseground: -> (ground mask over P, plane, points R-VPF removed, ground count)"""
+    par = params or DEFAULT
+    NUM_ITER, UPRIGHT = par.num_iter, par.uprightness_thr
+    TH_SEEDS, TH_DIST, TH_SEEDS_V, TH_DIST_V = par.th_seeds, par.th_dist, par.th_seeds_v, par.th_dist_v
+    assert final_plane in ("by", "pl")
     alive = np.ones(len(P), dtype=bool)
     plane, removed = NAN_PLANE, 0
     for _ in range(NUM_ITER):
         Q = P[alive]
-        thr = seed_threshold(Q[:, 2], zone, TH_SEEDS_V)
+        thr = seed_threshold(Q[:, 2], zone, TH_SEEDS_V, par, seed_rule)
+        mg.seeds.append(thr)
         mg.rel(Q[:, 2] - thr, TH_SEEDS_V)
         plane = estimate_plane(Q[Q[:, 2] < thr], plane, mg)
         if zone == 0:
@@ -159,7 +223,8 @@ def piecewise_ground(P, zone, mg):
         alive[gone] = False
         removed += len(gone)
     Q = P[alive]
-    thr = seed_threshold(Q[:, 2], zone, TH_SEEDS)
+    thr = seed_threshold(Q[:, 2], zone, TH_SEEDS, par, seed_rule)
+    mg.seeds.append(thr)
     mg.rel(Q[:, 2] - thr, TH_SEEDS)
     plane = estimate_plane(Q[Q[:, 2] < thr], plane, mg)
     g = np.zeros(len(Q), dtype=bool)
@@ -168,15 +233,20 @@ def piecewise_ground(P, zone, mg):
         mg.rel(d - TH_DIST, TH_DIST)
         g = d < TH_DIST
         plane = estimate_plane(Q[g], plane, mg)
+    if final_plane == "pl":                    # the wrong rule: the set of the plane that was fitted last
+        g = plane_dist(plane, Q) < TH_DIST
     ground = np.zeros(len(P), dtype=bool)
     ground[np.flatnonzero(alive)[g]] = True
     return ground, plane, removed, int(g.sum())
 
 
-def segment(points):
+def segment(points, params=None, seed_rule=None, final_plane="by"):
+    par = params or DEFAULT
+    NUM_MIN_PTS, UPRIGHT, TH_DIST = par.num_min_pts, par.uprightness_thr, par.th_dist
     pts32 = np.asarray(points)[:, 0:3].astype(np.float32)
     n = len(pts32)
-    pid = patch_ids(pts32)
+    pid = patch_ids(pts32, par)
+    seeds, covs = {}, {}
     nonground = np.ones(n, dtype=bool)
     table = np.zeros((PATCHES, COLS))
     margin, gap = np.full(PATCHES, np.inf), np.full(PATCHES, np.inf)
@@ -195,7 +265,10 @@ def segment(points):
                 if len(rows) < NUM_MIN_PTS:
                     continue
                 mg = _Margin()
-                ground, pl, removed, count = piecewise_ground(pts32[rows].astype(np.float64), zone, mg)
+                ground, pl, removed, count = piecewise_ground(pts32[rows].astype(np.float64), zone, mg, par, seed_rule, final_plane)
+                seeds[p] = list(mg.seeds)
+                if "cov" in pl:
+                    covs[p] = (pl["cov"], pl["size"])
                 sv, mean, normal = pl["sv"], pl["mean"], pl["normal"]
                 upright, not_elevated, flat, near = normal[2] > UPRIGHT, mean[2] < 0.0, sv[2] < 0.0, c < NEAR_RINGS
                 heading = 0.0
@@ -258,17 +331,17 @@ def segment(points):
                         nonground[ground_rows[q]] = False
                     margin[q] = min(margin[q], m.margin)
                 listed = []
-    return dict(nonground=nonground, table=table, patch=pid, margin=margin, gap=gap, border=border_distance(pts32), rings=rings)
+    return dict(nonground=nonground, table=table, patch=pid, margin=margin, gap=gap, border=border_distance(pts32, par), rings=rings, seeds=seeds, covs=covs)
 
 
-def determined(res):
-    """bool [504]: the patches (of at least 10 points) whose every decision is clear of its threshold"""
-    return (res["table"][:, 0] >= NUM_MIN_PTS) & (res["margin"] > MARGIN_BAR) & (res["gap"] > GAP_BAR)
+def determined(res, params=None):
+    """bool [504]: the patches (of at least num_min_pts points) whose every decision is clear of its threshold"""
+    return (res["table"][:, 0] >= (params or DEFAULT).num_min_pts) & (res["margin"] > MARGIN_BAR) & (res["gap"] > GAP_BAR)
 
 
-def rows_to_compare(res):
+def rows_to_compare(res, params=None):
     """bool [n]: the rows whose label is pinned -- every row that is not in an undetermined patch"""
-    und = (res["table"][:, 0] >= NUM_MIN_PTS) & ~determined(res)
+    und = (res["table"][:, 0] >= (params or DEFAULT).num_min_pts) & ~determined(res, params)
     keep = np.ones(len(res["patch"]), dtype=bool)
     inside = res["patch"] >= 0
     keep[inside] = ~und[res["patch"][inside]]

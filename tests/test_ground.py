@@ -187,3 +187,15 @@ def test_scene_is_clear_of_the_thresholds(name):
     und = big & ~gr.determined(res)
     print(name, "patches of >= 10 points:", int(big.sum()), "undetermined:", int(und.sum()))
     assert big.sum() >= 3 and und.sum() <= 0.01 * big.sum()
+
+
+def test_default_params_are_bit_for_bit_what_the_module_constants_gave():
+    """segment(pts) without params on two existing scenes against the values from before it took any, kept in tests/golden"""
+    import ground_scenes as gs
+    before = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ground_restatement_before_params.npz"))
+    for name in ("walls", "platform"):
+        pts, _ = gs.ALL[name]()
+        for res in (gr.segment(pts), gr.segment(pts, gr.Params())):
+            for k in ("nonground", "table", "margin", "gap"):
+                assert res[k].tobytes() == before[f"{name}_{k}"].tobytes(), (name, k)
+    assert gr.DEFAULT.lo == gr.LO and gr.DEFAULT.ring_size == gr.RING_SIZE
