@@ -137,6 +137,7 @@ SIGNATURES = {
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "icpflow_selftest_vote_quotient": (_i, [_p, _i, _f, _f, _p, _p, _p]),
     "icpflow_selftest_kabsch": (_i, [_p, _p, _i, _i, _p, _p, _p, _p]),
+    "icpflow_selftest_peaks_u32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _f, _p, _p, _p, _p, _sz, _p]),
     "icpflow_selftest_workspace_layout": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_sz), _i]),
     "icpflow_profile_create": (_i, [_i, ctypes.POINTER(_p)]),
     "icpflow_profile_collect": (_i, [_p, ctypes.POINTER(_d), ctypes.POINTER(_i)]),

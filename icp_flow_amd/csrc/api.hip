@@ -628,6 +628,30 @@ int icpflow_selftest_kabsch(const double *d_H, const double *d_gsum, int n, int 
     return 0;
 }
 
+// the peak search as the fused entry points run it: uint32 vote counters in, the candidate translations decoded in the same launch
+int icpflow_selftest_peaks_u32(const uint32_t *d_bins_u32, int B, int len_x, int len_y, int len_z, int k, int kernel_size,
+                               const float *d_edges_x, const float *d_edges_y, const float *d_edges_z, float decode_shift,
+                               float *d_votes, int64_t *d_idx, float *d_cand, void *d_ws, size_t ws_bytes, icpflow_stream_t stream)
+{
+    if (!d_bins_u32 || !d_votes || !d_idx) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_peaks_u32: null pointer");
+    if (d_cand && (!d_edges_x || !d_edges_y || !d_edges_z))
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_peaks_u32: candidates need the three edge arrays");
+    if (B <= 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_peaks_u32: B must be positive");
+    if (int r = check_hist_dims("icpflow_selftest_peaks_u32", len_x, len_y, len_z)) return r;
+    if (k <= 0 || k > 8) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_peaks_u32: k must be in 1..8 (got %d)", k);
+    if (kernel_size <= 0 || kernel_size % 2 == 0)
+        return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_peaks_u32: kernel_size must be odd and positive");
+    const size_t L = (size_t)len_x * len_y * len_z;
+    if ((size_t)k > L) return report_errorf(ICPFLOW_E_ARG, "icpflow_selftest_peaks_u32: k exceeds the number of bins");
+    const size_t vol = align256((size_t)B * L * 4);
+    if (int r = check_ws(d_ws, ws_bytes, 2 * vol)) return r;
+    PeakDecode dec;
+    dec.ex = d_edges_x; dec.ey = d_edges_y; dec.ez = d_edges_z; dec.shift = decode_shift; dec.cand = d_cand;
+    ICPFLOW_TRY(launch_hist_peaks_u32(d_bins_u32, B, len_x, len_y, len_z, k, kernel_size, (uint32_t *)d_ws,
+                                      (uint32_t *)((char *)d_ws + vol), d_votes, d_idx, (hipStream_t)stream, dec));
+    return 0;
+}
+
 // host only: the carve of the fused entry points on a null base, as the size queries build it (order: icpflow_hip.h)
 int icpflow_selftest_workspace_layout(int B, int N, int Lx, int Ly, int Lz, size_t *h_offsets, int count)
 {

@@ -1065,7 +1065,7 @@ __device__ unsigned long long g_peakClock[1024][8];
 #define PEAK_STAMP(k) do { } while (0)
 #endif
 // MEM = 0: scratch volumes in global memory (any size); MEM = 1: three volumes in dynamic LDS
-// (3 * L * 4 bytes <= 150 KiB, i.e. up to 113 x 113 x 3 bins)
+// (3 * L * 4 bytes <= 150 KiB, i.e. up to L = 12800 bins: 65 x 65 x 3 fits, 66 x 66 x 3 does not)
 template <typename BinT, int MEM>
 __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
     const BinT *__restrict__ bins, int Lx, int Ly, int Lz, int k, int radius,
@@ -1100,7 +1100,7 @@ __global__ __launch_bounds__(kPeakBlock) void hist_peaks_kernel(
                 const uint32_t m = max(max(v0, v1), v2);
                 H0[f0] = v0; H0[f0 + 1] = v1; H0[f0 + 2] = v2;
                 A[f0] = m; A[f0 + 1] = m; A[f0 + 2] = m;
-            } else if (Lz <= 2 * radius + 1) {                    // the window is the whole column
+            } else if (Lz <= radius + 1) {                        // the window is the whole column: z = 0 reaches z = Lz - 1
                 uint32_t m = 0;
                 for (int z = 0; z < Lz; ++z) { const uint32_t v = (uint32_t)h[f0 + z]; H0[f0 + z] = v; m = max(m, v); }
                 for (int z = 0; z < Lz; ++z) A[f0 + z] = m;

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define ICPFLOW_VERSION 214 /* (icpflow_seq_bucket_table, the cells of the bucket-normalised EPE per class, icpflow_seq_class_table, the per-class and per-speed table of a sample, icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed; so is ICPFLOW_OPT_NO_FRONT_ROLES, the axis sort and the occupancy grids as workgroups of the vote's launch) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
+#define ICPFLOW_VERSION 215 /* 0.2.15: icpflow_selftest_peaks_u32 (the peak search on uint32 counters with the fused candidate decode, test only); (icpflow_seq_bucket_table, the cells of the bucket-normalised EPE per class, icpflow_seq_class_table, the per-class and per-speed table of a sample, icpflow_cluster_pcd and icpflow_track_frame_points, cluster_pcd behind the C ABI, icpflow_seq_*, the evaluation of a sequence, icpflow_ego_*, the ego-motion estimate, and icpflow_egomotion_*, its motion compensation and fixed threshold, are additions under the same number: nothing that existed changed; so is ICPFLOW_OPT_NO_FRONT_ROLES, the axis sort and the occupancy grids as workgroups of the vote's launch) 0.2.14: ICPFLOW_OPT_NO_DIR_KEYS (sort keys of the sweeps: horizontal directions next to the axes); 0.2.13: ICPFLOW_OPT_TWO_LAUNCH (ICP of batches of a few rounds: the persistent grid drained for a second launch of whole-CU workgroups; off by default); 0.2.12: ICPFLOW_OPT_NO_SCORE_PREBOUND (scoring sweeps: a scan's whole sum bounded from below by the other cloud's occupancy grid before any target is evaluated); 0.2.11: ICPFLOW_OPT_NO_CHECK_REUSE (hist_icp: the roll-back check takes its sum under the initial pose from the scoring); 0.2.10: ICPFLOW_OPT_NO_VOTE_LIST (the vote's work list on ragged batches); 0.2.9: icpflow_register_stage_begin / _finish, icpflow_associate_frame_begun (stage 2's initial poses beside stage 1's ICP), ICPFLOW_E_HOSTMEM; 0.2.8: ICPFLOW_OPT_NO_SHARED_SCANS (teams: window scans shared by a member's waves); 0.2.7: icpflow_track_frame (one frame pair per call, host half in C++); team-launch chains per device instead of per host thread; 0.2.6: icpflow_register_stage, icpflow_associate_frame (a stage / the rest of match_pcds per call); 0.2.5: options.d_pair_active, icpflow_assoc_assign / _collect (device-side association of a frame pair), ICPFLOW_OPT_TEAMS_HALF_GPU; 0.2.3: icpflow_hist_icp_eval; 0.2.2: icpflow_hist_icp_many; 0.2.1: per-call options replace the process-global switches of 0.1;
                                icpflow_icp takes an initial transform and returns its per-iteration history */
 
 #define ICPFLOW_OK 0
@@ -212,7 +212,8 @@ int icpflow_hist_vote(const float *d_X, const float *d_Y, int B, int NX, int NY,
  * d_votes float32 [B,k], d_idx int64 [B,k] (flat index into [Lx,Ly,Lz]).
  * Order: vote descending, ties by ascending flat index (torch.topk's order among
  * equal votes is implementation-defined; this rule is deterministic).
- * d_ws: at least 2 * B*Lx*Ly*Lz * 4 bytes of scratch.
+ * The bins are vote counts, i.e. non-negative integers, read as uint32_t (the vote returned is float32 of that integer).
+ * d_ws: at least 2 * (B*Lx*Ly*Lz * 4 rounded up to a multiple of 256) bytes of scratch.
  * ------------------------------------------------------------------------- */
 int icpflow_hist_peaks(const float *d_bins, int B, int len_x, int len_y, int len_z,
                        int k, int kernel_size, float *d_votes, int64_t *d_idx,
@@ -1661,6 +1662,21 @@ int icpflow_selftest_vote_quotient(const float *d_a, int n, float min_v, float m
  * ------------------------------------------------------------------------- */
 int icpflow_selftest_kabsch(const double *d_H, const double *d_gsum, int n, int mode, double *d_R, double *d_lam,
                             int32_t *d_path, icpflow_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Diagnostics: the peak search as icpflow_estimate_init_pose / icpflow_hist_icp run it (hist.hip, launch_hist_peaks_u32):
+ * d_bins_u32 uint32 [B, len_x, len_y, len_z], the vote's counters as they are, compared as integers (any value of uint32_t
+ * but 2^32 - 1 in bin 0 of a volume: that bin's selection key, all ones, is the selection's "nothing taken yet"; a vote
+ * counts pairs of points and stays far below); k, kernel_size, d_votes, d_idx, d_ws / ws_bytes and the order as
+ * icpflow_hist_peaks (d_votes is float32 of the integer vote).
+ * d_cand: NULL, or float32 [B, k + 1, 3]: candidate r of pair b is (d_edges_x[ix] + decode_shift, d_edges_y[iy] +
+ * decode_shift, d_edges_z[iz] + decode_shift) of peak r's bin (ix, iy, iz), each one float32 addition; the zero
+ * translation comes last.  d_edges_* float32 [len_*] are read only with d_cand.
+ * ------------------------------------------------------------------------- */
+int icpflow_selftest_peaks_u32(const uint32_t *d_bins_u32, int B, int len_x, int len_y, int len_z, int k, int kernel_size,
+                               const float *d_edges_x, const float *d_edges_y, const float *d_edges_z, float decode_shift,
+                               float *d_votes, int64_t *d_idx, float *d_cand, void *d_ws, size_t ws_bytes,
+                               icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Diagnostics, host only (no launch, no device access): byte offsets, from the d_ws a fused entry point

@@ -28,7 +28,7 @@ def test_the_symbol_is_declared_bound_and_exported():
     assert re.search(r"\b" + name + r"\s*\(", hdr), f"{name} not declared"
     assert hasattr(lib, name), f"{name} not exported"
     assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == 22, f"{name} not bound"
-    assert _lib.VERSION == 214 and "#define ICPFLOW_VERSION 214" in hdr
+    assert _lib.VERSION == 215 and "#define ICPFLOW_VERSION 215" in hdr
     assert "#define ICPFLOW_ARGO_MAX_BACKGROUND 64" in hdr and _lib.ARGO_MAX_BACKGROUND == 64
     assert "#define ICPFLOW_DTYPE_FLOAT32 0" in hdr and "#define ICPFLOW_DTYPE_FLOAT64 1" in hdr
     assert (_lib.DTYPE_FLOAT32, _lib.DTYPE_FLOAT64) == (0, 1)

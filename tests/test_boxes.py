@@ -23,7 +23,7 @@ def test_the_library_is_built_from_the_box_sources_and_keeps_its_number():
     assert "boxes.hip" in build.SOURCES and "boxes.hpp" in build.HEADERS
     for name in ("icpflow_segment_boxes", "icpflow_segment_boxes_workspace_bytes", "icpflow_pair_objects", "icpflow_pair_objects_default_params"):
         assert name in _lib.SIGNATURES and hasattr(_lib._L, name)
-    assert _lib.VERSION == 214 and (_lib.BOX_COLS, _lib.OBJECT_COLS, _lib.OBJECT_COUNTS) == (br.BOX_COLS, br.OBJECT_COLS, 4)
+    assert _lib.VERSION == 215 and (_lib.BOX_COLS, _lib.OBJECT_COLS, _lib.OBJECT_COUNTS) == (br.BOX_COLS, br.OBJECT_COLS, 4)
     p = _lib.ObjectParams.defaults()
     assert (p.struct_size, p.seconds, p.min_speed) == (ctypes.sizeof(_lib.ObjectParams), 0.1, 0.5) and ctypes.sizeof(_lib.ObjectParams) == 24
 

@@ -28,7 +28,7 @@ def test_the_library_is_built_from_carry_hip_and_keeps_its_number():
     hdr = open(os.path.join(os.path.dirname(build.HERE), "include", "icpflow_hip.h")).read()
     for name in NEW:
         assert name + "(" in hdr and name in _lib.SIGNATURES and hasattr(_lib._L, name)
-    assert "8(l)  object tracks across the files of a log" in hdr and _lib.VERSION == 214
+    assert "8(l)  object tracks across the files of a log" in hdr and _lib.VERSION == 215
     assert (_lib.CARRY_COUNTS, _lib.PAIR_ROW_ID_COUNTS, _lib.PAIR_ROW_ID_MAX_PAIRS, _lib.TRACK_PATH_COLS, _lib.TRACK_PATH_COUNTS) == (
         cr.CARRY_COUNTS, cr.ROW_ID_COUNTS, cr.MAX_PAIRS, cr.PATH_COLS, cr.PATH_COUNTS)
     for define, value in (("ICPFLOW_CARRY_COUNTS", 6), ("ICPFLOW_PAIR_ROW_ID_COUNTS", 3), ("ICPFLOW_PAIR_ROW_ID_MAX_PAIRS", 4096),

@@ -171,7 +171,7 @@ def test_single_segment_lmax_exact_overflow_and_empty():
     from icp_flow_amd import utils_flow
     with pytest.raises(RuntimeError, match="distinct labels"):
         utils_flow.segment_table(G(pts), G(labels), max_segments=64)
-    assert _lib.VERSION == 214
+    assert _lib.VERSION == 215
 
 
 def test_determinism_across_runs_and_streams():

@@ -23,7 +23,7 @@ E_ARG, E_WORKSPACE, E_LIMIT = -1, -2, -3
 
 def test_exports_are_bound_and_sized():
     from icp_flow_amd import _lib
-    assert _lib.VERSION == 214
+    assert _lib.VERSION == 215
     for name, n_args in (("icpflow_nn_residual_workspace_bytes", 4), ("icpflow_nn_residual", 17)):
         assert hasattr(_lib._L, name) and len(_lib.SIGNATURES[name][1]) == n_args
     assert _lib.SIGNATURES["icpflow_nn_residual_workspace_bytes"][0] is ctypes.c_size_t

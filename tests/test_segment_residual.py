@@ -27,7 +27,7 @@ FN = "icpflow_nn_residual_segments"
 
 def test_exports_are_bound_and_sized():
     from icp_flow_amd import _lib, build
-    assert _lib.VERSION == 214
+    assert _lib.VERSION == 215
     for name, n_args in ((FN + "_workspace_bytes", 4), (FN, 19)):
         assert hasattr(_lib._L, name) and len(_lib.SIGNATURES[name][1]) == n_args
     assert _lib.SIGNATURES[FN + "_workspace_bytes"][0] is ctypes.c_size_t

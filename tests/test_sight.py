@@ -28,7 +28,7 @@ NAMES = ("icpflow_sight_default_params", "icpflow_sight_build", "icpflow_sight_q
 
 def test_exports_are_bound_and_sized():
     from icp_flow_amd import _lib, build
-    assert _lib.VERSION == 214
+    assert _lib.VERSION == 215
     for name, n_args in zip(NAMES, (1, 7, 10, 2, 20)):
         assert hasattr(_lib._L, name) and len(_lib.SIGNATURES[name][1]) == n_args
     assert _lib.SIGNATURES["icpflow_sight_segments_workspace_bytes"][0] is ctypes.c_size_t

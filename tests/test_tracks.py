@@ -26,7 +26,7 @@ def test_the_library_is_built_from_the_track_sources_and_keeps_its_number():
     for name in ("icpflow_label_overlap", "icpflow_label_overlap_workspace_bytes", "icpflow_object_tracks_default_params",
                  "icpflow_object_tracks_extend", "icpflow_object_tracks_extend_workspace_bytes", "icpflow_object_tracks_fit"):
         assert name + "(" in hdr and name in _lib.SIGNATURES and hasattr(_lib._L, name)
-    assert "8(k)  object tracks" in hdr and _lib.VERSION == 214
+    assert "8(k)  object tracks" in hdr and _lib.VERSION == 215
     assert (_lib.OVERLAP_COLS, _lib.OVERLAP_COUNTS, _lib.TRACK_SEGMENT_COLS, _lib.TRACK_OBS_COLS, _lib.TRACK_COLS, _lib.TRACK_EXTEND_COUNTS,
             _lib.TRACK_FIT_COUNTS) == (trk.OVERLAP_COLS, trk.OVERLAP_COUNTS, trk.SEGMENT_COLS, trk.OBS_COLS, trk.TRACK_COLS, 6, 5)
     for define, value in (("ICPFLOW_OVERLAP_COLS", 10), ("ICPFLOW_TRACK_SEGMENT_COLS", 6), ("ICPFLOW_TRACK_OBS_COLS", 13), ("ICPFLOW_TRACK_COLS", 16)):

@@ -27,7 +27,7 @@ ONE = ctypes.c_void_p(4096)
 
 def test_exports_are_bound_and_sized():
     from icp_flow_amd import _lib, build, utils_eval
-    assert _lib.VERSION == 214
+    assert _lib.VERSION == 215
     for name, n_args in zip(NAMES, (1, 18)):
         assert hasattr(_lib._L, name) and len(_lib.SIGNATURES[name][1]) == n_args and _lib.SIGNATURES[name][0] is ctypes.c_int
     assert "trust.hip" in build.SOURCES and "trust.hpp" in build.HEADERS and "labelkey.hpp" in build.HEADERS
