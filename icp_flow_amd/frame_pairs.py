@@ -861,7 +861,7 @@ def _pca_inputs(args, path, device, F, ground, pose_sources):
     # resident before the clock starts: what the evaluation reads besides the flows, and where each frame's rows are
     on = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device).to(dt)   # noqa: E731
     data = dict(raw_points=on(sample["raw_points"][:, 0:3], torch.float64 if sample["raw_points"].dtype == np.float64 else torch.float32),
-                time_indice=on(t, torch.int32), sd_labels=on(sample["sd_labels"], torch.int32),
+                time_indice=on(utils_eval.narrow_time_indices(t, F), torch.int32), sd_labels=on(sample["sd_labels"], torch.int32),
                 fb_labels=on(sample["fb_labels"], torch.int32), scene_flow=on(sample["scene_flow"], torch.float64))
     if not (np.isin(sample["sd_labels"], (0, 1)).all() and np.isin(sample["fb_labels"], (0, 1)).all()):
         data["sd_labels"], data["fb_labels"] = utils_eval._binary_labels(sample["sd_labels"], device), utils_eval._binary_labels(sample["fb_labels"], device)

@@ -158,6 +158,40 @@ def _binary_labels(labels, device):
     return utils_loading.to_device(np.where(a == 0, 0, np.where(a == 1, 1, 2)).astype(np.int32), torch.int32, device)
 
 
+def narrow_time_indices(time_indice, F):
+    """Time indices as the kernels read them (int32), narrowed the way _binary_labels narrows the labels: compared on the sample's
+    own type first.  A value that equals an integer of [0, F) -- the reference's `time_indice == j` is true for one j -- keeps
+    it; every other value (an int64 beyond int32 that a plain cast would wrap into [0, F), a fraction that it would truncate, NaN,
+    +-inf) becomes -1, which the kernels count as OUTSIDE and in no cell.  numpy array or tensor -> the same kind, int32."""
+    import torch
+    F = int(F)
+    if isinstance(time_indice, torch.Tensor):
+        t = time_indice if time_indice.is_floating_point() else time_indice.to(torch.int64)
+        inside = (t >= 0) & (t < F)
+        if t.is_floating_point():
+            inside = inside & (t == torch.floor(t))
+        return torch.where(inside, t, torch.full_like(t, -1)).to(torch.int32)
+    a = np.asarray(time_indice)
+    if a.dtype == object:
+        raise TypeError("an object array cannot be evaluated on the device")
+    if a.dtype.kind != "f":
+        a = a.astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        inside = (a >= 0) & (a < F)
+        if a.dtype.kind == "f":
+            inside = inside & (a == np.floor(a))
+        return np.where(inside, a, -1).astype(np.int32)
+
+
+def _time_indices(time_indice, F, device):
+    """narrow_time_indices on the device the call runs on"""
+    import torch
+    from . import utils_loading
+    if isinstance(time_indice, torch.Tensor):
+        return narrow_time_indices(utils_loading.to_device(time_indice, time_indice.dtype, device), F).contiguous()
+    return utils_loading.to_device(narrow_time_indices(time_indice, F), torch.int32, device)
+
+
 def _crop_arguments(args, raw):
     """calculate_metrics' crop as the kernels take it -> (ICPFLOW_SEQ_CROP_*, range_x, range_y, z_min)"""
     from . import _lib
@@ -170,7 +204,10 @@ def _crop_arguments(args, raw):
 def sequence_table(args, data, flow_seq):
     """icpflow_seq_metrics on one sequence -> (table int64 [F,6,6] numpy, sum of e float64 [F,6] numpy, kept points of
     frame 0, rows with a time index outside [0,F)).  Inputs may live on either side; with device tensors the only
-    device -> host copy is the table (F * 36 + 2 words, one copy)."""
+    device -> host copy is the table (F * 36 + 2 words, one copy).
+    OUTSIDE is every time index that equals no integer of [0, F) on the sample's own type -- the reference's `time_indice == j`
+    holds for no j: -1, F, an int64 such as 2^32 + 1 (never wrapped to 1), 1.5 (never truncated to 1), NaN.  Such a row is
+    counted there, in no cell and not in kept0 (narrow_time_indices); class_table and bucket_table read it the same way."""
     import ctypes
     import torch
     from . import _lib, utils_loading
@@ -179,7 +216,7 @@ def sequence_table(args, data, flow_seq):
     raw = data["raw_points"]
     pts = utils_loading.to_device(raw, torch.float64, device)[:, 0:3].contiguous()
     m = pts.shape[0]
-    tim = utils_loading.to_device(data["time_indice"], torch.int32, device)
+    tim = _time_indices(data["time_indice"], F, device)
     sd, fb = _binary_labels(data["sd_labels"], device), _binary_labels(data["fb_labels"], device)
     gt = utils_loading.to_device(data["scene_flow"], torch.float64, device)[:, 0:3].contiguous()
     pred = utils_loading.to_device(flow_seq, torch.float32, device)[:, 0:3].contiguous()
@@ -393,7 +430,7 @@ def class_table(args, data, flow_seq, classes=None, speed_edges=ARGO_SPEED_EDGES
     raw = data["raw_points"]
     pts = utils_loading.to_device(raw, torch.float64, device)[:, 0:3].contiguous()
     m = pts.shape[0]
-    tim = utils_loading.to_device(data["time_indice"], torch.int32, device)
+    tim = _time_indices(data["time_indice"], F, device)
     cls = utils_loading.to_device(data["classes"] if classes is None else classes, torch.float64, device)
     gt = utils_loading.to_device(data["scene_flow"], torch.float64, device)[:, 0:3].contiguous()
     pred = utils_loading.to_device(flow_seq, torch.float32, device)[:, 0:3].contiguous()
@@ -539,7 +576,7 @@ def bucket_table(args, data, flow_seq, classes=None, speed_edges=ARGO_BUCKET_EDG
     raw = data["raw_points"]
     pts = utils_loading.to_device(raw, torch.float64, device)[:, 0:3].contiguous()
     m = pts.shape[0]
-    tim = utils_loading.to_device(data["time_indice"], torch.int32, device)
+    tim = _time_indices(data["time_indice"], F, device)
     cls = utils_loading.to_device(data["classes"] if classes is None else classes, torch.float64, device)
     gt = utils_loading.to_device(data["scene_flow"], torch.float64, device)[:, 0:3].contiguous()
     pred = utils_loading.to_device(flow_seq, torch.float32, device)[:, 0:3].contiguous()

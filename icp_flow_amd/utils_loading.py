@@ -48,9 +48,6 @@ def seq_transform(points, time_indice, inst_labels, ego, inst_tsfm, output):
         raise ValueError(f"points: expected [m, >=3], got {tuple(pts.shape)}")
     pts = pts[:, 0:3].contiguous()
     m = pts.shape[0]
-    tim = to_device(time_indice, torch.int32, device)
-    if tim.shape != (m,):
-        raise ValueError("time_indice: one entry per point required")
     F = K = 0
     ego_d = tsfm_d = inst = None
     if ego is not None:
@@ -66,6 +63,10 @@ def seq_transform(points, time_indice, inst_labels, ego, inst_tsfm, output):
         inst = to_device(inst_labels, torch.int32, device)
         if inst.shape != (m,):
             raise ValueError("inst_labels: one entry per point required")
+    from . import utils_eval
+    tim = utils_eval._time_indices(time_indice, F, device)      # a value that equals no integer of [0, F) is -1: refused below
+    if tim.shape != (m,):
+        raise ValueError("time_indice: one entry per point required")
     out = torch.empty((m, 3), dtype=torch.float64, device=device)
     bad = torch.empty(1, dtype=torch.int64, device=device)
     with torch.cuda.device(device):

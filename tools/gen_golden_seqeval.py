@@ -20,7 +20,15 @@ relative error r lies within 1e-9 (relative) of a predicate threshold, and no co
 bound -- so a last-bit difference in e, r or the ground truth cannot move a point across.  The seed of a case is the first
 one, counting up from its base, for which the reference's own numbers meet the condition.
 
-Usage:  python tools/gen_golden_seqeval.py
+g13_seqeval_rows.npz is of another kind: the hand-built rows of tests/eval_rows_cases.py, which stand ON the thresholds and
+the crop faces or one step off them, with the reference's own verdict -- compute_epe_test on one row at a time (its five
+numbers are then that row's e and its four flags), crop_data's kept rows, and calculate_metrics' meters for an F = 3
+arrangement of the rows with float64 and with float32 points.  The predicate rows are judged twice: with the float64
+scene_flow every other fixture stores, and with scene_flow rounded to float32, where the reference subtracts, takes the
+norm and compares in float32.  THE MARGIN CONDITION DOES NOT APPLY TO THIS FILE: being on the margin is its purpose.
+
+Usage:  python tools/gen_golden_seqeval.py          every file
+        python tools/gen_golden_seqeval.py rows     g13_seqeval_rows.npz alone
 """
 import contextlib
 import io
@@ -33,6 +41,7 @@ REF = "/root/reference"
 sys.path.insert(0, REPO)
 sys.path.insert(0, REF)
 sys.path.insert(0, os.path.join(REPO, "tools", "standins"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import matplotlib  # noqa: E402
 
@@ -42,6 +51,7 @@ import numpy as np  # noqa: E402
 import utils_eval  # noqa: E402  (reference)
 import utils_loading  # noqa: E402  (reference)
 
+import eval_rows_cases as ec  # noqa: E402  (tests/)
 from icp_flow_amd.synthetic import _shell_points  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden")
@@ -155,8 +165,8 @@ def margin_ok(raw, gt, pred):
     return True
 
 
-def reference_meters(raw, s, gt, pred, num_frames, eval_ground):
-    args = SimpleNamespace(num_frames=num_frames, eval_ground=bool(eval_ground), **CROP)
+def reference_meters(raw, s, gt, pred, num_frames, eval_ground, crop=None):
+    args = SimpleNamespace(num_frames=num_frames, eval_ground=bool(eval_ground), **(CROP if crop is None else crop))
     meters = {f"{c}_{k:d}": utils_eval.AverageMeter() for c in CLASSES for k in range(num_frames + 1)}    # main.py:173-180
     data = dict(raw_points=raw, time_indice=s["time_indice"], sd_labels=s["sd_labels"], fb_labels=s["fb_labels"],
                 ego_motion_gt=s["ego_motion_gt"], scene_flow=gt, data_path="")
@@ -206,7 +216,60 @@ def save(name, arrays):
     print(f"wrote {path}  ({size / 1024:.1f} KiB)")
 
 
+def reference_rows(gt, pred):
+    """compute_epe_test on one row at a time -> (e [n] in the type the reference computed it in, flags uint8 [n,4])"""
+    e, flags = [], []
+    with np.errstate(all="ignore"):
+        for k in range(len(gt)):
+            out = utils_eval.compute_epe_test(pred[k:k + 1], gt[k:k + 1])
+            e.append(out[0])
+            flags.append([int(v) for v in out[1:]])
+            assert all(v in (0.0, 1.0) for v in out[1:])
+    return np.array(e), np.array(flags, dtype=np.uint8)
+
+
+def reference_keep(pts, eval_ground=False):
+    """the rows crop_data keeps, read off an index array sent through it in the place of the labels"""
+    n = len(pts)
+    args = SimpleNamespace(eval_ground=eval_ground, range_x=ec.RANGE_X, range_y=ec.RANGE_Y, range_z=ec.RANGE_Z, ground_slack=ec.GROUND_SLACK)
+    data = dict(raw_points=pts, time_indice=np.zeros(n, np.int64), sd_labels=np.arange(n), fb_labels=np.zeros(n, np.int64),
+                ego_motion_gt=None, scene_flow=np.zeros((n, 3)), data_path="")
+    with np.errstate(all="ignore"):
+        cropped, _ = utils_eval.crop_data(args, data, np.zeros((n, 3), np.float32))
+    keep = np.zeros(n, bool)
+    keep[cropped["sd_labels"]] = True
+    return keep
+
+
+def build_rows():
+    p = ec.predicate_rows()
+    out = dict(pred_name=p.name, pred_gt=p.gt, pred_pred=p.pred)
+    out["pred_e"], out["pred_flags"] = reference_rows(p.gt, p.pred)
+    gt32 = p.gt.astype(np.float32)
+    out["pred32_e"], out["pred32_flags"] = reference_rows(gt32, p.pred)
+    assert out["pred_e"].dtype == np.float64 and out["pred32_e"].dtype == np.float32
+    for dtype, tag in ((np.float64, "f64"), (np.float32, "f32")):
+        c = ec.crop_rows(dtype)
+        out[f"crop_{tag}_name"], out[f"crop_{tag}_pts"], out[f"crop_{tag}_keep"] = c.name, c.pts, reference_keep(c.pts)
+        out[f"crop_{tag}_keep_xy"] = reference_keep(c.pts, eval_ground=True)        # (crop_data's x-y half, which calculate_metrics never uses alone)
+        s = ec.meter_sample(dtype)
+        crop = dict(range_x=ec.RANGE_X, range_y=ec.RANGE_Y, range_z=ec.RANGE_Z, ground_slack=ec.GROUND_SLACK)
+        prefix = f"m{tag[1:]}__"
+        out.update({prefix + k: v for k, v in s.data.items()})
+        out[prefix + "pred_flow"], out[prefix + "num_frames"] = s.pred, np.array(s.F)
+        out.update({prefix + k: np.array(v) for k, v in crop.items()})
+        for g in (0, 1):
+            rec, names = reference_meters(s.data["raw_points"], dict(s.data, ego_motion_gt=None), s.data["scene_flow"], s.pred, s.F, g, crop)
+            out.update({prefix + f"eg{g}_{k}": v for k, v in rec.items()})
+        out[prefix + "meter_names"] = np.array(names)
+    return out
+
+
 def main():
+    if sys.argv[1:] == ["rows"]:
+        save("g13_seqeval_rows", build_rows())
+        return
+    save("g13_seqeval_rows", build_rows())
     for F, base in ((3, 300), (5, 500)):
         for dtype, tag in ((np.float32, "f32"), (np.float64, "f64")):
             c = build_case(base, F, dtype)
