@@ -132,6 +132,11 @@ SIGNATURES = {
     "icpflow_object_tracks_extend_side": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "icpflow_object_tracks_path_default_params": (_i, [_p]),
     "icpflow_object_tracks_path": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p, _p]),
+    "icpflow_object_tracks_suspects": (_i, [_p, _i, _i, _p, _p, _p, _p]),
+    "icpflow_pairs_repair_default_params": (_i, [_p]),
+    "icpflow_pairs_repair_select": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "icpflow_pairs_reregister_workspace_bytes": (_sz, [_i, _i]),
+    "icpflow_pairs_reregister": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -181,6 +186,8 @@ TRACK_SEGMENT_COLS, TRACK_OBS_COLS, TRACK_COLS = 6, 13, 16        # icpflow_obje
 TRACK_EXTEND_COUNTS, TRACK_FIT_COUNTS = 6, 5                      # ... words of their d_counts
 CARRY_COUNTS, PAIR_ROW_ID_COUNTS, PAIR_ROW_ID_MAX_PAIRS = 6, 3, 4096   # icpflow_rows_carry, icpflow_pair_row_ids: words of d_counts; P at most
 TRACK_PATH_COLS, TRACK_PATH_COUNTS = 24, 5                        # icpflow_object_tracks_path: columns of a row; words of d_counts
+TRACK_PLAN_COLS, TRACK_PLAN_COUNTS, TRACK_PLAN_MAX_ROWS = 8, 4, 1 << 16   # icpflow_object_tracks_suspects: columns; words of d_counts; M at most
+REPAIR_COLS, REPAIR_COUNTS = 12, 8                                # icpflow_pairs_repair_select: columns of a report row; words of d_counts
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical
@@ -406,6 +413,26 @@ class TrackPathParams(ctypes.Structure):
 
     def as_dict(self):
         return dict(max_dv=self.max_dv, min_speed=self.min_speed)
+
+
+class RepairParams(ctypes.Structure):
+    """icpflow_repair_params_t: the association's four thresholds and the distance from the predicted displacement a repaired
+    pose stays within (icpflow_pairs_repair_select, icpflow_pairs_reregister)."""
+    _fields_ = [("struct_size", _sz), ("translation_frame", _d), ("thres_iou", _d), ("rot_limit_deg", _d), ("thres_error", _d), ("max_residual", _d)]
+
+    @staticmethod
+    def defaults(**over):
+        p = RepairParams()
+        call("icpflow_pairs_repair_default_params", ctypes.byref(p))
+        for k, v in over.items():
+            if k == "struct_size" or k not in dict(RepairParams._fields_):
+                raise TypeError(f"RepairParams: no parameter {k!r}")
+            setattr(p, k, float(v))
+        return p
+
+    def as_dict(self):
+        return dict(translation_frame=self.translation_frame, thres_iou=self.thres_iou, rot_limit_deg=self.rot_limit_deg, thres_error=self.thres_error,
+                    max_residual=self.max_residual)
 
 
 class ObjectParams(ctypes.Structure):

@@ -27,9 +27,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 OUT = os.path.join(HERE, "libicpflow_hip.so")
-SOURCES = ["api.hip", "hist.hip", "nn.hip", "icp.hip", "icp_prep.hip", "icp_plan.hip", "icp_epilogue.hip", "device.hip", "icp_fp32.hip", "pose.hip", "sort.hip", "cluster.hip", "hdbscan.hip", "clusterpcd.hip", "table.hip", "assoc.hip", "frame.hip", "ego.hip", "seqeval.hip", "classeval.hip", "bucketeval.hip", "segeval.hip", "ground.hip", "nnresid.hip", "segresid.hip", "sight.hip", "trust.hip", "boxes.hip", "overlap.hip", "tracks.hip", "carry.hip",
+SOURCES = ["api.hip", "hist.hip", "nn.hip", "icp.hip", "icp_prep.hip", "icp_plan.hip", "icp_epilogue.hip", "device.hip", "icp_fp32.hip", "pose.hip", "sort.hip", "cluster.hip", "hdbscan.hip", "clusterpcd.hip", "table.hip", "assoc.hip", "frame.hip", "ego.hip", "seqeval.hip", "classeval.hip", "bucketeval.hip", "segeval.hip", "ground.hip", "nnresid.hip", "segresid.hip", "sight.hip", "trust.hip", "boxes.hip", "overlap.hip", "tracks.hip", "carry.hip", "repair.hip",
            "hdbscan_tree.cpp"]
-HEADERS = ["common.hpp", "scan.hpp", "kernels.hpp", "kabsch.hpp", "posefuse.hpp", "scorepick.hpp", "votekey.hpp", "cluster_util.hpp", "sortdir.hpp", "sortclouds.hpp", "occgrid.hpp", "host.hpp", "carver.hpp", "rowerr.hpp", "clusterpcd_host.hpp", "gridhash.hpp", "nnresid.hpp", "sight.hpp", "labelkey.hpp", "trust.hpp", "boxes.hpp", "overlap.hpp", "icp_instr.hip",
+HEADERS = ["common.hpp", "scan.hpp", "kernels.hpp", "kabsch.hpp", "posefuse.hpp", "scorepick.hpp", "votekey.hpp", "cluster_util.hpp", "sortdir.hpp", "sortclouds.hpp", "occgrid.hpp", "host.hpp", "carver.hpp", "rowerr.hpp", "clusterpcd_host.hpp", "gridhash.hpp", "nnresid.hpp", "sight.hpp", "labelkey.hpp", "trust.hpp", "boxes.hpp", "overlap.hpp", "rejecttest.hpp", "icp_instr.hip",
            os.path.join("..", "..", "include", "icpflow_hip.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]

@@ -9,6 +9,7 @@
 // (icpflow_options_t::d_pair_active keeps the switched-off ones out of the ICP's batch-global stop).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rejecttest.hpp"
 
 namespace icpflow {
 namespace {
@@ -23,26 +24,15 @@ struct AssignParams {
     int K2; const int32_t *si2, *di2; int64_t *seg2; uint8_t *active2;
 };
 
-// check_transformation (utils_check.py:51-66) of candidate k in the fp32 arithmetic of the numpy mirror (utils_check.py of this
-// package): ~(sqrt((t0*t0 + t1*t1) + t2*t2) > tf) & ~(min(iou) < thres_iou) & ~(max(|rot_1|, |rot_2|) > thres_rot * 90).  numpy's
-// minimum / maximum PROPAGATE a NaN and every comparison with a NaN is false, i.e. a NaN passes the test it sits in; fminf /
-// fmaxf drop a NaN, so the NaN cases are spelled out.  err = min(error_src, error_dst), NaN if either is.
+// check_transformation (utils_check.py:51-66) of candidate k: rejecttest.hpp's test on the stage's result arrays.
+// err = min(error_src, error_dst), NaN if either is.
 __device__ __forceinline__ bool assoc_keep(const AssignParams &p, int k, float &err)
 {
     const int K = p.K;
     const float *errors = p.r + 16 * (size_t)K, *ious = p.r + 22 * (size_t)K, *tr = p.r + 24 * (size_t)K, *rot = p.r + 27 * (size_t)K;
-    const float t0 = tr[3 * k], t1 = tr[3 * k + 1], t2 = tr[3 * k + 2];
-    const float nrm = sqrtf((t0 * t0 + t1 * t1) + t2 * t2);
-    const float i0 = ious[2 * k], i1 = ious[2 * k + 1];
-    const float r1 = rot[3 * k + 1], r2 = rot[3 * k + 2];
-    const float e0 = errors[2 * k], e1 = errors[2 * k + 1];
-    err = (e0 != e0 || e1 != e1) ? __int_as_float(0x7fc00000) : fminf(e0, e1);
-    const bool farOff = nrm > p.tf;                                                   // (NaN: false)
-    // (Python's builtin min(iou) on the two-element tensor, utils_match.py:99: iou[1] if iou[1] < iou[0] else iou[0] -- a NaN in
-    // iou[1] leaves iou[0] to be tested, a NaN in iou[0] is the result and passes the comparison)
-    const bool lowIou = ((i1 < i0) ? i1 : i0) < p.iouMin;
-    const bool turned = (r1 == r1 && r2 == r2) && fmaxf(fabsf(r1), fabsf(r2)) > p.rotMax;
-    return !farOff && !lowIou && !turned;
+    const RejectTest t = reject_test(errors, ious, tr, rot, k, p.tf, p.iouMin, p.rotMax);
+    err = t.err;
+    return t.keep;
 }
 
 __global__ __launch_bounds__(kAssocBlock) void assoc_assign_kernel(AssignParams p)

@@ -1,7 +1,9 @@
 // tracks.hip -- the clusters of a sample's shared sweep linked across its gaps, and a constant velocity per track
 // (include/icpflow_hip.h, "8(k) object tracks": icpflow_object_tracks_extend, icpflow_object_tracks_fit); the same extension
 // on the SOURCE side of a pair and one row per track over a log ("8(l)": icpflow_object_tracks_extend_side,
-// icpflow_object_tracks_path -- trk_path_kernel, a thread per track like the fit).
+// icpflow_object_tracks_path -- trk_path_kernel, a thread per track like the fit); which observation breaks its track
+// ("8(m) track repair": icpflow_object_tracks_suspects -- trk_suspects_kernel, a thread per OBSERVATION, the fit leave-one-out;
+// repair.hip registers the named pairs again).
 //
 // icpflow_object_tracks_extend, one gap:
 //   1. trk_labels_kernel    "track id per row" as a float32 labelling (an id is its own label, no track is -1)
@@ -45,6 +47,7 @@ constexpr int kFitCounts = ICPFLOW_TRACK_FIT_COUNTS;
 static_assert(ICPFLOW_TRACK_EXTEND_COUNTS == 6, "segments, inherited, fresh, observations with and without an id, overflow");
 constexpr int kMaxId = 1 << 24;                        // ids travel as float32 labels: exact up to here
 constexpr int kMaxFitRows = 1 << 24;
+constexpr int kMaxSuspectRows = 1 << 16;               // the plan's walk is quadratic in the observations
 
 // what an extension carves out of its workspace, in this order (the size query runs it on a null base)
 struct Carve {
@@ -267,6 +270,76 @@ __global__ __launch_bounds__(kThreads) void trk_fit_kernel(const double *__restr
     }
 }
 
+// Which observation breaks its track (8(m)): a thread per observation j fits the OTHER observations of its track and asks
+// whether they agree among themselves and j does not agree with them.  Two walks over the M rows in ascending order, fp64,
+// every operation written out -- the fit's style, leave-one-out.
+__global__ __launch_bounds__(kThreads) void trk_suspects_kernel(const double *__restrict__ obs, int M, int T, double maxResidual,
+                                                                double *__restrict__ plan, unsigned long long *__restrict__ counts)
+{
+    constexpr int kCols = ICPFLOW_TRACK_PLAN_COLS, kCounts = ICPFLOW_TRACK_PLAN_COUNTS;
+    __shared__ int sh[kWaves][kCounts];
+    const int j = blockIdx.x * kThreads + (int)threadIdx.x;
+    const bool live = j < M;
+    bool withId = false, eligible = false, agreed = false, suspect = false;
+    if (live) {
+        const double *me = obs + (size_t)j * kObsCols;
+        const double id = me[0];
+        double row[kCols] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        withId = id >= 0.0 && id < (double)T;           // (a NaN is outside)
+        if (withId) {
+            int others = 0;
+            unsigned long long mask = 0ull;
+            double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
+            for (int k = 0; k < M; ++k) {
+                const double *o = obs + (size_t)k * kObsCols;
+                if (k == j || o[0] != id) continue;
+                const double s = o[2];
+                den += s * s;
+                num[0] += s * o[3], num[1] += s * o[4], num[2] += s * o[5];
+                if (o[1] >= 0.0 && o[1] < 64.0) mask |= 1ull << (int)o[1];
+                ++others;
+            }
+            const int gaps = __popcll(mask);
+            row[1] = (double)others, row[2] = (double)gaps;
+            eligible = gaps >= 2 && den > 0.0;
+            if (eligible) {
+                const double v[3] = {num[0] / den, num[1] / den, num[2] / den};
+                double inner = 0.0;
+                for (int k = 0; k < M; ++k) {
+                    const double *o = obs + (size_t)k * kObsCols;
+                    if (k == j || o[0] != id) continue;
+                    const double rx = o[3] - o[2] * v[0], ry = o[4] - o[2] * v[1];
+                    const double r2 = rx * rx + ry * ry;
+                    inner = r2 > inner ? r2 : inner;
+                }
+                const double s = me[2];
+                const double p[3] = {s * v[0], s * v[1], s * v[2]};
+                const double rx = me[3] - p[0], ry = me[4] - p[1];
+                const double r2 = rx * rx + ry * ry, m2 = maxResidual * maxResidual;
+                agreed = inner <= m2;
+                suspect = agreed && r2 > m2;
+                row[0] = suspect ? 1.0 : 0.0, row[3] = p[0], row[4] = p[1], row[5] = p[2], row[6] = sqrt(r2), row[7] = sqrt(inner);
+            }
+        }
+        double *out = plan + (size_t)j * kCols;
+#pragma unroll
+        for (int c = 0; c < kCols; ++c) out[c] = row[c];
+    }
+    const bool flag[kCounts] = {withId, eligible, agreed, suspect};
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kCounts; ++k) {                // (every lane takes every round: the ballots see whole waves)
+        const int c = __popcll(__ballot(flag[k]));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh[wave][k] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCounts) {
+        int c = 0;
+        for (int w = 0; w < kWaves; ++w) c += sh[w][threadIdx.x];
+        if (c != 0) atomicAdd(&counts[threadIdx.x], (unsigned long long)c);
+    }
+}
+
 // One row per track over a log (8(l)): a thread per track walks the M observations in row order; of the observations of one
 // step the one with the most source points is COUNTED (the lower row on a tie) -- a step's rows are contiguous, the steps are
 // non-decreasing, so the walk keeps one candidate and counts it when the step changes.  fp64, every operation written out.
@@ -472,6 +545,29 @@ int icpflow_object_tracks_fit(const double *d_obs, int M, int T, const icpflow_t
     if (T == 0) return ICPFLOW_OK;
     trk_fit_kernel<<<(T + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_obs, M, T, params->max_residual, params->min_speed, d_tracks,
                                                                        (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    return ICPFLOW_OK;
+}
+
+int icpflow_object_tracks_suspects(const double *d_obs, int M, int T, const icpflow_track_params_t *params, double *d_plan, int64_t *d_counts,
+                                   icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_object_tracks_suspects";
+    if (M < 0 || T < 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_suspects: M = %d, T = %d: a negative size", M, T);
+    if (M > kMaxSuspectRows || T > kMaxFitRows)
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_suspects: M = %d, T = %d: at most %d observations (the walk is quadratic) and %d tracks",
+                             M, T, kMaxSuspectRows, kMaxFitRows);
+    if (!params || !d_counts || (M > 0 && (!d_obs || !d_plan))) return pointer_error(fn);
+    if (params->struct_size != sizeof(icpflow_track_params_t))
+        return report_errorf(ICPFLOW_E_ARG, "%s: params->struct_size = %zu, this library's icpflow_track_params_t has %zu bytes", fn, params->struct_size,
+                             sizeof(icpflow_track_params_t));
+    if (!(params->max_residual >= 0.0) || !std::isfinite(params->max_residual))
+        return report_errorf(ICPFLOW_E_ARG, "%s: max_residual = %g: max_residual must be finite and not negative", fn, params->max_residual);
+
+    hipStream_t st = (hipStream_t)stream;
+    ICPFLOW_TRY(hipMemsetAsync(d_counts, 0, ICPFLOW_TRACK_PLAN_COUNTS * sizeof(int64_t), st));
+    if (M == 0) return ICPFLOW_OK;
+    trk_suspects_kernel<<<(M + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_obs, M, T, params->max_residual, d_plan, (unsigned long long *)d_counts);
     ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }

@@ -18,7 +18,7 @@ import time
 import numpy as np
 import torch
 
-from . import utils_eval, utils_objects, utils_tracks
+from . import utils_check, utils_eval, utils_flow, utils_objects, utils_tracks
 from .pair_data import _input
 
 
@@ -145,23 +145,92 @@ def _frame_objects_device(fp, out, device, seconds, min_speed, delta=utils_objec
 
 
 def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, min_speed=utils_tracks.MIN_SPEED, min_iou=utils_tracks.MIN_IOU,
-                 max_residual=utils_tracks.MAX_RESIDUAL, Lmax=4096):
+                 max_residual=utils_tracks.MAX_RESIDUAL, Lmax=4096, repair=False, args=None):
     """The object tracks of ONE sample (utils_tracks), everything on the device: `fps` the sample's frame pairs in gap order --
     they share the destination sweep, row for row -- and `outs` their registrations.  Per gap the object rows of frame_objects
     (not read back), then the shared sweep's clusters linked to the tracks so far (icpflow_object_tracks_extend); at the end one
-    fit over all gaps and ONE read-back.  A gap of `gap` sweeps spans gap * sweep_seconds.  -> utils_tracks.Tracks"""
+    fit over all gaps and ONE read-back.  A gap of `gap` sweeps spans gap * sweep_seconds.  -> utils_tracks.Tracks
+
+    repair=True (with `args`, what the frame pairs were registered with): the gaps that alone break a track's constant velocity
+    are registered again (include/icpflow_hip.h, 8(m)).  After the tracks as above, icpflow_object_tracks_suspects over all
+    observations and its one read-back (with the pairs' labels); a sample without a suspect launches nothing more.  Per gap with
+    suspects one icpflow_pairs_reregister from the pure translations the other gaps predict -- a pair with a cluster longer than
+    args.max_points is not retried (reason 6: its subsample would draw random numbers); every `out` of such a gap gets NEW
+    tensors under `transformations` (the accepted poses in their rows), `pairs` (their error, inlier, ratio and iou columns from
+    the new metrics) and `flow` (utils_flow.flow_estimation_torch on the patched rows); then the object rows and the tracks are
+    computed again.  -> the Tracks after repair, its `repair` a utils_tracks.Repair (the Tracks before, the retried pairs)."""
     device = torch.device(device)
     n = len(fps[0].points_dst)
     if any(len(fp.points_dst) != n for fp in fps):
         raise ValueError(f"object tracks: the frame pairs of {fps[0].sequence or fps[0].name!r} disagree on the rows of the shared sweep "
                          f"({sorted({len(fp.points_dst) for fp in fps})}): they are not the gaps of one sample")
-    state = utils_tracks.TrackState(n, device, Lmax, min_iou, max_residual, min_speed)
-    for fp, out in zip(fps, outs):
-        seconds = float(fp.gap) * float(sweep_seconds)
-        rows, _, ld = _frame_objects_device(fp, out, device, seconds, min_speed)
-        state.extend(ld, rows, fp.gap, seconds)
-    state.fit()
-    return state.read()
+
+    def chain():
+        state, tables = utils_tracks.TrackState(n, device, Lmax, min_iou, max_residual, min_speed), []
+        for fp, out in zip(fps, outs):
+            seconds = float(fp.gap) * float(sweep_seconds)
+            rows, _, ld = _frame_objects_device(fp, out, device, seconds, min_speed)
+            state.extend(ld, rows, fp.gap, seconds)
+            tables.append(rows)
+        state.fit()
+        return state, tables
+
+    state, tables = chain()
+    if not repair:
+        return state.read()
+    if args is None:
+        raise ValueError("frame_tracks(repair=True) registers again: it needs the `args` the frame pairs were registered with")
+    plan, plan_counts = utils_tracks.suspects_device(torch.cat(state.obs), state.bound, max_residual)
+    before = state.read()
+    t0 = time.perf_counter()                                 # (the read-back above left the stream empty; the last one below drains it)
+    sizes = [int(t.shape[0]) for t in tables]
+    labels = [out["pairs"][:, 0:2].to(device=device, dtype=torch.float64).reshape(-1) for out in outs]
+    host = torch.cat([plan_counts.to(torch.float64), plan.reshape(-1)] + labels).cpu().numpy()        # the plan's one read-back
+    plan_counts, at = np.rint(host[:4]).astype(np.int64), 4 + 8 * sum(sizes)
+    h_plan = host[4: at].reshape(-1, 8)
+    retried, counts, results, first = [], np.zeros(8, np.int64), [], 0
+    for g, (fp, out, rows, P) in enumerate(zip(fps, outs, tables, sizes)):
+        pair_labels, at = host[at: at + 2 * P].reshape(P, 2), at + 2 * P
+        mine, first = np.flatnonzero(h_plan[first: first + P, 0] == 1.0), first + P
+        if len(mine) == 0:
+            continue
+        ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+        ls, ld = _source_labels(fp, out, device), out["labels_dst"].to(device).float() if out.get("labels_dst") is not None else _input(fp, "labels_dst", device).float()
+        st, dt = utils_check.ClusterTable.pair(ps, ls, pd, ld)
+        si, di = st.find_host(pair_labels[mine, 0]), dt.find_host(pair_labels[mine, 1])
+        fits = (si >= 0) & (di >= 0)
+        fits[fits] = (st.h_count[si[fits]] <= int(args.max_points)) & (dt.h_count[di[fits]] <= int(args.max_points))
+        entry = lambda p, g=g, pair_labels=pair_labels: dict(gap=g, pair=int(p), labels=[float(v) for v in pair_labels[p]], track=int(before.observation_ids[g][p]))   # noqa: E731
+        for p in mine[~fits]:
+            retried.append(dict(entry(p), reason=utils_tracks.REPAIR_TOO_LONG, accepted=False))
+            counts[utils_tracks.REPAIR_TOO_LONG] += 1
+        mine, si, di = mine[fits], si[fits], di[fits]
+        if len(mine) == 0:
+            continue
+        idx = torch.from_numpy(mine).to(device)
+        T = out["transformations"].to(device=device, dtype=torch.float32).reshape(P, 16)
+        params = utils_tracks.repair_params(args, out["translation_frame"], max_residual)
+        res = utils_tracks.reregister_device(args, st, dt, si, di, T[idx], rows[idx, 4:7], plan[first - P + idx, 3:6], params)
+        T, pairs = T.clone(), out["pairs"].to(device).clone()
+        T[idx] = res["T"].reshape(-1, 16)                       # (a rejected pair's row is its old one, bit for bit)
+        fresh = torch.cat([res["errors"], res["inliers"], res["ratios"], res["ious"]], dim=1)
+        pairs[idx, 2:10] = torch.where(res["report"][:, 11:12] == 1.0, fresh, pairs[idx, 2:10])
+        out["pairs"], out["transformations"] = pairs, T.view(P, 4, 4)
+        flow_src = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+        out["flow"] = utils_flow.flow_estimation_torch(args, flow_src, pd, ls, ld, pairs, out["transformations"], torch.from_numpy(fp.pose).to(device))
+        results.append((mine, entry, res))
+    if results:
+        host = torch.cat([torch.cat([r["counts"].to(torch.float64), r["report"].reshape(-1)]) for _, _, r in results]).cpu().numpy()
+        at = 0
+        for mine, entry, _ in results:
+            counts += np.rint(host[at: at + 8]).astype(np.int64)
+            report, at = host[at + 8: at + 8 + 12 * len(mine)].reshape(-1, 12), at + 8 + 12 * len(mine)
+            for p, r in zip(mine, report):
+                retried.append(dict(entry(p), reason=int(r[0]), e_old=float(r[2]), e_new=float(r[1]), distance=float(r[6]), accepted=bool(r[11])))
+        state, _ = chain()                                   # the object rows and the tracks, again, on the repaired gaps
+    after = state.read() if results else before
+    after.repair = utils_tracks.Repair(before, plan_counts, sorted(retried, key=lambda e: (e["gap"], e["pair"])), counts, (time.perf_counter() - t0) * 1e3)
+    return after
 
 
 def log_frames(poses):
@@ -498,15 +567,16 @@ class ObjectJudge:
         self.min_speed = float(getattr(args, "objects_min_speed", utils_objects.MIN_SPEED))
         self.device = device
         self.lines, self.ms, self.counts, self.gap = {}, [], np.zeros(5, np.int64), None    # frame pair -> its line of the file
+        self.parts = {}                            # frame pair -> what it added to the counts, its largest centre gap
 
     def account(self, number, fp, out):
         with timed(self.device, self.ms):
             seen = frame_objects(fp, out, self.device, float(fp.gap) * self.sweep_seconds, self.min_speed)
         s = seen.summary()
-        self.counts += [s[name] for name in utils_objects.COUNT_NAMES] + [s["pairs"]]
-        gap = seen.largest_centre_gap()
-        if gap is not None and (self.gap is None or gap > self.gap):
-            self.gap = gap
+        # (a frame pair accounted a second time -- the TrackJudge's repair of its gap -- replaces what it added the first time)
+        self.parts[number] = (np.array([s[name] for name in utils_objects.COUNT_NAMES] + [s["pairs"]], np.int64), seen.largest_centre_gap())
+        self.counts = sum((c for c, _ in self.parts.values()), np.zeros(5, np.int64))
+        self.gap = max((g for _, g in self.parts.values() if g is not None), default=None)
         self.lines[number] = dict(frame_pair=number, path=fp.name, seconds=seen.seconds, counts=s, objects=seen.as_list())
 
     def summarise(self, out):
@@ -532,7 +602,15 @@ class TrackJudge:
     `ms_tracks_per_sample` (device-synchronised around the chain and its one read-back); with a file name, one JSON line per
     sample is written there (counts, per observed track its velocity, residuals, verdicts and size, and per gap the track of
     every object row) and the summary names it as `tracks_file`.  Where the ObjectJudge keeps lines, every object entry gains
-    `track`.  sample_of, samples: the maps that frame_pairs._by_sample fills as the frame pairs go by."""
+    `track`.  sample_of, samples: the maps that frame_pairs._by_sample fills as the frame pairs go by.
+
+    args.tracks_repair = True (`--tracks-repair`; needs args.tracks): `frame_tracks(repair=True)` -- a gap that alone breaks its
+    track is registered again and, where accepted, the `out` of that frame pair carries the new transform, pair row and flow from
+    then on; the ObjectJudge accounts such a frame pair again (its line and its counts are replaced).  A sample's line gains
+    `repair` (per retried pair its gap, frame pair, pair row, labels, track, reason, e_old, e_new, distance from the prediction,
+    accepted), the summary `tracks_repair` (suspects, retried, accepted, a count per reason, consistent_before / consistent_after)
+    and `ms_tracks_repair_per_sample` (behind the tracks' first read-back, to the end of the second chain).  What run_stream
+    scored of a frame pair's flow at its delivery (files with ground truth) is of the registration as delivered."""
 
     def __init__(self, args, world, device, objects, sample_of, samples):
         self.file = getattr(args, "tracks", None)
@@ -544,6 +622,12 @@ class TrackJudge:
         self.device, self.objects, self.sample_of, self.samples = device, objects, sample_of, samples
         self.lines, self.ms = {}, []               # sample -> its line of the file
         self.totals = dict(tracks=0, observed=0, judged=0, consistent=0, inconsistent=0, moving=0, overflow=0)
+        self.repair, self.args = bool(getattr(args, "tracks_repair", False)), args
+        if self.repair and not self.on:
+            raise ValueError("args.tracks_repair goes with args.tracks (it registers again what the tracks name)")
+        self.ms_repair = []
+        self.repaired = dict(suspects=0, retried=0, accepted=0, reasons={name: 0 for name in utils_tracks.REPAIR_REASONS}, consistent_before=0,
+                             consistent_after=0)
 
     def account(self, number, fp, out):
         sample = self.samples[self.sample_of.pop(number)]
@@ -557,12 +641,25 @@ class TrackJudge:
         fps = [sample["outs"][k][0] for k in ks]
         with timed(self.device, self.ms):
             seen = frame_tracks(fps, [sample["outs"][k][1] for k in ks], self.device, self.objects.sweep_seconds, self.objects.min_speed,
-                                self.min_iou, self.max_residual)
+                                self.min_iou, self.max_residual, repair=self.repair, args=self.args)
         summary = seen.summary()
         for name in self.totals:
             self.totals[name] += summary[name]
         self.lines[s] = dict(sample=s, path=fps[0].sequence or fps[0].name, frame_pairs=ks, gaps=[fp.gap for fp in fps], counts=summary,
                              tracks=seen.as_list(), observations=[ids.tolist() for ids in seen.observation_ids])
+        if self.repair:
+            done = seen.repair.summary(seen)
+            for name, v in done.items():
+                if name == "reasons":
+                    for reason, c in v.items():
+                        self.repaired["reasons"][reason] += c
+                else:
+                    self.repaired[name] += v
+            self.ms_repair.append(seen.repair.ms)
+            self.lines[s]["repair"] = [dict(e, frame_pair=ks[e["gap"]], reason=utils_tracks.REPAIR_REASONS[e["reason"]]) for e in seen.repair.retried]
+            if self.objects.on:                     # the objects of a repaired gap, again: its line and its counts are replaced
+                for g in sorted({e["gap"] for e in seen.repair.retried if e["accepted"]}):
+                    self.objects.account(ks[g], fps[g], sample["outs"][ks[g]][1])
         for k, ids in zip(ks, seen.observation_ids):
             for e in self.objects.lines.get(k, {}).get("objects", []):
                 e["track"] = int(ids[e["pair"]])
@@ -571,6 +668,9 @@ class TrackJudge:
         out["tracks"] = dict(self.totals, samples=len(self.lines), min_iou=self.min_iou, max_residual=self.max_residual,
                              min_speed=self.objects.min_speed, sweep_seconds=self.objects.sweep_seconds)
         out["ms_tracks_per_sample"] = sum(self.ms) / max(len(self.ms), 1)
+        if self.repair:
+            out["tracks_repair"] = dict(self.repaired)
+            out["ms_tracks_repair_per_sample"] = sum(self.ms_repair) / max(len(self.ms_repair), 1)
         if isinstance(self.file, str):
             with open(self.file, "w") as f:
                 for s in sorted(self.lines):        # one JSON line per sample, in their order

@@ -198,6 +198,94 @@ class TrackState:
         return Tracks(rows, fit_counts, next_id, list(self.gaps), ids, extend_counts, self.params.as_dict())
 
 
+REPAIR_REASONS = ("accepted", "reject_test", "error", "off_prediction", "not_better", "abandoned", "too_long")
+REPAIR_TOO_LONG = 6            # a cluster longer than args.max_points: not retried (its subsample would draw random numbers)
+
+
+def suspects_device(obs, T, max_residual=MAX_RESIDUAL):
+    """icpflow_object_tracks_suspects enqueued on the current stream, nothing read back.  obs float64 [M, 13]: the observations of
+    every gap, concatenated as `TrackState.fit` concatenates them; T: the tracks (an upper bound).  -> (plan float64 [M, 8],
+    counts int64 [4]) on the device: per observation whether it alone breaks its track, and the displacement the others predict."""
+    import torch
+    from . import _lib
+    _lib.require_gpu(obs)
+    M, device = int(obs.shape[0]), obs.device
+    if obs.dtype != torch.float64 or tuple(obs.shape) != (M, _lib.TRACK_OBS_COLS):
+        raise ValueError(f"suspects: observations {tuple(obs.shape)} {obs.dtype}, expected float64 [M, {_lib.TRACK_OBS_COLS}]")
+    rows = obs.contiguous()
+    plan = torch.empty((M, _lib.TRACK_PLAN_COLS), dtype=torch.float64, device=device)
+    counts = torch.empty(_lib.TRACK_PLAN_COUNTS, dtype=torch.int64, device=device)
+    params = _lib.TrackParams.defaults(max_residual=max_residual)
+    with torch.cuda.device(device):
+        _lib.call("icpflow_object_tracks_suspects", _lib.ptr(rows) if M else None, M, int(T), ctypes.byref(params), _lib.ptr(plan) if M else None,
+                  _lib.ptr(counts), _lib.stream(device))
+    return plan, counts
+
+
+def repair_params(args, translation_frame, max_residual=MAX_RESIDUAL):
+    """_lib.RepairParams of the association's thresholds in `args` (thres_iou, thres_rot * 90 degrees, thres_error), the gap's
+    translation_frame and the tracks' max_residual"""
+    from . import _lib
+    return _lib.RepairParams.defaults(translation_frame=float(translation_frame), thres_iou=float(args.thres_iou), rot_limit_deg=float(args.thres_rot) * 90.0,
+                                      thres_error=float(args.thres_error), max_residual=float(max_residual))
+
+
+def reregister_device(args, st, dt, si, di, T_old, centre, pred, params):
+    """icpflow_pairs_reregister enqueued on the current stream, nothing read back: K pairs of ONE frame pair registered again
+    from the pure translations [I | pred].  st, dt: the gap's utils_check.ClusterTable of the ego-compensated source and of the
+    destination (fetched); si, di: the K pairs' rows of the two tables (numpy), none of them longer than args.max_points -- the
+    repair draws no random numbers; T_old float32 [K, 4, 4], centre and pred float64 [K, 3]: device tensors; params: a
+    _lib.RepairParams.  -> dict(T float32 [K, 4, 4], report float64 [K, 12], counts int64 [8], T_new, errors, inliers, ratios,
+    ious [K, 2], iterations int32 [1]) on the device; the metrics are the new poses', views of the call's workspace."""
+    import torch
+    from . import _lib, utils_match
+    _lib.require_gpu(T_old, centre, pred)
+    device, K = st.points.device, len(si)
+    if K < 1 or len(di) != K or int(max(st.h_count[si].max(), dt.h_count[di].max())) > int(args.max_points):
+        raise ValueError(f"reregister: {K} source and {len(di)} destination clusters, the longest beyond max_points = {args.max_points}?")
+    old = T_old.to(device=device, dtype=torch.float32).reshape(K, 16).contiguous()
+    c, p = (t.to(device=device, dtype=torch.float64).reshape(K, 3).contiguous() for t in (centre, pred))
+    init = torch.eye(4, dtype=torch.float32, device=device).repeat(K, 1, 1)
+    init[:, 0:3, 3] = p.to(torch.float32)
+    key, base, _, N, has_perm = utils_match._stage_rows(args, st, dt, si, di)
+    assert not has_perm
+    max_it, rel, stop = utils_match._icp_options(args)
+    reg = _lib.Registration(None, None, None, 0, 0, 0, 0.0, float(args.thres_dist), float(rel), int(max_it), int(stop))
+    tables = _lib.Tables(st.points.data_ptr(), st.order.data_ptr(), st._packed.data_ptr() + 8, dt.points.data_ptr(), dt.order.data_ptr(),
+                         dt._packed.data_ptr() + 8, len(st.h_labels), len(dt.h_labels), 9)
+    clouds = torch.empty((2, K, N, 4), dtype=torch.float32, device=device)
+    T = torch.empty((K, 16), dtype=torch.float32, device=device)
+    report = torch.empty((K, _lib.REPAIR_COLS), dtype=torch.float64, device=device)
+    counts = torch.empty(_lib.REPAIR_COUNTS, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        need = int(_lib._L.icpflow_pairs_reregister_workspace_bytes(K, N))
+        ws = torch.empty(need, dtype=torch.uint8, device=device)        # (its first region is handed back: not the cached scratch)
+        _lib.call("icpflow_pairs_reregister", ctypes.byref(tables), K, N, ctypes.c_void_p(base), _lib.ptr(clouds), _lib.ptr(init), _lib.ptr(old),
+                  _lib.ptr(c), _lib.ptr(p), ctypes.byref(reg), ctypes.byref(params), _lib.ptr(T), _lib.ptr(report), _lib.ptr(counts), _lib.ptr(ws),
+                  ctypes.c_size_t(need), _lib.stream(device), _lib.opt())
+    utils_match._Staging.done(key)
+    words = ws[: 4 * (44 * K + 1)].view(torch.float32)
+    part = lambda a, b, cols: words[a * K: b * K].view(K, cols)    # noqa: E731
+    return dict(T=T.view(K, 4, 4), report=report, counts=counts, T_new=part(0, 16, 16).view(K, 4, 4), errors=part(16, 18, 2), inliers=part(18, 20, 2),
+                ratios=part(20, 22, 2), ious=part(22, 24, 2), iterations=words[44 * K:].view(torch.int32), keep=(ws, clouds, init, old, c, p))
+
+
+class Repair:
+    """What frame_tracks(repair=True) did to one sample, on the host: `before` the Tracks as the registrations left them,
+    `plan_counts` icpflow_object_tracks_suspects' four counts, `retried` one dict per suspect pair (gap: its index among the
+    sample's frame pairs, pair: its row of that gap's tables, labels, track, reason, e_old, e_new, distance: of the new
+    displacement from the predicted one in xy, accepted), `counts` the eight words (reasons 0 to 5 by the device, 6 by the host)."""
+
+    def __init__(self, before, plan_counts, retried, counts, ms=0.0):
+        self.before, self.retried, self.ms = before, list(retried), float(ms)     # ms: the repair's wall time behind the first read-back
+        self.plan_counts, self.counts = np.asarray(plan_counts, np.int64).reshape(4), np.asarray(counts, np.int64).reshape(8)
+
+    def summary(self, after):
+        return dict(suspects=int(self.plan_counts[3]), retried=int(self.counts[:6].sum()), accepted=int(self.counts[0]),
+                    reasons={name: int(v) for name, v in zip(REPAIR_REASONS, self.counts)},
+                    consistent_before=int(self.before.fit_counts[3]), consistent_after=int(after.fit_counts[3]))
+
+
 class Tracks:
     """The tracks of one sample on the host (icpflow_object_tracks_fit's table, read back once)."""
 
@@ -207,6 +295,7 @@ class Tracks:
         self.next_id, self.gaps, self.params = int(next_id), list(gaps), dict(params)
         self.observation_ids = [np.asarray(i, np.int64) for i in observation_ids]      # per gap, one per object row (-1: none)
         self.extend_counts = [np.asarray(c, np.int64).reshape(6) for c in extend_counts]
+        self.repair = None                    # a Repair: set by pair_judges.frame_tracks(repair=True)
 
     def summary(self):
         _, observed, judged, consistent, moving = (int(v) for v in self.fit_counts)

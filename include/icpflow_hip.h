@@ -1580,6 +1580,104 @@ int icpflow_object_tracks_path(const double *d_obs, const int32_t *d_step, int M
                                icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 8(m)  track repair: the gap that breaks a track's constant velocity registered again from the motion the other gaps predict.
+ * 8(k) ends in a verdict -- a track is not consistent --; here the observation that breaks it is named, its pair is registered
+ * once more from the predicted displacement, and the new pose replaces the old one only where the data prefer it.  Multi-frame
+ * samples only (all gaps share the destination sweep).  No counterpart in the reference; which gap is retried, the acceptance
+ * rule and its numbers are stated policies (COVERAGE.md, named deviations).  The partner of a pair is not chosen again, a gap
+ * without a pair is not filled.
+ *
+ * icpflow_object_tracks_suspects -- which observation breaks its track:
+ *   d_obs double [M][ICPFLOW_TRACK_OBS_COLS], the gaps concatenated as icpflow_object_tracks_fit takes them; T: the tracks;
+ *   params: icpflow_track_params_t, of which only max_residual is read; d_plan double [M][ICPFLOW_TRACK_PLAN_COLS]; d_counts
+ *   int64 [ICPFLOW_TRACK_PLAN_COUNTS].  One thread per observation j walks the M rows in ascending order, twice, fp64, every
+ *   operation written out, no fma.  Observation j HAS AN ID iff its column 0, t, has 0 <= t < T (a NaN has none); without one
+ *   its plan row is zeros.  First walk, over the rows i != j whose column 0 equals t, with s = seconds and d the displacement:
+ *   A += s_i s_i; B += s_i d_i per axis; the bit of gap_i is set for a gap in [0, 63]; others += 1.  j is ELIGIBLE iff at least
+ *   two distinct gaps were seen and A > 0; then v = B / A per axis.  Second walk, over the same rows:
+ *   inner = the largest (dx_i - s_i vx)^2 + (dy_i - s_i vy)^2.  With p = s_j v, r2 = (dx_j - p_x)^2 + (dy_j - p_y)^2 and
+ *   m2 = max_residual * max_residual (one product), j is SUSPECT iff eligible, inner <= m2 and r2 > m2: the other gaps agree
+ *   among themselves on one velocity, and this gap does not agree with it.  Row j of d_plan:
+ *       0  suspect    1  others    2  the distinct gaps among the others    3-5  p    6  sqrt(r2)    7  sqrt(inner)
+ *   (columns 0 and 3-7 are zero for a row that is not eligible).  d_counts: rows with an id, eligible rows, eligible rows with
+ *   inner <= m2, suspects; by ballot and popcount, integer atomics only.  One launch, no workspace, asynchronous on `stream`.
+ *   Refusals, before any launch: a null required pointer (d_obs and d_plan with M > 0, params, d_counts), M < 0, T < 0, a
+ *   struct_size mismatch, a negative or non-finite max_residual are ICPFLOW_E_ARG; M > 2^16 (the walk is quadratic) or
+ *   T > 2^24 is ICPFLOW_E_LIMIT.  M = 0 succeeds with four zeros.
+ *
+ * icpflow_pairs_repair_select -- does the new pose replace the old one; one thread per retried pair, one launch, no workspace:
+ *   d_T_new, d_T_old float32 [K][16], row-major 4 x 4; d_iters int32 [1]: the iteration count of the ICP batch that made
+ *   d_T_new, negative when the batch was abandoned; d_errors, d_ious float32 [K][2], d_translations, d_rotations float32
+ *   [K][3]: the metrics of the new pose as icpflow_match_eval leaves them; d_errors_old float32 [K][2]: the errors of the old
+ *   pose on the same clouds; d_centre double [K][3]: columns 4-6 of the pair's row of icpflow_pair_objects; d_pred double
+ *   [K][3]: columns 3-5 of its plan row.  params: icpflow_repair_params_t, its defaults (icpflow_pairs_repair_default_params) 2.0, 0.2,
+ *   9.0, 0.2, 0.2; the four thresholds of the association are narrowed to float32 and compared as the association compares them.
+ *   e = min(error_src, error_dst) in float32, NaN if either is (e_new of d_errors, e_old of d_errors_old).
+ *   d = T_new c - c in fp64 in the order of icpflow_pair_objects' columns 7-9.  The REASON is the first test that fails:
+ *       5  *d_iters < 0: the batch was abandoned
+ *       1  the association's reject test on the new pose (icpflow_assoc_assign: translation norm, min(iou) by the reference's
+ *          rule, the two angles; the same device code, csrc/rejecttest.hpp) fails
+ *       2  e_new is NaN or not < thres_error
+ *       3  (d_x - p_x)^2 + (d_y - p_y)^2 > max_residual * max_residual: the new pose is not where the track predicts
+ *       4  e_new > e_old, a NaN e_old read as +inf (a new pose with an error replaces an old one without): the data must
+ *          prefer the new pose -- an object that really left its line is not slid back onto it; e_new == e_old accepts
+ *       0  otherwise: accepted
+ *   d_T_out float32 [K][16]: T_new when accepted, T_old bit for bit otherwise.  d_report double [K][ICPFLOW_REPAIR_COLS]:
+ *       0  reason    1  e_new    2  e_old    3-5  d    6  the xy distance of d from p    7  *d_iters    8  min(iou)
+ *       9  the translation norm    10  fmaxf of the two tested angles' magnitudes    11  accepted
+ *   (every column is written whatever the reason).  d_counts int64 [ICPFLOW_REPAIR_COUNTS]: one count per reason 0 to 5, then
+ *   two zeros (word 6 is the caller's: pairs it did not retry).  Refusals, before any launch: a null required pointer, K < 0, a
+ *   struct_size mismatch, a negative or non-finite parameter are ICPFLOW_E_ARG; K > 2^24 is ICPFLOW_E_LIMIT.  K = 0 succeeds
+ *   with eight zeros.
+ *
+ * icpflow_pairs_reregister -- K pairs of one frame pair registered again, everything enqueued on `stream`, no host
+ *   synchronisation, no allocation:  tables: both clouds as icpflow_cluster_table leaves them (d_table_*, S, D and
+ *   label_stride are not read); d_seg int64 [2,3,K]: the segment rows of icpflow_gather_segments, source cloud first, every
+ *   length <= N and every offset -1 (no subsample: a cluster longer than N is the caller's to leave out); d_clouds float32
+ *   [2,K,N,4]: scratch for the padded batch; d_init float32 [K][16]; d_T_old, d_centre, d_pred as above; reg: thres_dist,
+ *   relative_rmse_thr, max_iterations and stop_mode are read, the edges are not.  In this order:
+ *   icpflow_gather_segments of both sides; icpflow_apply_icp, source onto destination from d_init (unlike icpflow_hist_icp
+ *   there is no swap by length); icpflow_match_eval of T_new; icpflow_match_eval of T_old (source, destination, as
+ *   icpflow_register_stage orders them); the select.  T_new and both sets of metrics are, bit for bit, what those entry points
+ *   give on the gathered batch.  d_T_out, d_report, d_counts: the select's.
+ *   Workspace, the caller's, 16-byte aligned: icpflow_pairs_reregister_workspace_bytes(K, N) =
+ *       a256(4 (44 K + 1)) + a256(icpflow_workspace_bytes(K, N, 0, 0, 0)),
+ *   a multiple of 256, non-decreasing in K and N, 0 for sizes the call refuses (and for K = 0, which needs none); nothing in
+ *   it is read before it is written.  Its first region holds, after the call, float32 [T_new 16K | errors 2K | inliers 2K |
+ *   ratios 2K | ious 2K | translations 3K | rotations 3K | the same six arrays of T_old, 14K | the iteration count (int32)].
+ *   Refusals, before any launch: a null required pointer, K < 0, N < 1, max_iterations outside [1, 1024], an unknown stop_mode,
+ *   a negative or non-finite thres_dist, the parameter block as above, a misaligned workspace are ICPFLOW_E_ARG; K N > 2^30 is
+ *   ICPFLOW_E_LIMIT; a missing or short workspace is ICPFLOW_E_WORKSPACE.  An options block the cores refuse is refused by
+ *   them, behind the gathers.  K = 0 succeeds with eight zeros in d_counts and touches nothing else.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_TRACK_PLAN_COLS 8
+#define ICPFLOW_TRACK_PLAN_COUNTS 4
+#define ICPFLOW_REPAIR_COLS 12
+#define ICPFLOW_REPAIR_COUNTS 8
+typedef struct icpflow_repair_params {
+    size_t struct_size;       /* sizeof(icpflow_repair_params_t) */
+    double translation_frame; /* the association's bound on the translation norm, metres; default 2.0 */
+    double thres_iou;         /* ... on min(iou); default 0.2 */
+    double rot_limit_deg;     /* ... on the two tested angles, degrees (thres_rot * 90); default 9.0 */
+    double thres_error;       /* ... on min(error), metres; default 0.2 */
+    double max_residual;      /* metres: the new displacement lies this close to the predicted one in xy; default 0.2 */
+} icpflow_repair_params_t;
+int icpflow_object_tracks_suspects(const double *d_obs, int M, int T, const icpflow_track_params_t *params, double *d_plan,
+                                   int64_t *d_counts, icpflow_stream_t stream);
+int icpflow_pairs_repair_default_params(icpflow_repair_params_t *params);
+int icpflow_pairs_repair_select(const float *d_T_new, const float *d_T_old, const int32_t *d_iters, const float *d_errors,
+                                const float *d_ious, const float *d_translations, const float *d_rotations,
+                                const float *d_errors_old, const double *d_centre, const double *d_pred, int K,
+                                const icpflow_repair_params_t *params, float *d_T_out, double *d_report, int64_t *d_counts,
+                                icpflow_stream_t stream);
+size_t icpflow_pairs_reregister_workspace_bytes(int K, int N);
+int icpflow_pairs_reregister(const icpflow_tables_t *tables, int K, int N, const int64_t *d_seg, float *d_clouds,
+                             const float *d_init, const float *d_T_old, const double *d_centre, const double *d_pred,
+                             const icpflow_registration_t *reg, const icpflow_repair_params_t *params, float *d_T_out,
+                             double *d_report, int64_t *d_counts, void *d_ws, size_t ws_bytes, icpflow_stream_t stream,
+                             const icpflow_options_t *opt);
+
+/* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
  * every cloud (utils_ground.py:52-58), so the adaptive elevation and flatness thresholds stay {0,0,0,0} during the only
  * call; RNR off, R-VPF and TGR on.  A restatement of the method in fp64, not of Eigen's fp32 bits (COVERAGE.md, named
