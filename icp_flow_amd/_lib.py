@@ -137,6 +137,8 @@ SIGNATURES = {
     "icpflow_pairs_repair_select": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "icpflow_pairs_reregister_workspace_bytes": (_sz, [_i, _i]),
     "icpflow_pairs_reregister": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "icpflow_object_tracks_missing": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "icpflow_pairs_fill_candidates": (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _d, _i, _p, _p, _p]),
     "icpflow_ground_default_params": (_i, [_p]),
     "icpflow_ground_workspace_bytes": (_sz, [_i, _p]),
     "icpflow_ground_segment": (_i, [_p, _i, _i, _p, _p, _p, _p, _sz, _p]),
@@ -188,6 +190,8 @@ CARRY_COUNTS, PAIR_ROW_ID_COUNTS, PAIR_ROW_ID_MAX_PAIRS = 6, 3, 4096   # icpflow
 TRACK_PATH_COLS, TRACK_PATH_COUNTS = 24, 5                        # icpflow_object_tracks_path: columns of a row; words of d_counts
 TRACK_PLAN_COLS, TRACK_PLAN_COUNTS, TRACK_PLAN_MAX_ROWS = 8, 4, 1 << 16   # icpflow_object_tracks_suspects: columns; words of d_counts; M at most
 REPAIR_COLS, REPAIR_COUNTS = 12, 8                                # icpflow_pairs_repair_select: columns of a report row; words of d_counts
+TRACK_MISSING_COLS, TRACK_MISSING_COUNTS, TRACK_MISSING_MAX_SLOTS = 14, 4, 64   # icpflow_object_tracks_missing: columns; words of d_counts per slot; G at most
+FILL_CHOICE_COLS, FILL_COUNTS, FILL_MAX_ROWS = 8, 4, 1 << 16      # icpflow_pairs_fill_candidates: columns of a choice row; words of d_counts; K at most
 SEARCH_AUTO, SEARCH_SCAN, SEARCH_GRID, SEARCH_SWEEP = 0, 1, 2, 3
 ARITH_FP64, ARITH_FP32_REFERENCE = 0, 1
 # developer switches (include/icpflow_hip.h ICPFLOW_OPT_*): each turns one optimisation off, results identical

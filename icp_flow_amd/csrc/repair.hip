@@ -10,6 +10,11 @@
 //   5. repair_select_kernel      a thread per pair: the first test that fails is the reason; T_new or, bit for bit, T_old
 // 1 to 4 are the existing cores, called through their entry points; the reject test of 5 is the association's
 // (rejecttest.hpp).  The select is a few dozen operations per pair: one launch, one thread per pair, no workspace.
+//
+// icpflow_pairs_fill_candidates ("8(n) track fill"; the plan that names the gaps is tracks.hip's icpflow_object_tracks_missing):
+// the source cluster of a gap in which a track found no pair -- the nearest unmatched box within a radius of the predicted
+// centre.  fill_choose_kernel, a workgroup per missing row; fill_settle_kernel, a thread per row, settles rows that chose one
+// segment.  The pair is then registered by icpflow_pairs_reregister from [I | p] with T_old the identity.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -142,9 +147,159 @@ void carve(void *base, int K, int N, Carve *c)
     c->total = ws.total();
 }
 
+// ---- 8(n): the source cluster of a gap in which a track found no pair ----------------------------------------------------------
+constexpr int kChoiceCols = ICPFLOW_FILL_CHOICE_COLS, kFillCounts = ICPFLOW_FILL_COUNTS, kBoxCols = ICPFLOW_BOX_COLS;
+constexpr int kFillLmax = 4096, kFillEach = kFillLmax / kThreads, kPairTile = 1024, kMaxFillRows = 1 << 16;
+static_assert(ICPFLOW_FILL_CHOICE_COLS == 8 && ICPFLOW_FILL_COUNTS == 4, "reason, segment, label, rows, distance, centre; chosen, none, lost, candidates");
+
+// d2 of box centre (X, Y) from q in xy: fp64, every operation written out -- both launches compute it, bit for bit the same
+__device__ __forceinline__ double fill_d2(const double *__restrict__ box, const double *__restrict__ q)
+{
+    const double dx = box[6] - q[0], dy = box[7] - q[1];
+    return dx * dx + dy * dy;
+}
+
+// Launch 1: workgroup k strides over the segments -- thread t holds segments t, t + 256, ... -- marks the ones a pair row already
+// names (the rows' column 0 through LDS in tiles of 1024), and reduces the minimum of (d2, c) among the reachable candidates
+// through the wave and then LDS.  Row k of `choice` is written whole, reason 0 or 1; workgroup 0 counts the candidates.
+__global__ __launch_bounds__(kThreads) void fill_choose_kernel(const double *__restrict__ q, const double *__restrict__ boxes,
+                                                               const int32_t *__restrict__ numSrc, int Lmax, const float *__restrict__ pairRows, int P,
+                                                               int stride, double radius, double maxRows, double *__restrict__ choice,
+                                                               unsigned long long *__restrict__ counts)
+{
+    __shared__ float tile[kPairTile];
+    __shared__ double shD[kWaves];
+    __shared__ int shC[kWaves], shN[kWaves];
+    const int k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & (kWave - 1);
+    const int L = max(0, min(*numSrc, Lmax));
+    float label[kFillEach];
+    unsigned open = 0u;                                 // bit e: segment tid + 256 e has a box, is short enough and (so far) unmatched
+#pragma unroll
+    for (int e = 0; e < kFillEach; ++e) {
+        const int c = tid + e * kThreads;
+        label[e] = 0.0f;
+        if (c < L) {
+            const double *box = boxes + (size_t)c * kBoxCols;
+            label[e] = (float)box[0];
+            if (box[3] >= 0.0 && box[1] <= maxRows) open |= 1u << e;
+        }
+    }
+    for (int base = 0; base < P; base += kPairTile) {
+        const int rows = min(kPairTile, P - base);
+        __syncthreads();                                // (the tile before is read out)
+        for (int r = tid; r < rows; r += kThreads) tile[r] = pairRows[(size_t)(base + r) * stride];
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < kFillEach; ++e) {
+            if (!(open >> e & 1u)) continue;
+            bool hit = false;
+            for (int r = 0; r < rows; ++r) hit |= tile[r] == label[e];     // IEEE ==: +0 and -0 are one label, a NaN equals none
+            if (hit) open &= ~(1u << e);
+        }
+    }
+    const double r2 = radius * radius;
+    double best = 0.0;
+    int bestC = -1;
+#pragma unroll
+    for (int e = 0; e < kFillEach; ++e) {               // ascending c: a tie keeps the lower one
+        if (!(open >> e & 1u)) continue;
+        const int c = tid + e * kThreads;
+        const double d2 = fill_d2(boxes + (size_t)c * kBoxCols, q + (size_t)k * 3);
+        if (d2 <= r2 && (bestC < 0 || d2 < best)) best = d2, bestC = c;      // (a NaN is not within reach)
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const double od = __shfl_xor(best, o, kWave);
+        const int oc = __shfl_xor(bestC, o, kWave);
+        if (oc >= 0 && (bestC < 0 || od < best || (od == best && oc < bestC))) best = od, bestC = oc;
+    }
+    const int mine = icpflow::wave_sum((int)__popc(open));
+    if (lane == 0) shD[wave] = best, shC[wave] = bestC, shN[wave] = mine;
+    __syncthreads();
+    if (tid != 0) return;
+    int candidates = 0;
+    best = 0.0, bestC = -1;
+    for (int w = 0; w < kWaves; ++w) {
+        candidates += shN[w];
+        if (shC[w] >= 0 && (bestC < 0 || shD[w] < best || (shD[w] == best && shC[w] < bestC))) best = shD[w], bestC = shC[w];
+    }
+    double *row = choice + (size_t)k * kChoiceCols;
+    if (bestC < 0) {
+        row[0] = 1.0, row[1] = -1.0;
+#pragma unroll
+        for (int c = 2; c < kChoiceCols; ++c) row[c] = 0.0;
+    } else {
+        const double *box = boxes + (size_t)bestC * kBoxCols;
+        row[0] = 0.0, row[1] = (double)bestC, row[2] = box[0], row[3] = box[1], row[4] = sqrt(best), row[5] = box[6], row[6] = box[7], row[7] = box[8];
+    }
+    if (k == 0 && candidates != 0) atomicAdd(&counts[3], (unsigned long long)candidates);
+}
+
+// Launch 2: a thread per row settles the shared choices.  It reads column 1 of the other rows (launch 1's, never written here)
+// and computes their d2 again from the same box; it writes its own column 0 only.
+__global__ __launch_bounds__(kThreads) void fill_settle_kernel(const double *__restrict__ q, const double *__restrict__ boxes, int K,
+                                                               double *__restrict__ choice, unsigned long long *__restrict__ counts)
+{
+    __shared__ int sh[kWaves][3];
+    const int k = blockIdx.x * kThreads + (int)threadIdx.x;
+    int reason = -1;
+    if (k < K) {
+        const double seg = choice[(size_t)k * kChoiceCols + 1];
+        reason = seg < 0.0 ? 1 : 0;
+        if (reason == 0) {
+            const double *box = boxes + (size_t)(int)seg * kBoxCols;
+            const double mine = fill_d2(box, q + (size_t)k * 3);
+            for (int j = 0; j < K; ++j) {
+                if (j == k || choice[(size_t)j * kChoiceCols + 1] != seg) continue;
+                const double d2 = fill_d2(box, q + (size_t)j * 3);
+                if (d2 < mine || (d2 == mine && j < k)) reason = 2;
+            }
+            if (reason == 2) choice[(size_t)k * kChoiceCols] = 2.0;
+        }
+    }
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {                      // (every lane takes every round: the ballots see whole waves)
+        const int c = __popcll(__ballot(reason == r));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh[wave][r] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        int c = 0;
+        for (int w = 0; w < kWaves; ++w) c += sh[w][threadIdx.x];
+        if (c != 0) atomicAdd(&counts[threadIdx.x], (unsigned long long)c);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int icpflow_pairs_fill_candidates(const double *d_q, int K, const double *d_boxes_src, const int32_t *d_num_src, int Lmax,
+                                  const float *d_pair_rows, int P, int pair_stride, double radius, int max_rows, double *d_choice,
+                                  int64_t *d_counts, icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_pairs_fill_candidates";
+    if (K < 0 || P < 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_pairs_fill_candidates: K = %d, P = %d: a negative size", K, P);
+    if (K > kMaxFillRows) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_pairs_fill_candidates: K = %d: at most %d rows", K, kMaxFillRows);
+    if (Lmax < 1) return report_errorf(ICPFLOW_E_ARG, "icpflow_pairs_fill_candidates: Lmax = %d: Lmax must be at least 1", Lmax);
+    if (Lmax > kFillLmax) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_pairs_fill_candidates: Lmax = %d: at most %d segments", Lmax, kFillLmax);
+    if (pair_stride < 1) return report_errorf(ICPFLOW_E_ARG, "icpflow_pairs_fill_candidates: pair_stride = %d: pair_stride must be at least 1", pair_stride);
+    if (!(radius > 0.0 && radius <= 1e3)) return report_errorf(ICPFLOW_E_ARG, "icpflow_pairs_fill_candidates: radius = %g: radius must lie in (0, 1e3]", radius);
+    if (max_rows < 1) return report_errorf(ICPFLOW_E_ARG, "icpflow_pairs_fill_candidates: max_rows = %d: max_rows must be at least 1", max_rows);
+    if (!d_boxes_src || !d_num_src || !d_counts || (K > 0 && (!d_q || !d_choice))) return pointer_error(fn);
+    if (P > 0 && !d_pair_rows) return report_errorf(ICPFLOW_E_ARG, "icpflow_pairs_fill_candidates: P = %d and no pair rows", P);
+
+    hipStream_t st = (hipStream_t)stream;
+    ICPFLOW_TRY(hipMemsetAsync(d_counts, 0, kFillCounts * sizeof(int64_t), st));
+    if (K == 0) return ICPFLOW_OK;
+    fill_choose_kernel<<<K, kThreads, 0, st>>>(d_q, d_boxes_src, d_num_src, Lmax, d_pair_rows, P, pair_stride, radius, (double)max_rows, d_choice,
+                                              (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    fill_settle_kernel<<<(K + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_q, d_boxes_src, K, d_choice, (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    return ICPFLOW_OK;
+}
 
 int icpflow_pairs_repair_default_params(icpflow_repair_params_t *params)
 {

@@ -3,7 +3,9 @@
 // on the SOURCE side of a pair and one row per track over a log ("8(l)": icpflow_object_tracks_extend_side,
 // icpflow_object_tracks_path -- trk_path_kernel, a thread per track like the fit); which observation breaks its track
 // ("8(m) track repair": icpflow_object_tracks_suspects -- trk_suspects_kernel, a thread per OBSERVATION, the fit leave-one-out;
-// repair.hip registers the named pairs again).
+// repair.hip registers the named pairs again); which segment of the shared sweep lacks a pair in its gap ("8(n) track fill":
+// icpflow_object_tracks_missing -- trk_missing_kernel, a thread per (gap slot, segment), the suspects' two walks through one
+// device function; repair.hip finds the source cluster and registers the pair).
 //
 // icpflow_object_tracks_extend, one gap:
 //   1. trk_labels_kernel    "track id per row" as a float32 labelling (an id is its own label, no track is -1)
@@ -270,6 +272,47 @@ __global__ __launch_bounds__(kThreads) void trk_fit_kernel(const double *__restr
     }
 }
 
+// The two walks that 8(m) and 8(n) share: the rows of track `id` in ascending order, fp64, every operation written out.  Row
+// `skipRow` is left out (8(m): the observation itself; -1 leaves none out); a row whose gap equals `skipGap` is COUNTED as
+// observed and enters nothing else (8(n): the slot's own gap; a NaN equals none).
+struct OthersWalk {
+    int others = 0, observed = 0;
+    unsigned long long mask = 0ull;
+    double num[3] = {0.0, 0.0, 0.0}, den = 0.0, land[3] = {0.0, 0.0, 0.0};   // sum s d, sum s s, sum (c + d)
+};
+
+__device__ __forceinline__ void walk_others(const double *__restrict__ obs, int M, double id, int skipRow, double skipGap, OthersWalk &w)
+{
+    for (int k = 0; k < M; ++k) {
+        const double *o = obs + (size_t)k * kObsCols;
+        if (k == skipRow || o[0] != id) continue;
+        if (o[1] == skipGap) {
+            ++w.observed;
+            continue;
+        }
+        const double s = o[2];
+        w.den += s * s;
+        w.num[0] += s * o[3], w.num[1] += s * o[4], w.num[2] += s * o[5];
+        w.land[0] += o[10] + o[3], w.land[1] += o[11] + o[4], w.land[2] += o[12] + o[5];
+        if (o[1] >= 0.0 && o[1] < 64.0) w.mask |= 1ull << (int)o[1];
+        ++w.others;
+    }
+}
+
+// the largest squared xy residual of the same rows against d = s v
+__device__ __forceinline__ double walk_inner(const double *__restrict__ obs, int M, double id, int skipRow, double skipGap, const double *v)
+{
+    double inner = 0.0;
+    for (int k = 0; k < M; ++k) {
+        const double *o = obs + (size_t)k * kObsCols;
+        if (k == skipRow || o[0] != id || o[1] == skipGap) continue;
+        const double rx = o[3] - o[2] * v[0], ry = o[4] - o[2] * v[1];
+        const double r2 = rx * rx + ry * ry;
+        inner = r2 > inner ? r2 : inner;
+    }
+    return inner;
+}
+
 // Which observation breaks its track (8(m)): a thread per observation j fits the OTHER observations of its track and asks
 // whether they agree among themselves and j does not agree with them.  Two walks over the M rows in ascending order, fp64,
 // every operation written out -- the fit's style, leave-one-out.
@@ -287,31 +330,15 @@ __global__ __launch_bounds__(kThreads) void trk_suspects_kernel(const double *__
         double row[kCols] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         withId = id >= 0.0 && id < (double)T;           // (a NaN is outside)
         if (withId) {
-            int others = 0;
-            unsigned long long mask = 0ull;
-            double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
-            for (int k = 0; k < M; ++k) {
-                const double *o = obs + (size_t)k * kObsCols;
-                if (k == j || o[0] != id) continue;
-                const double s = o[2];
-                den += s * s;
-                num[0] += s * o[3], num[1] += s * o[4], num[2] += s * o[5];
-                if (o[1] >= 0.0 && o[1] < 64.0) mask |= 1ull << (int)o[1];
-                ++others;
-            }
-            const int gaps = __popcll(mask);
-            row[1] = (double)others, row[2] = (double)gaps;
-            eligible = gaps >= 2 && den > 0.0;
+            const double none = __longlong_as_double(0x7ff8000000000000ll);   // no gap equals a NaN: every other row enters
+            OthersWalk w;
+            walk_others(obs, M, id, j, none, w);
+            const int gaps = __popcll(w.mask);
+            row[1] = (double)w.others, row[2] = (double)gaps;
+            eligible = gaps >= 2 && w.den > 0.0;
             if (eligible) {
-                const double v[3] = {num[0] / den, num[1] / den, num[2] / den};
-                double inner = 0.0;
-                for (int k = 0; k < M; ++k) {
-                    const double *o = obs + (size_t)k * kObsCols;
-                    if (k == j || o[0] != id) continue;
-                    const double rx = o[3] - o[2] * v[0], ry = o[4] - o[2] * v[1];
-                    const double r2 = rx * rx + ry * ry;
-                    inner = r2 > inner ? r2 : inner;
-                }
+                const double v[3] = {w.num[0] / w.den, w.num[1] / w.den, w.num[2] / w.den};
+                const double inner = walk_inner(obs, M, id, j, none, v);
                 const double s = me[2];
                 const double p[3] = {s * v[0], s * v[1], s * v[2]};
                 const double rx = me[3] - p[0], ry = me[4] - p[1];
@@ -337,6 +364,66 @@ __global__ __launch_bounds__(kThreads) void trk_suspects_kernel(const double *__
         int c = 0;
         for (int w = 0; w < kWaves; ++w) c += sh[w][threadIdx.x];
         if (c != 0) atomicAdd(&counts[threadIdx.x], (unsigned long long)c);
+    }
+}
+
+// Which segment of the shared sweep lacks a pair in its gap, and what the other gaps predict for it (8(n)): a thread per
+// (slot g = blockIdx.y, segment c) walks the observations of the segment's track as the suspects' threads do -- the rows of the
+// slot's own gap say OBSERVED and enter nothing else.  The slots' gaps and seconds travel in the kernel arguments.
+struct MissingSlots {
+    int32_t gap[ICPFLOW_TRACK_MISSING_MAX_SLOTS];
+    double seconds[ICPFLOW_TRACK_MISSING_MAX_SLOTS];
+};
+
+__global__ __launch_bounds__(kThreads) void trk_missing_kernel(const double *__restrict__ obs, int M, int T, const double *__restrict__ segments,
+                                                               const int32_t *__restrict__ num, int Lmax, MissingSlots slots, double maxResidual,
+                                                               double *__restrict__ plan, unsigned long long *__restrict__ counts)
+{
+    constexpr int kCols = ICPFLOW_TRACK_MISSING_COLS, kCounts = ICPFLOW_TRACK_MISSING_COUNTS;
+    __shared__ int sh[kWaves][kCounts];
+    const int g = blockIdx.y, c = blockIdx.x * kThreads + (int)threadIdx.x;
+    const int L = min(num[g], Lmax);                    // (negative: no row of this slot)
+    const bool live = c < L;
+    bool withId = false, unseen = false, eligible = false, missing = false;
+    if (live) {
+        const double *seg = segments + ((size_t)g * Lmax + c) * kSegCols;
+        const double id = seg[2];
+        double row[kCols] = {0.0, id, seg[0], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, seg[1]};
+        withId = id >= 0.0 && id < (double)T;           // (a NaN is outside)
+        if (withId) {
+            const double gap = (double)slots.gap[g];
+            OthersWalk w;
+            walk_others(obs, M, id, -1, gap, w);
+            const int gaps = __popcll(w.mask);
+            row[3] = (double)w.observed, row[4] = (double)w.others, row[5] = (double)gaps;
+            unseen = w.observed == 0;
+            eligible = unseen && gaps >= 2 && w.den > 0.0;
+            if (eligible) {
+                const double v[3] = {w.num[0] / w.den, w.num[1] / w.den, w.num[2] / w.den};
+                const double inner = walk_inner(obs, M, id, -1, gap, v);
+                const double s = slots.seconds[g], n = (double)w.others;
+                const double p[3] = {s * v[0], s * v[1], s * v[2]};
+                missing = inner <= maxResidual * maxResidual;
+                row[0] = missing ? 1.0 : 0.0, row[6] = p[0], row[7] = p[1], row[8] = p[2];
+                row[9] = w.land[0] / n - p[0], row[10] = w.land[1] / n - p[1], row[11] = w.land[2] / n - p[2], row[12] = sqrt(inner);
+            }
+        }
+        double *out = plan + ((size_t)g * Lmax + c) * kCols;
+#pragma unroll
+        for (int k = 0; k < kCols; ++k) out[k] = row[k];
+    }
+    const bool flag[kCounts] = {withId, withId && unseen, eligible, missing};
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kCounts; ++k) {                // (every lane takes every round: the ballots see whole waves)
+        const int t = __popcll(__ballot(flag[k]));
+        if ((threadIdx.x & (kWave - 1)) == 0) sh[wave][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCounts) {
+        int t = 0;
+        for (int w = 0; w < kWaves; ++w) t += sh[w][threadIdx.x];
+        if (t != 0) atomicAdd(&counts[(size_t)g * kCounts + threadIdx.x], (unsigned long long)t);
     }
 }
 
@@ -568,6 +655,44 @@ int icpflow_object_tracks_suspects(const double *d_obs, int M, int T, const icpf
     ICPFLOW_TRY(hipMemsetAsync(d_counts, 0, ICPFLOW_TRACK_PLAN_COUNTS * sizeof(int64_t), st));
     if (M == 0) return ICPFLOW_OK;
     trk_suspects_kernel<<<(M + kThreads - 1) / kThreads, kThreads, 0, st>>>(d_obs, M, T, params->max_residual, d_plan, (unsigned long long *)d_counts);
+    ICPFLOW_TRY(hipGetLastError());
+    return ICPFLOW_OK;
+}
+
+int icpflow_object_tracks_missing(const double *d_obs, int M, int T, const double *d_segments, const int32_t *d_num, int G, int Lmax,
+                                  const int32_t *h_gap, const double *h_seconds, const icpflow_track_params_t *params, double *d_plan,
+                                  int64_t *d_counts, icpflow_stream_t stream)
+{
+    const char *fn = "icpflow_object_tracks_missing";
+    constexpr int kSlots = ICPFLOW_TRACK_MISSING_MAX_SLOTS;
+    if (M < 0 || T < 0) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_missing: M = %d, T = %d: a negative size", M, T);
+    if (G < 1 || G > kSlots) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_missing: G = %d: G must lie in [1, %d]", G, kSlots);
+    if (Lmax < 1) return report_errorf(ICPFLOW_E_ARG, "icpflow_object_tracks_missing: Lmax = %d: Lmax must be at least 1", Lmax);
+    if (M > kMaxSuspectRows || T > kMaxFitRows)
+        return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_missing: M = %d, T = %d: at most %d observations (every segment walks them) and %d tracks",
+                             M, T, kMaxSuspectRows, kMaxFitRows);
+    if (Lmax > kLmax) return report_errorf(ICPFLOW_E_LIMIT, "icpflow_object_tracks_missing: Lmax = %d: at most %d segments", Lmax, kLmax);
+    if (!params || !d_segments || !d_num || !h_gap || !h_seconds || !d_plan || !d_counts || (M > 0 && !d_obs)) return pointer_error(fn);
+    if (params->struct_size != sizeof(icpflow_track_params_t))
+        return report_errorf(ICPFLOW_E_ARG, "%s: params->struct_size = %zu, this library's icpflow_track_params_t has %zu bytes", fn, params->struct_size,
+                             sizeof(icpflow_track_params_t));
+    if (!(params->max_residual >= 0.0) || !std::isfinite(params->max_residual))
+        return report_errorf(ICPFLOW_E_ARG, "%s: max_residual = %g: max_residual must be finite and not negative", fn, params->max_residual);
+    MissingSlots slots{};
+    unsigned long long seen = 0ull;
+    for (int g = 0; g < G; ++g) {
+        if (h_gap[g] < 0 || h_gap[g] > 63) return report_errorf(ICPFLOW_E_ARG, "%s: h_gap[%d] = %d: a gap must lie in [0, 63]", fn, g, h_gap[g]);
+        if (seen >> h_gap[g] & 1ull) return report_errorf(ICPFLOW_E_ARG, "%s: h_gap[%d] = %d: the gaps must be distinct", fn, g, h_gap[g]);
+        if (!(h_seconds[g] > 0.0) || !std::isfinite(h_seconds[g]))
+            return report_errorf(ICPFLOW_E_ARG, "%s: h_seconds[%d] = %g: seconds must be positive and finite", fn, g, h_seconds[g]);
+        seen |= 1ull << h_gap[g];
+        slots.gap[g] = h_gap[g], slots.seconds[g] = h_seconds[g];
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    ICPFLOW_TRY(hipMemsetAsync(d_counts, 0, (size_t)G * ICPFLOW_TRACK_MISSING_COUNTS * sizeof(int64_t), st));
+    trk_missing_kernel<<<dim3((Lmax + kThreads - 1) / kThreads, G), kThreads, 0, st>>>(d_obs, M, T, d_segments, d_num, Lmax, slots, params->max_residual,
+                                                                                       d_plan, (unsigned long long *)d_counts);
     ICPFLOW_TRY(hipGetLastError());
     return ICPFLOW_OK;
 }

@@ -1364,6 +1364,11 @@ def argument_parser():
                     help="with --tracks: a gap that alone breaks its track's constant velocity is registered again from the motion the other "
                          "gaps predict, and the new pose replaces the old one where the data prefer it (transforms, pair rows, flow, objects "
                          "and tracks of that gap); not with --tracks-log, not with --protocol reference")
+    ap.add_argument("--tracks-fill", action="store_true",
+                    help="with --tracks: a gap in which a track found no pair is registered from what the other gaps predict -- the nearest "
+                         "unmatched source cluster, the track's destination cluster, the predicted translation -- and an accepted pair is appended "
+                         "to that gap's pair rows and transforms (flow, objects and tracks of that gap follow); after --tracks-repair when both are "
+                         "given; not with --tracks-log, not with --protocol reference")
     ap.add_argument("--tracks-log", nargs="?", const=True, default=None, metavar="FILE",
                     help="object tracks over a log: the directory's frame-pair files are consecutive (file k registers sweep k onto "
                          "sweep k + 1; the source of a file is the destination of the one before, carried over by the file's pose); "
@@ -1403,6 +1408,10 @@ def main(argv=None):
         raise SystemExit("--sweep-seconds must be positive and --objects-min-speed must not be negative")
     if ns.tracks_repair and ns.tracks is None:
         raise SystemExit("--tracks-repair goes with --tracks (it registers again the gaps the tracks name; --tracks-log has no repair)")
+    if ns.tracks_fill and ns.tracks is None:
+        raise SystemExit("--tracks-fill goes with --tracks (it fills the gaps the tracks name; --tracks-log has no fill)")
+    if ns.tracks_fill and ns.tracks_log is not None:
+        raise SystemExit("--tracks-fill is not built into --tracks-log: a log's files share no sweep whose other gaps could predict the missing one")
     if ns.tracks is not None and ns.protocol == "reference":
         raise SystemExit("--tracks is not built into --protocol reference (COVERAGE.md row 18): run the frame pairs without --protocol")
     if ns.tracks is not None and not (ns.sweep_seconds > 0 and ns.objects_min_speed >= 0 and 0 < ns.tracks_min_iou <= 1 and ns.tracks_max_residual >= 0):
@@ -1512,6 +1521,8 @@ def main(argv=None):
         args.tracks_min_iou, args.tracks_max_residual = ns.tracks_min_iou, ns.tracks_max_residual
         if ns.tracks_repair:
             args.tracks_repair = True
+        if ns.tracks_fill:
+            args.tracks_fill = True
     if ns.tracks_log is not None:
         args.tracks_log, args.sweep_seconds, args.objects_min_speed, args.tracks_min_iou = ns.tracks_log, ns.sweep_seconds, ns.objects_min_speed, ns.tracks_min_iou
         args.tracks_log_radius, args.tracks_log_min_share, args.tracks_log_max_dv = ns.tracks_log_radius, ns.tracks_log_min_share, ns.tracks_log_max_dv

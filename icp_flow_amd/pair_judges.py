@@ -126,8 +126,9 @@ def frame_objects(fp, out, device, seconds=None, min_speed=utils_objects.MIN_SPE
     return utils_objects.Objects.read(rows, counts, seconds, min_speed)     # the one read-back
 
 
-def _frame_objects_device(fp, out, device, seconds, min_speed, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS):
-    """frame_objects' three calls, nothing read back -> (rows float64 [P, 24], counts int64 [4], the destination's labels)"""
+def _frame_objects_device(fp, out, device, seconds, min_speed, delta=utils_objects.BOX_DELTA, A=utils_objects.BOX_DIRECTIONS, boxes=False):
+    """frame_objects' three calls, nothing read back -> (rows float64 [P, 24], counts int64 [4], the destination's labels); with
+    `boxes` a fourth: (the source's box table, its number), as the first call left them"""
     device = torch.device(device)
     ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
     ls = _source_labels(fp, out, device)
@@ -141,11 +142,11 @@ def _frame_objects_device(fp, out, device, seconds, min_speed, delta=utils_objec
     boxes_dst, num_dst = utils_objects.segment_boxes_device(pd, ld, delta, A)
     rows, counts = utils_objects.pair_objects_device(boxes_src, num_src, out["pairs"].to(device), out["transformations"].to(device),
                                                      boxes_dst, num_dst, seconds, min_speed)
-    return rows, counts, ld
+    return (rows, counts, ld, (boxes_src, num_src)) if boxes else (rows, counts, ld)
 
 
 def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, min_speed=utils_tracks.MIN_SPEED, min_iou=utils_tracks.MIN_IOU,
-                 max_residual=utils_tracks.MAX_RESIDUAL, Lmax=4096, repair=False, args=None):
+                 max_residual=utils_tracks.MAX_RESIDUAL, Lmax=4096, repair=False, args=None, fill=False):
     """The object tracks of ONE sample (utils_tracks), everything on the device: `fps` the sample's frame pairs in gap order --
     they share the destination sweep, row for row -- and `outs` their registrations.  Per gap the object rows of frame_objects
     (not read back), then the shared sweep's clusters linked to the tracks so far (icpflow_object_tracks_extend); at the end one
@@ -158,7 +159,19 @@ def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, m
     args.max_points is not retried (reason 6: its subsample would draw random numbers); every `out` of such a gap gets NEW
     tensors under `transformations` (the accepted poses in their rows), `pairs` (their error, inlier, ratio and iou columns from
     the new metrics) and `flow` (utils_flow.flow_estimation_torch on the patched rows); then the object rows and the tracks are
-    computed again.  -> the Tracks after repair, its `repair` a utils_tracks.Repair (the Tracks before, the retried pairs)."""
+    computed again.  -> the Tracks after repair, its `repair` a utils_tracks.Repair (the Tracks before, the retried pairs).
+
+    fill=True (with `args`; after the repair when both are asked for, on the repaired tracks): the gaps in which a track found no
+    pair are registered from what the other gaps predict (include/icpflow_hip.h, 8(n)).  icpflow_object_tracks_missing over all
+    gap slots; its missing rows are compacted on the device and read back once with the counts (FILL_READ_ROWS of them; a sample
+    with more reads a second time); a sample without a missing row launches nothing more.  Per gap with missing rows
+    icpflow_pairs_fill_candidates on that gap's source boxes (the chain's own, not computed twice) and one read-back of every
+    choice; a chosen pair with a destination cluster longer than args.max_points is left out (reason 6); the others are registered
+    by icpflow_pairs_reregister from [I | p] with T_old = identity, so the select's reason 4 compares the new pose with the ego
+    motion alone on the same clouds.  Accepted pairs are APPENDED, in ascending plan-row order, to NEW tensors under `pairs`
+    (the chosen source label, the plan's destination label, then the new metrics in the repair's order) and `transformations`
+    of that gap's `out` -- the old rows keep every bit --, `flow` is computed again, and so are the object rows and the tracks.
+    -> the Tracks after the fill, its `fill` a utils_tracks.Fill (the Tracks before, one entry per missing row)."""
     device = torch.device(device)
     n = len(fps[0].points_dst)
     if any(len(fp.points_dst) != n for fp in fps):
@@ -166,20 +179,32 @@ def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, m
                          f"({sorted({len(fp.points_dst) for fp in fps})}): they are not the gaps of one sample")
 
     def chain():
-        state, tables = utils_tracks.TrackState(n, device, Lmax, min_iou, max_residual, min_speed), []
+        state, tables, boxes = utils_tracks.TrackState(n, device, Lmax, min_iou, max_residual, min_speed), [], []
         for fp, out in zip(fps, outs):
             seconds = float(fp.gap) * float(sweep_seconds)
-            rows, _, ld = _frame_objects_device(fp, out, device, seconds, min_speed)
+            rows, _, ld, box = _frame_objects_device(fp, out, device, seconds, min_speed, boxes=True)
             state.extend(ld, rows, fp.gap, seconds)
-            tables.append(rows)
+            tables.append(rows), boxes.append(box)
         state.fit()
-        return state, tables
+        return state, tables, boxes
 
-    state, tables = chain()
-    if not repair:
+    state, tables, boxes = chain()
+    if not repair and not fill:
         return state.read()
     if args is None:
-        raise ValueError("frame_tracks(repair=True) registers again: it needs the `args` the frame pairs were registered with")
+        raise ValueError(f"frame_tracks({'repair' if repair else 'fill'}=True) registers again: it needs the `args` the frame pairs were registered with")
+    if repair:
+        after, state, tables, boxes = _repair_tracks(fps, outs, device, args, max_residual, state, tables, boxes, chain)
+    else:
+        after = state.read()
+    if fill:
+        after = _fill_tracks(fps, outs, device, args, max_residual, [float(fp.gap) * float(sweep_seconds) for fp in fps], state, boxes, chain, after)
+    return after
+
+
+def _repair_tracks(fps, outs, device, args, max_residual, state, tables, boxes, chain):
+    """frame_tracks(repair=True) behind the first chain -> (the Tracks after repair, and the state, object tables and source boxes
+    they were computed from: the second chain's where a pair was retried)"""
     plan, plan_counts = utils_tracks.suspects_device(torch.cat(state.obs), state.bound, max_residual)
     before = state.read()
     t0 = time.perf_counter()                                 # (the read-back above left the stream empty; the last one below drains it)
@@ -227,9 +252,107 @@ def frame_tracks(fps, outs, device, sweep_seconds=utils_objects.SWEEP_SECONDS, m
             report, at = host[at + 8: at + 8 + 12 * len(mine)].reshape(-1, 12), at + 8 + 12 * len(mine)
             for p, r in zip(mine, report):
                 retried.append(dict(entry(p), reason=int(r[0]), e_old=float(r[2]), e_new=float(r[1]), distance=float(r[6]), accepted=bool(r[11])))
-        state, _ = chain()                                   # the object rows and the tracks, again, on the repaired gaps
+        state, tables, boxes = chain()                       # the object rows and the tracks, again, on the repaired gaps
     after = state.read() if results else before
     after.repair = utils_tracks.Repair(before, plan_counts, sorted(retried, key=lambda e: (e["gap"], e["pair"])), counts, (time.perf_counter() - t0) * 1e3)
+    return after, state, tables, boxes
+
+
+FILL_READ_ROWS = 1024            # missing rows the plan's one read-back has room for; a sample with more reads the plan a second time
+
+
+def _fill_tracks(fps, outs, device, args, max_residual, seconds, state, boxes, chain, before):
+    """frame_tracks(fill=True) behind the chain (and the repair) -> the Tracks after the fill, its `fill` a utils_tracks.Fill;
+    `before`: the Tracks read from `state`"""
+    t0 = time.perf_counter()                                 # (the tracks' read-back left the stream empty; the last one below drains it)
+    R, f64 = utils_tracks.FILL_REASONS, torch.float64
+    segments, nums = torch.stack([s for s, _ in state.segments]), torch.cat([k for _, k in state.segments])
+    G, Lmax = int(segments.shape[0]), int(segments.shape[1])
+    plan, plan_counts = utils_tracks.missing_device(torch.cat(state.obs), state.bound, segments, nums, state.gaps, seconds, max_residual)
+    flat = plan.view(G * Lmax, -1)
+    cap = min(G * Lmax, FILL_READ_ROWS)
+    first = torch.argsort(flat[:, 0], descending=True, stable=True)[:cap]     # the missing rows first, in ascending plan-row order
+    host = torch.cat([plan_counts.to(f64).reshape(-1), first.to(f64), flat[first].reshape(-1)]).cpu().numpy()   # the plan's one read-back
+    plan_counts = np.rint(host[: 4 * G]).astype(np.int64).reshape(G, 4).sum(axis=0)
+    K = int(plan_counts[3])
+    if K > cap:
+        first = torch.argsort(flat[:, 0], descending=True, stable=True)[:K]
+        host = np.concatenate([host[: 4 * G], torch.cat([first.to(f64), flat[first].reshape(-1)]).cpu().numpy()])
+        cap = K
+    where = np.rint(host[4 * G: 4 * G + cap]).astype(np.int64)[:K]
+    h_plan = host[4 * G + cap:].reshape(cap, -1)[:K]
+    counts, entries = np.zeros(len(R), np.int64), []
+    for w, r in zip(where, h_plan):
+        entries.append(dict(gap=int(w // Lmax), segment=int(w % Lmax), track=int(r[1]), labels=[None, float(r[2])], reason=None, accepted=False, pair=None))
+    by_gap = {g: [k for k, e in enumerate(entries) if e["gap"] == g] for g in sorted({e["gap"] for e in entries})}
+    # the candidates of every gap with missing rows, and their one read-back
+    chosen = {}
+    for g, ks in by_gap.items():
+        q = flat[torch.from_numpy(where[ks]).to(device), 9:12]
+        chosen[g] = utils_tracks.fill_candidates_device(q, boxes[g][0], boxes[g][1], outs[g]["pairs"].to(device), utils_tracks.FILL_RADIUS, int(args.max_points))[0]
+    h_choice = torch.cat([chosen[g].reshape(-1) for g in by_gap]).cpu().numpy().reshape(-1, 8) if by_gap else np.zeros((0, 8))
+    results, at = [], 0
+    for g, ks in by_gap.items():
+        fp, out = fps[g], outs[g]
+        choice, at = h_choice[at: at + len(ks)], at + len(ks)
+        for k, c in zip(ks, choice):
+            if c[0] != 0.0:
+                entries[k]["reason"] = utils_tracks.FILL_NO_CANDIDATE if c[0] == 1.0 else utils_tracks.FILL_LOST
+                counts[entries[k]["reason"]] += 1
+            else:
+                entries[k]["labels"][0] = float(c[2])
+        live = [j for j, c in enumerate(choice) if c[0] == 0.0]
+        if not live:
+            continue
+        ps, pd = _input(fp, "points_src", device), _input(fp, "points_dst", device)
+        ls, ld = _source_labels(fp, out, device), out["labels_dst"].to(device).float() if out.get("labels_dst") is not None else _input(fp, "labels_dst", device).float()
+        st, dt = utils_check.ClusterTable.pair(ps, ls, pd, ld)
+        si, di = st.find_host(choice[live, 2]), dt.find_host(h_plan[np.asarray(ks)[live], 2])
+        fits = (si >= 0) & (di >= 0)
+        fits[fits] = (st.h_count[si[fits]] <= int(args.max_points)) & (dt.h_count[di[fits]] <= int(args.max_points))
+        for j in np.asarray(live)[~fits]:
+            entries[ks[j]]["reason"] = utils_tracks.REPAIR_TOO_LONG
+            counts[utils_tracks.REPAIR_TOO_LONG] += 1
+        live, si, di = np.asarray(live)[fits], si[fits], di[fits]
+        if len(live) == 0:
+            continue
+        rows = torch.from_numpy(where[np.asarray(ks)[live]]).to(device)
+        centre = torch.from_numpy(np.ascontiguousarray(choice[live, 5:8])).to(device)
+        unmoved = torch.eye(4, dtype=torch.float32, device=device).repeat(len(live), 1, 1)      # T_old: the ego motion alone, what the flow gave the cluster
+        params = utils_tracks.repair_params(args, out["translation_frame"], max_residual)
+        res = utils_tracks.reregister_device(args, st, dt, si, di, unmoved, centre, flat[rows, 6:9], params)
+        results.append((g, [ks[j] for j in live], res, (ps, pd, ls, ld)))
+    filled = False
+    if results:
+        host = torch.cat([torch.cat([r["counts"].to(f64), r["report"].reshape(-1)]) for _, _, r, _ in results]).cpu().numpy()
+        at = 0
+        for g, ks, res, (ps, pd, ls, ld) in results:
+            fp, out = fps[g], outs[g]
+            counts[:8] += np.rint(host[at: at + 8]).astype(np.int64)
+            report, at = host[at + 8: at + 8 + 12 * len(ks)].reshape(-1, 12), at + 8 + 12 * len(ks)
+            pairs, T = out["pairs"].to(device), out["transformations"].to(device)
+            P = int(pairs.shape[0])
+            for k, r in zip(ks, report):
+                entries[k].update(reason=int(r[0]), e_old=float(r[2]), e_new=float(r[1]), distance=float(r[6]), accepted=bool(r[11]))
+            took = [j for j, r in enumerate(report) if r[11] == 1.0]
+            if not took:
+                continue
+            for row, j in enumerate(took):
+                entries[ks[j]]["pair"] = P + row
+            idx = torch.from_numpy(np.asarray(took, np.int64)).to(device)
+            labels = torch.tensor([entries[ks[j]]["labels"] for j in took], dtype=torch.float64, device=device)
+            fresh = torch.cat([labels.to(pairs.dtype), res["errors"][idx].to(pairs.dtype), res["inliers"][idx].to(pairs.dtype),
+                               res["ratios"][idx].to(pairs.dtype), res["ious"][idx].to(pairs.dtype)], dim=1)
+            out["pairs"] = torch.cat([pairs.reshape(P, -1), fresh])              # NEW tensors: the old rows keep every bit
+            out["transformations"] = torch.cat([T.reshape(P, 4, 4), res["T"][idx].to(T.dtype).reshape(-1, 4, 4)])
+            flow_src = ps if fp.points_src_raw is None else _input(fp, "points_src_raw", device)
+            out["flow"] = utils_flow.flow_estimation_torch(args, flow_src, pd, ls, ld, out["pairs"], out["transformations"], torch.from_numpy(fp.pose).to(device))
+            filled = True
+    if filled:
+        state, _, _ = chain()                                # the object rows and the tracks, again, on the filled gaps
+    after = state.read() if filled else before
+    after.repair = before.repair
+    after.fill = utils_tracks.Fill(before, plan_counts, entries, counts, (time.perf_counter() - t0) * 1e3)
     return after
 
 
@@ -610,7 +733,15 @@ class TrackJudge:
     `repair` (per retried pair its gap, frame pair, pair row, labels, track, reason, e_old, e_new, distance from the prediction,
     accepted), the summary `tracks_repair` (suspects, retried, accepted, a count per reason, consistent_before / consistent_after)
     and `ms_tracks_repair_per_sample` (behind the tracks' first read-back, to the end of the second chain).  What run_stream
-    scored of a frame pair's flow at its delivery (files with ground truth) is of the registration as delivered."""
+    scored of a frame pair's flow at its delivery (files with ground truth) is of the registration as delivered.
+
+    args.tracks_fill = True (`--tracks-fill`; needs args.tracks): `frame_tracks(fill=True)`, after the repair when both are set -- a
+    gap in which a track found no pair is registered from what the other gaps predict and, where accepted, the `out` of that
+    frame pair carries one more pair row and transform and the flow of that cluster from then on; the ObjectJudge accounts such a
+    frame pair again.  A sample's line gains `fill` (per missing (track, gap) its gap, frame pair, destination segment, track,
+    labels, reason, and where it was registered e_old, e_new, distance from the prediction, accepted, the appended pair row), the
+    summary `tracks_fill` (missing, retried, accepted, a count per reason, observed_before / observed_after, judged_before /
+    judged_after) and `ms_tracks_fill_per_sample` (behind the tracks' read-back, to the end of the last chain)."""
 
     def __init__(self, args, world, device, objects, sample_of, samples):
         self.file = getattr(args, "tracks", None)
@@ -626,6 +757,12 @@ class TrackJudge:
         if self.repair and not self.on:
             raise ValueError("args.tracks_repair goes with args.tracks (it registers again what the tracks name)")
         self.ms_repair = []
+        self.fill = bool(getattr(args, "tracks_fill", False))
+        if self.fill and not self.on:
+            raise ValueError("args.tracks_fill goes with args.tracks (it fills the gaps the tracks name)")
+        self.ms_fill = []
+        self.filled = dict(missing=0, retried=0, accepted=0, reasons={name: 0 for name in utils_tracks.FILL_REASONS}, observed_before=0, observed_after=0,
+                           judged_before=0, judged_after=0)
         self.repaired = dict(suspects=0, retried=0, accepted=0, reasons={name: 0 for name in utils_tracks.REPAIR_REASONS}, consistent_before=0,
                              consistent_after=0)
 
@@ -641,14 +778,14 @@ class TrackJudge:
         fps = [sample["outs"][k][0] for k in ks]
         with timed(self.device, self.ms):
             seen = frame_tracks(fps, [sample["outs"][k][1] for k in ks], self.device, self.objects.sweep_seconds, self.objects.min_speed,
-                                self.min_iou, self.max_residual, repair=self.repair, args=self.args)
+                                self.min_iou, self.max_residual, repair=self.repair, args=self.args, **(dict(fill=True) if self.fill else {}))
         summary = seen.summary()
         for name in self.totals:
             self.totals[name] += summary[name]
         self.lines[s] = dict(sample=s, path=fps[0].sequence or fps[0].name, frame_pairs=ks, gaps=[fp.gap for fp in fps], counts=summary,
                              tracks=seen.as_list(), observations=[ids.tolist() for ids in seen.observation_ids])
         if self.repair:
-            done = seen.repair.summary(seen)
+            done = seen.repair.summary(seen.fill.before if self.fill else seen)       # (the repair's block is what it is alone)
             for name, v in done.items():
                 if name == "reasons":
                     for reason, c in v.items():
@@ -659,6 +796,19 @@ class TrackJudge:
             self.lines[s]["repair"] = [dict(e, frame_pair=ks[e["gap"]], reason=utils_tracks.REPAIR_REASONS[e["reason"]]) for e in seen.repair.retried]
             if self.objects.on:                     # the objects of a repaired gap, again: its line and its counts are replaced
                 for g in sorted({e["gap"] for e in seen.repair.retried if e["accepted"]}):
+                    self.objects.account(ks[g], fps[g], sample["outs"][ks[g]][1])
+        if self.fill:
+            done = seen.fill.summary(seen)
+            for name, v in done.items():
+                if name == "reasons":
+                    for reason, c in v.items():
+                        self.filled["reasons"][reason] += c
+                else:
+                    self.filled[name] += v
+            self.ms_fill.append(seen.fill.ms)
+            self.lines[s]["fill"] = [dict(e, frame_pair=ks[e["gap"]], reason=utils_tracks.FILL_REASONS[e["reason"]]) for e in seen.fill.retried]
+            if self.objects.on:                     # the objects of a filled gap, again: its line and its counts are replaced
+                for g in sorted({e["gap"] for e in seen.fill.retried if e["accepted"]}):
                     self.objects.account(ks[g], fps[g], sample["outs"][ks[g]][1])
         for k, ids in zip(ks, seen.observation_ids):
             for e in self.objects.lines.get(k, {}).get("objects", []):
@@ -671,6 +821,9 @@ class TrackJudge:
         if self.repair:
             out["tracks_repair"] = dict(self.repaired)
             out["ms_tracks_repair_per_sample"] = sum(self.ms_repair) / max(len(self.ms_repair), 1)
+        if self.fill:
+            out["tracks_fill"] = dict(self.filled)
+            out["ms_tracks_fill_per_sample"] = sum(self.ms_fill) / max(len(self.ms_fill), 1)
         if isinstance(self.file, str):
             with open(self.file, "w") as f:
                 for s in sorted(self.lines):        # one JSON line per sample, in their order

@@ -286,6 +286,93 @@ class Repair:
                     consistent_before=int(self.before.fit_counts[3]), consistent_after=int(after.fit_counts[3]))
 
 
+FILL_RADIUS = 1.0              # metres: below the centre distance of two parked cars side by side, above the wander of a box centre
+                               # between two views of one object -- a stated policy
+FILL_REASONS = REPAIR_REASONS + ("no_candidate", "lost")
+FILL_NO_CANDIDATE, FILL_LOST = 7, 8
+
+
+def missing_device(obs, T, segments, nums, gaps, seconds, max_residual=MAX_RESIDUAL):
+    """icpflow_object_tracks_missing enqueued on the current stream, nothing read back.  obs float64 [M, 13]: the observations of
+    every gap, concatenated; T: the tracks (an upper bound); segments float64 [G, Lmax, 6] and nums int32 [G]: what
+    `TrackState.extend` left per gap slot, stacked; gaps, seconds: per slot (HOST) the gap its observations carry and the seconds
+    it spans.  -> (plan float64 [G, Lmax, 14], counts int64 [G, 4]) on the device: per segment of every slot whether its track
+    lacks a pair there, and what the other gaps predict (p: the displacement, q: the source box's centre).  The plan is allocated
+    as zeros: the rows the call does not write read as not missing."""
+    import torch
+    from . import _lib
+    _lib.require_gpu(obs, segments, nums)
+    M, device = int(obs.shape[0]), segments.device
+    G, Lmax = (int(v) for v in segments.shape[:2]) if segments.dim() == 3 else (0, 0)
+    if obs.dtype != torch.float64 or tuple(obs.shape) != (M, _lib.TRACK_OBS_COLS) or obs.device != device:
+        raise ValueError(f"missing: observations {tuple(obs.shape)} {obs.dtype}, expected float64 [M, {_lib.TRACK_OBS_COLS}]")
+    if segments.dtype != torch.float64 or tuple(segments.shape) != (G, Lmax, _lib.TRACK_SEGMENT_COLS) or nums.dtype != torch.int32 or tuple(nums.shape) != (G,):
+        raise ValueError(f"missing: segments {tuple(segments.shape)} {segments.dtype}, numbers {tuple(nums.shape)} {nums.dtype}: expected float64 "
+                         f"[G, Lmax, {_lib.TRACK_SEGMENT_COLS}] and int32 [G]")
+    h_gap = np.ascontiguousarray(np.asarray(gaps, np.int32).reshape(-1))
+    h_seconds = np.ascontiguousarray(np.asarray(seconds, np.float64).reshape(-1))
+    if len(h_gap) != G or len(h_seconds) != G:
+        raise ValueError(f"missing: {len(h_gap)} gaps and {len(h_seconds)} seconds for {G} slots")
+    rows, seg, num = obs.contiguous(), segments.contiguous(), nums.contiguous()
+    plan = torch.zeros((G, Lmax, _lib.TRACK_MISSING_COLS), dtype=torch.float64, device=device)
+    counts = torch.empty((G, _lib.TRACK_MISSING_COUNTS), dtype=torch.int64, device=device)
+    params = _lib.TrackParams.defaults(max_residual=max_residual)
+    with torch.cuda.device(device):
+        _lib.call("icpflow_object_tracks_missing", _lib.ptr(rows) if M else None, M, int(T), _lib.ptr(seg), _lib.ptr(num), G, Lmax,
+                  h_gap.ctypes.data_as(ctypes.c_void_p), h_seconds.ctypes.data_as(ctypes.c_void_p), ctypes.byref(params), _lib.ptr(plan),
+                  _lib.ptr(counts), _lib.stream(device))
+    return plan, counts
+
+
+def fill_candidates_device(q, boxes_src, num_src, pair_rows, radius=FILL_RADIUS, max_rows=10000):
+    """icpflow_pairs_fill_candidates enqueued on the current stream, nothing read back.  q float64 [K, 3]: the predicted source
+    box centres of ONE gap's missing rows; boxes_src float64 [Lmax, 16], num_src int32 [1]: utils_objects.segment_boxes_device's
+    table of that gap's ego-compensated source; pair_rows float32 [P, >= 1] (or None): column 0 the source labels already
+    matched.  -> (choice float64 [K, 8], counts int64 [4]) on the device: per row the nearest unmatched box within `radius`."""
+    import torch
+    from . import _lib
+    _lib.require_gpu(q, boxes_src, num_src, pair_rows)
+    K, device, Lmax = int(q.shape[0]), boxes_src.device, int(boxes_src.shape[0])
+    if q.dtype != torch.float64 or tuple(q.shape) != (K, 3) or q.device != device:
+        raise ValueError(f"fill_candidates: q {tuple(q.shape)} {q.dtype}, expected float64 [K, 3] on the boxes' device")
+    if boxes_src.dtype != torch.float64 or tuple(boxes_src.shape) != (Lmax, _lib.BOX_COLS) or num_src.dtype != torch.int32:
+        raise ValueError(f"fill_candidates: boxes {tuple(boxes_src.shape)} {boxes_src.dtype}, expected float64 [Lmax, {_lib.BOX_COLS}] and an int32 number")
+    P = 0 if pair_rows is None else int(pair_rows.shape[0])
+    rows, stride = None, 1
+    if P > 0:
+        rows = pair_rows.to(device=device, dtype=torch.float32).contiguous()
+        if rows.dim() != 2 or rows.shape[1] < 1:
+            raise ValueError(f"fill_candidates: pair rows {tuple(rows.shape)}, expected [P, >= 1]")
+        stride = int(rows.shape[1])
+    centres, boxes, num = q.contiguous(), boxes_src.contiguous(), num_src.contiguous()
+    choice = torch.empty((K, _lib.FILL_CHOICE_COLS), dtype=torch.float64, device=device)
+    counts = torch.empty(_lib.FILL_COUNTS, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        _lib.call("icpflow_pairs_fill_candidates", _lib.ptr(centres) if K else None, K, _lib.ptr(boxes), _lib.ptr(num), Lmax, _lib.ptr(rows), P, stride,
+                  float(radius), int(max_rows), _lib.ptr(choice) if K else None, _lib.ptr(counts), _lib.stream(device))
+    return choice, counts
+
+
+class Fill:
+    """What frame_tracks(fill=True) did to one sample, on the host: `before` the Tracks as the registrations (and the repair) left
+    them, `plan_counts` icpflow_object_tracks_missing's four counts added over the gap slots, `retried` one dict per missing
+    (track, gap) (gap: its index among the sample's frame pairs, segment: the destination segment of that gap's labelling,
+    track, labels: the chosen source label and the destination label, reason, and where it was registered e_old, e_new,
+    distance: of the new displacement from the predicted one in xy, accepted, pair: its row of the gap's new tables), `counts`
+    one word per FILL_REASONS (reasons 0 to 5 by the device's select, 6 to 8 by the host from the candidates' table)."""
+
+    def __init__(self, before, plan_counts, retried, counts, ms=0.0):
+        self.before, self.retried, self.ms = before, list(retried), float(ms)     # ms: the fill's wall time behind the tracks' read-back
+        self.plan_counts = np.asarray(plan_counts, np.int64).reshape(4)
+        self.counts = np.asarray(counts, np.int64).reshape(len(FILL_REASONS))
+
+    def summary(self, after):
+        return dict(missing=int(self.plan_counts[3]), retried=int(self.counts[:6].sum()), accepted=int(self.counts[0]),
+                    reasons={name: int(v) for name, v in zip(FILL_REASONS, self.counts)},
+                    observed_before=int(self.before.fit_counts[1]), observed_after=int(after.fit_counts[1]),
+                    judged_before=int(self.before.fit_counts[2]), judged_after=int(after.fit_counts[2]))
+
+
 class Tracks:
     """The tracks of one sample on the host (icpflow_object_tracks_fit's table, read back once)."""
 
@@ -296,6 +383,7 @@ class Tracks:
         self.observation_ids = [np.asarray(i, np.int64) for i in observation_ids]      # per gap, one per object row (-1: none)
         self.extend_counts = [np.asarray(c, np.int64).reshape(6) for c in extend_counts]
         self.repair = None                    # a Repair: set by pair_judges.frame_tracks(repair=True)
+        self.fill = None                      # a Fill: set by pair_judges.frame_tracks(fill=True)
 
     def summary(self):
         _, observed, judged, consistent, moving = (int(v) for v in self.fit_counts)

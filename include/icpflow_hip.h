@@ -1584,8 +1584,8 @@ int icpflow_object_tracks_path(const double *d_obs, const int32_t *d_step, int M
  * 8(k) ends in a verdict -- a track is not consistent --; here the observation that breaks it is named, its pair is registered
  * once more from the predicted displacement, and the new pose replaces the old one only where the data prefer it.  Multi-frame
  * samples only (all gaps share the destination sweep).  No counterpart in the reference; which gap is retried, the acceptance
- * rule and its numbers are stated policies (COVERAGE.md, named deviations).  The partner of a pair is not chosen again, a gap
- * without a pair is not filled.
+ * rule and its numbers are stated policies (COVERAGE.md, named deviations).  The partner of a pair is not chosen again; a gap
+ * without a pair is filled by 8(n).
  *
  * icpflow_object_tracks_suspects -- which observation breaks its track:
  *   d_obs double [M][ICPFLOW_TRACK_OBS_COLS], the gaps concatenated as icpflow_object_tracks_fit takes them; T: the tracks;
@@ -1676,6 +1676,75 @@ int icpflow_pairs_reregister(const icpflow_tables_t *tables, int K, int N, const
                              const icpflow_registration_t *reg, const icpflow_repair_params_t *params, float *d_T_out,
                              double *d_report, int64_t *d_counts, void *d_ws, size_t ws_bytes, icpflow_stream_t stream,
                              const icpflow_options_t *opt);
+
+/* ---------------------------------------------------------------------------
+ * 8(n)  track fill: the gap in which a track found no pair registered from what the other gaps predict.  A cluster the
+ * association missed in one gap is in no pair row, and the flow gives its points the ego motion only.  Where the same object
+ * was registered in two or more other gaps that agree on one velocity, they predict where its source cluster lies in the
+ * missing gap, which destination cluster it belongs to (the segment of the shared sweep that carries the track's id in that
+ * gap's labelling) and the translation to start ICP from; icpflow_pairs_reregister (8(m)) registers the pair from there, with
+ * T_old the identity -- the cluster unmoved, which is what the flow gave it -- and its select decides.  Multi-frame samples
+ * only.  No counterpart in the reference; which (track, gap) is filled, with which source cluster, and the acceptance rule
+ * are stated policies (COVERAGE.md, named deviations).
+ *
+ * icpflow_object_tracks_missing -- which segment of the shared sweep lacks a pair in its gap, over all gap slots at once:
+ *   d_obs double [M][ICPFLOW_TRACK_OBS_COLS], M, T and params as icpflow_object_tracks_suspects takes them (only max_residual
+ *   is read); d_segments double [G][Lmax][ICPFLOW_TRACK_SEGMENT_COLS] and d_num int32 [G]: what icpflow_object_tracks_extend
+ *   left per gap slot, concatenated; h_gap int32 [G] and h_seconds double [G] (HOST), 1 <= G <= ICPFLOW_TRACK_MISSING_MAX_SLOTS:
+ *   the gap value the observations of slot g carry in column 1, and the seconds the slot spans -- copied before the call
+ *   returns (they travel in the kernel arguments).  One thread per (slot g, segment c < min(d_num[g], Lmax)); the arithmetic
+ *   is the suspects' (one device function walks for both): fp64, every operation written out, no fma, rows ascending.
+ *   t = column 2 of the segment; the segment HAS AN ID iff 0 <= t < T.  First walk, over the rows i whose column 0 equals t:
+ *   a row with gap_i == h_gap[g] makes the segment OBSERVED -- it is counted and enters nothing else; for every other row
+ *   A += s_i s_i; B += s_i d_i per axis; L += (c_i + d_i) per axis, c columns 10-12 (one addition, then the accumulation);
+ *   the bit of gap_i is set for a gap in [0, 63]; others += 1.  The segment is ELIGIBLE iff it is not observed, at least two
+ *   distinct gaps were seen and A > 0; then v = B / A.  Second walk, over the same rows: inner = the largest
+ *   (dx_i - s_i vx)^2 + (dy_i - s_i vy)^2.  p = h_seconds[g] v; q = L / others - p (the mean landing point on the shared sweep,
+ *   moved back by p: the predicted centre of the source box); m2 = max_residual * max_residual (one product).  MISSING iff
+ *   eligible and inner <= m2.  Row (g, c) of d_plan double [G][Lmax][ICPFLOW_TRACK_MISSING_COLS]:
+ *       0  missing    1  t    2  the segment's label    3  rows observed in this gap    4  others    5  distinct gaps
+ *       6-8  p        9-11  q                           12  sqrt(inner)                  13  the segment's rows
+ *   (columns 0 and 6-12 are zero for a row that is not eligible, 3-5 too for a segment without an id).  Rows from d_num[g] on
+ *   are not written; a slot with a negative d_num[g] writes none.  d_counts int64 [G][ICPFLOW_TRACK_MISSING_COUNTS]: segments
+ *   with an id, of them not observed, eligible, missing; by ballot and popcount, integer atomics only.  One launch, no
+ *   workspace, asynchronous on `stream`.  Refusals, before any launch: a null required pointer (d_obs with M > 0, every other
+ *   one), M < 0, T < 0, G outside [1, 64], Lmax < 1, h_gap values outside [0, 63] or not distinct, seconds not positive and
+ *   finite, a struct_size mismatch, a negative or non-finite max_residual are ICPFLOW_E_ARG; M > 2^16, T > 2^24 or Lmax > 4096
+ *   is ICPFLOW_E_LIMIT.
+ *
+ * icpflow_pairs_fill_candidates -- the source cluster of each missing row of ONE gap:
+ *   d_q double [K][3]: columns 9-11 of the K missing rows; d_boxes_src double [Lmax][ICPFLOW_BOX_COLS] and d_num_src:
+ *   icpflow_segment_boxes' table of the ego-compensated source (a count above Lmax is read as Lmax, a negative one as 0);
+ *   d_pair_rows float32 [P][pair_stride], pair_stride >= 1: column 0 the source labels already matched; radius (metres) in
+ *   (0, 1e3]; max_rows >= 1.  Segment c is a CANDIDATE iff its column 3 >= 0 (it has a box), its column 1 <= max_rows, and its
+ *   label narrowed to float equals no column 0 of the pair rows (IEEE ==: +0 and -0 are one label, a NaN equals none; the pair
+ *   rows pass through LDS in tiles of 1024).  For row k: dx = X_c - q_x, dy = Y_c - q_y (box columns 6, 7),
+ *   d2 = dx dx + dy dy in fp64 without fma; the candidate is WITHIN REACH iff d2 <= radius * radius (one product; a NaN is
+ *   not).  The CHOICE of row k is the reachable candidate with the smallest d2, ties to the lower c.  Where several rows
+ *   choose one segment the row with the smallest d2 keeps it, ties to the lower k; the others LOSE it and get no second
+ *   choice.  Row k of d_choice double [K][ICPFLOW_FILL_CHOICE_COLS]:
+ *       0  reason: 0 chosen, 1 none within reach, 2 lost    1  the segment, or -1 (a loser names the segment it lost)
+ *       2  its label    3  its rows    4  sqrt(d2)    5-7  its box centre (columns 6-8)        (1-7: -1 and zeros for reason 1)
+ *   d_counts int64 [ICPFLOW_FILL_COUNTS]: chosen, none, lost, candidates.  Two launches: a 256-thread workgroup per row strides
+ *   over the segments, the minimum of (d2, c) goes through the wave and then LDS -- a minimum does not depend on the order, so
+ *   the result is a function of the arguments alone --; a thread per row then settles the shared choices.  No workspace, no
+ *   floating-point atomic, asynchronous on `stream`.  Refusals, before any launch: a null required pointer (d_boxes_src,
+ *   d_num_src, d_counts; d_q and d_choice with K > 0), K < 0, P < 0, Lmax < 1, pair_stride < 1, P > 0 with no pair rows, a radius
+ *   outside (0, 1e3] (a NaN too), max_rows < 1 are ICPFLOW_E_ARG; K > 2^16 or Lmax > 4096 is ICPFLOW_E_LIMIT.  K = 0 succeeds
+ *   with four zeros.
+ * ------------------------------------------------------------------------- */
+#define ICPFLOW_TRACK_MISSING_COLS 14
+#define ICPFLOW_TRACK_MISSING_COUNTS 4
+#define ICPFLOW_TRACK_MISSING_MAX_SLOTS 64
+#define ICPFLOW_FILL_CHOICE_COLS 8
+#define ICPFLOW_FILL_COUNTS 4
+int icpflow_object_tracks_missing(const double *d_obs, int M, int T, const double *d_segments, const int32_t *d_num, int G,
+                                  int Lmax, const int32_t *h_gap, const double *h_seconds,
+                                  const icpflow_track_params_t *params, double *d_plan, int64_t *d_counts,
+                                  icpflow_stream_t stream);
+int icpflow_pairs_fill_candidates(const double *d_q, int K, const double *d_boxes_src, const int32_t *d_num_src, int Lmax,
+                                  const float *d_pair_rows, int P, int pair_stride, double radius, int max_rows,
+                                  double *d_choice, int64_t *d_counts, icpflow_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * 8(f)  ground segmentation of one cloud: the method of Patchwork++ as the reference configures it -- a fresh object for
